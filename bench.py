@@ -8,14 +8,19 @@ value     = transcipherings all ranks completed / max-over-ranks time (inputs re
 --gpus N  = N > 1 without a launcher: this process starts N rank processes itself (launch_ranks); under
             torch.distributed.run the ranks come from the environment.  Ranks shard by independent items,
             no data-path collective; RCCL only carries the barrier and the MAX/SUM of (time, units).
-roofline  = the dominant kernel (ks_row_kernel): its average launch duration is measured live with HIP events on the
+roofline  = `path`: the whole transciphering with SURVEY 8(d)'s op-level model (A_block) over the timed steps.  With --full also
+            the dominant kernel (ks_row_kernel): its average launch duration is measured live with HIP events on the
             stream it is launched on (hhe_ctx_profile: one more step of the same workload with every launch bracketed),
-            against the bytes it must move; `path` repeats the same for the whole transciphering
-            with SURVEY 8(d)'s op-level model (A_block).
-cpu_baseline = the CPU oracle (a C port of the reference schedule) on the host cores, rank 0, N=1 only.
-extras    = (N=1 only) BASELINE config 5: a 512-step rotate_rows chain at N=2^16 / 6 primes; config 3 shape: MNIST-shaped samples
+            against the bytes it must move.
+cpu_baseline = (--full) the CPU oracle (a C port of the reference schedule) on the host cores, rank 0, N=1 only.
+extras    = (--full, N=1 only) BASELINE config 5: a 512-step rotate_rows chain at N=2^16 / 6 primes; config 3 shape: MNIST-shaped samples
             through hhe_decompose + the 784x10 FC; the reference's default parameters (N=2^14, BFVDefault 9 primes); the drop-in's
             per-record call shape (one 784-word / one 300-word record per hhe_decompose call, ms per call).
+--full    = runs the kernel-timing step, the CPU baseline and the extras above (each can still be switched off on its own);
+            a plain run sets up, warms up, times --steps steps and prints the line.
+--dump-outputs DIR = after the timed steps, the output ciphertexts of the last step as DIR/<name>_{lo32,hi32}.npy (float64: the
+            low / high 32 bits of every u64 word, exact); an output of more than DUMP_WORDS words is a fixed seeded sample of
+            them, whose flat indices go to DIR/<name>_index.npy.  Inputs are seeded, so two builds compare output for output.
 --workload mnist-e2e = BASELINE config 3 as its own bench: every rank runs hhe_decompose + the 10 FC rows on ITS contiguous
             sample range (sharding.shard_samples), value = samples/s (SUM of samples / MAX of time), decompose and FC rooflines.
 """
@@ -49,6 +54,7 @@ PMC_PROFILE = os.path.join(ROOT, "profiles", "r3_pmc_summary.json")
 VALU_CYCLES_PER_INST = 4.4
 SUSTAINED_GHZ = 2.1
 SIMDS = 1024
+DUMP_WORDS = 1 << 20  # words per dumped output (all ranks together): 3 float64 arrays = 24 MB, two outputs stay under 64 MB
 
 
 def a_block_bytes(n, L, K):
@@ -218,6 +224,24 @@ class Device:
         return time.perf_counter() - t0, e0.elapsed_time(e1)
 
 
+def dump_outputs(D, outdir, outputs, rank, world):
+    """writes each u64 output tensor of `outputs` ({name: tensor}) as exact float64 halves; a tensor of more than
+    DUMP_WORDS / world words is sampled at fixed seeded flat indices (the same for every run of the same shape)"""
+    os.makedirs(outdir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    cap = DUMP_WORDS // world
+    for name, t in outputs.items():
+        flat = t.reshape(-1)
+        path = os.path.join(outdir, prefix + name)
+        if flat.numel() > cap:
+            idx = np.sort(np.random.default_rng(2024).choice(flat.numel(), cap, replace=False))
+            flat = flat.index_select(0, D.torch.from_numpy(idx).to(flat.device))
+            np.save(path + "_index.npy", idx.astype(np.float64))
+        w = flat.cpu().numpy().view(np.uint64)
+        np.save(path + "_lo32.npy", (w & np.uint64(0xFFFFFFFF)).astype(np.float64))
+        np.save(path + "_hi32.npy", (w >> np.uint64(32)).astype(np.float64))
+
+
 def make_context(api, lib, D, logn, q, t, local_rank):
     X = api.Context(logn, q, t, device=0 if D.rehearsal else local_rank, lib=lib)
     if D.stream is not None:
@@ -292,7 +316,7 @@ class MnistFlow:
             else np.zeros((0, self.nin), np.uint64)
 
     def run(self, recs, warm=False):
-        """decompose + FC of `recs`; returns (decompose ms, FC ms) on the library's stream"""
+        """decompose + FC of `recs`; returns (decompose ms, FC ms) on the library's stream and keeps both outputs in self.outputs"""
         D, X, S = self.D, self.X, len(recs)
         flat = D.zeros((S, 2, self.L, self.n))
         _, dec_ms = D.timed(lambda: X.decompose(self.enc_key, recs, flat, rk=self.pasta, gk=self.pasta, flatten_gk=self.csp_gk))
@@ -300,6 +324,7 @@ class MnistFlow:
             np.repeat(flat, self.neurons, axis=0)  # item = (sample, neuron), neuron = item % neurons
         out = D.zeros(tuple(vi.shape))
         _, fc_ms = D.timed(lambda: X.fc_row(vi, self.w, self.neurons, self.nin, out, S * self.neurons, rk=self.csp_rk, gk=self.analyst_gk))
+        self.outputs = {"decompose_out": flat, "fc_out": out}
         return dec_ms, fc_ms
 
     def rooflines(self, S, dec_ms, fc_ms):
@@ -414,11 +439,17 @@ def main():
     ap.add_argument("--params", default="config2", choices=["config2", "default16384", "tiny"],
                     help="config2: N=2^15, 4x60-bit (BASELINE metric); default16384: the reference's defaults N=2^14, BFVDefault 9 primes; "
                          "tiny: N=2^10 (plumbing rehearsals only)")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also run what the headline figure does not need: --kernel-timing, --cpu-baseline, --extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step to DIR/*.npy")
+    ap.add_argument("--cpu-baseline", type=int, default=None, help="CPU oracle leg (default: 1 with --full, else 0)")
     ap.add_argument("--cpu-blocks-per-thread", type=int, default=3)
-    ap.add_argument("--extras", type=int, default=1, help="config-5 rotation chain and MNIST-shaped legs (N=1 only)")
-    ap.add_argument("--kernel-timing", type=int, default=1, help="extra step with HIP events around every launch of the dominant kernel (roofline block)")
+    ap.add_argument("--extras", type=int, default=None, help="config-5 rotation chain and MNIST-shaped legs (N=1 only; default: 1 with --full, else 0)")
+    ap.add_argument("--kernel-timing", type=int, default=None,
+                    help="extra step with HIP events around every launch of the dominant kernel (roofline block; default: 1 with --full, else 0)")
     args = ap.parse_args()
+    for k in ("cpu_baseline", "extras", "kernel_timing"):
+        if getattr(args, k) is None:
+            setattr(args, k, int(args.full))
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -480,6 +511,8 @@ def main():
     sh.barrier()
     elapsed, dev_ms = D.timed(lambda: [step() for _ in range(args.steps)])
     sh.barrier()
+    if args.dump_outputs:
+        dump_outputs(D, args.dump_outputs, {"transcipher_out": out}, rank, world)
     red_dev = D.dev if (world > 1 and not rehearsal and os.environ.get("HHE_BENCH_BACKEND", "nccl") == "nccl") else "cpu"
     el_max, units = sh.reduce_max_sum(elapsed, B * args.steps, device=red_dev)
     value = units / el_max
@@ -614,6 +647,8 @@ def main_mnist_e2e(args, api, lib, sh, D, rank, world, local_rank, rehearsal, ba
     D.sync()
     elapsed = time.perf_counter() - t0
     sh.barrier()
+    if args.dump_outputs:
+        dump_outputs(D, args.dump_outputs, F.outputs, rank, world)
     red_dev = D.dev if (world > 1 and not rehearsal and os.environ.get("HHE_BENCH_BACKEND", "nccl") == "nccl") else "cpu"
     el_max, units = sh.reduce_max_sum(elapsed, (hi - lo) * args.steps, device=red_dev)
     if rank == 0:

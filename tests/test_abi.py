@@ -18,6 +18,9 @@ PKG = "privacy-preserving-ml-through-hhe_amd"
 def product_lib():
     build = importlib.import_module(PKG + ".build")
     path = build.build()  # hipcc --offload-arch=gfx950 (cross-compiles without a GPU)
+    # torch first, as api.load_library does: its HIP runtime is loaded as libamdhip64.so, ours asks for libamdhip64.so.7, and
+    # loading ours first leaves two HIP runtimes in this process, which breaks every later GPU test of the same pytest run
+    import torch  # noqa: F401
     return ctypes.CDLL(path)
 
 

@@ -3,6 +3,6 @@
 rounds=$1; shift
 for r in $(seq 1 $rounds); do
   for lib in "$@"; do
-    HHE_LIB=$lib timeout -k 10 200 python bench.py --cpu-baseline 0 --extras 0 --steps 3 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); print('$lib', round(d['value'],1), round(d['roofline']['avg_launch_us'],1))"
+    HHE_LIB=$lib timeout -k 10 200 python bench.py --full --cpu-baseline 0 --extras 0 --steps 3 2>/dev/null | python -c "import json,sys; d=json.load(sys.stdin); print('$lib', round(d['value'],1), round(d['roofline']['avg_launch_us'],1))"
   done
 done

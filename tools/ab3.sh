@@ -5,7 +5,7 @@ for r in $(seq 1 $rounds); do
   for lib in "$@"; do
     HHE_LIB=$lib timeout -k 10 300 python - <<PY
 import json, subprocess, sys, os
-p = subprocess.run([sys.executable, "bench.py", "--cpu-baseline", "0", "--extras", "0", "--steps", "3"], capture_output=True, text=True)
+p = subprocess.run([sys.executable, "bench.py", "--full", "--cpu-baseline", "0", "--extras", "0", "--steps", "3"], capture_output=True, text=True)
 d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
 import importlib, torch, numpy as np
 import bench
