@@ -71,7 +71,10 @@ int hhe_ctx_sync(hhe_ctx *c);
 int hhe_ctx_profile(hhe_ctx *c, int enable);
 int hhe_ctx_profile_read(hhe_ctx *c, char *kernel_name, size_t name_cap, uint64_t *launches, double *total_ms, uint64_t *items);
 /* derived parameters, for cross-checking against SEAL's context: what in
- * {"root" i<K, "bsk" i<=L (B_0.., m_sk), "gamma", "galois_elt" i=step, "fc_fallbacks", "fc_csum_closes"} */
+ * {"root" i<K, "bsk" i<=L (B_0.., m_sk), "gamma", "galois_elt" i=step, "fc_fallbacks", "fc_csum_closes"};
+ * which kernels the context dispatches to (read-only diagnostics): "row_kernel" (1 = the fused key-switch row kernels run,
+ * 0 = the separate-kernel path), "pm_ok" i<K (coefficient prime i has the pseudo-Mersenne form the lazy kernels need),
+ * "digit_reduce" (key-switch digits are reduced before their transforms: some q_I >= 4 q_J) */
 uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i);
 
 /* ---- keys.  Key words must be reduced modulo their coefficient primes (what SEAL's safe load checks, is_data_valid_for):

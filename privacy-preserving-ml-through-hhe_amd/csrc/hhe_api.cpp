@@ -11,9 +11,6 @@
 namespace {
 
 int fail(int code, const std::string &msg) { hhe_set_error(msg); return code; }
-// the fused key-switch row kernel runs when the row pass has one of its sizes AND every key-level modulus has the pseudo-Mersenne
-// form its arithmetic is written for (SEAL's own primes do); other contexts take the separate-kernel path (any N, any primes < 2^61)
-bool use_row_kernel(const hhe_ctx *c) { return k_ks_row_supported(c->logn) && ntt_lazy8(c, 0, c->K); }
 int dev_fail(const char *where) { return fail(HHE_ERR_DEVICE, std::string(where) + ": " + rt_last_error()); }
 
 int need(hhe_ctx *c, size_t B)
@@ -550,7 +547,8 @@ int matmul_diagonal_fused(hhe_ctx *c, int layer, const u64 *const *d_pdiag_ptrs,
         a1.store_op = STORE_KS1; a1.aux_r = r; a1.aux_out = c->w->ws_d; a1.gal_elt = g;
         k_ntt_pass(a1, true, true, c->w->stream);
     };
-    // N < 4096 (ragged tiles) -- the same step with the inner product as its own kernel: T and S are materialised
+    // every context without the row kernel (use_row_kernel: N < 4096 with its ragged tiles, or ANY N when a coefficient prime lacks
+    // the pseudo-Mersenne form, e.g. BFVDefault(4096)) -- the same step with the inner product as its own kernel: T and S are materialised
     auto step_separate = [&](size_t shift) {
         const NttArgs a = digit_args();
         KsMacArgs m;

@@ -531,6 +531,9 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "fc_csum_closes") return c->fc_csum_closes;
     if (w == "block_cache_bytes") return c->block_bytes;
     if (w == "block_cache_entries") return c->blocks.size();
+    if (w == "row_kernel") return use_row_kernel(c) ? 1 : 0;
+    if (w == "pm_ok" && i >= 0 && i < c->K) return (u64)c->pm_ok[i];
+    if (w == "digit_reduce") return (u64)c->digit_reduce;
     return 0;
 }
 

@@ -171,6 +171,11 @@ inline int ntt_lazy8(const hhe_ctx *c, int mod_base, int mod_cycle)
         if (!c->pm_ok[i]) return 0;
     return 1;
 }
+// the fused key-switch row kernel runs when the row pass has one of its sizes AND every key-level modulus has the pseudo-Mersenne
+// form its arithmetic is written for; other contexts take the separate-kernel path (any N, any primes < 2^61).  SEAL's primes of
+// 42 bits and more at these degrees have the form; smaller ones (BFVDefault(4096): 36+36+37 bits) and primes that are not just
+// below a power of two do not.  hhe_ctx_query("row_kernel") reports the decision.
+inline bool use_row_kernel(const hhe_ctx *c) { return k_ks_row_supported(c->logn) && ntt_lazy8(c, 0, c->K); }
 
 struct DevBuf {  // scoped device allocation (freed on every exit path unless released)
     void *p = nullptr;

@@ -35,6 +35,51 @@ class TorchMem:
         return b.cpu().numpy().view(np.uint64)
 
 
+def setup_from_primes(orc, logn, q, t, all_galois=False, extra_steps=(), base_steps=(-1, 0, 128)):
+    """conftest.Setup for an explicit list of coefficient primes (the last one is the special prime) instead of SEAL's
+    CoeffModulus::Create(bit sizes): same seeds, same keys, same PASTA key.  base_steps: the rotation steps that always get
+    a key (the PASTA matmul needs -1, 128 and the column swap)."""
+    from conftest import Setup
+    S = Setup.__new__(Setup)
+    S.t, S.logn, S.n = int(t), logn, 1 << logn
+    S.q = [int(v) for v in q]
+    S.O = O = orc.Oracle(logn, S.q, S.t)
+    S.sk = O.keygen_secret(1)
+    S.pk = O.keygen_public(S.sk, 2)
+    S.rk = O.keygen_relin(S.sk, 3)
+    steps = [s for s in base_steps if not (s == 128 and S.n // 2 == 128)] + list(extra_steps)
+    elts = [int(e) for e in O.galois_elts_all()] if all_galois else []
+    elts = list(dict.fromkeys(elts + [int(O.galois_elt(s)) for s in steps]))
+    S.gk = O.keygen_galois(S.sk, elts, 7)
+    S.key = np.array([(i * 2654435761 + 12345) % S.t for i in range(256)], dtype=np.uint64)
+    S.enc_key = O.encrypt(S.pk, O.pasta_pack_key(S.key), 11)
+    return S
+
+
+def pm_ok(q):
+    """The predicate of the product's fill_mod (csrc/hhe_context.cpp), restated: q = 2^b - c with 33 <= b <= 60, c < 2^32 and
+    2^b + 2^(64-b) c <= 2q.  Python integers, so nothing here can overflow."""
+    q = int(q)
+    b = q.bit_length()
+    c = (1 << b) - q
+    return int(33 <= b <= 60 and c < (1 << 32) and c * ((1 << (64 - b)) + 2) <= (1 << b))
+
+
+def assert_dispatch(X, q, row_kernel, digit_reduce=None):
+    """The context reports, prime by prime, the form this file computes for it, and takes the path the test means to run."""
+    logn = X.logn
+    for i, qi in enumerate(q):
+        assert X.query("pm_ok", i) == pm_ok(qi), (i, qi)
+    n2 = logn - logn // 2
+    supported = logn >= 12 and 6 <= n2 <= 8
+    assert X.query("row_kernel") == int(supported and all(pm_ok(v) for v in q))
+    assert X.query("row_kernel") == row_kernel, [pm_ok(v) for v in q]
+    qmax, qmin = max(q[:-1]), min(q)
+    assert X.query("digit_reduce") == int(qmax // 4 >= qmin)
+    if digit_reduce is not None:
+        assert X.query("digit_reduce") == digit_reduce
+
+
 def check_context_constants(X, O):
     for i in range(O.K):
         assert X.query("root", i) == O.query("root", i)
@@ -52,6 +97,8 @@ def check_ntt(X, O, mem, seed=0):
     nm = 2 * O.K  # coeff primes + Bsk primes
     polys = np.stack([rng.integers(0, 1 << 40, O.n, dtype=np.uint64) for _ in range(nm + 1)])
     polys[nm] %= O.t
+    for i in range(nm):   # residues: a no-op for primes above 2^40, needed for the 33..40-bit primes of the dispatch cases
+        polys[i] %= np.uint64(O.q[i] if i < O.K else O.query("bsk", i - O.K))
     ref = np.stack([O.ntt_fwd(i, polys[i]) for i in range(nm)] + [O.ntt_fwd(-1, polys[nm])])
     d = mem.to_dev(polys)
     X.ntt(d, nm + 1, 0, nm + 1, False)
@@ -366,6 +413,134 @@ def check_key_sets(X, S, orc, mem, threads=True):
     assert (res["A"][0] == O.rotate_rows(cts[0], -128, gkA)[0]).all() and (res["B"][0] == O.rotate_rows(cts[0], -128, gkB)[0]).all()
     for ks in (A, Bs, R2):
         ks.close()
+
+
+def check_hot_path(X, S, orc, mem, make_ctx=None, monkeypatch=None, n_in=9, B=2, seed=0, ntt=True):
+    """Everything the hot path is made of, on ONE parameter set, word for word against the oracle: context constants, the
+    transforms (random and extreme residues), every evaluator op (rotations by every key of S, BEHZ multiply, relinearize),
+    a ragged two-block transciphering (blocks 0 and 2 of a 300-word record: 128 and 44 words), BaseCSP::decompose of that
+    record (3 transcipherings + mask + flatten; S must hold the keys of steps -128 and -256) and, with make_ctx, the FC's
+    execution variants.  S: keys already loaded into X.  Noise budgets may be exhausted at the moduli this is used with:
+    words are compared, never decryptions."""
+    O = S.O
+    check_context_constants(X, O)
+    if ntt:
+        check_ntt(X, O, mem, seed=seed)
+    check_ops(X, S, mem, B=B, seed=seed)
+    pt = np.array([(7 * i + 3 + seed) % 256 for i in range(300)], dtype=np.uint64)
+    cw, ncw = S.sym_blocks(orc, pt)
+    assert list(ncw) == [128, 128, 44]
+    blocks = [O.transcipher_block(S.enc_key, S.rk, S.gk, cw[b, :ncw[b]], b) for b in range(3)]
+    out = mem.empty((2,) + O.ct_shape)
+    X.transcipher(mem.to_dev(S.enc_key), cw[[0, 2]], ncw[[0, 2]], [0, 2], out)
+    res = mem.to_host(out)
+    assert (res[0] == blocks[0]).all(), "block 0 differs from the oracle"
+    assert (res[1] == blocks[2]).all(), "ragged block 2 differs from the oracle"
+    rec = orc.pasta_encrypt(S.t, S.key, pt)
+    flat = mem.empty((1,) + O.ct_shape)
+    X.decompose(mem.to_dev(S.enc_key), rec[None], flat, mask_last=True)
+    masked = list(blocks)
+    masked[2] = O.mask(blocks[2], np.ones(44, np.uint64))
+    assert (mem.to_host(flat)[0] == O.flatten(np.stack(masked), S.gk)).all(), "decompose differs from the oracle"
+    if make_ctx is not None:
+        check_fc_variants(make_ctx, S, orc, mem, monkeypatch, n_in=n_in)
+
+
+def adversarial_words(S, size, pattern):
+    """a size-`size` 'ciphertext' with every word at q_j - 1 ('alt': alternating with 0)"""
+    a = np.zeros((size, S.O.L, S.O.n), np.uint64)
+    for j in range(S.O.L):
+        if pattern == "alt":
+            a[:, j, ::2] = S.q[j] - 1
+        else:
+            a[:, j, :] = S.q[j] - 1
+    return a
+
+
+def adversarial_keys(S, orc, pattern):
+    """(relin key, Galois keys) of S, or -- 'max_keys' -- keys whose every word is q_j - 1"""
+    if pattern != "max_keys":
+        return S.rk, S.gk
+    rk = np.zeros_like(S.rk)
+    for j in range(S.O.K):
+        rk[:, :, j, :] = S.q[j] - 1
+    return rk, orc.GaloisKeys(S.gk.elts, np.stack([rk] * len(S.gk.elts)))
+
+
+def check_keyswitch_adversarial(X, S, orc, mem, pattern, n_in=11):
+    """The generic key switch (rotations: both sums inverse-transformed, mod-down in the store of the last pass), BEHZ multiply,
+    relinearize and -- pattern 'max' -- one FC row (shared digits, leaf sums) on worst-case residues: a size-2 and a size-3
+    'ciphertext' with every word at q_j - 1 (or alternating with 0) and, for 'max_keys', every key word at q_j - 1.  Nothing here
+    is a valid encryption; the oracle's exact 128-bit arithmetic defines the expected words, as in check_matmul_adversarial.
+    S needs the keys of steps -1, 0 and, for the FC, every default Galois element."""
+    O = S.O
+    ct2, ct3 = adversarial_words(S, 2, pattern), adversarial_words(S, 3, pattern)
+    rk, gk = adversarial_keys(S, orc, pattern)
+    ks = X.keyset()
+    ks.set_relin(rk)
+    for e, k in zip(gk.elts, gk.keys):
+        ks.set_galois(int(e), k)
+    d2, out = mem.to_dev(ct2[None]), mem.empty((1,) + O.ct_shape)
+    X.rotate_rows(d2, -1, out, 1, gk=ks)
+    ref, nks = O.rotate_rows(ct2, -1, gk)
+    assert nks == 1 and (mem.to_host(out)[0] == ref).all(), (pattern, "rotate_rows")
+    X.rotate_columns(d2, out, 1, gk=ks)
+    assert (mem.to_host(out)[0] == O.rotate_columns(ct2, gk)).all(), (pattern, "rotate_columns")
+    o3 = mem.empty((1, 3, O.L, O.n))
+    X.multiply(d2, d2, o3, 1)
+    assert (mem.to_host(o3)[0] == O.multiply(ct2, ct2)).all(), (pattern, "multiply")
+    X.relinearize(mem.to_dev(ct3[None]), out, 1, rk=ks)
+    assert (mem.to_host(out)[0] == O.relinearize(ct3, rk)).all(), (pattern, "relinearize")
+    if pattern == "max":
+        X.fc_row(d2, d2, 1, n_in, out, 1, rk=ks, gk=ks)
+        assert (mem.to_host(out)[0] == O.fc_row(ct2, ct2, rk, gk, n_in)[0]).all(), (pattern, "fc_row")
+    ks.close()
+
+
+T16 = 65537
+T33 = 8088322049   # the reference's plain modulus at N = 65536 (65537 cannot batch there)
+NEAR_3_2_58 = [864691128455086081, 864691128454914049, 864691128454594561, 864691128454438913]  # 60-bit primes = 1 mod 8192, none pm_ok
+
+
+def dispatch_case(orc, api, lib, name):
+    """Parameter sets chosen for the kernels they select (dispatch matrix):
+    (logn, coefficient primes, t, expected row_kernel, expected digit_reduce).  A-G lack the pseudo-Mersenne form on at least one
+    prime and take the separate-kernel path at full tiles; H and I have the LARGEST c = 2^b - q (with q = 1 mod 2N) that pm_fold's
+    guarantee still admits, where its bound is tightest."""
+    cm = orc.coeff_modulus_create
+    if name == "A":   # BFVDefault(4096): what SEALZpCipher::create_context(4096) picks, 36 + 36 + 37 bits
+        return 12, api.bfv_default_coeff_modulus(4096, lib), T16, 0, 0
+    if name == "B":   # 40-bit primes at N = 8192, L = 5: all non-pm
+        return 13, cm(8192, [40] * 6), T16, 0, 0
+    if name == "C":   # 256-point rows without the row kernel
+        return 15, cm(32768, [36] * 4), T16, 0, 0
+    if name == "D":
+        return 16, cm(65536, [40] * 3), T33, 0, 0
+    if name == "E":   # caller-supplied 60-bit primes that do not hug a power of two
+        return 12, NEAR_3_2_58, T16, 0, 0
+    if name == "F":   # pm data primes, non-pm special prime.  Digits come from the DATA primes only (50 bits, below 4 q_J for
+        return 12, cm(4096, [50, 50]) + NEAR_3_2_58[:1], T16, 0, 0   # every J): no digit reduction is needed or done
+    if name == "F2":  # the same mix with the 60-bit non-pm prime among the data primes: its digits are reduced for the 50-bit primes
+        return 12, [cm(4096, [50])[0], NEAR_3_2_58[0], NEAR_3_2_58[1]], T16, 0, 1
+    if name == "G":   # one non-pm data prime, and q_I >= 4 q_J
+        return 12, cm(4096, [36, 50, 50, 50]), T16, 0, 1
+    if name == "H":
+        return 12, [(1 << 42) - c for c in (802815, 974847, 999423)] + [(1 << 43) - 4186111], T16, 1, 0
+    if name == "I":
+        return 15, [(1 << 44) - c for c in (13041663, 13631487, 14352383)] + [(1 << 45) - 65798143], T16, 1, 0
+    raise KeyError(name)
+
+
+def dispatch_setup(orc, api, lib, name, all_galois=True, extra_steps=(-128, -256)):
+    """(Setup, context factory) of a dispatch case; every context the factory returns has asserted its path"""
+    logn, q, t, row_kernel, digit_reduce = dispatch_case(orc, api, lib, name)
+    S = setup_from_primes(orc, logn, q, t, all_galois=all_galois, extra_steps=extra_steps)
+
+    def make_ctx():
+        X = api.Context(logn, q, t, lib=lib)
+        assert_dispatch(X, q, row_kernel, digit_reduce)
+        return X
+    return S, make_ctx
 
 
 def check_matmul_adversarial(X, S, orc, mem, pattern):

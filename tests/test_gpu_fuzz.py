@@ -46,17 +46,28 @@ def test_random_parameter_sets(orc, api, mem, seed):
     assert (mem.to_host(o)[0] == S.O.fc_row(vi, wc, S.rk, S.gk, n_in)[0]).all(), (seed, n_in)
 
 
-@pytest.mark.parametrize("seed,logn", [(505, 12), (606, 13)])
-def test_random_parameter_sets_full_tiles(orc, api, mem, seed, logn):
+@pytest.mark.parametrize("seed,logn,lo,hi,row_kernel", [
+    pytest.param(505, 12, 44, 61, 1, id="505-12"), pytest.param(606, 13, 44, 61, 1, id="606-13"),
+    pytest.param(707, 12, 33, 42, 0, id="707-12-small-primes"),      # 33..41 bits: none of the primes this seed draws has the pseudo-Mersenne form (asserted)
+    pytest.param(808, 13, None, None, 0, id="808-13-mixed-primes"),  # <= 41 and >= 44 bits mixed: one non-pm prime is enough
+])
+def test_random_parameter_sets_full_tiles(orc, api, mem, seed, logn, lo, hi, row_kernel):
     """the same sweep at N >= 4096, where the matmul loop and every generic key switch run through ks_row_kernel
-    (L up to 6: the lazy sums are folded after the fourth digit)"""
+    (L up to 6: the lazy sums are folded after the third digit) -- and, for the two seeds with primes below 42 bits, through the
+    separate-kernel fallback at full tiles"""
     lib = api.load_library()
     rng = np.random.default_rng(seed)
     K = int(rng.integers(5, 8))
-    bits = [int(b) for b in rng.integers(44, 61, K)]
+    if lo is None:   # at least one prime of <= 41 bits among primes of >= 44 bits
+        bits = [int(b) for b in rng.integers(44, 61, K)]
+        for i in rng.choice(K - 1, size=int(rng.integers(1, K - 1)), replace=False):
+            bits[int(i)] = int(rng.integers(33, 42))
+    else:
+        bits = [int(b) for b in rng.integers(lo, hi, K)]
     bits[-1] = max(bits)
     S = Setup(orc, logn, bits, all_galois=True)
     X = api.Context(S.logn, S.q, S.t, lib=lib)
+    pc.assert_dispatch(X, S.q, row_kernel)
     S.load_keys(X)
     pc.check_ops(X, S, mem, B=3, seed=seed)
     nwords = int(rng.integers(129, 257))

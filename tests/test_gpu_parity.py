@@ -211,6 +211,7 @@ def test_config5_n65536_six_primes_rotation_chain_and_multiply(orc, api, lib, me
     S = Setup(orc, 16, [60] * 6, t=t)
     O = S.O
     X = api.Context(S.logn, S.q, t, lib=lib)
+    assert X.query("row_kernel") == 1
     S.load_keys(X)
     rng = np.random.default_rng(5)
     B = 2
@@ -254,6 +255,7 @@ def test_config5_rotation_chain_128_steps(orc, api, lib, mem):
     S = Setup(orc, 16, [60] * 6, t=t)
     O = S.O
     X = api.Context(S.logn, S.q, t, lib=lib)
+    assert X.query("row_kernel") == 1
     S.load_keys(X)
     rng = np.random.default_rng(5)
     cts = np.stack([O.encrypt(S.pk, O.encode(rng.integers(0, 1 << 30, O.n)), 40 + b) for b in range(2)])
@@ -399,9 +401,14 @@ def test_fc_row_variants_bench_shape_n32768(orc, api, lib, mem, monkeypatch):
     LDS twiddle heap, leaf groups across trie nodes, the slot pool -- every word against the oracle; then the same without the fused
     row kernel of the non-leaf children (HHE_FC_ROWFUSED=0)"""
     S = Setup(orc, 15, [60] * 4, all_galois=True)
-    pc.check_fc_variants(lambda: api.Context(S.logn, S.q, S.t, lib=lib), S, orc, mem, monkeypatch, n_in=14)
+
+    def make_ctx():
+        X = api.Context(S.logn, S.q, S.t, lib=lib)
+        assert X.query("row_kernel") == 1
+        return X
+    pc.check_fc_variants(make_ctx, S, orc, mem, monkeypatch, n_in=14)
     monkeypatch.setenv("HHE_FC_ROWFUSED", "0")
-    pc.check_fc_variants(lambda: api.Context(S.logn, S.q, S.t, lib=lib), S, orc, mem, monkeypatch, n_in=14)
+    pc.check_fc_variants(make_ctx, S, orc, mem, monkeypatch, n_in=14)
 
 
 def test_config4_two_layer_chain(orc, api, lib, mem):
@@ -530,6 +537,7 @@ def test_key_sets_have_identity(orc, api, lib, mem):
     for logn, bits in ((12, [55] * 4), (11, [50] * 4)):
         S = Setup(orc, logn, bits)
         X = api.Context(S.logn, S.q, S.t, lib=lib)   # default set empty
+        assert X.query("row_kernel") == (1 if logn == 12 else 0)
         pc.check_key_sets(X, S, orc, mem)
         X.close()
 
@@ -540,5 +548,6 @@ def test_matmul_loop_adversarial_residues(orc, api, lib, mem, pattern):
     for logn in (12, 15):
         S = Setup(orc, logn, [60] * (3 if logn == 12 else 4))
         X = api.Context(S.logn, S.q, S.t, lib=lib)
+        assert X.query("row_kernel") == 1
         pc.check_matmul_adversarial(X, S, orc, mem, pattern)
         X.close()

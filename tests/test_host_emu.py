@@ -330,16 +330,22 @@ def test_config4_two_layer_chain(orc, api, emu_lib, mem):
     pc.check_two_layer_chain(X, S, mem)
 
 
-@pytest.mark.parametrize("logn,bits", [(12, [50, 50, 50]), (13, [40] * 6)])
-def test_fused_row_kernel_full_tiles(orc, api, emu_lib, mem, logn, bits):
-    """N >= 4096: the matmul loop runs ks_row_kernel (row pass of the digit transforms + key inner product with Shoup key
-    products + inverse row pass in one kernel; the c0 branch rides in its grid).  Same words as the oracle; L = 5 also
-    exercises the fold of the lazy sums after the fourth digit."""
+@pytest.mark.parametrize("logn,bits,row_kernel", [
+    pytest.param(12, [50, 50, 50], 1, id="12-bits0"),
+    pytest.param(13, [40] * 6, 0, id="13-bits1"),            # the fallback at full tiles: no 40-bit prime = 1 mod 16384 from the top is pm_ok
+    pytest.param(13, [44] * 6, 1, id="13-row-kernel-l5"),
+])
+def test_fused_row_kernel_full_tiles(orc, api, emu_lib, mem, logn, bits, row_kernel):
+    """N >= 4096 with pseudo-Mersenne primes: the matmul loop runs ks_row_kernel (row pass of the digit transforms + key inner
+    product with Shoup key products + inverse row pass in one kernel; the c0 branch rides in its grid).  Same words as the
+    oracle; 6 x 44 bits (L = 5) also exercises the fold of the lazy sums after the third digit.  6 x 40 bits at N = 8192 is NOT
+    that path (all six primes lack the form): it is the separate-kernel fallback at full tiles, L = 5, and is kept as such."""
     S = Setup(orc, logn, bits)
     pt = [(13 * i + 7) % 256 for i in range(100)]
     cw, ncw = S.sym_blocks(orc, pt)
     ref = S.O.transcipher_block(S.enc_key, S.rk, S.gk, cw[0, :ncw[0]], 3)
     X = api.Context(S.logn, S.q, S.t, lib=emu_lib)
+    pc.assert_dispatch(X, S.q, row_kernel)
     S.load_keys(X)
     out = mem.empty((2,) + S.O.ct_shape)
     X.transcipher(mem.to_dev(S.enc_key), np.concatenate([cw, cw]), [ncw[0], ncw[0]], [3, 3], out)
@@ -362,6 +368,7 @@ def test_row_kernel_lds_twiddle_heap_n32768(orc, api, emu_lib, mem):
     grid) and the generic key switches (rotation, relinearize: S_0 inverse-transformed too), same words as the oracle."""
     S = Setup(orc, 15, [50, 50, 50])
     X = api.Context(S.logn, S.q, S.t, lib=emu_lib)
+    assert X.query("row_kernel") == 1
     S.load_keys(X)
     O = S.O
     rng = np.random.default_rng(15)
@@ -417,6 +424,7 @@ def test_generic_key_switch_through_the_row_kernel(orc, api, emu_lib, mem):
     inverse row pass of S_0 as well and the mod-down fused into the store of the last inverse pass (STORE_KSF)"""
     S = Setup(orc, 12, [50, 50, 50, 50])
     X = api.Context(S.logn, S.q, S.t, lib=emu_lib)
+    assert X.query("row_kernel") == 1
     S.load_keys(X)
     pc.check_ops(X, S, mem, B=2, seed=21)
 
@@ -425,10 +433,15 @@ def test_fc_row_variants_full_tiles(orc, api, emu_lib, mem, monkeypatch):
     """the FC's execution variants at N = 4096 (full tiles): the epilogues that carry the mod-down (STORE_KSF with the
     Galois-gathered base) and the leaf sums (STORE_RACC with q_sp * galois(c0)) on the tile geometry the GPU runs"""
     S = Setup(orc, 12, [50] * 3, all_galois=True)
-    pc.check_fc_variants(lambda: api.Context(S.logn, S.q, S.t, lib=emu_lib), S, orc, mem, monkeypatch, n_in=21)
+
+    def make_ctx():
+        X = api.Context(S.logn, S.q, S.t, lib=emu_lib)
+        assert X.query("row_kernel") == 1
+        return X
+    pc.check_fc_variants(make_ctx, S, orc, mem, monkeypatch, n_in=21)
     # non-leaf children without ks_perm_row_kernel (inner product and inverse row passes as separate launches)
     monkeypatch.setenv("HHE_FC_ROWFUSED", "0")
-    pc.check_fc_variants(lambda: api.Context(S.logn, S.q, S.t, lib=emu_lib), S, orc, mem, monkeypatch, n_in=21)
+    pc.check_fc_variants(make_ctx, S, orc, mem, monkeypatch, n_in=21)
 
 
 @pytest.mark.parametrize("pattern", ["max", "alt", "max_keys"])
@@ -438,7 +451,45 @@ def test_matmul_loop_adversarial_residues(orc, api, emu_lib, mem, pattern):
     lazy difference that goes negative aborts instead of hiding behind a congruent result"""
     S = Setup(orc, 12, [60, 60, 60])
     X = api.Context(S.logn, S.q, S.t, lib=emu_lib)
+    assert X.query("row_kernel") == 1
     pc.check_matmul_adversarial(X, S, orc, mem, pattern)
+
+
+@pytest.mark.parametrize("name", ["A", "E", "F", "F2", "G"])
+def test_fallback_path_at_full_tiles(orc, api, emu_lib, mem, monkeypatch, name):
+    """N = 4096 WITHOUT the fused row kernel (a coefficient prime lacks the pseudo-Mersenne form; A = BFVDefault(4096), the
+    reference's own N = 4096 parameters): step_separate, k_ntt / ks_mac / ks_finish, galois_kernel and the ks_mac branch of the FC on
+    the full-tile geometry, under the range check.  The same check the GPU suite runs (test_gpu_dispatch.py)."""
+    S, make_ctx = pc.dispatch_setup(orc, api, emu_lib, name)
+    X = make_ctx()
+    S.load_keys(X)
+    pc.check_hot_path(X, S, orc, mem, make_ctx, monkeypatch, n_in=9, seed=ord(name[0]))
+
+
+def test_row_kernel_at_the_largest_admitted_c(orc, api, emu_lib, mem, monkeypatch):
+    """case H: 42/43-bit primes with the largest c = 2^b - q that is still pm_ok, where pm_fold's bound (any 64-bit value -> below
+    2q) is tightest: the hot path and worst-case residues on the row kernels, a fold that leaves 2q or more aborts here"""
+    S, make_ctx = pc.dispatch_setup(orc, api, emu_lib, "H")
+    X = make_ctx()
+    S.load_keys(X)
+    pc.check_hot_path(X, S, orc, mem, make_ctx, monkeypatch, n_in=9, seed=ord("H"))
+    for pattern in ("max", "alt", "max_keys"):
+        pc.check_matmul_adversarial(X, S, orc, mem, pattern)
+        pc.check_keyswitch_adversarial(X, S, orc, mem, pattern)
+
+
+@pytest.mark.parametrize("pattern", ["max", "alt", "max_keys"])
+@pytest.mark.parametrize("K", [5, 8])
+def test_row_kernel_folds_at_60_bits(orc, api, emu_lib, mem, K, pattern):
+    """the folds of the row kernels' lazy sums (after every third digit) with every word at q_j - 1 and 60-bit primes, 14q just
+    under 2^64: L = 4 (one fold, then one digit) and L = 7 (two folds, last digit folded by the flush) -- matmul loop, rotations,
+    multiply, relinearize, one FC row; a sum that wraps aborts under the range check.  (Up to L = 7 a fold after every FOURTH
+    digit would be just as safe -- 4 x 4q < 16q < 2^64, then 2q + 3 x 4q = 14q -- so this pins words and ranges, not the period.)"""
+    S = Setup(orc, 12, [60] * K, all_galois=True)
+    X = api.Context(S.logn, S.q, S.t, lib=emu_lib)
+    pc.assert_dispatch(X, S.q, 1, 0)
+    pc.check_matmul_adversarial(X, S, orc, mem, pattern)
+    pc.check_keyswitch_adversarial(X, S, orc, mem, pattern)
 
 
 def test_block_table_cache_is_bounded_lru(orc, api, emu_lib, mem, small):
