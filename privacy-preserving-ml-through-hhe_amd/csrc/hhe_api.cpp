@@ -472,7 +472,36 @@ struct ProfScope {
 //  - the 128 plain products are accumulated in the NTT domain, in the frame rotated by the Galois map
 //    (pdiag tables), so the NTT of galois(c1) computed for the key switch is reused for the product;
 //  - mod-down of c0 is finished in the NTT domain: NTT_j(r_0 mod q_j - half) replaces INTT+NTT.
-int matmul_diagonal_fused(hhe_ctx *c, int layer, const u64 *const *d_pdiag_ptrs, size_t B)
+// Shared first layer (`cap`, B = 1, state = the key ciphertext every item starts from): the chain's own plain products are not
+// needed (they go to a scratch accumulator).  Instead the chain leaves state i where it is: c0 (NTT form) in slot i % S of cap->c0
+// and the Galois-mapped c1 (the digit source d) in slot i % S of cap->d -- the step writes its successor's straight into the next
+// slots, so the chain has no launch more than a plain one.  Once S states are there, l0_flush turns them into the two operands
+// the plain products of those steps consume, in the frame in which pdiag multiplies them -- R0_i = c0 read through the NTT-domain
+// map of g (one gather launch for all slots), R1_i = NTT_j(d_j) (one transform launch pair, in place) -- and adds the items'
+// diagonal sums of the S steps into `out`.
+struct L0Capture {
+    u64 *c0, *r0, *d;  // [S][L][N] each: c0 of the states | R0 | d of the states, then R1
+    int S;             // >= 2: a step reads slot i and writes slot i + 1
+    u64 *out;          // [B][2][L][N]: accp0 | accp1 of item b (NTT form, rotated frame)
+    size_t B;
+};
+void l0_flush(hhe_ctx *c, const L0Capture &cap, int first, int steps)
+{
+    const size_t ln = (size_t)c->L * c->n;
+    PermArgs p;
+    memset(&p, 0, sizeof(p));
+    p.in = cap.c0; p.out = cap.r0; p.mods = c->d_mods; p.logn = c->logn; p.count = steps * c->L; p.L = c->L;
+    p.out_item_stride = ln; p.elt = galois_elt_from_step(c, -1);
+    k_perm(p, c->w->stream);
+    op_ntt(c, cap.d, (size_t)steps * c->L, 0, c->L, false);
+    memset(&p, 0, sizeof(p));
+    p.steps = steps; p.carry = first > 0; p.in = cap.r0; p.in2 = cap.d; p.in_step_stride = ln;
+    p.out = cap.out; p.out2 = cap.out + ln; p.out_item_stride = 2 * ln;
+    p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(cap.B * c->L); p.L = c->L;
+    p.mul_ptrs = c->l0_ptrs; p.mul_shift = (size_t)first * ln; p.mul_step_stride = ln;
+    k_perm(p, c->w->stream);
+}
+int matmul_diagonal_fused(hhe_ctx *c, int layer, const u64 *const *d_pdiag_ptrs, size_t B, const L0Capture *cap = nullptr)
 {
     const int L = c->L, K = c->K;
     const size_t n = c->n, ln = (size_t)L * n, bln = B * ln;
@@ -491,20 +520,25 @@ int matmul_diagonal_fused(hhe_ctx *c, int layer, const u64 *const *d_pdiag_ptrs,
     u64 *c0n[2] = {c->w->ws_ct[2], c->w->ws_ct[2] + bln};
     u64 *scr = c->w->ws_ct[3], *r = c->w->ws_ct[3] + bln, *scr2 = c->w->ws_ct3;
     rt_memset(c->w->ws_ct[1], 0, 2 * bln * 8, c->w->stream);
+    // state i of the chain: its c0 in NTT form and its digit source
+    auto c0_of = [&](int i) { return cap ? cap->c0 + (size_t)(i % cap->S) * ln : c0n[i & 1]; };
+    auto d_of = [&](int i) { return cap ? cap->d + (size_t)(i % cap->S) * ln : c->w->ws_d; };
+    u64 *d_src = d_of(0), *d_dst = d_of(1);  // the current step's
     {   // c0 -> NTT form ; d = galois(c1)
-        NttArgs a = ntt_args(c, state, c0n[0], B * L, 0, L);
+        NttArgs a = ntt_args(c, state, c0_of(0), B * L, 0, L);
         a.src_item_polys = L; a.src_item_stride = 2 * ln;
         k_ntt(a, false, c->w->stream);
         GaloisArgs ga;
         memset(&ga, 0, sizeof(ga));
         ga.mods = c->d_mods; ga.logn = c->logn; ga.count = (int)(B * L); ga.L = L; ga.einv = ginv;
-        ga.in = state + ln; ga.in_item_stride = 2 * ln; ga.out = c->w->ws_d; ga.out_item_stride = ln;
+        ga.in = state + ln; ga.in_item_stride = 2 * ln; ga.out = d_src; ga.out_item_stride = ln;
         k_galois(ga, c->w->stream);
     }
-    int cur = 0;
     // The c0 branch of step i only feeds the c0 branch of step i+1, and like the digit transforms of step i+1 it depends on
     // nothing later than the inverse transforms of step i: it is held back (k5) and launched in the grids of step i+1.
-    const bool rowk = use_row_kernel(c);
+    // the shared chain takes the separate-kernel step for every N: one ciphertext is latency-bound either way, and the row kernel's
+    // profile counters (hhe_ctx_profile) keep counting batch launches only
+    const bool rowk = use_row_kernel(c) && !cap;
     const size_t pdiag_words = (size_t)(PASTA_R + 1) * PASTA_T * ln;  // the Shoup quotients of pdiag follow the table (ensure_block)
     const u64 *key_s = nullptr;
     if (rowk) {
@@ -515,7 +549,7 @@ int matmul_diagonal_fused(hhe_ctx *c, int layer, const u64 *const *d_pdiag_ptrs,
     bool k5_pending = false;
     // digit transforms of the current d: T[I][J] = NTT_J(d[I] mod q_J)
     auto digit_args = [&]() {
-        NttArgs a = ntt_args(c, c->w->ws_d, c->w->ws_T, B * L * K, 0, K);
+        NttArgs a = ntt_args(c, d_src, c->w->ws_T, B * L * K, 0, K);
         a.src_div = K; a.src_item_polys = L * K; a.src_item_stride = ln; a.load_op = LOAD_DIGIT; a.digit_reduce = c->digit_reduce;
         a.store_op = STORE_LAZY;
         return a;
@@ -544,7 +578,7 @@ int matmul_diagonal_fused(hhe_ctx *c, int layer, const u64 *const *d_pdiag_ptrs,
         as.store_op = STORE_RSP;
         k_ntt_pass(as, true, true, c->w->stream);
         NttArgs a1 = ntt_args(c, scr, scr, B * L, 0, L);
-        a1.store_op = STORE_KS1; a1.aux_r = r; a1.aux_out = c->w->ws_d; a1.gal_elt = g;
+        a1.store_op = STORE_KS1; a1.aux_r = r; a1.aux_out = d_dst; a1.gal_elt = g;
         k_ntt_pass(a1, true, true, c->w->stream);
     };
     // every context without the row kernel (use_row_kernel: N < 4096 with its ragged tiles, or ANY N when a coefficient prime lacks
@@ -554,7 +588,7 @@ int matmul_diagonal_fused(hhe_ctx *c, int layer, const u64 *const *d_pdiag_ptrs,
         KsMacArgs m;
         memset(&m, 0, sizeof(m));
         m.T = c->w->ws_T; m.key = key; m.S = c->w->ws_S; m.mods = c->d_mods; m.logn = c->logn; m.B = (int)B; m.L = L; m.K = K;
-        m.acc = accp1; m.mul_ptrs = d_pdiag_ptrs; m.mul_shift = shift;  // the I = J digit also feeds the plain product
+        if (!cap) { m.acc = accp1; m.mul_ptrs = d_pdiag_ptrs; m.mul_shift = shift; }  // the I = J digit also feeds the plain product
         if (k5_pending) { k_ntt2_fwd(k5, a, c->w->stream); k5_pending = false; }
         else k_ntt(a, false, c->w->stream);
         k_ks_mac(m, c->w->stream);
@@ -562,33 +596,46 @@ int matmul_diagonal_fused(hhe_ctx *c, int layer, const u64 *const *d_pdiag_ptrs,
         as.src_item_polys = 1; as.src_item_stride = (size_t)K * n; as.store_op = STORE_RSP;
         NttArgs a1 = ntt_args(c, c->w->ws_S + (size_t)K * n, scr, B * L, 0, L);
         a1.src_item_polys = L; a1.src_item_stride = (size_t)2 * K * n; a1.store_op = STORE_KS1;
-        a1.aux_r = r; a1.aux_out = c->w->ws_d; a1.gal_elt = g;
+        a1.aux_r = r; a1.aux_out = d_dst; a1.gal_elt = g;
         k_ntt2_inv(as, a1, c->w->stream);
     };
     for (int i = 0; i < PASTA_T - 1; ++i) {
         const size_t shift = ((size_t)layer * PASTA_T + i) * ln;
+        d_src = d_of(i); d_dst = d_of(i + 1);
+        if (cap && (i + 1) % cap->S == 0) {
+            // the table is full (state i sits in its last slot) and this step writes state i + 1 into slot 0: finish state i's c0,
+            // keep its d for this step (the flush transforms the slots in place), hand the S states to the items
+            if (k5_pending) { k_ntt(k5, false, c->w->stream); k5_pending = false; }
+            rt_d2d(c->w->ws_d, d_src, ln * 8, c->w->stream);
+            d_src = c->w->ws_d;
+            l0_flush(c, *cap, i + 1 - cap->S, cap->S);
+        }
         if (rowk) step_row_kernel(i, shift);
         else step_separate(shift);
         {   // c0 of the next state in NTT form + permuted-frame product of the current c0
             NttArgs a = ntt_args(c, r, scr2, B * L, 0, L);
             a.src_item_polys = L; a.src_item_stride = 2 * n; a.src_div = L; a.load_op = LOAD_RNEG;
-            a.store_op = STORE_KS0; a.aux_in = c0n[cur]; a.aux_out = c0n[cur ^ 1]; a.acc = accp0;
+            a.store_op = STORE_KS0; a.aux_in = c0_of(i); a.aux_out = c0_of(i + 1); a.acc = accp0;
             a.aux_r = c->w->ws_S + (rowk ? (size_t)(i & 1) * K * n : 0);
             a.mul_ptrs = d_pdiag_ptrs; a.mul_shift = shift; a.gal_elt = g; a.mul_s_off = pdiag_words;
             k5 = a; k5_pending = true;  // launched in the grid of the next step's digit transforms
         }
-        cur ^= 1;
     }
     if (krc) return dev_fail("matmul: key-switch row kernel");
     if (k5_pending) k_ntt(k5, false, c->w->stream);
+    if (cap) {   // the last block of states; the items' tails (shared_l0_tail) follow on their own lanes
+        const int first = (PASTA_T - 1) / cap->S * cap->S;
+        l0_flush(c, *cap, first, PASTA_T - first);
+        return HHE_OK;
+    }
     const size_t shift = ((size_t)layer * PASTA_T + (PASTA_T - 1)) * ln;
     {   // last state: products only (a "virtual" rotation keeps the frame uniform)
-        NttArgs a = ntt_args(c, c->w->ws_d, scr, B * L, 0, L);
+        NttArgs a = ntt_args(c, d_of(PASTA_T - 1), scr, B * L, 0, L);
         a.store_op = STORE_MAC; a.mul_ptrs = d_pdiag_ptrs; a.mul_shift = shift; a.mul_cycle = L; a.mul_item_polys = L; a.acc = accp1;
         k_ntt(a, false, c->w->stream);
         PermArgs p;
         memset(&p, 0, sizeof(p));
-        p.in = c0n[cur]; p.out = accp0; p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(B * L); p.L = L;
+        p.in = c0_of(PASTA_T - 1); p.out = accp0; p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(B * L); p.L = L;
         p.out_item_stride = ln; p.elt = g; p.mac = 1; p.mul_ptrs = d_pdiag_ptrs; p.mul_shift = shift;
         k_perm(p, c->w->stream);
         // back to the unrotated frame, then to coefficient form
@@ -600,6 +647,54 @@ int matmul_diagonal_fused(hhe_ctx *c, int layer, const u64 *const *d_pdiag_ptrs,
     }
     op_ntt(c, state, B * 2 * L, 0, L, true);
     return HHE_OK;
+}
+
+// Shared first layer, once per transciphering call on lane 0 before the chunks fork: the rotation chain of layer 0 on the ONE key
+// ciphertext and, per block of S steps, the diagonal sums of all B items into `out` (which nothing else touches before a chunk's
+// last kernel).  The operand table is a workspace of the context: S = 128 states when 128 * 3 * L * N words fit the budget.
+int shared_l0_chain(hhe_ctx *c, const u64 *enc_key, const u64 *const *h_pdiag_ptrs, size_t B, u64 *out)
+{
+    Lane &main = c->lanes[0];
+    c->w = &main;
+    int rc = lane_reserve(c, main, 1);
+    if (rc) return rc;
+    const size_t ln = (size_t)c->L * c->n;
+    const size_t S = std::max<size_t>(2, std::min<size_t>(PASTA_T, c->l0_budget / (3 * ln * 8)));
+    if (c->l0_tab_steps != S || !c->l0_tab || c->l0_ptr_cap < B) sync_ctx(c);
+    if (c->l0_tab_steps != S || !c->l0_tab) {
+        rt_free(c->l0_tab);
+        c->l0_tab_steps = 0;
+        if (!(c->l0_tab = (u64 *)rt_malloc(S * 3 * ln * 8))) return dev_fail("shared first layer: operand table");
+        c->l0_tab_steps = S;
+    }
+    if (c->l0_ptr_cap < B) {
+        rt_free((void *)c->l0_ptrs);
+        c->l0_ptr_cap = 0;
+        if (!(c->l0_ptrs = (const u64 **)rt_malloc(B * sizeof(u64 *)))) return dev_fail("shared first layer: pointer table");
+        c->l0_ptr_cap = B;
+    }
+    rt_h2d(c->l0_ptrs, h_pdiag_ptrs, B * sizeof(u64 *), main.stream);  // the caller's array outlives the call's final sync
+    rt_d2d(main.ws_ct[0], enc_key, c->ct_words() * 8, main.stream);
+    L0Capture cap;
+    cap.c0 = c->l0_tab; cap.r0 = cap.c0 + S * ln; cap.d = cap.r0 + S * ln; cap.S = (int)S; cap.out = out; cap.B = B;
+    return matmul_diagonal_fused(c, 0, c->l0_ptrs, 1, &cap);
+}
+// ... and per chunk: the sums go back to the unrotated frame and to coefficient form, as at the end of matmul_diagonal_fused
+void shared_l0_tail(hhe_ctx *c, const u64 *sums, size_t B)
+{
+    const int L = c->L;
+    const size_t ln = (size_t)L * c->n;
+    u64 *state = c->w->ws_ct[0];
+    PermArgs p;
+    memset(&p, 0, sizeof(p));
+    p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(B * L); p.L = L;
+    p.in_item_stride = 2 * ln; p.out_item_stride = 2 * ln;
+    p.elt = (u32)nt_invmod(galois_elt_from_step(c, -1), 2 * c->n);
+    p.in = sums; p.out = state;
+    k_perm(p, c->w->stream);
+    p.in = sums + ln; p.out = state + ln;
+    k_perm(p, c->w->stream);
+    op_ntt(c, state, B * 2 * L, 0, L, true);
 }
 
 }  // namespace
@@ -732,8 +827,9 @@ extern "C" int hhe_relinearize_slot(hhe_ctx *c, int slot, const uint64_t *a3, ui
 }
 
 // one chunk of the batch on the current lane (c->w): the schedule of PASTA_SEAL::decomposition (pasta_3_seal.cpp:123-170)
+// shared_l0: `out` holds the items' first-layer sums (shared_l0_chain)
 static int transcipher_chunk(hhe_ctx *c, const u64 *enc_key, const u64 *const *d_diag, const u64 *const *d_rc,
-                             const u64 *cw_padded_host, u64 *out, size_t B, bool bsgs)
+                             const u64 *cw_padded_host, u64 *out, size_t B, bool bsgs, bool shared_l0)
 {
     const size_t n = c->n;
     const int L = c->L;
@@ -742,9 +838,10 @@ static int transcipher_chunk(hhe_ctx *c, const u64 *enc_key, const u64 *const *d
     rt_h2d(c->w->ws_vals, cw_padded_host, B * PASTA_T * 8, c->w->stream);
     u64 *state = c->w->ws_ct[0], *tmp = c->w->ws_ct[1], *t3 = c->w->ws_ct3;
     // state <- enc_ssk[0] for every item (pasta_3_seal.cpp:126)
-    op_elt(c, ELT_BCAST, nullptr, enc_key, state, B * 2 * L, 0, L, 2 * L);
+    if (!shared_l0) op_elt(c, ELT_BCAST, nullptr, enc_key, state, B * 2 * L, 0, L, 2 * L);
     for (int r = 0; r <= PASTA_R && !rc; ++r) {
-        if ((rc = bsgs ? matmul_bsgs(c, r, d_diag, B) : fused ? matmul_diagonal_fused(c, r, d_diag, B) : matmul_diagonal(c, r, d_diag, B))) break;
+        if (r == 0 && shared_l0) shared_l0_tail(c, out, B);
+        else if ((rc = bsgs ? matmul_bsgs(c, r, d_diag, B) : fused ? matmul_diagonal_fused(c, r, d_diag, B) : matmul_diagonal(c, r, d_diag, B))) break;
         // add_rc (:205-211)
         op_add_plain(c, state, nullptr, d_rc, (size_t)r * n, false, false, false, state, B);
         // mix (:417-423)
@@ -807,12 +904,14 @@ static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t 
         memcpy(&cwp[b * PASTA_T], cw + b * PASTA_T, ncw[b] * 8);
     }
     const int ns = c->nstreams;
+    // fused diagonal method: layer 0 acts on the same ciphertext for every item -- its chain runs once, here (HHE_SHARED_L0)
+    const bool shared = c->matmul_mode == 1 && !use_bsgs && c->shared_l0 > 0 && B >= (size_t)c->shared_l0;
     if (ns == 0) {
-        if (!(rc = lane_reserve(c, main, B))) {
+        if (!(rc = lane_reserve(c, main, B)) && !(shared && (rc = shared_l0_chain(c, enc_key, ptrs.data(), B, out)))) {
             std::vector<const u64 *> lp(2 * main.ptr_cap, nullptr);
             for (size_t b = 0; b < B; ++b) { lp[b] = ptrs[b]; lp[main.ptr_cap + b] = ptrs[B + b]; }
             rt_h2d(main.d_ptrs, lp.data(), lp.size() * sizeof(u64 *), main.stream);
-            rc = transcipher_chunk(c, enc_key, main.d_ptrs, main.d_ptrs + main.ptr_cap, cwp.data(), out, B, use_bsgs != 0);
+            rc = transcipher_chunk(c, enc_key, main.d_ptrs, main.d_ptrs + main.ptr_cap, cwp.data(), out, B, use_bsgs != 0, shared);
         }
     } else {
         // independent chunks round-robin over the internal streams: a chunk's working set stays cache resident and
@@ -822,6 +921,7 @@ static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t 
         if (nch > 1) nch = (nch + ns - 1) / ns * ns;
         const size_t per = (B + nch - 1) / nch;
         for (int s = 1; s <= ns && !rc; ++s) rc = lane_reserve(c, c->lanes[s], per);
+        if (!rc && shared) rc = shared_l0_chain(c, enc_key, ptrs.data(), B, out);
         if (!rc) {
             rt_event_record(c->ev_fork, main.stream);
             for (int s = 1; s <= ns; ++s) rt_stream_wait_event(c->lanes[s].stream, c->ev_fork);
@@ -835,7 +935,7 @@ static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t 
                 std::vector<const u64 *> &lp = keep.back();
                 for (size_t b = 0; b < bc; ++b) { lp[b] = ptrs[b0 + b]; lp[ln.ptr_cap + b] = ptrs[B + b0 + b]; }
                 rt_h2d(ln.d_ptrs, lp.data(), lp.size() * sizeof(u64 *), ln.stream);
-                rc = transcipher_chunk(c, enc_key, ln.d_ptrs, ln.d_ptrs + ln.ptr_cap, &cwp[b0 * PASTA_T], out + b0 * c->ct_words(), bc, use_bsgs != 0);
+                rc = transcipher_chunk(c, enc_key, ln.d_ptrs, ln.d_ptrs + ln.ptr_cap, &cwp[b0 * PASTA_T], out + b0 * c->ct_words(), bc, use_bsgs != 0, shared);
             }
             for (int s = 1; s <= ns; ++s) {
                 rt_event_record(c->lanes[s].ev_done, c->lanes[s].stream);

@@ -235,6 +235,15 @@ struct PermArgs {  // NTT-domain Galois permutation: out[p][x] (op)= in[p][pi_el
     int mac;                   // 1: out[p][x] += in[p][pi(x)] * mul_ptrs[b][shift + j*N + x]
     const u64 *const *mul_ptrs;
     size_t mul_shift;
+    size_t in_item_stride;     // words between items in `in` (0: in is [count][N])
+    // steps > 0 -- diagonal sum over shared operands (first affine layer of the fused matmul; diag_sum_body), no index map:
+    //   out [b][j][x] (+)= sum_{i < steps} in [i * in_step_stride + j*N + x] * mul_ptrs[b][mul_shift + i * mul_step_stride + j*N + x]
+    //   out2[b][j][x] (+)= sum_{i < steps} in2[i * in_step_stride + j*N + x] * (the same multiplier)
+    // in / in2 are shared by all items (canonical words); out / out2 use out_item_stride; carry = 1 adds to what out / out2 hold
+    int steps, carry;
+    const u64 *in2;
+    u64 *out2;
+    size_t in_step_stride, mul_step_stride;
 };
 
 struct LeafSumArgs {  // out[b][k][j] += qsp_inv_j * (accS[b][k][j] (INTT'd) + accH[b][k][j])

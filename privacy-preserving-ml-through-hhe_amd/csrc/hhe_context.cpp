@@ -330,6 +330,8 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
         c->ksc.hq2[j] = 2 * dq[j] + nt_mulmod(kf.half_mod[j], kf.qsp_inv[j], dq[j]);
     }
     if (const char *mm = getenv("HHE_MATMUL")) c->matmul_mode = atoi(mm);
+    if (const char *e = getenv("HHE_SHARED_L0")) c->shared_l0 = std::max(0, atoi(e));
+    if (const char *e = getenv("HHE_SHARED_L0_MB")) c->l0_budget = (size_t)(std::max(0.0, atof(e)) * (double)(1 << 20));
     if (const char *e = getenv("HHE_BLOCK_CACHE_MB")) c->block_cache_limit = (size_t)std::max(0, atoi(e)) << 20;
     if (const char *e = getenv("HHE_FC_ROWFUSED")) c->fc_row_fused = atoi(e);
     if (const char *e = getenv("HHE_FC_CSUM")) c->fc_csum = atoi(e);
@@ -443,6 +445,7 @@ extern "C" void hhe_ctx_destroy(hhe_ctx *c)
     rt_free(c->d_zero_corr);
     rt_free(c->d_qsp_poly);
     rt_free(c->d_blocks); rt_free(c->d_flags);
+    rt_free(c->l0_tab); rt_free((void *)c->l0_ptrs);
     rt_free(c->d_tables); rt_free(c->d_mods); rt_free(c->d_behz); rt_free(c->d_slot_map);
     delete c;
 }
@@ -532,6 +535,8 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "block_cache_bytes") return c->block_bytes;
     if (w == "block_cache_entries") return c->blocks.size();
     if (w == "row_kernel") return use_row_kernel(c) ? 1 : 0;
+    if (w == "shared_l0") return (u64)c->shared_l0;       // smallest batch that takes the shared first layer (0: none)
+    if (w == "shared_l0_steps") return c->l0_tab_steps;   // steps per block of the operand table of the last shared first layer (0: none ran)
     if (w == "pm_ok" && i >= 0 && i < c->K) return (u64)c->pm_ok[i];
     if (w == "digit_reduce") return (u64)c->digit_reduce;
     return 0;

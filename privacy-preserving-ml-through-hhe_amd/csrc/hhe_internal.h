@@ -101,6 +101,15 @@ struct hhe_ctx {
     size_t fc_chunk = 160;         // items per internal chunk of hhe_fc_row (0 = whole batch); ms per MNIST sample (784x10, 16 samples): 64: 60.5, 80: 60.6, 96: 60.6, 128: 59.5, 160: 58.4
                                    // (round 1: 40: 67.1, 80: 64.9, 160: 64.0); the trie's small launches (2 polynomials per item) want more than one round of workgroups
     int matmul_mode = 1;           // 1: fused 20-transform pipeline (default), 0: op-by-op schedule
+    int shared_l0 = 12;            // fused pipeline, first affine layer: in calls of at least this many items its rotation chain runs once, on the one key
+                                   // ciphertext every item starts from, and an item only multiplies its diagonals into the shared rotated states
+                                   // (HHE_SHARED_L0; 1: every call, 0: never = per-item chain).  A few items cost what one costs (latency-bound either
+                                   // way), so below the threshold sharing saves nothing and adds the sum launches: ms per call shared / per item at 4, 8, 12, 16, 32 items: 38.4 / 36.3, 44.5 / 44.1, 54.7 / 58.2, 61.7 / 66.8, 98.5 / 113.4
+    size_t l0_budget = (size_t)512 << 20;  // bytes the operand table of that chain may take (HHE_SHARED_L0_MB); a chain that needs more runs in blocks of steps
+    u64 *l0_tab = nullptr;         // [S][2][L][N] operands of S chain steps (workspace, allocated on first use, freed with the context)
+    size_t l0_tab_steps = 0;
+    const u64 **l0_ptrs = nullptr; // [l0_ptr_cap] per-item diagonal tables of the running call
+    size_t l0_ptr_cap = 0;
     KsConsts ksc{};
 
     // device tables

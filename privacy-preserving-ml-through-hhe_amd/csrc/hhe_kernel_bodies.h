@@ -562,16 +562,61 @@ HD void galois_body(const GaloisArgs &a, size_t gid)
     st2(o, v);
 }
 
+// First affine layer of the fused matmul on shared operands (PermArgs::steps > 0; DESIGN.md "shared first layer"): every item
+// starts from the same key ciphertext, so the rotated states of the layer are computed once per call and an item only needs
+// its own diagonals times them.  gid over [count][N / 2], two adjacent points per lane (16-byte accesses); both sums of the
+// lane are 128-bit lazy sums held in registers across the steps, the diagonal is loaded once for both, one Barrett reduction
+// at the end.  Operands and diagonals are canonical (< q < 2^61): DIAG_SUM_FOLD products stay below 2^127, the folded sum
+// below 2^61 rides along (checked under -DHHE_RANGE_CHECK).
+constexpr int DIAG_SUM_FOLD = 32;
+HD void diag_sum_body(const PermArgs &a, size_t gid)
+{
+    const size_t n = (size_t)1 << a.logn;
+    const size_t p = gid >> (a.logn - 1);
+    if (p >= (size_t)a.count) return;
+    const size_t item = p / a.L, j = p % a.L;
+    const size_t off = j * n + ((gid & ((n >> 1) - 1)) << 1);
+    const ModDev m = mod_at(a.mods, (int)j);
+    const u64 *r0 = a.in + off, *r1 = a.in2 + off;
+    const gptr d = as_global(a.mul_ptrs[item]) + a.mul_shift + off;
+    u64 *o0 = a.out + item * a.out_item_stride + off, *o1 = a.out2 + item * a.out_item_stride + off;
+    Acc128 s0[2] = {{0, 0}, {0, 0}}, s1[2] = {{0, 0}, {0, 0}};
+    if (a.carry) {
+        const U2 c0 = ld2(o0), c1 = ld2(o1);
+        s0[0].lo = c0.a; s0[1].lo = c0.b; s1[0].lo = c1.a; s1[1].lo = c1.b;
+    }
+#pragma unroll 4
+    for (int i = 0; i < a.steps; i++) {
+        const U2 u = ld2(r0 + (size_t)i * a.in_step_stride), v = ld2(r1 + (size_t)i * a.in_step_stride);
+        const U2 w = ld2g(d + (size_t)i * a.mul_step_stride);
+        acc_mac_nw(s0[0], u.a, w.a); acc_mac_nw(s0[1], u.b, w.b);
+        acc_mac_nw(s1[0], v.a, w.a); acc_mac_nw(s1[1], v.b, w.b);
+        if ((i & (DIAG_SUM_FOLD - 1)) == DIAG_SUM_FOLD - 1) {
+            for (int k = 0; k < 2; k++) {
+                s0[k].lo = barrett128(s0[k].lo, s0[k].hi, m); s0[k].hi = 0;
+                s1[k].lo = barrett128(s1[k].lo, s1[k].hi, m); s1[k].hi = 0;
+            }
+        }
+    }
+    st2(o0, U2{barrett128(s0[0].lo, s0[0].hi, m), barrett128(s0[1].lo, s0[1].hi, m)});
+    st2(o1, U2{barrett128(s1[0].lo, s1[0].hi, m), barrett128(s1[1].lo, s1[1].hi, m)});
+}
+
 // NTT-domain Galois gather, optionally multiply-accumulating with a per-item table: gid over [count][N]
+// (steps > 0: the diagonal sum above on the first half of the ids -- host loops only: on the device k_perm launches
+// diag_sum_kernel for it, and perm_kernel keeps the registers of a gather)
 HD void perm_body(const PermArgs &a, size_t gid)
 {
+#if !defined(__HIP_DEVICE_COMPILE__)
+    if (a.steps) { diag_sum_body(a, gid); return; }
+#endif
     const size_t n = (size_t)1 << a.logn;
     const size_t p = gid >> a.logn;
     if (p >= (size_t)a.count) return;
     const u32 x = (u32)(gid & (n - 1));
     const size_t item = p / a.L, j = p % a.L;
     const ModDev m = mod_at(a.mods, j);
-    const u64 v = a.in[p * n + ntt_perm_index(x, a.logn, a.elt)];
+    const u64 v = (a.in_item_stride ? a.in + item * a.in_item_stride + j * n : a.in + p * n)[ntt_perm_index(x, a.logn, a.elt)];
     u64 *o = a.out + item * a.out_item_stride + j * n + x;
     if (a.mac) *o = addmod(*o, mulmod(v, a.mul_ptrs[item][a.mul_shift + j * n + x], m), m.q);
     else *o = v;

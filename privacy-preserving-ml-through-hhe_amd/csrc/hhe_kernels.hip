@@ -492,6 +492,18 @@ __global__ void __launch_bounds__(ELT_THREADS) elt_kernel(EltArgs a, int op) { e
 __global__ void __launch_bounds__(ELT_THREADS) copy_items_kernel(CopyItemsArgs a) { copy_items_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) galois_kernel(GaloisArgs a) { galois_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) perm_kernel(PermArgs a) { perm_body(a, GID); }
+// PermArgs::steps > 0.  The operands are shared by all items, so consecutive workgroups take the same (limb, 512 points) of
+// consecutive items: the operand lines one workgroup pulls in are hit in L2 / Infinity Cache by the other items' workgroups
+// running beside it, and only the per-item diagonals stream from HBM.  items = 0: plain order (fewer than 512 points per limb).
+__global__ void __launch_bounds__(ELT_THREADS) diag_sum_kernel(PermArgs a, unsigned items)
+{
+    size_t gid = GID;
+    if (items) {
+        const size_t per_item = ((size_t)a.L << (a.logn - 1)) / ELT_THREADS;  // workgroups of one item
+        gid = ((blockIdx.x % items) * per_item + blockIdx.x / items) * ELT_THREADS + threadIdx.x;
+    }
+    diag_sum_body(a, gid);
+}
 __global__ void __launch_bounds__(ELT_THREADS) ks_mac_kernel(KsMacArgs a) { ks_mac_body(a, GID); }
 template <int LL, int MODE> __global__ void __launch_bounds__(ELT_THREADS) ks_mac_t_kernel(KsMacArgs a) { ks_mac_body_t<LL, MODE>(a, GID); }
 template <int LL> __global__ void __launch_bounds__(ELT_THREADS) ks_mac_leaves_kernel(KsMacLeavesArgs a) { ks_mac_leaves_body<LL>(a, GID); }
@@ -519,7 +531,16 @@ __global__ void __launch_bounds__(ELT_THREADS) behz_floor_kernel(BehzFloorArgs a
 void k_elt(const EltArgs &a, int op, rt_stream s) { LAUNCH1D(elt_kernel, (size_t)a.count << a.logn, s, a, op); }
 void k_copy_items(const CopyItemsArgs &a, rt_stream s) { LAUNCH1D(copy_items_kernel, a.count * (a.words >> 1), s, a); }
 void k_galois(const GaloisArgs &a, rt_stream s) { LAUNCH1D(galois_kernel, (size_t)a.count << (a.logn - 1), s, a); }
-void k_perm(const PermArgs &a, rt_stream s) { LAUNCH1D(perm_kernel, (size_t)a.count << a.logn, s, a); }
+void k_perm(const PermArgs &a, rt_stream s)
+{
+    if (a.steps) {
+        const size_t half = (size_t)1 << (a.logn - 1);
+        const unsigned items = half % ELT_THREADS == 0 ? (unsigned)(a.count / a.L) : 0;
+        LAUNCH1D(diag_sum_kernel, (size_t)a.count * half, s, a, items);
+        return;
+    }
+    LAUNCH1D(perm_kernel, (size_t)a.count << a.logn, s, a);
+}
 template <int MODE> static void launch_ks_mac_t(const KsMacArgs &a, rt_stream s)
 {
     const size_t total = ((size_t)a.B * a.K) << (a.logn - 1);

@@ -115,6 +115,13 @@ HD void acc_mac(Acc128 &a, u64 x, u64 y)
     a.lo += plo;
     a.hi += phi + (a.lo < plo);
 }
+// the same with the high word under the range check (long sums: the caller folds before 2^128)
+HD void acc_mac_nw(Acc128 &a, u64 x, u64 y)
+{
+    u64 plo = x * y, phi = mulhi64(x, y);
+    a.lo += plo;
+    a.hi = add_nw(a.hi, phi + (a.lo < plo));
+}
 HD void acc_add(Acc128 &a, u64 x)
 {
     a.lo += x;
