@@ -569,3 +569,286 @@ def check_matmul_adversarial(X, S, orc, mem, pattern):
     X.transcipher(mem.to_dev(enc), cw, [128], [0], out, rk=ks, gk=ks)
     assert (mem.to_host(out)[0] == O.transcipher_block(enc, rk, gk, cw[0], 0)).all(), pattern
     ks.close()
+
+
+# ---- the FC row at the shapes where it is used (tests/test_fc_shapes.py, tests/golden/make_fc784.py) ----
+BFV_DEFAULT_16384 = [281474976546817, 281474976317441, 281474975662081, 562949952798721, 562949952700417,
+                     562949952274433, 562949951979521, 562949951881217, 562949951619073]  # CoeffModulus::BFVDefault(16384), SURVEY A.10
+
+CSUM_MAX = 2000   # FcWalk::CSUM_MAX (csrc/hhe_api.cpp)
+
+
+def galois_elt_py(n, step):
+    """GaloisTool::get_elt_from_step (seal/util/galois.cpp), restated: 3^step mod 2N for a left rotation by `step` of a row of
+    N/2 slots, a right rotation by s being the left rotation by N/2 - s; step 0 is the column swap 2N - 1."""
+    m, row = 2 * n, n // 2
+    if step == 0:
+        return m - 1
+    assert abs(step) < row
+    return pow(3, step if step > 0 else row - (-step), m)
+
+
+def default_galois_elts_py(n):
+    """what GaloisKeys created without arguments hold (GaloisTool::get_elts_all): 3^(2^k), their inverses and the column swap"""
+    m, elts, g, gi = 2 * n, [2 * n - 1], 3, pow(3, -1, 2 * n)
+    for _ in range(n.bit_length() - 2):
+        elts += [g, gi]
+        g, gi = g * g % m, gi * gi % m
+    return list(dict.fromkeys(elts))
+
+
+class FcTrie:
+    """Model of the rotation trie of one hhe_fc_row chunk, built by the rule of fc_row_chunk (csrc/hhe_api.cpp) and nothing else of
+    the library: for i = 1 .. n_in-1, step -i is ONE term [-i] if the key set holds its element and (i is a power of two, or the
+    call sees the whole set: hhe_fc_row_ks, or default_galois_only = 0); otherwise its terms are naf(-i) without those equal to
+    +-N/2.  Node 0 is the root (the relinearized product); term[k] / parent[k] / kids[k] / mult[k] describe node k, mult = how many
+    steps end there.  A leaf is a node without children that ends exactly one step."""
+
+    def __init__(self, orc, n, n_in, key_elts, whole_set):
+        self.n, self.n_in = n, n_in
+        keys = set(int(e) for e in key_elts)
+        self.term, self.parent, self.kids, self.mult, self.depth = [0], [-1], [[]], [0], [0]
+        for i in range(1, n_in):
+            if galois_elt_py(n, -i) in keys and (i & (i - 1) == 0 or whole_set):
+                terms = [-i]
+            else:
+                terms = [t for t in orc.naf(-i) if abs(t) != n // 2]
+            node = 0
+            for t in terms:
+                assert galois_elt_py(n, t) in keys, ("Galois key not present", i, t)
+                nxt = next((k for k in self.kids[node] if self.term[k] == t), -1)
+                if nxt < 0:
+                    nxt = len(self.term)
+                    self.term.append(t); self.parent.append(node); self.kids.append([]); self.mult.append(0)
+                    self.depth.append(self.depth[node] + 1)
+                    self.kids[node].append(nxt)
+                node = nxt
+            self.mult[node] += 1
+        assert self.mult[0] == 0 and max(self.mult) <= 1   # distinct steps have distinct term sequences
+        self.nodes = len(self.term) - 1                     # key switches of the trie: every node but the root
+        self.leaf = [k > 0 and not self.kids[k] and self.mult[k] == 1 for k in range(len(self.term))]
+        self.leaves = sum(self.leaf)
+        self.elt = [0] + [galois_elt_py(n, t) for t in self.term[1:]]
+        # leaves per Galois element of their last term.  Two different terms can name one element: step -(N/2 - 2^k) and step +2^k
+        self.leaves_per_elt = {}
+        for k in range(1, len(self.term)):
+            if self.leaf[k]:
+                self.leaves_per_elt[self.elt[k]] = self.leaves_per_elt.get(self.elt[k], 0) + 1
+        self.closes, self.closed_sums = self._closes()
+
+    def _closes(self):
+        """c1 sums closed in one chunk, by the rule of FcWalk::csum_leaf / fc_dfs_shared: the walk visits a node's leaf children
+        first (in the order they were created), then descends into the others; a leaf joins the sum of its element, which is closed
+        BEFORE the leaf is added once it holds CSUM_MAX terms, and every sum that holds any term is closed once at the end.
+        The wrap byte: a term is below q < 2^60, so CSUM_MAX = 2000 < 2^11 terms stay below 2^71 and wrap the 64-bit word at most
+        2000 q / 2^64 < 125 times (about half that with random residues): a byte holds it.  No open sum may exceed CSUM_MAX terms."""
+        count, closed = {}, []
+        stack = [0]
+        while stack:
+            node = stack.pop()
+            for k in self.kids[node]:
+                if self.leaf[k]:
+                    e = self.elt[k]
+                    if count.get(e, 0) >= CSUM_MAX:
+                        closed.append((e, count[e]))
+                        count[e] = 0
+                    count[e] = count.get(e, 0) + 1
+                    assert count[e] <= CSUM_MAX
+            stack.extend(k for k in reversed(self.kids[node]) if not self.leaf[k])
+        closed += [(e, c) for e, c in count.items() if c]
+        return len(closed), closed
+
+    def leaves_per_step(self, steps):
+        """{step: leaves whose last term has the element of `step`}, and nothing left over"""
+        got = {s: self.leaves_per_elt.get(galois_elt_py(self.n, s), 0) for s in steps}
+        assert sum(got.values()) == self.leaves, (got, self.leaves_per_elt)
+        return got
+
+
+FC_SHAPES = {
+    # the benchmarked shape (bench.py MnistFlow: N = 2^15, 4 x 60 bits, 784 inputs): 5 items over 2 weight rows
+    "fc784_n32768": dict(logn=15, bits=[60] * 4, n_in=784, B=5, W=2, seed=784),
+    # the deployed shape: the only parameter set the reference ships, and the only one of the three that decrypts
+    "fc784_n16384": dict(logn=14, primes=BFV_DEFAULT_16384, n_in=784, B=2, W=1, seed=785),
+    # the widest row the ABI admits at N = 2^14: one element collects 2731 leaves, more than CSUM_MAX
+    "fc8192_n16384": dict(logn=14, bits=[60] * 3, n_in=8192, B=1, W=1, seed=8192),
+}
+
+
+def fc_shape_setup(orc, name):
+    """keys of an FC_SHAPES case: Setup seeds (sk 1, pk 2, rk 3, gk 7), Galois keys = exactly what create_galois_keys() without
+    arguments makes (steps -1, 0 and 128 are among them)"""
+    p = FC_SHAPES[name]
+    if "primes" in p:
+        S = setup_from_primes(orc, p["logn"], p["primes"], T16, all_galois=True)
+    else:
+        from conftest import Setup
+        S = Setup(orc, p["logn"], p["bits"], all_galois=True)
+    assert sorted(int(e) for e in S.gk.elts) == sorted(int(e) for e in set(S.O.galois_elts_all()))
+    assert sorted(int(e) for e in S.gk.elts) == sorted(default_galois_elts_py(S.n))
+    return S
+
+
+def fc_shape_inputs(S, name, items=None):
+    """(v [B][n_in] in [0,4), w [W][n_in] in [-8,9), their encryptions): default_rng(seed), encrypt seeds 100 + b and 200 + r.
+    items: encrypt these items only (the others stay zero words and must not be used)."""
+    p = FC_SHAPES[name]
+    O = S.O
+    rng = np.random.default_rng(p["seed"])
+    v = rng.integers(0, 4, (p["B"], p["n_in"]))
+    w = rng.integers(-8, 9, (p["W"], p["n_in"]))
+    vi = np.zeros((p["B"],) + O.ct_shape, np.uint64)
+    for b in (range(p["B"]) if items is None else items):
+        vi[b] = O.encrypt(S.pk, O.encode(v[b]), 100 + b)
+    wc = np.stack([O.encrypt(S.pk, O.encode(w[r] % S.t), 200 + r) for r in range(p["W"])])
+    return v, w, vi, wc
+
+
+def limb_hashes(ct):
+    """SHA-256 per (polynomial, limb) of a ciphertext's words: a mismatch names the limb"""
+    import hashlib
+    ct = np.ascontiguousarray(ct, dtype=np.uint64)
+    return [[hashlib.sha256(ct[p, j].tobytes()).hexdigest() for j in range(ct.shape[1])] for p in range(ct.shape[0])]
+
+
+def assert_limb_hashes(got, want, what):
+    h = limb_hashes(got)
+    bad = [(p, j) for p in range(len(want)) for j in range(len(want[p])) if h[p][j] != want[p][j]]
+    assert len(h) == len(want) and len(h[0]) == len(want[0]) and not bad, (what, "(polynomial, limb) that differ from the oracle:", bad)
+
+
+# ---- real zero coefficients: the exactness fallback of the shared digits (csrc/hhe_api.cpp, "shared digits") ----
+# (logn, prime bit sizes, n_in, B, expected digit_reduce, what the case reaches).  Primes this small make zero coefficients
+# of c1 a matter of course (N L nodes / q per item is of order one); none of these contexts runs the fused row kernels.
+ZERO_CASES = {
+    "n1024_18x4": (10, [18] * 4, 60, 8, 0, "single-tile transform"),
+    "n1024_17_20_20": (10, [17, 20, 20], 60, 8, 1, "digit_reduce == 1"),
+    "n1024_19x6": (10, [19] * 6, 60, 8, 0, "L = 5: no leaf groups, no c1 sums"),
+    "n4096_19x3": (12, [19] * 3, 30, 10, 0, "two-pass transform, row_kernel == 0"),
+    "n8192_20x3": (13, [20] * 3, 20, 8, 0, "the same with larger tiles"),
+}
+_zero_cache = {}
+
+
+def zero_case(orc, name):
+    """(Setup, n_in, vi [B], wc, oracle rows [B], zeros) of a ZERO_CASES entry; inputs as in check_fc_variants (default_rng(8), v in
+    [0,4), w in [-8,9) mod t, encrypt seeds 41 + b and 43).  zeros is the PREDICTION, made from the oracle alone: a list of (item,
+    depth, limb) for every limb of c1 that holds a 0 in a trie node WITH children (the root, depth 0, included) -- the nodes whose
+    digit transforms the children share, where a flipped 0 stays 0 instead of becoming q_I.  Every node is computed with
+    O.apply_galois from O.relinearize(O.multiply(vi, w), rk) along the model's trie."""
+    if name in _zero_cache:
+        return _zero_cache[name]
+    from conftest import Setup
+    logn, bits, n_in, B, _, _ = ZERO_CASES[name]
+    S = Setup(orc, logn, bits, all_galois=True)
+    O = S.O
+    rng = np.random.default_rng(8)
+    v, w = rng.integers(0, 4, n_in), rng.integers(-8, 9, n_in)
+    wc = O.encrypt(S.pk, O.encode(w), 43)
+    vi = np.stack([O.encrypt(S.pk, O.encode(v), 41 + b) for b in range(B)])
+    refs = [O.fc_row(vi[b], wc, S.rk, S.gk, n_in)[0] for b in range(B)]
+    trie = FcTrie(orc, S.n, n_in, S.gk.elts, whole_set=True)
+    key = {int(e): S.gk.keys[i] for i, e in enumerate(S.gk.elts)}
+    zeros = []
+    for b in range(B):
+        cts = {0: O.relinearize(O.multiply(vi[b], wc), S.rk)}
+        for k in range(len(trie.term)):   # a node's index is larger than its parent's
+            if not trie.kids[k]:
+                continue
+            if k:
+                cts[k] = O.apply_galois(cts[trie.parent[k]], trie.elt[k], key[trie.elt[k]])
+            zeros += [(b, trie.depth[k], j) for j in range(O.L) if (cts[k][1, j] == 0).any()]
+    _zero_cache[name] = (S, n_in, vi, wc, refs, zeros)
+    return _zero_cache[name]
+
+
+def assert_zero_cases_valid(orc, name):
+    """The conditions under which these cases test anything, asserted on the prediction before the library is looked at: the case
+    has an item that must fall back and one that must not; over all cases there is a zero below the root and one outside limb 0."""
+    allz = {c: zero_case(orc, c)[5] for c in ZERO_CASES}
+    assert any(d > 0 for z in allz.values() for _, d, _ in z), "no zero in a node below the root: choose other seeds or primes"
+    assert any(j > 0 for z in allz.values() for _, _, j in z), "no zero outside limb 0: choose other seeds or primes"
+    items = sorted(set(b for b, _, _ in allz[name]))
+    assert 0 < len(items) < ZERO_CASES[name][3], (name, items)
+    return items
+
+
+def check_fc_real_zeros(make_ctx, orc, mem, monkeypatch, name):
+    """A zero coefficient of c1 in a node whose digits are shared is DETECTED -- for exactly the items the oracle-side walk predicts,
+    in whatever limb and node -- and the recomputed chunk returns the oracle's words.  fc_fallbacks counts recomputed chunks: with one
+    item per chunk it equals the number of predicted items exactly (a spurious fallback is a performance bug the counter exists to
+    show), with two per chunk the number of chunks that hold one, and without shared digits it is 0.
+    make_ctx(q, t, digit_reduce) returns a fresh context that has asserted its dispatch; the knobs are read at creation."""
+    items = assert_zero_cases_valid(orc, name)
+    S, n_in, vi, wc, refs, zeros = zero_case(orc, name)
+    logn, bits, _, B, digit_reduce, _ = ZERO_CASES[name]
+    O = S.O
+
+    def run(expect, **env):
+        for k, v in env.items():
+            monkeypatch.setenv(k, str(v))
+        X = make_ctx(logn, S.q, S.t, digit_reduce)
+        for k in env:
+            monkeypatch.delenv(k)
+        S.load_keys(X)
+        out = mem.empty((B,) + O.ct_shape)
+        X.fc_row(mem.to_dev(vi), mem.to_dev(wc[None]), 1, n_in, out, B, relin_slot=0, default_galois_only=False)
+        got = mem.to_host(out)
+        for b in range(B):
+            assert (got[b] == refs[b]).all(), (name, env, "item", b, "predicted to fall back:", items, "zeros (item, depth, limb):", zeros)
+        assert X.query("fc_fallbacks") == expect, (name, env, X.query("fc_fallbacks"), expect, items)
+        X.close()
+
+    # the c1-sum path negates an integer sum, where a flipped 0 matters in the same way: every leaf scheme on the same inputs
+    for csum in (1, 0):
+        for leafsum in (1, 0):
+            for group in (4, 1):
+                run(len(items), HHE_FC_CHUNK=1, HHE_FC_CSUM=csum, HHE_FC_LEAFSUM=leafsum, HHE_FC_LEAFGROUP=group)
+    run(len(set(b // 2 for b in items)), HHE_FC_CHUNK=2)
+    run(0, HHE_FC_CHUNK=1, HHE_FC_SHARED=0)
+
+
+def check_fc_transparent_row_kernel(make_ctx, orc, mem, monkeypatch):
+    """Zero detection on the path of the fused row kernels (ks_perm_row_kernel, c0hat, the digit load of the strided first pass):
+    N = 4096, 3 x 60-bit primes, n_in = 9, three items over three weight rows in one chunk, item 0 the product of two TRANSPARENT
+    ciphertexts (c1 = 0 in vi[0] and in w[0], c0 uniform words below their primes): its c1 is 0 in every node of the trie.
+    This pins that the digit loads of that path raise the flag at all, and that the recomputed chunk is right for the ordinary items
+    as well.  It does not pin a single isolated zero there: those kernels need pseudo-Mersenne primes of 33 bits and more, where a
+    zero coefficient of a real ciphertext has probability below 10^-4 per row, and a ciphertext cannot be crafted to have one zero
+    coefficient in c1 after BEHZ multiply and relinearize without inverting them."""
+    from conftest import Setup
+    S = Setup(orc, 12, [60] * 3, all_galois=True)
+    O = S.O
+    n_in, B = 9, 3
+    rng = np.random.default_rng(9)
+    v, w = rng.integers(0, 4, (B, n_in)), rng.integers(-8, 9, (B, n_in))
+    vi = np.stack([O.encrypt(S.pk, O.encode(v[b]), 41 + b) for b in range(B)])
+    wc = np.stack([O.encrypt(S.pk, O.encode(w[b]), 51 + b) for b in range(B)])
+    for ct in (vi, wc):
+        ct[0, 1] = 0
+        for j in range(O.L):
+            ct[0, 0, j] = rng.integers(0, S.q[j], O.n, dtype=np.uint64)
+    refs = [O.fc_row(vi[b], wc[b], S.rk, S.gk, n_in)[0] for b in range(B)]
+    # on the oracle, not assumed: item 0's c1 is 0 in the root and in every node with children, its c0 is not
+    trie = FcTrie(orc, S.n, n_in, S.gk.elts, whole_set=True)
+    key = {int(e): S.gk.keys[i] for i, e in enumerate(S.gk.elts)}
+    cts = {0: O.relinearize(O.multiply(vi[0], wc[0]), S.rk)}
+    assert any(trie.kids[k] for k in range(1, len(trie.term))), "the trie has no inner node below the root"
+    for k in range(len(trie.term)):
+        if k:
+            cts[k] = O.apply_galois(cts[trie.parent[k]], trie.elt[k], key[trie.elt[k]])
+        assert not cts[k][1].any() and cts[k][0].any(), k
+    for b in (1, 2):
+        assert (O.relinearize(O.multiply(vi[b], wc[b]), S.rk)[1] != 0).all()
+    monkeypatch.setenv("HHE_FC_CHUNK", "1")   # rounded up to the three weight rows: one chunk
+    X = make_ctx(12, S.q, S.t, 0)
+    monkeypatch.delenv("HHE_FC_CHUNK")
+    assert X.query("row_kernel") == 1
+    S.load_keys(X)
+    out = mem.empty((B,) + O.ct_shape)
+    X.fc_row(mem.to_dev(vi), mem.to_dev(wc), B, n_in, out, B, relin_slot=0, default_galois_only=False)
+    got = mem.to_host(out)
+    for b in range(B):
+        assert (got[b] == refs[b]).all(), b
+    assert X.query("fc_fallbacks") == 1
+    X.close()
