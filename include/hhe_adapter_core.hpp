@@ -1,0 +1,382 @@
+// hhe_adapter_core.hpp -- everything the two C++ adapters do that is not type conversion, once, on plain words, over the C ABI of
+// libhhe_gfx950.so.  pasta_seal_gfx950.hpp (word containers; executed by the tests) and pasta_seal_gfx950_seal.hpp (seal:: types;
+// type-checked only) derive their context class from hhe::AdapterCore and turn their boundary types into `const uint64_t *` and
+// output sinks; which buffers, which lock, which key set and which order of C-ABI calls is decided here and nowhere else.
+//   KeySetCache  maps every RelinKeys / GaloisKeys OBJECT the caller passes to one device key set (hhe_keyset), recognised by a
+//                hash over ALL of its words.  The reference copies its key objects by value into every cipher object and every
+//                call (SEAL_Cipher.cpp:9-36, CSP.cpp:238-242), so pointers say nothing; contents do.  An object is uploaded
+//                once and stays resident with everything derived from it; beyond `max_sets` (a CSP that serves many analysts) the
+//                cache lets go of the least recently used sets.
+//   DeviceArena  grow-only device buffers reused across calls instead of a hipMalloc / hipFree pair per call.
+//   AdapterCore  the hhe_ctx, its cache, its arena, the resident encrypted PASTA key and the call bodies.
+//
+// Ownership and threading, stated once:
+//   * A key set is a std::shared_ptr (KeySet).  The cache holds one reference, every cipher object holds one for each key member
+//     it was built with, every call holds one for each key object it names.  Eviction drops the cache's reference only: a set is
+//     destroyed when its last holder lets go, never under a call or a live cipher object.  Holders declare their KeySet members
+//     after their context member, so a set dies before its context.
+//   * An empty key object gives a null KeySet.  A cipher object's method then runs with the context's one empty set (and reports
+//     the missing key as SEAL would) instead of falling through to the library's default set; a free function that names a key
+//     object throws at once.
+//   * Every method that touches the arena takes the arena's lock for its whole duration, and looks up the key sets it names under
+//     that lock.  Lock order: arena, then cache, then the library's own per-context lock.  The methods on RAII buffers (multiply,
+//     add, square_relinearize, relinearize, vec_sum, pasta_crypt, decrypt) take no adapter lock; their key sets are kept alive by
+//     the reference the call holds.
+//   * Results leave through a sink `uint64_t *dst(size_t item)`: the host destination of item i, asked for after every input has
+//     been uploaded (so a destination may alias an input) and written straight from the device.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <list>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+#include "hhe_gfx950.h"
+
+namespace hhe {
+
+inline void check(int rc)  // return code -> the exception the reference / SEAL throw
+{
+    if (rc == HHE_OK) return;
+    const std::string msg = hhe_last_error();
+    switch (rc) {
+    case HHE_ERR_NO_GALOIS_KEY:
+    case HHE_ERR_NO_RELIN_KEY:
+    case HHE_ERR_INVALID: throw std::invalid_argument(msg);  // what SEAL throws for these
+    default: throw std::runtime_error(msg);                  // incl. HHE_ERR_TOO_FEW_SLOTS (pasta_3_seal.cpp:376-377)
+    }
+}
+
+struct DevBuf {  // RAII device buffer
+    void *p = nullptr;
+    explicit DevBuf(size_t bytes) : p(hhe_malloc(bytes)) { if (!p) throw std::runtime_error("hhe_malloc failed"); }
+    ~DevBuf() { hhe_free(p); }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    uint64_t *u64() const { return static_cast<uint64_t *>(p); }
+};
+
+// 128 bits over every word (two independent multiply-xorshift lanes) plus the length: a 4-word sample cannot tell two key
+// objects of one key generator apart reliably, the whole content can
+struct ContentHash {
+    uint64_t a = 0x243F6A8885A308D3ULL, b = 0x13198A2E03707344ULL, n = 0;
+    void add(const uint64_t *w, size_t count)
+    {
+        for (size_t i = 0; i < count; i++) {
+            a = (a ^ w[i]) * 0x9E3779B97F4A7C15ULL; a ^= a >> 29;
+            b = (b + w[i]) * 0xC2B2AE3D27D4EB4FULL; b ^= b >> 31;
+        }
+        n += count;
+    }
+    void add_tag(uint64_t t) { add(&t, 1); }
+    bool operator<(const ContentHash &o) const { return a != o.a ? a < o.a : b != o.b ? b < o.b : n < o.n; }
+    bool operator!=(const ContentHash &o) const { return *this < o || o < *this; }
+};
+
+typedef std::shared_ptr<hhe_keyset> KeySet;
+// The words of one key object as its adapter holds them; an object without keys is "empty".
+// `own`: backing store of an adapter whose key objects are not contiguous in memory.
+struct RelinWords {  // RelinKeys::key(2): [L digits][2][K][N], NTT form
+    const uint64_t *key = nullptr;
+    size_t words = 0;
+    std::vector<uint64_t> own;
+};
+struct GaloisWords {
+    std::vector<std::pair<uint32_t, const uint64_t *>> keys;  // (Galois element, its [L][2][K][N] words)
+    size_t words = 0;                                         // per key
+    std::vector<std::vector<uint64_t>> own;
+};
+
+class KeySetCache {
+public:
+    explicit KeySetCache(hhe_ctx *ctx, size_t max_sets = 16) : ctx_(ctx), max_sets_(max_sets) {}
+    KeySet galois(const GaloisWords &g)
+    {
+        if (g.keys.empty()) return nullptr;
+        ContentHash h;
+        h.add_tag(0x6b67);  // "gk"
+        for (auto &kv : g.keys) { h.add_tag(kv.first); h.add(kv.second, g.words); }
+        return lookup(h, [&](hhe_keyset *ks) {
+            for (auto &kv : g.keys)
+                if (int rc = hhe_keyset_set_galois(ks, kv.first, kv.second)) return rc;
+            return (int)HHE_OK;
+        });
+    }
+    KeySet relin(const RelinWords &r)
+    {
+        if (!r.words) return nullptr;
+        ContentHash h;
+        h.add_tag(0x726b);  // "rk"
+        h.add(r.key, r.words);
+        return lookup(h, [&](hhe_keyset *ks) { return hhe_keyset_set_relin(ks, r.key); });
+    }
+    KeySet new_set() const  // a set without keys, not cached
+    {
+        hhe_keyset *ks = nullptr;
+        check(hhe_keyset_create(ctx_, &ks));
+        return KeySet(ks, hhe_keyset_destroy);
+    }
+    size_t resident() const { return lru_.size(); }
+    uint64_t uploads() const { return uploads_; }   // how many objects were sent to the device (a repeated object is not)
+
+private:
+    template <typename F> KeySet lookup(const ContentHash &h, F &&fill)
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        auto it = index_.find(h);
+        if (it != index_.end()) {
+            lru_.splice(lru_.begin(), lru_, it->second);  // most recently used first
+            return it->second->second;
+        }
+        KeySet ks = new_set();
+        check(fill(ks.get()));
+        ++uploads_;
+        lru_.emplace_front(h, ks);
+        index_[h] = lru_.begin();
+        while (lru_.size() > max_sets_) {  // the cache's reference goes; whoever still holds the set keeps it alive
+            index_.erase(lru_.back().first);
+            lru_.pop_back();
+        }
+        return ks;
+    }
+    hhe_ctx *ctx_;
+    size_t max_sets_;
+    std::mutex mu_;
+    std::list<std::pair<ContentHash, KeySet>> lru_;
+    std::map<ContentHash, std::list<std::pair<ContentHash, KeySet>>::iterator> index_;
+    uint64_t uploads_ = 0;
+};
+
+// A few grow-only device buffers ("slots"); a call takes the arena's lock for its duration (the library serialises calls on one
+// context anyway) and gets buffers that survive the call.
+class DeviceArena {
+public:
+    static constexpr int SLOTS = 6;
+    ~DeviceArena() { for (auto &s : buf_) hhe_free(s.first); }
+    std::mutex &mutex() { return mu_; }
+    uint64_t *get(int slot, size_t bytes)  // caller holds mutex()
+    {
+        auto &s = buf_[slot];
+        if (s.second < bytes) {
+            hhe_free(s.first);
+            s.first = hhe_malloc(bytes);
+            s.second = s.first ? bytes : 0;
+            if (!s.first) throw std::runtime_error("hhe_malloc failed");
+        }
+        return static_cast<uint64_t *>(s.first);
+    }
+private:
+    std::mutex mu_;
+    std::pair<void *, size_t> buf_[SLOTS] = {};
+};
+
+class AdapterCore {
+public:
+    // q: coeff_modulus incl. the special prime; max_sets: capacity of the key-set cache
+    AdapterCore(int logn, const std::vector<uint64_t> &q, uint64_t t, int device = 0, size_t max_sets = 16)
+        : n_((size_t)1 << logn), L_(q.size() - 1), t_(t), h_(create(logn, q, t, device), hhe_ctx_destroy), keys_(h_.get(), max_sets),
+          empty_(keys_.new_set()) {}
+
+    size_t poly_modulus_degree() const { return n_; }
+    size_t data_limbs() const { return L_; }
+    size_t ct_words(size_t size = 2) const { return size * L_ * n_; }
+    uint64_t plain_modulus() const { return t_; }
+    KeySetCache &keys() { return keys_; }
+    uint64_t key_uploads = 0;  // instrumentation: how often an encrypted PASTA key was sent to the device
+
+    // SEALZpCipher::mask (SEAL_Cipher.cpp:161-166)
+    template <class Sink> void mask(const uint64_t *ct, const uint64_t *vals, size_t count, Sink dst)
+    {
+        std::lock_guard<std::mutex> lk(arena_.mutex());
+        uint64_t *d = arena_.get(0, ct_words() * 8);
+        upload(d, ct);
+        check(hhe_mask(h(), d, vals, count, d, 1));
+        download(d, 1, 2, dst);
+    }
+    // SEALZpCipher::flatten (SEAL_Cipher.cpp:170-181): out = sum_i rotate_rows(in[i], -i * plain_size, gk).  GK: a held KeySet or
+    // the GaloisWords of the object the call names
+    template <class GK, class Sink> void flatten(const std::vector<const uint64_t *> &in, const GK &gk, Sink dst)
+    {
+        if (in.empty()) throw std::invalid_argument("flatten: empty input");
+        const size_t w = ct_words();
+        std::lock_guard<std::mutex> lk(arena_.mutex());
+        const KeySet g = or_empty(set(gk));
+        uint64_t *d = arena_.get(0, in.size() * w * 8), *o = arena_.get(1, w * 8);
+        for (size_t i = 0; i < in.size(); i++) upload(d + i * w, in[i]);
+        check(hhe_flatten_ks(h(), g.get(), d, in.size(), o, 1));
+        download(o, 1, 2, dst);
+    }
+
+    // Evaluator::multiply -> size 3; add of two size-`size` ciphertexts; square + relinearize_inplace(rk); relinearize_inplace(rk)
+    template <class Sink> void multiply(const uint64_t *e1, const uint64_t *e2, Sink dst)
+    {
+        DevBuf a(ct_words() * 8), b(ct_words() * 8), o3(ct_words(3) * 8);
+        upload(a.u64(), e1);
+        upload(b.u64(), e2);
+        check(hhe_multiply(h(), a.u64(), b.u64(), o3.u64(), 1));
+        download(o3.u64(), 1, 3, dst);
+    }
+    template <class Sink> void add(const uint64_t *e1, const uint64_t *e2, size_t size, Sink dst)
+    {
+        DevBuf a(ct_words(size) * 8), b(ct_words(size) * 8);
+        upload(a.u64(), e1, size);
+        upload(b.u64(), e2, size);
+        check(hhe_add(h(), a.u64(), b.u64(), a.u64(), 1, (int)size));
+        download(a.u64(), 1, size, dst);
+    }
+    template <class Sink> void square_relinearize(const uint64_t *vi, const KeySet &rk, Sink dst)
+    {
+        DevBuf a(ct_words() * 8), o3(ct_words(3) * 8);
+        upload(a.u64(), vi);
+        check(hhe_multiply(h(), a.u64(), a.u64(), o3.u64(), 1));
+        check(hhe_relinearize_ks(h(), or_empty(rk).get(), o3.u64(), a.u64(), 1));
+        download(a.u64(), 1, 2, dst);
+    }
+    template <class Sink> void relinearize(const uint64_t *e3, const RelinWords &rk, Sink dst)  // CSP.cpp:306
+    {
+        const KeySet r = named(keys_.relin(rk), "relin_keys is not valid for encryption parameters");
+        DevBuf a3(ct_words(3) * 8), o(ct_words() * 8);
+        upload(a3.u64(), e3, 3);
+        check(hhe_relinearize_ks(h(), r.get(), a3.u64(), o.u64(), 1));
+        download(o.u64(), 1, 2, dst);
+    }
+
+    // PASTA_SEAL::decomposition (pasta_3_seal.cpp:106-172): every 128-word block of the record, one batched call; item b of the
+    // sink is block b of blocks_of(record.size()).  enc_key: enc_ssk[0], ct_words() words.
+    static size_t blocks_of(size_t words) { return (words + 127) / 128; }
+    template <class Sink>
+    void transcipher(const std::vector<uint64_t> &record, const uint64_t *enc_key, const KeySet &rk, const KeySet &gk, bool bsgs, Sink dst)
+    {
+        const size_t nb = blocks_of(record.size());
+        if (nb == 0) return;
+        std::vector<uint64_t> cw(nb * 128, 0), bidx(nb);
+        std::vector<uint32_t> ncw(nb);
+        std::copy(record.begin(), record.end(), cw.begin());  // blocks are contiguous; the ragged last one is zero-padded
+        for (size_t b = 0; b < nb; b++) {
+            ncw[b] = (uint32_t)std::min<size_t>(128, record.size() - b * 128);
+            bidx[b] = b;  // pasta.init_shake(nonce, b) (:122)
+        }
+        std::lock_guard<std::mutex> lk(arena_.mutex());
+        uint64_t *key = encrypted_key(enc_key), *out = arena_.get(3, nb * ct_words() * 8);
+        check(hhe_pasta3_transcipher_ks(h(), or_empty(rk).get(), or_empty(gk).get(), key, cw.data(), ncw.data(), bidx.data(), nb, bsgs ? 1 : 0, out));
+        download(out, nb, 2, dst);
+    }
+    // BaseCSP::decompose's per-record loop (CSP.cpp:247-278) as ONE device call: decomposition of every record, the mask of the
+    // ragged last block (mask_last) and flatten with `flatten_gk`; item s of the sink is record s
+    template <class Sink>
+    void decompose(const std::vector<std::vector<uint64_t>> &records, const uint64_t *enc_key, const KeySet &rk, const KeySet &gk,
+                   const GaloisWords &flatten_gk, bool mask_last, Sink dst)
+    {
+        if (records.empty()) return;
+        const size_t nwords = records[0].size();
+        std::vector<uint64_t> flat(records.size() * nwords);
+        for (size_t s = 0; s < records.size(); s++) {
+            if (records[s].size() != nwords) throw std::invalid_argument("decompose: records of different lengths");
+            std::copy(records[s].begin(), records[s].end(), flat.begin() + s * nwords);
+        }
+        std::lock_guard<std::mutex> lk(arena_.mutex());
+        const KeySet fgk = or_empty(keys_.galois(flatten_gk));
+        uint64_t *key = encrypted_key(enc_key), *out = arena_.get(3, records.size() * ct_words() * 8);
+        check(hhe_decompose_ks(h(), or_empty(rk).get(), or_empty(gk).get(), fgk.get(), key, flat.data(), records.size(), nwords, mask_last ? 1 : 0, out));
+        download(out, records.size(), 2, dst);
+    }
+
+    // sealhelper::encrypted_vec_sum (sealhelper.cpp:385-391), literally:
+    // destination = in; for i = -1 .. -(vec_size-1): destination += rotate_rows(in, i, gk)
+    template <class Sink> void vec_sum(const uint64_t *in_words, const GaloisWords &gk, size_t vec_size, Sink dst)
+    {
+        const KeySet g = named(keys_.galois(gk), "Galois key not present");
+        const size_t w = ct_words();
+        DevBuf in(w * 8), acc(w * 8), rot(w * 8);
+        upload(in.u64(), in_words);
+        check(hhe_rotate_rows_ks(h(), g.get(), in.u64(), 0, acc.u64(), 1));  // step 0: a copy, as in SEAL
+        for (size_t i = 1; i < vec_size; i++) {
+            check(hhe_rotate_rows_ks(h(), g.get(), in.u64(), -(int)i, rot.u64(), 1));
+            check(hhe_add(h(), acc.u64(), rot.u64(), acc.u64(), 1, 2));
+        }
+        download(acc.u64(), 1, 2, dst);
+    }
+    // packed_enc_multiply + relinearize_inplace(.., rk) + encrypted_vec_sum(.., gk, vec_size) for one weight row (CSP.cpp:296-316)
+    // as ONE device call: NAF-trie rotation sum, identical ciphertext words
+    template <class Sink>
+    void fc_row(const uint64_t *vi, const uint64_t *w_row, const RelinWords &rk, const GaloisWords &gk, size_t vec_size, Sink dst)
+    {
+        const size_t w = ct_words();
+        std::lock_guard<std::mutex> lk(arena_.mutex());
+        const KeySet r = named(keys_.relin(rk), "fc_row: empty key object"), g = named(keys_.galois(gk), "fc_row: empty key object");
+        uint64_t *a = arena_.get(0, w * 8), *b = arena_.get(1, w * 8), *o = arena_.get(3, w * 8);
+        upload(a, vi);
+        upload(b, w_row);
+        check(hhe_fc_row_ks(h(), r.get(), g.get(), a, b, 1, vec_size, o, 1));
+        download(o, 1, 2, dst);
+    }
+
+    // client end: pasta::PASTA::encrypt / decrypt (pasta_3_plain.cpp:9-46) of `count` words in place, key: 256 words
+    void pasta_crypt(const uint64_t *key, uint64_t *v, size_t count, bool dec)
+    {
+        if (!count) return;
+        DevBuf d(count * 8);
+        check(hhe_copy_h2d(h(), d.p, v, count * 8));
+        check(hhe_pasta3_plain_crypt(h(), key, d.u64(), 1, count, dec ? 1 : 0, d.u64()));
+        check(hhe_copy_d2h(h(), v, d.p, count * 8));
+    }
+    // analyst end: Decryptor::decrypt + BatchEncoder::decode; sk: [K][N] NTT form; vals: N slot values < t
+    void decrypt(const uint64_t *sk, const uint64_t *ct, uint64_t *vals)
+    {
+        DevBuf c(ct_words() * 8), v(n_ * 8);
+        upload(c.u64(), ct);
+        check(hhe_decrypt(h(), sk, c.u64(), 1, v.u64()));
+        check(hhe_copy_d2h(h(), vals, v.p, n_ * 8));
+    }
+
+private:
+    static hhe_ctx *create(int logn, const std::vector<uint64_t> &q, uint64_t t, int device)
+    {
+        hhe_ctx *h = nullptr;
+        check(hhe_ctx_create(logn, (int)q.size(), q.data(), t, device, &h));
+        return h;
+    }
+    hhe_ctx *h() const { return h_.get(); }
+    void upload(uint64_t *d, const uint64_t *src, size_t size = 2) { check(hhe_copy_h2d(h(), d, src, ct_words(size) * 8)); }
+    template <class Sink> void download(const uint64_t *d, size_t items, size_t size, Sink &dst)
+    {
+        for (size_t i = 0; i < items; i++) check(hhe_copy_d2h(h(), dst(i), d + i * ct_words(size), ct_words(size) * 8));
+    }
+    const KeySet &set(const KeySet &held) { return held; }
+    KeySet set(const GaloisWords &g) { return keys_.galois(g); }
+    const KeySet &or_empty(const KeySet &ks) const { return ks ? ks : empty_; }
+    static const KeySet &named(const KeySet &ks, const char *what_if_empty)
+    {
+        if (!ks) throw std::invalid_argument(what_if_empty);
+        return ks;
+    }
+    // enc_ssk[0] arrives by value with every call (CSP.cpp:249): it crosses PCIe only when its contents change.  Caller holds the
+    // arena's lock; the resident copy lives in arena slot 2.
+    uint64_t *encrypted_key(const uint64_t *words)
+    {
+        ContentHash hsh;
+        hsh.add(words, ct_words());
+        uint64_t *d = arena_.get(2, ct_words() * 8);
+        if (!key_resident_ || key_hash_ != hsh) {
+            upload(d, words);
+            key_hash_ = hsh;
+            key_resident_ = true;
+            ++key_uploads;
+        }
+        return d;
+    }
+    size_t n_, L_;
+    uint64_t t_;
+    std::unique_ptr<hhe_ctx, void (*)(hhe_ctx *)> h_;  // declared before the key sets: destroyed after every set the core holds
+    KeySetCache keys_;
+    KeySet empty_;   // what a cipher object built without some key runs with; nothing can put a key into it
+    DeviceArena arena_;
+    ContentHash key_hash_;
+    bool key_resident_ = false;
+};
+
+}  // namespace hhe

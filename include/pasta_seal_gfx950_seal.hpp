@@ -10,12 +10,12 @@
 // SEAL objects cross the boundary as their own words: Ciphertext::data() is [size][L][N] at the data level in coefficient
 // form, KSwitchKeys::data()[index][digit].data() is [2][K][N] in NTT form -- the layouts include/hhe_gfx950.h takes.
 //
-// tests/test_seal_adapter.py type-checks this file and the CSP's call sequence against the reference's SEAL 4.0.0 headers
-// (g++ -fsyntax-only; the prebuilt libseal is never linked or loaded), so it cannot be executed in this repository.
+// Only what needs seal:: types lives here: the registry of device contexts, the validity checks and the conversions between SEAL
+// objects and plain words.  Every call body is hhe::AdapterCore (hhe_adapter_core.hpp), the code pasta_seal_gfx950.hpp runs in
+// the tests on word containers.  tests/test_seal_adapter.py type-checks this file and the CSP's call sequence against the
+// reference's SEAL 4.0.0 headers (g++ -fsyntax-only; the prebuilt libseal is never linked or loaded): it is not executed here.
 #pragma once
 
-#include <array>
-#include <cmath>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -27,60 +27,22 @@
 #include "pasta_3_plain.h"  // reference: PASTA_PARAMS, PASTA_T
 #include "seal/seal.h"
 
-#include "hhe_gfx950.h"
-#include "hhe_keyset_cache.hpp"
+#include "hhe_adapter_core.hpp"
 
 namespace pasta {
 namespace gfx950 {
-
-inline void check(int rc)
-{
-    if (rc == HHE_OK) return;
-    const std::string msg = hhe_last_error();
-    switch (rc) {
-    case HHE_ERR_TOO_FEW_SLOTS: throw std::runtime_error(msg);  // pasta_3_seal.cpp:376-377
-    case HHE_ERR_NO_GALOIS_KEY:
-    case HHE_ERR_NO_RELIN_KEY:
-    case HHE_ERR_INVALID: throw std::invalid_argument(msg);     // what SEAL throws for these
-    default: throw std::runtime_error(msg);
-    }
-}
-
-struct DevBuf {  // RAII device buffer
-    void *p = nullptr;
-    explicit DevBuf(std::size_t bytes) : p(hhe_malloc(bytes)) { if (!p) throw std::runtime_error("hhe_malloc failed"); }
-    ~DevBuf() { hhe_free(p); }
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    std::uint64_t *u64() const { return static_cast<std::uint64_t *>(p); }
-};
 
 // One device context per SEAL parameter set, shared by every cipher object of the process: BaseCSP::decompose builds a
 // fresh PASTA_SEAL per request (CSP.cpp:238-242), the key-switch keys stay in HBM between requests.  Every RelinKeys /
 // GaloisKeys OBJECT that reaches the adapter (a constructor argument, the galois_keys of flatten, the keys of the FC calls) maps
 // to one device key set, recognised by a hash over all of its words (hhe::KeySetCache): analyst_he_gk and csp_he_gk, which
 // share elements but not words (Analyst.cpp:62-94), live side by side and every call uses the one it names.
-class DeviceContext {
+class DeviceContext : public hhe::AdapterCore {
 public:
     explicit DeviceContext(const seal::SEALContext &context, int device = 0)
-    {
-        const auto &parms = context.key_context_data()->parms();
-        std::vector<std::uint64_t> q;
-        for (const auto &m : parms.coeff_modulus()) q.push_back(m.value());
-        n_ = parms.poly_modulus_degree();
-        L_ = q.size() - 1;
-        t_ = parms.plain_modulus().value();
-        first_parms_id_ = context.first_parms_id();
-        check(hhe_ctx_create(seal::util::get_power_of_two(n_), static_cast<int>(q.size()), q.data(), t_, device, &h_));
-    }
-    ~DeviceContext() { keys_.reset(); hhe_ctx_destroy(h_); }   // key sets go before their context
-    DeviceContext(const DeviceContext &) = delete;
-    DeviceContext &operator=(const DeviceContext &) = delete;
-
-    hhe_ctx *handle() const { return h_; }
-    std::size_t n() const { return n_; }
-    std::size_t ct_words(std::size_t size = 2) const { return size * L_ * n_; }
-    const seal::parms_id_type &first_parms_id() const { return first_parms_id_; }
+        : hhe::AdapterCore(seal::util::get_power_of_two(context.key_context_data()->parms().poly_modulus_degree()),
+                           primes(context.key_context_data()->parms()), context.key_context_data()->parms().plain_modulus().value(), device),
+          first_parms_id_(context.first_parms_id()) {}
 
     // KSwitchKeys::data()[index] = one PublicKey per digit, each a size-2 K-limb NTT-form ciphertext -> [L][2][K][N]
     static std::vector<std::uint64_t> flatten_ksk(const std::vector<seal::PublicKey> &digits)
@@ -92,63 +54,69 @@ public:
         }
         return out;
     }
-    // the device key set of a key object (nullptr for an empty object: the call then reports the missing key as SEAL would)
-    hhe_keyset *relin_set(const seal::RelinKeys &rk)
+    // the words of a key object (empty for an empty object: the call then reports the missing key as SEAL would)
+    static hhe::RelinWords words(const seal::RelinKeys &rk)
     {
-        if (rk.data().empty() || rk.data()[0].empty()) return nullptr;
-        const auto words = flatten_ksk(rk.data()[seal::RelinKeys::get_index(2)]);
-        return keys().relin(words.data(), words.size());
+        hhe::RelinWords r;
+        if (rk.data().empty() || rk.data()[0].empty()) return r;
+        r.own = flatten_ksk(rk.data()[seal::RelinKeys::get_index(2)]);
+        r.key = r.own.data();
+        r.words = r.own.size();
+        return r;
     }
-    hhe_keyset *galois_set(const seal::GaloisKeys &gk)
+    static hhe::GaloisWords words(const seal::GaloisKeys &gk)
     {
-        std::vector<std::vector<std::uint64_t>> flat;
-        std::vector<std::pair<std::uint32_t, const std::uint64_t *>> v;
+        hhe::GaloisWords g;
         for (std::size_t idx = 0; idx < gk.data().size(); idx++) {
             if (gk.data()[idx].empty()) continue;
-            flat.push_back(flatten_ksk(gk.data()[idx]));   // GaloisKeys::get_index(elt) = (elt - 1) / 2
-            v.emplace_back(static_cast<std::uint32_t>(2 * idx + 1), nullptr);
+            g.own.push_back(flatten_ksk(gk.data()[idx]));   // GaloisKeys::get_index(elt) = (elt - 1) / 2
+            g.keys.emplace_back(static_cast<std::uint32_t>(2 * idx + 1), nullptr);
         }
-        if (v.empty()) return nullptr;
-        for (std::size_t i = 0; i < v.size(); i++) v[i].second = flat[i].data();
-        return keys().galois(v, flat[0].size());
+        for (std::size_t i = 0; i < g.keys.size(); i++) g.keys[i].second = g.own[i].data();
+        if (!g.own.empty()) g.words = g.own[0].size();
+        return g;
     }
-    hhe::KeySetCache &keys() { std::lock_guard<std::mutex> lk(mu_); if (!keys_) keys_.reset(new hhe::KeySetCache(h_)); return *keys_; }
-    hhe::DeviceArena &arena() { return arena_; }
-    // enc_ssk[0] arrives by value with every call (CSP.cpp:249): it crosses PCIe only when its contents change (arena slot 2;
-    // the caller holds the arena's lock)
-    std::uint64_t *encrypted_key(const seal::Ciphertext &ct)
-    {
-        if (ct.is_ntt_form() || ct.poly_modulus_degree() != n_ || ct.coeff_modulus_size() != L_ || ct.size() != 2)
-            throw std::invalid_argument("encrypted is not valid for encryption parameters");
-        hhe::ContentHash hsh;
-        hsh.add(ct.data(), ct_words());
-        std::uint64_t *d = arena_.get(2, ct_words() * 8);
-        if (!key_resident_ || key_hash_ < hsh || hsh < key_hash_) {
-            check(hhe_copy_h2d(h_, d, ct.data(), ct_words() * 8));
-            key_hash_ = hsh;
-            key_resident_ = true;
-        }
-        return d;
-    }
+    hhe::KeySet relin_set(const seal::RelinKeys &rk) { return keys().relin(words(rk)); }
+    hhe::KeySet galois_set(const seal::GaloisKeys &gk) { return keys().galois(words(gk)); }
 
-    void to_device(const seal::Ciphertext &ct, std::uint64_t *dptr) const
+    // a data-level, coefficient-form ciphertext of `size` polynomials as its words
+    const std::uint64_t *words(const seal::Ciphertext &ct, std::size_t size = 2) const
     {
-        if (ct.is_ntt_form() || ct.poly_modulus_degree() != n_ || ct.coeff_modulus_size() != L_)
+        if (ct.is_ntt_form() || ct.poly_modulus_degree() != poly_modulus_degree() || ct.coeff_modulus_size() != data_limbs() || ct.size() != size)
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
-        check(hhe_copy_h2d(h_, dptr, ct.data(), ct_words(ct.size()) * 8));
+        return ct.data();
     }
-    void from_device(const seal::SEALContext &context, const std::uint64_t *dptr, std::size_t size, seal::Ciphertext &ct) const
+    std::vector<const std::uint64_t *> words(const std::vector<seal::Ciphertext> &cts) const
     {
-        ct.resize(context, first_parms_id_, size);
-        ct.is_ntt_form() = false;
-        ct.scale() = 1.0;
-        check(hhe_copy_d2h(h_, ct.data(), dptr, ct_words(size) * 8));
+        std::vector<const std::uint64_t *> p;
+        for (const auto &ct : cts) p.push_back(words(ct));
+        return p;
+    }
+    // output sinks.  With the SEALContext at hand (cipher objects) the destination is resized at the data level ...
+    auto into(const seal::SEALContext &context, seal::Ciphertext &ct, std::size_t size = 2) const
+    {
+        return [this, &context, &ct, size](std::size_t) {
+            ct.resize(context, first_parms_id_, size);
+            ct.is_ntt_form() = false;
+            ct.scale() = 1.0;
+            return ct.data();
+        };
+    }
+    auto into(const seal::SEALContext &context, std::vector<seal::Ciphertext> &cts) const
+    {
+        return [this, &context, &cts](std::size_t i) { return into(context, cts[i])(0); };
+    }
+    // ... without it (free functions: a Ciphertext does not carry its SEALContext) it takes the parameters of an input of the
+    // call (same parms_id, pool) and is resized to `size` polynomials
+    static auto into(seal::Ciphertext &ct, const seal::Ciphertext &like, std::size_t size = 2)
+    {
+        return [&ct, &like, size](std::size_t) { ct = like; ct.resize(size); return ct.data(); };
     }
 
     // process-wide registry keyed by the data-level parms_id (what every ciphertext of the path carries)
     static std::shared_ptr<DeviceContext> get(const seal::SEALContext &context)
     {
-        std::lock_guard<std::mutex> lk(registry_mutex());
+        std::unique_lock<std::mutex> lk(registry_mutex());
         auto &reg = registry();
         auto it = reg.find(context.first_parms_id());
         if (it != reg.end()) return it->second;
@@ -158,7 +126,7 @@ public:
     }
     static std::shared_ptr<DeviceContext> find(const seal::parms_id_type &id)
     {
-        std::lock_guard<std::mutex> lk(registry_mutex());
+        std::unique_lock<std::mutex> lk(registry_mutex());
         auto it = registry().find(id);
         if (it == registry().end()) throw std::invalid_argument("no gfx950 device context for these encryption parameters (construct a pasta::PASTA_SEAL first)");
         return it->second;
@@ -175,15 +143,13 @@ private:
         static std::mutex m;
         return m;
     }
-    hhe_ctx *h_ = nullptr;
-    std::size_t n_ = 0, L_ = 0;
-    std::uint64_t t_ = 0;
+    static std::vector<std::uint64_t> primes(const seal::EncryptionParameters &parms)
+    {
+        std::vector<std::uint64_t> q;
+        for (const auto &m : parms.coeff_modulus()) q.push_back(m.value());
+        return q;
+    }
     seal::parms_id_type first_parms_id_{};
-    std::mutex mu_;
-    std::unique_ptr<hhe::KeySetCache> keys_;
-    hhe::DeviceArena arena_;
-    hhe::ContentHash key_hash_;
-    bool key_resident_ = false;
 };
 
 }  // namespace gfx950
@@ -224,19 +190,9 @@ protected:
     size_t bsgs_n2 = 0;
 
     std::shared_ptr<gfx950::DeviceContext> device;  // HBM-resident keys and tables, shared per parameter set
-    // the device key sets of he_rk / he_gk (owned by the device context's cache); an object built without a key gets an empty set of
-    // its own instead of falling through to another object's keys (declared after `device`: released while the context exists)
-    hhe_keyset *rk_set = nullptr, *gk_set = nullptr, *empty_set = nullptr;
-    std::shared_ptr<hhe_keyset> owned_empty;
-    const hhe_keyset *or_empty(const hhe_keyset *ks)
-    {
-        if (ks) return ks;
-        if (!empty_set) {
-            gfx950::check(hhe_keyset_create(device->handle(), &empty_set));
-            owned_empty.reset(empty_set, [](hhe_keyset *k) { hhe_keyset_destroy(k); });
-        }
-        return empty_set;
-    }
+    // the device key sets of he_rk / he_gk, shared with the device context's cache and kept alive by this object when the cache
+    // evicts them; null for an empty key object (declared after `device`: released while the context exists)
+    hhe::KeySet rk_set, gk_set;
 
 public:
     // src/pasta/SEAL_Cipher.cpp:9-36 (all arguments by value, as the reference takes them)
@@ -277,7 +233,7 @@ public:
             sec = seal::sec_level_type::none;
             uint64_t q[64];
             size_t cnt = 64;
-            gfx950::check(hhe_bfv_default_coeff_modulus(mod_degree, q, &cnt));  // the reference's hard-coded 29-prime chain (:50-60)
+            hhe::check(hhe_bfv_default_coeff_modulus(mod_degree, q, &cnt));  // the reference's hard-coded 29-prime chain (:50-60)
             std::vector<seal::Modulus> mods;
             for (size_t i = 0; i < cnt; i++) mods.emplace_back(q[i]);
             parms.set_coeff_modulus(mods);
@@ -298,53 +254,29 @@ public:
     // SEALZpCipher::mask (SEAL_Cipher.cpp:161-166): batch_encoder.encode(mask) + multiply_plain_inplace
     void mask(seal::Ciphertext &cipher, std::vector<uint64_t> &mask)
     {
-        std::lock_guard<std::mutex> lk(device->arena().mutex());
-        std::uint64_t *d = device->arena().get(0, device->ct_words() * 8);
-        device->to_device(cipher, d);
-        gfx950::check(hhe_mask(device->handle(), d, mask.data(), mask.size(), d, 1));
-        device->from_device(*context, d, 2, cipher);
+        device->mask(device->words(cipher), mask.data(), mask.size(), device->into(*context, cipher));
     }
-    // SEALZpCipher::flatten (SEAL_Cipher.cpp:170-181): out = sum_i rotate_rows(in[i], -i * plain_size, galois_keys)
+    // SEALZpCipher::flatten (SEAL_Cipher.cpp:170-181): out = sum_i rotate_rows(in[i], -i * plain_size, galois_keys), with the GaloisKeys
+    // object THIS call names (CSP.cpp:271-278: csp_he_gk)
     void flatten(std::vector<seal::Ciphertext> &in, seal::Ciphertext &out, const seal::GaloisKeys &galois_keys)
     {
-        if (in.empty()) throw std::invalid_argument("flatten: empty input");
-        const hhe_keyset *gk = or_empty(device->galois_set(galois_keys));   // the GaloisKeys object THIS call names (CSP.cpp:271-278: csp_he_gk)
-        const size_t w = device->ct_words();
-        std::lock_guard<std::mutex> lk(device->arena().mutex());
-        std::uint64_t *d = device->arena().get(0, in.size() * w * 8), *o = device->arena().get(1, w * 8);
-        for (size_t i = 0; i < in.size(); i++) device->to_device(in[i], d + i * w);
-        gfx950::check(hhe_flatten_ks(device->handle(), gk, d, in.size(), o, 1));
-        device->from_device(*context, o, 2, out);
+        device->flatten(device->words(in), gfx950::DeviceContext::words(galois_keys), device->into(*context, out));
     }
 
     // packed helpers of the FC (SEAL_Cipher.cpp:547-566)
     void packed_square(seal::Ciphertext &vo, const seal::Ciphertext &vi)
     {
-        const size_t w = device->ct_words();
-        gfx950::DevBuf a(w * 8), o3(device->ct_words(3) * 8);
-        device->to_device(vi, a.u64());
-        gfx950::check(hhe_multiply(device->handle(), a.u64(), a.u64(), o3.u64(), 1));
-        gfx950::check(hhe_relinearize_ks(device->handle(), or_empty(rk_set), o3.u64(), a.u64(), 1));
-        device->from_device(*context, a.u64(), 2, vo);
+        device->square_relinearize(device->words(vi), rk_set, device->into(*context, vo));
     }
     void packed_enc_mul(const seal::Ciphertext &encrypted1, const seal::Ciphertext &encrypted2, seal::Ciphertext &destination)
     {
-        const size_t w = device->ct_words();
-        gfx950::DevBuf a(w * 8), b(w * 8), o3(device->ct_words(3) * 8);
-        device->to_device(encrypted1, a.u64());
-        device->to_device(encrypted2, b.u64());
-        gfx950::check(hhe_multiply(device->handle(), a.u64(), b.u64(), o3.u64(), 1));
-        device->from_device(*context, o3.u64(), 3, destination);
+        device->multiply(device->words(encrypted1), device->words(encrypted2), device->into(*context, destination, 3));
     }
     void packed_enc_add(const seal::Ciphertext &encrypted1, const seal::Ciphertext &encrypted2, seal::Ciphertext &destination)
     {
         if (encrypted1.size() != encrypted2.size()) throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
-        const size_t w = device->ct_words(encrypted1.size());
-        gfx950::DevBuf a(w * 8), b(w * 8);
-        device->to_device(encrypted1, a.u64());
-        device->to_device(encrypted2, b.u64());
-        gfx950::check(hhe_add(device->handle(), a.u64(), b.u64(), a.u64(), 1, static_cast<int>(encrypted1.size())));
-        device->from_device(*context, a.u64(), encrypted1.size(), destination);
+        const size_t size = encrypted1.size();
+        device->add(device->words(encrypted1, size), device->words(encrypted2, size), size, device->into(*context, destination, size));
     }
 };
 
@@ -394,25 +326,9 @@ public:
     {
         (void)batch_encoder;  // ignored by the reference as well (:113)
         if (enc_ssk.empty()) throw std::invalid_argument("decomposition: enc_ssk is empty");
-        const size_t size = ciphertext.size();
-        const size_t num_block = static_cast<size_t>(std::ceil(static_cast<double>(size) / params.cipher_size));
-        std::vector<seal::Ciphertext> res(num_block);
-        if (num_block == 0) return res;
-        std::vector<uint64_t> cw(num_block * PASTA_T, 0), bidx(num_block);
-        std::vector<uint32_t> ncw(num_block);
-        for (size_t b = 0; b < num_block; b++) {
-            const size_t lo = b * params.cipher_size, hi = std::min(lo + params.cipher_size, size);
-            for (size_t i = lo; i < hi; i++) cw[b * PASTA_T + (i - lo)] = ciphertext[i];
-            ncw[b] = static_cast<uint32_t>(hi - lo);
-            bidx[b] = b;  // pasta.init_shake(nonce, b) (:122)
-        }
-        const size_t w = device->ct_words();
-        std::lock_guard<std::mutex> lk(device->arena().mutex());
-        std::uint64_t *key = device->encrypted_key(enc_ssk[0]);  // state <- enc_ssk[0] (:126); uploaded when its contents change
-        std::uint64_t *out = device->arena().get(3, num_block * w * 8);
-        gfx950::check(hhe_pasta3_transcipher_ks(device->handle(), or_empty(rk_set), or_empty(gk_set), key, cw.data(), ncw.data(), bidx.data(),
-                                                num_block, use_bsgs ? 1 : 0, out));
-        for (size_t b = 0; b < num_block; b++) device->from_device(*context, out + b * w, 2, res[b]);
+        std::vector<seal::Ciphertext> res(device->blocks_of(ciphertext.size()));
+        // state <- enc_ssk[0] (:126); uploaded when its contents change
+        device->transcipher(ciphertext, device->words(enc_ssk[0]), rk_set, gk_set, use_bsgs, device->into(*context, res));
         return res;
     }
 
@@ -425,18 +341,8 @@ public:
         std::vector<seal::Ciphertext> res(records.size());
         if (records.empty()) return res;
         if (enc_ssk.empty()) throw std::invalid_argument("decompose: enc_ssk is empty");
-        const size_t nwords = records[0].size(), w = device->ct_words();
-        std::vector<uint64_t> flat(records.size() * nwords);
-        for (size_t s = 0; s < records.size(); s++) {
-            if (records[s].size() != nwords) throw std::invalid_argument("decompose: records of different lengths");
-            std::copy(records[s].begin(), records[s].end(), flat.begin() + s * nwords);
-        }
-        const hhe_keyset *fgk = or_empty(device->galois_set(flatten_gk));
-        std::lock_guard<std::mutex> lk(device->arena().mutex());
-        std::uint64_t *key = device->encrypted_key(enc_ssk[0]), *out = device->arena().get(3, records.size() * w * 8);
-        gfx950::check(hhe_decompose_ks(device->handle(), or_empty(rk_set), or_empty(gk_set), fgk, key, flat.data(), records.size(), nwords,
-                                       mask_last ? 1 : 0, out));
-        for (size_t s = 0; s < records.size(); s++) device->from_device(*context, out + s * w, 2, res[s]);
+        device->decompose(records, device->words(enc_ssk[0]), rk_set, gk_set, gfx950::DeviceContext::words(flatten_gk), mask_last,
+                          device->into(*context, res));
         return res;
     }
 
@@ -475,57 +381,30 @@ private:
 // sealhelper::packed_enc_multiply / encrypted_vec_sum (src/util/sealhelper.h:84-129, sealhelper.cpp:268-274,379-392) with the
 // reference's signatures; the Evaluator argument is unused (the device context is found through the ciphertext's parms_id).
 namespace sealhelper {
+using pasta::gfx950::DeviceContext;
 
 inline void packed_enc_multiply(const seal::Ciphertext &encrypted1, const seal::Ciphertext &encrypted2, seal::Ciphertext &destination,
                                 const seal::Evaluator &evaluator)
 {
     (void)evaluator;
-    auto dev = pasta::gfx950::DeviceContext::find(encrypted1.parms_id());
-    const size_t w = dev->ct_words();
-    pasta::gfx950::DevBuf a(w * 8), b(w * 8), o3(dev->ct_words(3) * 8);
-    dev->to_device(encrypted1, a.u64());
-    dev->to_device(encrypted2, b.u64());
-    pasta::gfx950::check(hhe_multiply(dev->handle(), a.u64(), b.u64(), o3.u64(), 1));
-    // the result ciphertext keeps the parameters of its inputs; resize needs the SEALContext, which a Ciphertext does not
-    // carry: destination is sized from encrypted1 (same parms_id, pool) and grown to three polynomials
-    destination = encrypted1;
-    destination.resize(3);
-    pasta::gfx950::check(hhe_copy_d2h(dev->handle(), destination.data(), o3.u64(), dev->ct_words(3) * 8));
+    auto dev = DeviceContext::find(encrypted1.parms_id());
+    dev->multiply(dev->words(encrypted1), dev->words(encrypted2), DeviceContext::into(destination, encrypted1, 3));
 }
 
 // Evaluator::relinearize_inplace(record, csp_rk) as the CSP calls it between the two (CSP.cpp:306), on the device, with the
 // RelinKeys object the call names (its key set is uploaded the first time the object is seen).
 inline void relinearize_inplace(seal::Ciphertext &encrypted, const seal::RelinKeys &relin_keys)
 {
-    auto dev = pasta::gfx950::DeviceContext::find(encrypted.parms_id());
-    hhe_keyset *rk = dev->relin_set(relin_keys);
-    if (!rk) throw std::invalid_argument("relin_keys is not valid for encryption parameters");
-    pasta::gfx950::DevBuf a3(dev->ct_words(3) * 8), o(dev->ct_words() * 8);
-    if (encrypted.size() != 3) throw std::invalid_argument("encrypted is not valid for encryption parameters");
-    pasta::gfx950::check(hhe_copy_h2d(dev->handle(), a3.u64(), encrypted.data(), dev->ct_words(3) * 8));
-    pasta::gfx950::check(hhe_relinearize_ks(dev->handle(), rk, a3.u64(), o.u64(), 1));
-    encrypted.resize(2);
-    pasta::gfx950::check(hhe_copy_d2h(dev->handle(), encrypted.data(), o.u64(), dev->ct_words() * 8));
+    auto dev = DeviceContext::find(encrypted.parms_id());
+    dev->relinearize(dev->words(encrypted, 3), DeviceContext::words(relin_keys), DeviceContext::into(encrypted, encrypted));
 }
 
 inline void encrypted_vec_sum(const seal::Ciphertext &encrypted_inp, seal::Ciphertext &destination, const seal::Evaluator &evaluator,
                               const seal::GaloisKeys &gal_keys, const size_t vec_size)
 {
     (void)evaluator;
-    auto dev = pasta::gfx950::DeviceContext::find(encrypted_inp.parms_id());
-    hhe_keyset *gk = dev->galois_set(gal_keys);
-    if (!gk) throw std::invalid_argument("Galois key not present");
-    const size_t w = dev->ct_words();
-    pasta::gfx950::DevBuf in(w * 8), acc(w * 8), rot(w * 8);
-    dev->to_device(encrypted_inp, in.u64());
-    // destination = encrypted_inp; for i = -1 .. -(vec_size-1): destination += rotate_rows(encrypted_inp, i)  (sealhelper.cpp:385-391)
-    pasta::gfx950::check(hhe_rotate_rows_ks(dev->handle(), gk, in.u64(), 0, acc.u64(), 1));  // step 0: a copy, as in SEAL
-    for (size_t i = 1; i < vec_size; i++) {
-        pasta::gfx950::check(hhe_rotate_rows_ks(dev->handle(), gk, in.u64(), -static_cast<int>(i), rot.u64(), 1));
-        pasta::gfx950::check(hhe_add(dev->handle(), acc.u64(), rot.u64(), acc.u64(), 1, 2));
-    }
-    destination = encrypted_inp;
-    pasta::gfx950::check(hhe_copy_d2h(dev->handle(), destination.data(), acc.u64(), w * 8));
+    auto dev = DeviceContext::find(encrypted_inp.parms_id());
+    dev->vec_sum(dev->words(encrypted_inp), DeviceContext::words(gal_keys), vec_size, DeviceContext::into(destination, encrypted_inp));
 }
 
 // The three FC calls of CSP_hhe_pktnn_1fc::evaluateModel (CSP.cpp:296-316) as ONE device call: multiply, relinearize with
@@ -533,17 +412,8 @@ inline void encrypted_vec_sum(const seal::Ciphertext &encrypted_inp, seal::Ciphe
 inline void fc_row(const seal::Ciphertext &vi, const seal::Ciphertext &w_row, const seal::RelinKeys &csp_rk, const seal::GaloisKeys &gal_keys,
                    size_t vec_size, seal::Ciphertext &destination)
 {
-    auto dev = pasta::gfx950::DeviceContext::find(vi.parms_id());
-    hhe_keyset *rk = dev->relin_set(csp_rk), *gk = dev->galois_set(gal_keys);
-    if (!rk || !gk) throw std::invalid_argument("fc_row: empty key object");
-    const size_t w = dev->ct_words();
-    std::lock_guard<std::mutex> lk(dev->arena().mutex());
-    std::uint64_t *a = dev->arena().get(0, w * 8), *b = dev->arena().get(1, w * 8), *o = dev->arena().get(3, w * 8);
-    dev->to_device(vi, a);
-    dev->to_device(w_row, b);
-    pasta::gfx950::check(hhe_fc_row_ks(dev->handle(), rk, gk, a, b, 1, vec_size, o, 1));
-    destination = vi;
-    pasta::gfx950::check(hhe_copy_d2h(dev->handle(), destination.data(), o, w * 8));
+    auto dev = DeviceContext::find(vi.parms_id());
+    dev->fc_row(dev->words(vi), dev->words(w_row), DeviceContext::words(csp_rk), DeviceContext::words(gal_keys), vec_size, DeviceContext::into(destination, vi));
 }
 
 }  // namespace sealhelper

@@ -1,5 +1,6 @@
 // mirror_main.cpp -- drives include/pasta_seal_gfx950.hpp the way CSP.cpp:238-251 drives the reference
-// classes: build PASTA_SEAL from context + keys, call decomposition on one record, flatten the blocks.
+// classes: build PASTA_SEAL from context + keys, call decomposition on one record, flatten the blocks; then mask, the
+// three-call FC of CSP.cpp:296-316 and a key-set cache that is smaller than the number of live key objects.
 // Input/output are raw uint64 blobs written/read by tests/test_cpp_mirror.py.
 #include <cstdio>
 #include <cstdlib>
@@ -41,6 +42,16 @@ int main(int argc, char **argv)
     }
     pasta::RelinKeys csp_rk{read_words(f, ksk)};
     pasta::Ciphertext w_row{read_words(f, ctw), 2};
+    // two more analysts' key objects (same secret key, other randomness; same Galois elements as gk) for the eviction sequence
+    pasta::RelinKeys more_rk[2];
+    pasta::GaloisKeys more_gk[2];
+    for (int a = 0; a < 2; a++) {
+        more_rk[a].key = read_words(f, ksk);
+        for (uint64_t i = 0; i < hdr[3]; i++) {
+            uint32_t elt = (uint32_t)read_words(f, 1)[0];
+            more_gk[a].keys[elt] = read_words(f, ksk);
+        }
+    }
     fclose(f);
     try {
         auto ctx = std::make_shared<pasta::HheContext>(logn, q, hdr[2], 0);
@@ -94,6 +105,34 @@ int main(int argc, char **argv)
         fwrite(fc.words.data(), 8, fc.words.size(), o);
         printf("key objects uploaded: %llu, resident sets: %zu, encrypted-key uploads: %llu\n", (unsigned long long)ctx->keys().uploads(),
                ctx->keys().resident(), (unsigned long long)ctx->key_uploads);
+        // SEALZpCipher::mask on the ragged last block (300 = 2 * 128 + 44 words), as CSP.cpp:264-269 means to
+        std::vector<uint64_t> ones(record.size() % 128, 1);
+        pasta::Ciphertext masked = blocks.back();
+        HHE.mask(masked, ones);
+        fwrite(masked.words.data(), 8, masked.words.size(), o);
+        // the FC row as the three calls CSP.cpp:296-316 makes, with the key objects it names
+        pasta::Ciphertext fc3, sum3;
+        sealhelper::packed_enc_multiply(*ctx, batch[0], w_row, fc3);
+        sealhelper::relinearize_inplace(*ctx, fc3, csp_rk);
+        sealhelper::encrypted_vec_sum(*ctx, fc3, sum3, csp_gk, 3);
+        fwrite(sum3.words.data(), 8, sum3.words.size(), o);
+        // a cache of 2 sets under three live cipher objects of three analysts (6 key objects): the first object's sets have left the
+        // cache when it is used, and it still computes with ITS keys
+        {
+            auto small = std::make_shared<pasta::HheContext>(logn, q, hdr[2], 0, 2);
+            pasta::PASTA_SEAL first(small, pasta::PublicKey{}, pasta::SecretKey{}, rk, gk);
+            pasta::PASTA_SEAL second(small, pasta::PublicKey{}, pasta::SecretKey{}, more_rk[0], more_gk[0]);
+            pasta::PASTA_SEAL third(small, pasta::PublicKey{}, pasta::SecretKey{}, more_rk[1], more_gk[1]);
+            pasta::Ciphertext esq, eflat;
+            first.packed_square(esq, blocks[0]);
+            std::vector<pasta::Ciphertext> eb = first.decomposition(record, {enc_key}, true);
+            first.flatten(eb, eflat);
+            fwrite(esq.words.data(), 8, esq.words.size(), o);
+            for (auto &b : eb) fwrite(b.words.data(), 8, b.words.size(), o);
+            fwrite(eflat.words.data(), 8, eflat.words.size(), o);
+            printf("capacity 2: key objects uploaded: %llu, resident sets: %zu\n", (unsigned long long)small->keys().uploads(),
+                   small->keys().resident());
+        }
         fclose(o);
         try { pasta::PASTA bad(ctx, std::vector<uint64_t>(255, 1), hdr[2]); printf("NO THROW\n"); return 3; }
         catch (const std::runtime_error &e) { printf("throws: %s\n", e.what()); }
