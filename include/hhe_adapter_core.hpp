@@ -7,6 +7,8 @@
 //                call (SEAL_Cipher.cpp:9-36, CSP.cpp:238-242), so pointers say nothing; contents do.  An object is uploaded
 //                once and stays resident with everything derived from it; beyond `max_sets` (a CSP that serves many analysts) the
 //                cache lets go of the least recently used sets.
+//   MatrixCache  maps every public matrix (+ bias, + method) a packed affine layer is called with to one device handle (hhe_matrix), by
+//                the same kind of content hash: a CSP that applies the same layer per request uploads it once.
 //   DeviceArena  grow-only device buffers reused across calls instead of a hipMalloc / hipFree pair per call.
 //   AdapterCore  the hhe_ctx, its cache, its arena, the resident encrypted PASTA key and the call bodies.
 //
@@ -151,6 +153,64 @@ private:
     uint64_t uploads_ = 0;
 };
 
+// add_diagonal_indices / add_bsgs_indices (SEAL_Cipher.cpp:337-355): the rotation steps of a packed affine layer, appended
+inline void diagonal_indices(size_t slot_count, size_t size, std::vector<int> &gk_indices)
+{
+    if (size * 2 != slot_count) gk_indices.push_back(-((int)size));
+    gk_indices.push_back(1);
+}
+inline void bsgs_indices(size_t slot_count, uint64_t n1, uint64_t n2, std::vector<int> &gk_indices)
+{
+    diagonal_indices(slot_count, n1 * n2, gk_indices);
+    if (n1 == 1 || n2 == 1) return;
+    for (uint64_t k = 1; k < n2; k++) gk_indices.push_back((int)(k * n1));
+}
+
+// Public matrices of packed affine layers by content: (dim, n1, n2, every word of the matrix and of the bias).  Shared ownership
+// like KeySetCache: eviction beyond `max_matrices` drops the cache's reference, a call that still computes with a handle keeps it.
+typedef std::shared_ptr<hhe_matrix> Matrix;
+class MatrixCache {
+public:
+    explicit MatrixCache(hhe_ctx *ctx, size_t max_matrices = 8) : ctx_(ctx), max_(max_matrices) {}
+    // M: row-major dim x dim; bias: dim words or null; n1 = n2 = 0: diagonal method
+    Matrix get(const uint64_t *M, size_t dim, const uint64_t *bias, size_t n1, size_t n2)
+    {
+        ContentHash h;
+        h.add_tag(0x6d61);  // "ma"
+        h.add_tag(dim); h.add_tag(n1); h.add_tag(n2);
+        h.add(M, dim * dim);
+        h.add_tag(bias ? 1 : 0);
+        if (bias) h.add(bias, dim);
+        std::lock_guard<std::mutex> lk(mu_);
+        auto it = index_.find(h);
+        if (it != index_.end()) {
+            lru_.splice(lru_.begin(), lru_, it->second);
+            return it->second->second;
+        }
+        hhe_matrix *raw = nullptr;
+        check(hhe_matrix_create(ctx_, M, dim, bias, n1, n2, &raw));
+        Matrix m(raw, hhe_matrix_destroy);
+        ++uploads_;
+        lru_.emplace_front(h, m);
+        index_[h] = lru_.begin();
+        while (lru_.size() > max_) {
+            index_.erase(lru_.back().first);
+            lru_.pop_back();
+        }
+        return m;
+    }
+    size_t resident() const { return lru_.size(); }
+    uint64_t uploads() const { return uploads_; }   // how many matrices were sent to the device (a repeated one is not)
+
+private:
+    hhe_ctx *ctx_;
+    size_t max_;
+    std::mutex mu_;
+    std::list<std::pair<ContentHash, Matrix>> lru_;
+    std::map<ContentHash, std::list<std::pair<ContentHash, Matrix>>::iterator> index_;
+    uint64_t uploads_ = 0;
+};
+
 // A few grow-only device buffers ("slots"); a call takes the arena's lock for its duration (the library serialises calls on one
 // context anyway) and gets buffers that survive the call.
 class DeviceArena {
@@ -176,16 +236,17 @@ private:
 
 class AdapterCore {
 public:
-    // q: coeff_modulus incl. the special prime; max_sets: capacity of the key-set cache
-    AdapterCore(int logn, const std::vector<uint64_t> &q, uint64_t t, int device = 0, size_t max_sets = 16)
+    // q: coeff_modulus incl. the special prime; max_sets / max_matrices: capacities of the key-set and the matrix cache
+    AdapterCore(int logn, const std::vector<uint64_t> &q, uint64_t t, int device = 0, size_t max_sets = 16, size_t max_matrices = 8)
         : n_((size_t)1 << logn), L_(q.size() - 1), t_(t), h_(create(logn, q, t, device), hhe_ctx_destroy), keys_(h_.get(), max_sets),
-          empty_(keys_.new_set()) {}
+          empty_(keys_.new_set()), mats_(h_.get(), max_matrices) {}
 
     size_t poly_modulus_degree() const { return n_; }
     size_t data_limbs() const { return L_; }
     size_t ct_words(size_t size = 2) const { return size * L_ * n_; }
     uint64_t plain_modulus() const { return t_; }
     KeySetCache &keys() { return keys_; }
+    MatrixCache &matrices() { return mats_; }
     uint64_t key_uploads = 0;  // instrumentation: how often an encrypted PASTA key was sent to the device
 
     // SEALZpCipher::mask (SEAL_Cipher.cpp:161-166)
@@ -209,6 +270,30 @@ public:
         for (size_t i = 0; i < in.size(); i++) upload(d + i * w, in[i]);
         check(hhe_flatten_ks(h(), g.get(), d, in.size(), o, 1));
         download(o, 1, 2, dst);
+    }
+
+    // SEALZpCipher::packed_matMul / packed_affine (SEAL_Cipher.cpp:522-543): vo = M * vi (+ b) with the public matrix M, by
+    // babystep-giantstep when use_bsgs && n1 != 1 && n2 != 1, else by the diagonal method; bias: null for packed_matMul.  The rotations
+    // use the Galois keys the cipher object holds (he_gk).  The reference only warns when n1 * n2 != dim; here that is invalid_argument.
+    template <class Sink>
+    void packed_affine(const std::vector<std::vector<uint64_t>> &M, const std::vector<uint64_t> *bias, bool use_bsgs, size_t n1, size_t n2,
+                       const uint64_t *ct, const KeySet &gk, Sink dst)
+    {
+        const size_t dim = M.size();
+        if (!dim) throw std::invalid_argument("packed_matMul: empty matrix");
+        if (bias && bias->size() != dim) throw std::invalid_argument("packed_affine: bias and matrix dimensions differ");
+        std::vector<uint64_t> flat(dim * dim);
+        for (size_t r = 0; r < dim; r++) {
+            if (M[r].size() != dim) throw std::invalid_argument("packed_matMul: matrix is not square");
+            std::copy(M[r].begin(), M[r].end(), flat.begin() + r * dim);
+        }
+        const bool bsgs = use_bsgs && n1 != 1 && n2 != 1;
+        std::lock_guard<std::mutex> lk(arena_.mutex());
+        const Matrix m = mats_.get(flat.data(), dim, bias ? bias->data() : nullptr, bsgs ? n1 : 0, bsgs ? n2 : 0);
+        uint64_t *d = arena_.get(0, ct_words() * 8);
+        upload(d, ct);
+        check(hhe_packed_affine_ks(h(), or_empty(gk).get(), m.get(), d, d, 1));
+        download(d, 1, 2, dst);
     }
 
     // Evaluator::multiply -> size 3; add of two size-`size` ciphertexts; square + relinearize_inplace(rk); relinearize_inplace(rk)
@@ -374,6 +459,7 @@ private:
     std::unique_ptr<hhe_ctx, void (*)(hhe_ctx *)> h_;  // declared before the key sets: destroyed after every set the core holds
     KeySetCache keys_;
     KeySet empty_;   // what a cipher object built without some key runs with; nothing can put a key into it
+    MatrixCache mats_;   // declared after the context, like the key sets: every handle dies before it
     DeviceArena arena_;
     ContentHash key_hash_;
     bool key_resident_ = false;

@@ -194,6 +194,33 @@ int hhe_fc_row(hhe_ctx *c, const uint64_t *vi_dptr, const uint64_t *w_dptr, size
 int hhe_fc_row_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const uint64_t *vi_dptr, const uint64_t *w_dptr, size_t W,
                   size_t n_inputs, uint64_t *out_dptr, size_t B);
 
+/* ---- packed plain-matrix affine layers: SEALZpCipher::packed_matMul / packed_affine (src/pasta/SEAL_Cipher.cpp:522-543), a PUBLIC
+ *      dim x dim matrix times an encrypted packed vector plus a plain bias, by the diagonal method (:271-313) or babystep-giantstep
+ *      (:185-267).  The matrix is a resident handle, created once per matrix like a key set: it names its context, everything derived
+ *      from it lives with it, and it is destroyed explicitly (hhe_ctx_destroy releases forgotten ones).  M_hptr: row-major dim x dim,
+ *      entries < t; bias_hptr: dim words or NULL (packed_matMul).  n1 = n2 = 0: diagonal method; otherwise babystep-giantstep with
+ *      n1 * n2 == dim (else HHE_ERR_INVALID; the reference only warns and computes garbage); n1 == 1 or n2 == 1 takes the diagonal
+ *      method, as packed_matMul does.  dim need not be a power of two.  dim * 2 != N && dim * 4 > N: HHE_ERR_TOO_FEW_SLOTS (:192-193).
+ *      Device footprint (hhe_matrix_bytes): 2 * dim * L * N words for the diagonal method (multipliers in the rotated NTT frame and
+ *      their Shoup quotients), dim * L * N for babystep-giantstep, plus N words of bias: 201 MB / 101 MB at dim = 128, N = 2^15,
+ *      L = 3.  Handles are not part of the block-table cache and are never evicted.
+ *      One difference from SEAL: a diagonal that is all zero is multiplied like any other, where Evaluator::multiply_plain throws on
+ *      the transparent product. ---- */
+typedef struct hhe_matrix hhe_matrix;
+int hhe_matrix_create(hhe_ctx *c, const uint64_t *M_hptr, size_t dim, const uint64_t *bias_hptr, size_t n1, size_t n2, hhe_matrix **out);
+void hhe_matrix_destroy(hhe_matrix *m);
+size_t hhe_matrix_bytes(const hhe_matrix *m);
+/* out[b] = M * ct[b] (+ bias) for B ciphertexts [B][2][L][N] sharing the matrix; out_dptr == ct_dptr is allowed.  Includes the
+ * non-full-packed preparation ct += rotate_rows(ct, -dim) when N != 2 dim and add_plain(encode(bias)).  gk: the GaloisKeys object
+ * (NULL = the context's default set); it needs the steps of hhe_affine_galois_steps -- step +1 as a key of its own, the others directly
+ * or through their NAF terms -- else HHE_ERR_NO_GALOIS_KEY with out untouched.  The batch is chunked over the internal streams like
+ * hhe_pasta3_transcipher (HHE_CHUNK, HHE_STREAMS); babystep-giantstep keeps n1 + n2 ciphertexts per item of a chunk as workspace on top of
+ * the lane's.  Synchronous. */
+int hhe_packed_affine_ks(hhe_ctx *c, const hhe_keyset *gk, const hhe_matrix *mat, const uint64_t *ct_dptr, uint64_t *out_dptr, size_t B);
+/* add_diagonal_indices / add_bsgs_indices (:337-355), host only: the rotate_rows steps a layer needs keys for, in the reference's
+ * order.  *count: in = capacity of steps_out, out = number of steps (HHE_ERR_CAPACITY when too small). */
+int hhe_affine_galois_steps(size_t N, size_t dim, size_t n1, size_t n2, int *steps_out, size_t *count);
+
 /* PASTA-3 public randomness for one block as the kernels consume it (host; src/pasta/pasta_3_plain.cpp:56-119,286-295):
  * mats [4][2][128][128], rcs [4][2][128] */
 int hhe_pasta3_block_randomness(uint64_t t, uint64_t block_index, uint64_t *mats_hptr, uint64_t *rcs_hptr);

@@ -45,8 +45,8 @@ struct SecretKey { std::vector<uint64_t> words; };
 // context (keys(): the key-set cache, key_uploads); max_key_sets is the cache's capacity
 class HheContext : public hhe::AdapterCore {
 public:
-    HheContext(int logn, std::vector<uint64_t> coeff_modulus, uint64_t plain_modulus, int device = 0, size_t max_key_sets = 16)
-    try : hhe::AdapterCore(logn, coeff_modulus, plain_modulus, device, max_key_sets) {}
+    HheContext(int logn, std::vector<uint64_t> coeff_modulus, uint64_t plain_modulus, int device = 0, size_t max_key_sets = 16, size_t max_matrices = 8)
+    try : hhe::AdapterCore(logn, coeff_modulus, plain_modulus, device, max_key_sets, max_matrices) {}
     catch (const std::invalid_argument &e) { throw std::invalid_argument(std::string("encryption parameters are not set correctly: ") + e.what()); }
 };
 
@@ -76,6 +76,7 @@ inline auto into(const HheContext &ctx, std::vector<Ciphertext> &cts) { return [
 class SEALZpCipher {
 public:
     typedef std::vector<uint64_t> vector;
+    typedef std::vector<std::vector<uint64_t>> matrix;
 
     SEALZpCipher(ZpCipherParams params, std::shared_ptr<HheContext> con, PublicKey pk, SecretKey sk, RelinKeys rk, GaloisKeys gk)
         : params(params), context(std::move(con)), he_pk(std::move(pk)), he_sk(std::move(sk))
@@ -111,6 +112,8 @@ public:
     void activate_bsgs(bool activate) { use_bsgs = activate; }
     void set_bsgs_params(uint64_t n1, uint64_t n2) { bsgs_n1 = n1; bsgs_n2 = n2; }
     void add_some_gk_indices(std::vector<int> &gk_ind) { for (int i : gk_ind) gk_indices.push_back(i); }
+    void add_bsgs_indices(uint64_t n1, uint64_t n2) { hhe::bsgs_indices(mod_degree, n1, n2, gk_indices); }   // SEAL_Cipher.cpp:337-346
+    void add_diagonal_indices(size_t size) { hhe::diagonal_indices(mod_degree, size, gk_indices); }          // :350-355
     const std::vector<int> &get_gk_indices() const { return gk_indices; }
 
     // SEALZpCipher::mask (SEAL_Cipher.cpp:161-166)
@@ -140,6 +143,16 @@ public:
     void packed_square(Ciphertext &vo, const Ciphertext &vi)  // evaluator.square + relinearize_inplace(he_rk)
     {
         context->square_relinearize(detail::words(*context, vi), rk_set, detail::into(*context, vo));
+    }
+
+    // SEALZpCipher::packed_matMul / packed_affine (SEAL_Cipher.cpp:522-543): vo = M * vi (+ b), M public, with this object's Galois keys
+    void packed_matMul(Ciphertext &vo, const matrix &M, const Ciphertext &vi)
+    {
+        context->packed_affine(M, nullptr, use_bsgs, bsgs_n1, bsgs_n2, detail::words(*context, vi), gk_set, detail::into(*context, vo));
+    }
+    void packed_affine(Ciphertext &vo, const matrix &M, const Ciphertext &vi, const vector &b)
+    {
+        context->packed_affine(M, &b, use_bsgs, bsgs_n1, bsgs_n2, detail::words(*context, vi), gk_set, detail::into(*context, vo));
     }
 
 protected:

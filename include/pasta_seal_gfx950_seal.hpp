@@ -218,6 +218,8 @@ public:
     {
         for (auto &it : gk_ind) gk_indices.push_back(it);
     }
+    void add_bsgs_indices(uint64_t bsgs_n1, uint64_t bsgs_n2) { hhe::bsgs_indices(batch_encoder.slot_count(), bsgs_n1, bsgs_n2, gk_indices); }
+    void add_diagonal_indices(size_t size) { hhe::diagonal_indices(batch_encoder.slot_count(), size, gk_indices); }
     void create_gk() { keygen.create_galois_keys(gk_indices, he_gk); gk_set = device->galois_set(he_gk); }
 
     virtual std::string get_cipher_name() const = 0;
@@ -261,6 +263,16 @@ public:
     void flatten(std::vector<seal::Ciphertext> &in, seal::Ciphertext &out, const seal::GaloisKeys &galois_keys)
     {
         device->flatten(device->words(in), gfx950::DeviceContext::words(galois_keys), device->into(*context, out));
+    }
+
+    // SEALZpCipher::packed_matMul / packed_affine (SEAL_Cipher.cpp:522-543): vo = M * vi (+ b), M public, rotations with he_gk
+    void packed_matMul(seal::Ciphertext &vo, const matrix &M, const seal::Ciphertext &vi)
+    {
+        device->packed_affine(M, nullptr, use_bsgs, bsgs_n1, bsgs_n2, device->words(vi), gk_set, device->into(*context, vo));
+    }
+    void packed_affine(seal::Ciphertext &vo, const matrix &M, const seal::Ciphertext &vi, const vector &b)
+    {
+        device->packed_affine(M, &b, use_bsgs, bsgs_n1, bsgs_n2, device->words(vi), gk_set, device->into(*context, vo));
     }
 
     // packed helpers of the FC (SEAL_Cipher.cpp:547-566)

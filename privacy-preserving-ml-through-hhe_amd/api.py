@@ -38,6 +38,7 @@ _SYMBOLS = [
     "hhe_pasta3_set_block_cache_limit", "hhe_keyset_create", "hhe_keyset_destroy", "hhe_keyset_set_relin", "hhe_keyset_set_galois", "hhe_keyset_has_galois", "hhe_keyset_has_relin",
     "hhe_apply_galois_ks", "hhe_rotate_rows_ks", "hhe_rotate_columns_ks", "hhe_relinearize_ks", "hhe_pasta3_transcipher_ks",
     "hhe_flatten_ks", "hhe_decompose_ks", "hhe_fc_row_ks", "hhe_seal_load_relin_keys_ks", "hhe_seal_load_galois_keys_ks",
+    "hhe_matrix_create", "hhe_matrix_destroy", "hhe_matrix_bytes", "hhe_packed_affine_ks", "hhe_affine_galois_steps",
 ]
 
 
@@ -71,6 +72,10 @@ def load_library(path=None):
     lib.hhe_pasta3_clear_block_cache.argtypes = [C.c_void_p]
     lib.hhe_keyset_destroy.argtypes = [C.c_void_p]
     lib.hhe_keyset_destroy.restype = None
+    lib.hhe_matrix_destroy.argtypes = [C.c_void_p]
+    lib.hhe_matrix_destroy.restype = None
+    lib.hhe_matrix_bytes.argtypes = [C.c_void_p]
+    lib.hhe_matrix_bytes.restype = C.c_size_t
     return lib
 
 
@@ -141,6 +146,36 @@ class KeySet:
         used, cnt = C.c_size_t(0), C.c_uint32(0)
         self.ctx._chk(self.ctx.lib.hhe_seal_load_galois_keys_ks(self.h, buf, C.c_size_t(len(blob)), C.byref(used), C.byref(cnt)))
         return int(used.value), int(cnt.value)
+
+
+class Matrix:
+    """One public matrix of a packed affine layer on the device (hhe_matrix), with its optional bias."""
+
+    def __init__(self, ctx, M, bias=None, bsgs=None):
+        M = np.ascontiguousarray(M, dtype=np.uint64)
+        assert M.ndim == 2 and M.shape[0] == M.shape[1]
+        self.ctx, self.dim = ctx, M.shape[0]
+        self.n1, self.n2 = (int(bsgs[0]), int(bsgs[1])) if bsgs else (0, 0)
+        b = None if bias is None else np.ascontiguousarray(bias, dtype=np.uint64)
+        assert b is None or b.shape == (self.dim,)
+        h = C.c_void_p()
+        ctx._chk(ctx.lib.hhe_matrix_create(ctx.h, _ptr(M), C.c_size_t(self.dim), _ptr(b), C.c_size_t(self.n1), C.c_size_t(self.n2), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.hhe_matrix_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def nbytes(self):
+        return int(self.ctx.lib.hhe_matrix_bytes(self.h))
 
 
 class Context:
@@ -242,6 +277,14 @@ class Context:
 
     def rotate_columns(self, ct, out, B, gk=None):
         self._chk(self.lib.hhe_rotate_columns_ks(self.h, _ks(gk), _ptr(ct), _ptr(out), C.c_size_t(B)))
+
+    def matrix(self, M, bias=None, bsgs=None):
+        """resident plain matrix (+ bias) of a packed affine layer; bsgs = (n1, n2) or None for the diagonal method"""
+        return Matrix(self, M, bias, bsgs)
+
+    def packed_affine(self, ct, mat, out, B, gk=None):
+        """out[b] = M * ct[b] (+ bias) on packed ciphertexts (SEALZpCipher::packed_matMul / packed_affine)"""
+        self._chk(self.lib.hhe_packed_affine_ks(self.h, _ks(gk), mat.h, _ptr(ct), _ptr(out), C.c_size_t(B)))
 
     def multiply(self, a, b, out3, B):
         self._chk(self.lib.hhe_multiply(self.h, _ptr(a), _ptr(b), _ptr(out3), C.c_size_t(B)))
@@ -356,6 +399,17 @@ def bfv_default_coeff_modulus(n, lib=None):
     out = np.zeros(64, np.uint64)
     cnt = C.c_size_t(64)
     rc = lib.hhe_bfv_default_coeff_modulus(C.c_size_t(n), _ptr(out), C.byref(cnt))
+    if rc:
+        raise HheError(rc, lib.hhe_last_error().decode())
+    return [int(v) for v in out[:cnt.value]]
+
+
+def affine_galois_steps(n, dim, n1=0, n2=0, lib=None):
+    """the rotate_rows steps a packed affine layer needs Galois keys for (add_diagonal_indices / add_bsgs_indices)"""
+    lib = lib or load_library()
+    out = (C.c_int * 64)()
+    cnt = C.c_size_t(64)
+    rc = lib.hhe_affine_galois_steps(C.c_size_t(n), C.c_size_t(dim), C.c_size_t(n1), C.c_size_t(n2), out, C.byref(cnt))
     if rc:
         raise HheError(rc, lib.hhe_last_error().decode())
     return [int(v) for v in out[:cnt.value]]

@@ -501,17 +501,32 @@ void l0_flush(hhe_ctx *c, const L0Capture &cap, int first, int steps)
     p.mul_ptrs = c->l0_ptrs; p.mul_shift = (size_t)first * ln; p.mul_step_stride = ln;
     k_perm(p, c->w->stream);
 }
-int matmul_diagonal_fused(hhe_ctx *c, int layer, const u64 *const *d_pdiag_ptrs, size_t B, const L0Capture *cap = nullptr)
+// What the loop is run for: PASTA's affine layer `layer` (128 steps of rotate_rows(-1), the tables of ensure_block) or a plain-matrix
+// handle (hhe_matrix: dim steps of rotate_rows(+1), one table for every item)
+struct DiagSched {
+    int steps;      // diagonals = states of the chain
+    int rot_step;   // the chain's rotate_rows step; the tables are composed with the NTT-domain map of its Galois element
+    int pre_step;   // non-full-packed preparation: state += rotate_rows(state, pre_step); 0: none
+    size_t base;    // words from an item's table pointer to diagonal 0 ([steps][L][N] follow)
+    size_t s_off;   // words from a multiplier to its Shoup quotient
+};
+DiagSched pasta_sched(const hhe_ctx *c, int layer)
+{
+    const size_t ln = (size_t)c->L * c->n;
+    return DiagSched{PASTA_T, -1, c->n / 2 != (size_t)PASTA_T ? PASTA_T : 0, (size_t)layer * PASTA_T * ln, (size_t)(PASTA_R + 1) * PASTA_T * ln};
+}
+int matmul_diagonal_fused(hhe_ctx *c, const DiagSched &sch, const u64 *const *d_pdiag_ptrs, size_t B, const L0Capture *cap = nullptr)
 {
     const int L = c->L, K = c->K;
     const size_t n = c->n, ln = (size_t)L * n, bln = B * ln;
+    const int nsteps = sch.steps;
     u64 *state = c->w->ws_ct[0];
-    if (n / 2 != PASTA_T) {
-        int rc = op_rotate_rows(c, state, PASTA_T, c->w->ws_ct[2], B);
+    if (sch.pre_step) {
+        int rc = op_rotate_rows(c, state, sch.pre_step, c->w->ws_ct[2], B);
         if (rc) return rc;
         op_add(c, state, c->w->ws_ct[2], state, B, 2);
     }
-    const u32 g = galois_elt_from_step(c, -1);
+    const u32 g = galois_elt_from_step(c, sch.rot_step);
     auto it = c->gks->gk.find(g);
     if (it == c->gks->gk.end()) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
     const u64 *key = it->second;
@@ -539,7 +554,7 @@ int matmul_diagonal_fused(hhe_ctx *c, int layer, const u64 *const *d_pdiag_ptrs,
     // the shared chain takes the separate-kernel step for every N: one ciphertext is latency-bound either way, and the row kernel's
     // profile counters (hhe_ctx_profile) keep counting batch launches only
     const bool rowk = use_row_kernel(c) && !cap;
-    const size_t pdiag_words = (size_t)(PASTA_R + 1) * PASTA_T * ln;  // the Shoup quotients of pdiag follow the table (ensure_block)
+    const size_t pdiag_words = sch.s_off;  // the Shoup quotients of pdiag follow the table (ensure_block, hhe_matrix_create)
     const u64 *key_s = nullptr;
     if (rowk) {
         int rc = ensure_key_shoup(c, key, &key_s);
@@ -599,8 +614,8 @@ int matmul_diagonal_fused(hhe_ctx *c, int layer, const u64 *const *d_pdiag_ptrs,
         a1.aux_r = r; a1.aux_out = d_dst; a1.gal_elt = g;
         k_ntt2_inv(as, a1, c->w->stream);
     };
-    for (int i = 0; i < PASTA_T - 1; ++i) {
-        const size_t shift = ((size_t)layer * PASTA_T + i) * ln;
+    for (int i = 0; i < nsteps - 1; ++i) {
+        const size_t shift = sch.base + (size_t)i * ln;
         d_src = d_of(i); d_dst = d_of(i + 1);
         if (cap && (i + 1) % cap->S == 0) {
             // the table is full (state i sits in its last slot) and this step writes state i + 1 into slot 0: finish state i's c0,
@@ -624,18 +639,18 @@ int matmul_diagonal_fused(hhe_ctx *c, int layer, const u64 *const *d_pdiag_ptrs,
     if (krc) return dev_fail("matmul: key-switch row kernel");
     if (k5_pending) k_ntt(k5, false, c->w->stream);
     if (cap) {   // the last block of states; the items' tails (shared_l0_tail) follow on their own lanes
-        const int first = (PASTA_T - 1) / cap->S * cap->S;
-        l0_flush(c, *cap, first, PASTA_T - first);
+        const int first = (nsteps - 1) / cap->S * cap->S;
+        l0_flush(c, *cap, first, nsteps - first);
         return HHE_OK;
     }
-    const size_t shift = ((size_t)layer * PASTA_T + (PASTA_T - 1)) * ln;
+    const size_t shift = sch.base + (size_t)(nsteps - 1) * ln;
     {   // last state: products only (a "virtual" rotation keeps the frame uniform)
-        NttArgs a = ntt_args(c, d_of(PASTA_T - 1), scr, B * L, 0, L);
+        NttArgs a = ntt_args(c, d_of(nsteps - 1), scr, B * L, 0, L);
         a.store_op = STORE_MAC; a.mul_ptrs = d_pdiag_ptrs; a.mul_shift = shift; a.mul_cycle = L; a.mul_item_polys = L; a.acc = accp1;
         k_ntt(a, false, c->w->stream);
         PermArgs p;
         memset(&p, 0, sizeof(p));
-        p.in = c0_of(PASTA_T - 1); p.out = accp0; p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(B * L); p.L = L;
+        p.in = c0_of(nsteps - 1); p.out = accp0; p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(B * L); p.L = L;
         p.out_item_stride = ln; p.elt = g; p.mac = 1; p.mul_ptrs = d_pdiag_ptrs; p.mul_shift = shift;
         k_perm(p, c->w->stream);
         // back to the unrotated frame, then to coefficient form
@@ -677,7 +692,7 @@ int shared_l0_chain(hhe_ctx *c, const u64 *enc_key, const u64 *const *h_pdiag_pt
     rt_d2d(main.ws_ct[0], enc_key, c->ct_words() * 8, main.stream);
     L0Capture cap;
     cap.c0 = c->l0_tab; cap.r0 = cap.c0 + S * ln; cap.d = cap.r0 + S * ln; cap.S = (int)S; cap.out = out; cap.B = B;
-    return matmul_diagonal_fused(c, 0, c->l0_ptrs, 1, &cap);
+    return matmul_diagonal_fused(c, pasta_sched(c, 0), c->l0_ptrs, 1, &cap);
 }
 // ... and per chunk: the sums go back to the unrotated frame and to coefficient form, as at the end of matmul_diagonal_fused
 void shared_l0_tail(hhe_ctx *c, const u64 *sums, size_t B)
@@ -841,7 +856,7 @@ static int transcipher_chunk(hhe_ctx *c, const u64 *enc_key, const u64 *const *d
     if (!shared_l0) op_elt(c, ELT_BCAST, nullptr, enc_key, state, B * 2 * L, 0, L, 2 * L);
     for (int r = 0; r <= PASTA_R && !rc; ++r) {
         if (r == 0 && shared_l0) shared_l0_tail(c, out, B);
-        else if ((rc = bsgs ? matmul_bsgs(c, r, d_diag, B) : fused ? matmul_diagonal_fused(c, r, d_diag, B) : matmul_diagonal(c, r, d_diag, B))) break;
+        else if ((rc = bsgs ? matmul_bsgs(c, r, d_diag, B) : fused ? matmul_diagonal_fused(c, pasta_sched(c, r), d_diag, B) : matmul_diagonal(c, r, d_diag, B))) break;
         // add_rc (:205-211)
         op_add_plain(c, state, nullptr, d_rc, (size_t)r * n, false, false, false, state, B);
         // mix (:417-423)
@@ -1669,4 +1684,246 @@ static int fc_row_chunk(hhe_ctx *c, Lane &lane, bool shared, const uint64_t *vi,
     };
     if (!shared || max_depth == 0) return run(false);
     return run(true);
+}
+
+// ====================================================================== packed plain-matrix affine layers
+// SEALZpCipher::packed_matMul / packed_affine (src/pasta/SEAL_Cipher.cpp:522-543) over diagonal (:271-313) and babystep_giantstep
+// (:185-267) with a resident matrix handle.
+namespace {
+// add_bsgs_indices / add_diagonal_indices (:337-355): the rotate_rows steps of one layer, in the reference's order
+int affine_steps(size_t N, size_t dim, size_t n1, size_t n2, std::vector<int> &steps)
+{
+    if (N == 0 || dim == 0 || (n1 == 0) != (n2 == 0)) return fail(HHE_ERR_INVALID, "affine layer: bad dimensions");
+    if (n1 && n1 * n2 != dim) return fail(HHE_ERR_INVALID, "affine layer: n1 * n2 != dim");
+    if (dim * 2 != N && dim * 4 > N) return fail(HHE_ERR_TOO_FEW_SLOTS, "too little slots for matmul implementation!");
+    steps.clear();
+    if (dim * 2 != N) steps.push_back(-(int)dim);
+    steps.push_back(1);
+    if (n1 > 1 && n2 > 1)
+        for (size_t k = 1; k < n2; ++k) steps.push_back((int)(k * n1));
+    return HHE_OK;
+}
+// can Evaluator::rotate_rows serve `step` from the named set: its key, or every term of its NAF (recursively, as op_rotate_rows goes)
+bool rot_reachable(const hhe_ctx *c, int step)
+{
+    if (step == 0) return true;
+    const u32 elt = galois_elt_from_step(c, step);
+    if (!elt) return false;
+    if (c->gks->gk.count(elt)) return true;
+    const std::vector<int> terms = nt_naf(step);
+    if (terms.size() == 1) return false;
+    for (int term : terms) {
+        if ((size_t)std::abs(term) == c->n / 2) continue;
+        if (!rot_reachable(c, term)) return false;
+    }
+    return true;
+}
+
+// one chunk on the current lane: in / out [B][2][L][N] (may be the same buffer)
+int affine_chunk(hhe_ctx *c, const hhe_matrix *m, const u64 *in, u64 *out, size_t B)
+{
+    const int L = c->L;
+    const size_t ln = (size_t)L * c->n, ctw = 2 * ln;
+    Lane &w = *c->w;
+    const int pre = m->dim * 2 != c->n ? -(int)m->dim : 0;
+    const u64 *res = nullptr;
+    int rc;
+    if (!m->n1) {
+        // diagonal (:271-313): the fused loop of the PASTA layers with dim steps of rotate_rows(+1) and the one table for every item
+        rt_d2d(w.ws_ct[0], in, B * ctw * 8, w.stream);
+        const DiagSched sch{(int)m->dim, 1, pre, 0, m->dim * ln};
+        if ((rc = matmul_diagonal_fused(c, sch, m->self, B))) return rc;
+        res = w.ws_ct[0];
+    } else {
+        // babystep_giantstep (:185-267).  The baby steps are a sequential chain (each key switch's rounding feeds the next); then ONE
+        // forward transform over all of them, all n2 inner sums in one kernel, ONE inverse transform, and the giant rotations
+        const size_t n1 = (size_t)m->n1, n2 = (size_t)m->n2;
+        u64 *rot = w.ws_aff, *inner = rot + n1 * B * ctw;  // [n1][B][2][L][N] | [n2][B][2][L][N]
+        rt_d2d(rot, in, B * ctw * 8, w.stream);
+        if (pre) {
+            if ((rc = op_rotate_rows(c, rot, pre, w.ws_ct[2], B))) return rc;
+            op_add(c, rot, w.ws_ct[2], rot, B, 2);
+        }
+        for (size_t j = 1; j < n1; ++j)
+            if ((rc = op_rotate_rows(c, rot + (j - 1) * B * ctw, 1, rot + j * B * ctw, B))) return rc;
+        op_ntt(c, rot, n1 * B * 2 * L, 0, L, false);
+        PermArgs p;
+        memset(&p, 0, sizeof(p));
+        p.bsgs_n1 = (int)n1; p.bsgs_n2 = (int)n2;
+        p.in = rot; p.in_step_stride = B * ctw; p.in_item_stride = ctw;
+        p.out = inner; p.out_step_stride = B * ctw; p.out_item_stride = ctw;
+        p.mul_ptrs = m->self; p.mul_step_stride = ln;
+        p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(B * 2 * L); p.L = L;
+        k_perm(p, w.stream);
+        op_ntt(c, inner, n2 * B * 2 * L, 0, L, true);
+        // the generic key switch adds its base polynomials of the ROTATED ciphertext only (STORE_KSF), so the outer sum is an op_add
+        for (size_t k = 1; k < n2; ++k) {
+            u64 *ik = inner + k * B * ctw;
+            if ((rc = op_rotate_rows(c, ik, (int)(k * n1), ik, B))) return rc;
+            op_add(c, inner, ik, inner, B, 2);
+        }
+        res = inner;
+    }
+    if (m->bias) op_add_plain(c, res, m->bias, nullptr, 0, true, false, false, out, B);
+    else rt_d2d(out, res, B * ctw * 8, w.stream);
+    return HHE_OK;
+}
+// grow-only per-call state: the handle's pointer array and the lane's BSGS workspace for chunks of `per` items
+int affine_reserve(hhe_ctx *c, hhe_matrix *m, Lane &ln, size_t per)
+{
+    int rc = lane_reserve(c, ln, per);
+    if (rc) return rc;
+    if (m->self_cap < per) {
+        sync_ctx(c);
+        rt_free((void *)m->self);
+        m->self_cap = 0;
+        if (!(m->self = (const u64 **)rt_malloc(per * sizeof(u64 *)))) return dev_fail("hhe_packed_affine: pointer table");
+        std::vector<const u64 *> h(per, m->tab);
+        if (rt_h2d((void *)m->self, h.data(), per * sizeof(u64 *), ln.stream) || rt_sync(ln.stream)) return dev_fail("hhe_packed_affine: pointer table");
+        m->self_cap = per;
+    }
+    const size_t need_words = m->n1 ? (size_t)(m->n1 + m->n2) * per * c->ct_words() : 0;
+    if (ln.aff_cap < need_words) {
+        sync_ctx(c);
+        rt_free(ln.ws_aff);
+        ln.aff_cap = 0;
+        if (!(ln.ws_aff = (u64 *)rt_malloc(need_words * 8))) return dev_fail("hhe_packed_affine: babystep-giantstep workspace");
+        ln.aff_cap = need_words;
+    }
+    return HHE_OK;
+}
+}  // namespace
+
+void matrix_free(hhe_matrix *m)
+{
+    if (!m) return;
+    rt_free(m->tab); rt_free(m->bias); rt_free((void *)m->self);
+    delete m;
+}
+
+extern "C" int hhe_affine_galois_steps(size_t N, size_t dim, size_t n1, size_t n2, int *steps_out, size_t *count)
+{
+    if (!count) return fail(HHE_ERR_INVALID, "hhe_affine_galois_steps: null argument");
+    std::vector<int> steps;
+    int rc = affine_steps(N, dim, n1, n2, steps);
+    if (rc) return rc;
+    const size_t cap = *count;
+    *count = steps.size();
+    if (!steps_out || cap < steps.size()) return fail(HHE_ERR_CAPACITY, "hhe_affine_galois_steps: output too small");
+    std::copy(steps.begin(), steps.end(), steps_out);
+    return HHE_OK;
+}
+
+extern "C" int hhe_matrix_create(hhe_ctx *c, const uint64_t *M, size_t dim, const uint64_t *bias, size_t n1, size_t n2, hhe_matrix **out)
+{
+    HHE_LOCK(c);
+    if (!c || !M || !out) return fail(HHE_ERR_INVALID, "hhe_matrix_create: null argument");
+    std::vector<int> steps;
+    int rc = affine_steps(c->n, dim, n1, n2, steps);
+    if (rc) return rc;
+    if (n1 == 1 || n2 == 1) n1 = n2 = 0;  // packed_matMul (:526): degenerate parameters take the diagonal method
+    for (size_t i = 0; i < dim * dim; ++i)
+        if (M[i] >= c->t) return fail(HHE_ERR_INVALID, "hhe_matrix_create: matrix entry not below the plain modulus");
+    for (size_t i = 0; bias && i < dim; ++i)
+        if (bias[i] >= c->t) return fail(HHE_ERR_INVALID, "hhe_matrix_create: bias entry not below the plain modulus");
+    const size_t n = c->n, ln = (size_t)c->L * n;
+    const bool full = dim * 2 == n;
+    // the slot vectors BatchEncoder::encode receives, zero padded to one length: diag_i[j] = M[j][(i + j) % dim] (:290-301); BSGS
+    // rotates diag_i right by k n1, k = i / n1, and in the non-full-packed case moves its first k n1 entries behind the end (:201-224)
+    const size_t stride = n1 && !full ? dim + (n2 - 1) * n1 : dim;
+    std::vector<u64> vals(dim * stride, 0), d(dim);
+    for (size_t i = 0; i < dim; ++i) {
+        for (size_t j = 0; j < dim; ++j) d[j] = M[j * dim + (i + j) % dim];
+        u64 *v = &vals[i * stride];
+        const size_t r = n1 ? i / n1 * n1 : 0;
+        for (size_t j = 0; j < dim; ++j) v[(j + r) % dim] = d[j];
+        if (!full)
+            for (size_t j = 0; j < r; ++j) { v[dim + j] = v[j]; v[j] = 0; }
+    }
+    c->w = &c->lanes[0];
+    hhe_matrix *m = new hhe_matrix();
+    m->ctx = c; m->dim = dim; m->n1 = (int)n1; m->n2 = (int)n2;
+    DevBuf dv(vals.size() * 8), plain(dim * n * 8), diag(dim * ln * 8), bv(dim * 8);
+    bool ok = dv.p && plain.p && diag.p && bv.p;
+    if (ok && !n1) ok = !!(m->tab = (u64 *)rt_malloc(2 * dim * ln * 8));
+    if (ok && bias) ok = !!(m->bias = (u64 *)rt_malloc(n * 8));
+    if (!ok) { matrix_free(m); return dev_fail("hhe_matrix_create: table alloc"); }
+    rt_stream st = c->w->stream;
+    rt_h2d(dv.p, vals.data(), vals.size() * 8, st);
+    op_encode(c, dv.w(), dim, (int)stride, (int)stride, -1, plain.w());
+    op_lift_ntt(c, plain.w(), dim, diag.w());
+    if (!n1) {
+        // multipliers in the frame of rotate_rows(+1) and their Shoup quotients: the `pdiag` form of ensure_block
+        PermArgs p;
+        memset(&p, 0, sizeof(p));
+        p.in = diag.w(); p.out = m->tab; p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(dim * c->L); p.L = c->L;
+        p.out_item_stride = ln; p.elt = galois_elt_from_step(c, 1);
+        k_perm(p, st);
+        op_elt(c, ELT_SHOUP, m->tab, nullptr, m->tab + dim * ln, dim * c->L, 0, c->L);
+    }
+    if (bias) {
+        rt_h2d(bv.p, bias, dim * 8, st);
+        op_encode(c, bv.w(), 1, (int)dim, (int)dim, -1, m->bias);
+    }
+    if (rt_sync(st)) { matrix_free(m); return dev_fail("hhe_matrix_create"); }
+    if (n1) m->tab = diag.release();
+    m->bytes = (n1 ? 1 : 2) * dim * ln * 8 + (bias ? n * 8 : 0);
+    c->mats.push_back(m);
+    *out = m;
+    return HHE_OK;
+}
+extern "C" void hhe_matrix_destroy(hhe_matrix *m)
+{
+    if (!m) return;
+    hhe_ctx *c = m->ctx;
+    HHE_LOCK(c);
+    sync_ctx(c);
+    c->mats.erase(std::remove(c->mats.begin(), c->mats.end(), m), c->mats.end());
+    matrix_free(m);
+}
+extern "C" size_t hhe_matrix_bytes(const hhe_matrix *m) { return m ? m->bytes : 0; }
+
+extern "C" int hhe_packed_affine_ks(hhe_ctx *c, const hhe_keyset *gk, const hhe_matrix *mat, const uint64_t *ct, uint64_t *out, size_t B)
+{
+    HHE_LOCK(c);
+    if (!c || !mat || !ct || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_packed_affine: null argument or empty batch");
+    if (mat->ctx != c) return fail(HHE_ERR_INVALID, "matrix belongs to another context");
+    int rc = check_sets(c, gk);
+    if (rc) return rc;
+    KeyScope keys(c, gk, nullptr);
+    hhe_matrix *m = const_cast<hhe_matrix *>(mat);
+    // every rotation must be servable before anything is written.  Step +1 needs its own key: its NAF is the one term, so SEAL
+    // throws without it; the other steps may go through their NAF terms (op_rotate_rows)
+    std::vector<int> steps;
+    if ((rc = affine_steps(c->n, m->dim, (size_t)m->n1, (size_t)m->n2, steps))) return rc;
+    for (int s : steps)
+        if (s == 1 ? (m->dim > 1 && !c->gks->gk.count(galois_elt_from_step(c, 1))) : !rot_reachable(c, s)) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+    Lane &main = c->lanes[0];
+    c->w = &main;
+    const int ns = c->nstreams;
+    if (ns == 0) {
+        if (!(rc = affine_reserve(c, m, main, B))) rc = affine_chunk(c, m, ct, out, B);
+    } else {
+        // chunks round-robin over the internal streams, as hhe_pasta3_transcipher forms them
+        size_t nch = (B + c->chunk - 1) / c->chunk;
+        if (nch > 1) nch = (nch + ns - 1) / ns * ns;
+        const size_t per = (B + nch - 1) / nch;
+        for (int s = 1; s <= ns && !rc; ++s) rc = affine_reserve(c, m, c->lanes[s], per);
+        if (!rc) {
+            rt_event_record(c->ev_fork, main.stream);
+            for (int s = 1; s <= ns; ++s) rt_stream_wait_event(c->lanes[s].stream, c->ev_fork);
+            size_t idx = 0;
+            for (size_t b0 = 0; b0 < B && !rc; b0 += per, ++idx) {
+                c->w = &c->lanes[1 + idx % ns];
+                rc = affine_chunk(c, m, ct + b0 * c->ct_words(), out + b0 * c->ct_words(), std::min(per, B - b0));
+            }
+            for (int s = 1; s <= ns; ++s) {
+                rt_event_record(c->lanes[s].ev_done, c->lanes[s].stream);
+                rt_stream_wait_event(main.stream, c->lanes[s].ev_done);
+            }
+        }
+        c->w = &main;
+    }
+    if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_packed_affine");
+    return rc;
 }

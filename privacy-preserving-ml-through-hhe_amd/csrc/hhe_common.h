@@ -244,6 +244,13 @@ struct PermArgs {  // NTT-domain Galois permutation: out[p][x] (op)= in[p][pi_el
     const u64 *in2;
     u64 *out2;
     size_t in_step_stride, mul_step_stride;
+    // bsgs_n1 > 0 -- babystep-giantstep inner sums of a packed plain-matrix layer (bsgs_inner_sum_body), no index map; poly p = (item b,
+    // polynomial pl < 2L), limb j = pl % L, count = B * 2L:
+    //   out[k * out_step_stride + b * out_item_stride + pl*N + x] = sum_{i < bsgs_n1} in[i * in_step_stride + b * in_item_stride + pl*N + x]
+    //                                                 * mul_ptrs[b][mul_shift + (k * bsgs_n1 + i) * mul_step_stride + j*N + x]   for every k < bsgs_n2
+    // in and the multipliers are canonical words in NTT form
+    int bsgs_n1, bsgs_n2;
+    size_t out_step_stride;
 };
 
 struct LeafSumArgs {  // out[b][k][j] += qsp_inv_j * (accS[b][k][j] (INTT'd) + accH[b][k][j])

@@ -366,6 +366,7 @@ static void free_lane(Lane &ln)
     rt_free(ln.ws_T); rt_free(ln.ws_S); rt_free(ln.ws_d); rt_free(ln.ws_ct3); rt_free(ln.ws_plain); rt_free(ln.ws_vals);
     for (auto &p : ln.ws_ct) { rt_free(p); p = nullptr; }
     rt_free(ln.ws_rot); ln.ws_rot = nullptr; ln.rot_cap = 0;
+    rt_free(ln.ws_aff); ln.ws_aff = nullptr; ln.aff_cap = 0;
     for (auto &sl : ln.fc_slots) { rt_free(sl.tp); rt_free(sl.ct); rt_free(sl.c0hat); }
     ln.fc_slots.clear(); ln.fc_slot_cap = 0;
     for (u64 *p : ln.csum_bufs) rt_free(p);
@@ -440,6 +441,7 @@ extern "C" void hhe_ctx_destroy(hhe_ctx *c)
     keyset_clear(&c->keys0);
     for (auto &ks : c->rk_slots) keyset_clear(&ks);
     for (hhe_keyset *ks : c->sets) { keyset_clear(ks); delete ks; }  // sets the caller did not destroy
+    for (hhe_matrix *m : c->mats) matrix_free(m);  // handles the caller did not destroy
     for (auto &kv : c->d_key_shoup) rt_free(kv.second);
     rt_free(c->d_feistel_mask);
     rt_free(c->d_zero_corr);

@@ -30,6 +30,18 @@ struct hhe_keyset {
     std::map<u32, u64 *> gk;           // by Galois element: [L][2][K][N] each
     std::map<u32, u64 *> gk_corr;      // per Galois key of THIS set: shared-digit correction [2][K][N] (KsCorrArgs), built on first FC use
 };
+// One public (plain) matrix of a packed affine layer, resident with everything derived from it (hhe_matrix_create).  Not part of the
+// block-table cache: it lives until hhe_matrix_destroy (or its context goes).
+struct hhe_matrix {
+    hhe_ctx *ctx = nullptr;
+    size_t dim = 0;
+    int n1 = 0, n2 = 0;          // babystep-giantstep split; 0 / 0: diagonal method
+    u64 *tab = nullptr;          // diagonal: [dim][L][N] multipliers in the frame of rotate_rows(+1) | their Shoup quotients; BSGS: [dim][L][N]
+    u64 *bias = nullptr;         // [N] plaintext of the bias (coefficients mod t), or null
+    const u64 **self = nullptr;  // [self_cap] device pointers, all = tab: the per-item pointer array the kernels take
+    size_t self_cap = 0;
+    size_t bytes = 0;            // device footprint of tab + bias
+};
 struct Lane {   // one stream + the per-batch workspaces of the ops (capacity `cap` ciphertexts)
     rt_stream stream = nullptr;
     void *ev_done = nullptr;
@@ -50,6 +62,8 @@ struct Lane {   // one stream + the per-batch workspaces of the ops (capacity `c
     size_t ptr_cap = 0;
     u64 *ws_rot = nullptr;   // [B][16][2][L][N] babystep rotations (allocated on first BSGS use)
     size_t rot_cap = 0;
+    u64 *ws_aff = nullptr;   // [n1 + n2][B][2][L][N] baby-step ciphertexts | inner sums of hhe_packed_affine (BSGS; grow-only)
+    size_t aff_cap = 0;      // words
     // FC shared digits: one slot per trie node that is still needed -- the digit transforms of its un-rotated c1 (tp [B][L][K][N]) and its
     // ciphertext (ct [B][2][L][N]); refs = 1 while the depth-first walk is below the node + 1 per queued leaf key switch that reads it
     struct FcSlot { u64 *tp = nullptr, *ct = nullptr, *c0hat = nullptr; int refs = 0; int tp_polys = 0; };  // c0hat [B][L][N]: NTT form of the node's c0 (nodes with a non-leaf child)  // tp_polys: K, or 1 when tp holds the special-prime transforms only
@@ -128,6 +142,7 @@ struct hhe_ctx {
     hhe_keyset keys0;
     hhe_keyset rk_slots[HHE_RELIN_SLOTS];      // [0] unused (slot 0 is keys0.rk)
     std::vector<hhe_keyset *> sets;
+    std::vector<hhe_matrix *> mats;            // plain-matrix handles created on this context
     hhe_keyset *gks = &keys0, *rks = &keys0;
     std::map<const u64 *, u64 *> d_key_shoup;  // per key-switch key (by device address): Shoup quotients of its words (fused row kernel), built on first use
     hhe_keyset *relin_set(int slot) { return slot == 0 ? &keys0 : &rk_slots[slot]; }
@@ -221,3 +236,4 @@ void keyset_clear(hhe_keyset *ks);
 void hhe_set_error(const std::string &msg);
 int lane_reserve(hhe_ctx *c, Lane &ln, size_t B);
 void sync_ctx(hhe_ctx *c);  // waits for every stream of the context
+void matrix_free(hhe_matrix *m);  // hhe_api.cpp: device memory of a handle and the handle

@@ -602,6 +602,64 @@ HD void diag_sum_body(const PermArgs &a, size_t gid)
     st2(o1, U2{barrett128(s1[0].lo, s1[0].hi, m), barrett128(s1[1].lo, s1[1].hi, m)});
 }
 
+// Babystep-giantstep inner sums of a packed plain-matrix layer (PermArgs::bsgs_n1 > 0; DESIGN.md "packed affine"): all n2 sums
+// inner[k] = sum_{i < n1} NTT(rot[i]) * table[k * n1 + i] in one pass over the baby-step ciphertexts.  gid over [count][N / 2], two
+// adjacent points per lane (16-byte accesses).  G <= 8 giant steps share one pass: a word of rot[i] is loaded once and multiplied into
+// the G 128-bit lazy sums of the lane (4 G registers of 64 bits); n2 > 8 takes further passes of up to 8.  Operands and multipliers
+// are canonical (< q < 2^61), so DIAG_SUM_FOLD products stay below 2^127 and the folded sum below 2^61 rides along (add_nw inside
+// acc_mac_nw checks the bound under -DHHE_RANGE_CHECK); one Barrett reduction per output word.
+template <int G> HD void bsgs_inner_group(const PermArgs &a, const u64 *r, gptr d, u64 *o, const ModDev &m)
+{
+    Acc128 s[G][2];
+#pragma unroll
+    for (int k = 0; k < G; k++) s[k][0] = s[k][1] = Acc128{0, 0};
+    const size_t kstride = (size_t)a.bsgs_n1 * a.mul_step_stride;
+    for (int i = 0; i < a.bsgs_n1; i++) {
+        const U2 u = ld2(r + (size_t)i * a.in_step_stride);
+        const gptr di = d + (size_t)i * a.mul_step_stride;
+#pragma unroll
+        for (int k = 0; k < G; k++) {
+            const U2 w = ld2g(di + (size_t)k * kstride);
+            acc_mac_nw(s[k][0], u.a, w.a); acc_mac_nw(s[k][1], u.b, w.b);
+        }
+        if ((i & (DIAG_SUM_FOLD - 1)) == DIAG_SUM_FOLD - 1) {
+#pragma unroll
+            for (int k = 0; k < G; k++)
+                for (int e = 0; e < 2; e++) { s[k][e].lo = barrett128(s[k][e].lo, s[k][e].hi, m); s[k][e].hi = 0; }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < G; k++)
+        st2(o + (size_t)k * a.out_step_stride, U2{barrett128(s[k][0].lo, s[k][0].hi, m), barrett128(s[k][1].lo, s[k][1].hi, m)});
+}
+HD void bsgs_inner_sum_body(const PermArgs &a, size_t gid)
+{
+    const size_t n = (size_t)1 << a.logn;
+    const size_t p = gid >> (a.logn - 1);
+    if (p >= (size_t)a.count) return;
+    const size_t item = p / (2 * a.L), pl = p % (2 * a.L), j = pl % a.L;
+    const size_t x = (gid & ((n >> 1) - 1)) << 1;
+    const ModDev m = mod_at(a.mods, (int)j);
+    const u64 *r = a.in + item * a.in_item_stride + pl * n + x;
+    u64 *o = a.out + item * a.out_item_stride + pl * n + x;
+    const gptr d = as_global(a.mul_ptrs[item]) + a.mul_shift + j * n + x;
+    const size_t kstride = (size_t)a.bsgs_n1 * a.mul_step_stride;
+    for (int k0 = 0; k0 < a.bsgs_n2; k0 += 8) {
+        const gptr dk = d + (size_t)k0 * kstride;
+        u64 *ok = o + (size_t)k0 * a.out_step_stride;
+        switch (a.bsgs_n2 - k0) {
+        case 1: bsgs_inner_group<1>(a, r, dk, ok, m); break;
+        case 2: bsgs_inner_group<2>(a, r, dk, ok, m); break;
+        case 3: bsgs_inner_group<3>(a, r, dk, ok, m); break;
+        case 4: bsgs_inner_group<4>(a, r, dk, ok, m); break;
+        case 5: bsgs_inner_group<5>(a, r, dk, ok, m); break;
+        case 6: bsgs_inner_group<6>(a, r, dk, ok, m); break;
+        case 7: bsgs_inner_group<7>(a, r, dk, ok, m); break;
+        default: bsgs_inner_group<8>(a, r, dk, ok, m); break;
+        }
+    }
+}
+
 // NTT-domain Galois gather, optionally multiply-accumulating with a per-item table: gid over [count][N]
 // (steps > 0: the diagonal sum above on the first half of the ids -- host loops only: on the device k_perm launches
 // diag_sum_kernel for it, and perm_kernel keeps the registers of a gather)
@@ -609,6 +667,7 @@ HD void perm_body(const PermArgs &a, size_t gid)
 {
 #if !defined(__HIP_DEVICE_COMPILE__)
     if (a.steps) { diag_sum_body(a, gid); return; }
+    if (a.bsgs_n1) { bsgs_inner_sum_body(a, gid); return; }
 #endif
     const size_t n = (size_t)1 << a.logn;
     const size_t p = gid >> a.logn;

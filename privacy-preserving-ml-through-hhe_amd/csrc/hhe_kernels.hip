@@ -504,6 +504,17 @@ __global__ void __launch_bounds__(ELT_THREADS) diag_sum_kernel(PermArgs a, unsig
     }
     diag_sum_body(a, gid);
 }
+// PermArgs::bsgs_n1 > 0, ordered like diag_sum_kernel: the matrix table is shared by the items of a call, so consecutive workgroups take
+// the same (polynomial, 512 points) of consecutive items -- the table lines are hit in L2 / Infinity Cache and only rot streams
+__global__ void __launch_bounds__(ELT_THREADS) bsgs_inner_sum_kernel(PermArgs a, unsigned items)
+{
+    size_t gid = GID;
+    if (items) {
+        const size_t per_item = ((size_t)(2 * a.L) << (a.logn - 1)) / ELT_THREADS;  // workgroups of one item
+        gid = ((blockIdx.x % items) * per_item + blockIdx.x / items) * ELT_THREADS + threadIdx.x;
+    }
+    bsgs_inner_sum_body(a, gid);
+}
 __global__ void __launch_bounds__(ELT_THREADS) ks_mac_kernel(KsMacArgs a) { ks_mac_body(a, GID); }
 template <int LL, int MODE> __global__ void __launch_bounds__(ELT_THREADS) ks_mac_t_kernel(KsMacArgs a) { ks_mac_body_t<LL, MODE>(a, GID); }
 template <int LL> __global__ void __launch_bounds__(ELT_THREADS) ks_mac_leaves_kernel(KsMacLeavesArgs a) { ks_mac_leaves_body<LL>(a, GID); }
@@ -537,6 +548,12 @@ void k_perm(const PermArgs &a, rt_stream s)
         const size_t half = (size_t)1 << (a.logn - 1);
         const unsigned items = half % ELT_THREADS == 0 ? (unsigned)(a.count / a.L) : 0;
         LAUNCH1D(diag_sum_kernel, (size_t)a.count * half, s, a, items);
+        return;
+    }
+    if (a.bsgs_n1) {
+        const size_t half = (size_t)1 << (a.logn - 1);
+        const unsigned items = half % ELT_THREADS == 0 ? (unsigned)(a.count / (2 * a.L)) : 0;
+        LAUNCH1D(bsgs_inner_sum_kernel, (size_t)a.count * half, s, a, items);
         return;
     }
     LAUNCH1D(perm_kernel, (size_t)a.count << a.logn, s, a);
