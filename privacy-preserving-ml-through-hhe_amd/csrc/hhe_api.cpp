@@ -5,8 +5,8 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include "hhe_internal.h"
-#include "../../include/hhe_gfx950.h"
 
 namespace {
 
@@ -215,6 +215,14 @@ int op_rotate_rows(hhe_ctx *c, const u64 *ct, int step, u64 *out, size_t B)
     return HHE_OK;
 }
 
+// non-full-packed preparation of the matmul schedules (pasta_3_seal.cpp:330-336, :379-385; SEAL_Cipher.cpp:231, :279): state += rotate_rows(state, step)
+int op_prep_rows(hhe_ctx *c, u64 *state, int step, u64 *scratch, size_t B)
+{
+    int rc = op_rotate_rows(c, state, step, scratch, B);
+    if (!rc) op_add(c, state, scratch, state, B, 2);
+    return rc;
+}
+
 // Evaluator::bfv_multiply (BEHZ): a, b [B][2][L][N] -> out3 [B][3][L][N]
 void op_multiply(hhe_ctx *c, const u64 *x, const u64 *y, u64 *out3, size_t B)
 {
@@ -370,36 +378,25 @@ int ensure_bsgs_tables(hhe_ctx *c, u64 block, BlockTables *bt)
 
 // PASTA_SEAL::babystep_giantstep (pasta_3_seal.cpp:267-366), N1 = 16, N2 = 8 (pasta_3_seal.h:35-36): 15 baby
 // rotations by -1, 8 inner sums of 16 plain products (accumulated in the NTT domain), 7 giant
-// rotations by -16k.  State in ws_ct[0].
+// rotations by -16k.  State in ws_ct[0]; the lane's ws_rot holds ROT_SLOTS ciphertexts per item (reserved by the caller).
+constexpr int ROT_SLOTS = 16;  // Lane::ws_rot per item: the N1 baby steps here, the trie depths of the FC row
 int matmul_bsgs(hhe_ctx *c, int layer, const u64 *const *d_bsgs_ptrs, size_t B)
 {
-    constexpr int N1 = 16, N2 = 8;
+    constexpr int N1 = ROT_SLOTS, N2 = 8;
     const int L = c->L;
     const size_t n = c->n, ctw = c->ct_words();
     Lane &w = *c->w;
-    if (w.rot_cap < B) {
-        rt_sync(w.stream);
-        rt_free(w.ws_rot);
-        w.ws_rot = (u64 *)rt_malloc(B * N1 * ctw * 8);
-        if (!w.ws_rot) return dev_fail("bsgs workspace");
-        w.rot_cap = B;
-    }
     u64 *state = w.ws_ct[0], *inner = w.ws_ct[1], *scratch = w.ws_ct[2], *outer = w.ws_ct3;  // ct3 holds [B][3].. >= [B][2]
-    if (n / 2 != PASTA_T) {
-        int rc = op_rotate_rows(c, state, PASTA_T, scratch, B);
-        if (rc) return rc;
-        op_add(c, state, scratch, state, B, 2);
-    }
-    // rot[j] laid out [j][B][2][L][N]
-    rt_d2d(w.ws_rot, state, B * ctw * 8, w.stream);
-    for (int j = 1; j < N1; ++j) {
-        int rc = op_rotate_rows(c, w.ws_rot + (size_t)(j - 1) * B * ctw, -1, w.ws_rot + (size_t)j * B * ctw, B);
-        if (rc) return rc;
-    }
+    u64 *rot = w.ws_rot.p;  // rot[j] laid out [j][B][2][L][N]
+    int rc;
+    if (n / 2 != PASTA_T && (rc = op_prep_rows(c, state, PASTA_T, scratch, B))) return rc;
+    rt_d2d(rot, state, B * ctw * 8, w.stream);
+    for (int j = 1; j < N1; ++j)
+        if ((rc = op_rotate_rows(c, rot + (size_t)(j - 1) * B * ctw, -1, rot + (size_t)j * B * ctw, B))) return rc;
     for (int k = 0; k < N2; ++k) {
         rt_memset(inner, 0, B * ctw * 8, w.stream);
         for (int j = 0; j < N1; ++j) {
-            NttArgs a = ntt_args(c, w.ws_rot + (size_t)j * B * ctw, scratch, B * 2 * L, 0, L);
+            NttArgs a = ntt_args(c, rot + (size_t)j * B * ctw, scratch, B * 2 * L, 0, L);
             a.store_op = STORE_MAC; a.mul_ptrs = d_bsgs_ptrs; a.mul_shift = ((size_t)layer * PASTA_T + k * N1 + j) * L * n;
             a.mul_cycle = L; a.mul_item_polys = 2 * L; a.acc = inner;
             k_ntt(a, false, w.stream);
@@ -407,8 +404,7 @@ int matmul_bsgs(hhe_ctx *c, int layer, const u64 *const *d_bsgs_ptrs, size_t B)
         op_ntt(c, inner, B * 2 * L, 0, L, true);
         if (k == 0) rt_d2d(outer, inner, B * ctw * 8, w.stream);
         else {
-            int rc = op_rotate_rows(c, inner, -k * N1, inner, B);
-            if (rc) return rc;
+            if ((rc = op_rotate_rows(c, inner, -k * N1, inner, B))) return rc;
             op_add(c, outer, inner, outer, B, 2);
         }
     }
@@ -424,17 +420,11 @@ int matmul_diagonal(hhe_ctx *c, int layer, const u64 *const *d_diag_ptrs, size_t
     const int L = c->L;
     const size_t n = c->n;
     u64 *state = c->w->ws_ct[0], *acc = c->w->ws_ct[1], *scratch = c->w->ws_ct[2];
-    if (n / 2 != PASTA_T) {
-        int rc = op_rotate_rows(c, state, PASTA_T, scratch, B);
-        if (rc) return rc;
-        op_add(c, state, scratch, state, B, 2);
-    }
+    int rc;
+    if (n / 2 != PASTA_T && (rc = op_prep_rows(c, state, PASTA_T, scratch, B))) return rc;
     rt_memset(acc, 0, B * c->ct_words() * 8, c->w->stream);
     for (int i = 0; i < PASTA_T; ++i) {
-        if (i) {
-            int rc = op_rotate_rows(c, state, -1, state, B);
-            if (rc) return rc;
-        }
+        if (i && (rc = op_rotate_rows(c, state, -1, state, B))) return rc;
         NttArgs a = ntt_args(c, state, scratch, B * 2 * L, 0, L);
         a.store_op = STORE_MAC; a.mul_ptrs = d_diag_ptrs; a.mul_shift = ((size_t)layer * PASTA_T + i) * L * n;
         a.mul_cycle = L; a.mul_item_polys = 2 * L; a.acc = acc;
@@ -498,7 +488,7 @@ void l0_flush(hhe_ctx *c, const L0Capture &cap, int first, int steps)
     p.steps = steps; p.carry = first > 0; p.in = cap.r0; p.in2 = cap.d; p.in_step_stride = ln;
     p.out = cap.out; p.out2 = cap.out + ln; p.out_item_stride = 2 * ln;
     p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(cap.B * c->L); p.L = c->L;
-    p.mul_ptrs = c->l0_ptrs; p.mul_shift = (size_t)first * ln; p.mul_step_stride = ln;
+    p.mul_ptrs = c->l0_ptrs.p; p.mul_shift = (size_t)first * ln; p.mul_step_stride = ln;
     k_perm(p, c->w->stream);
 }
 // What the loop is run for: PASTA's affine layer `layer` (128 steps of rotate_rows(-1), the tables of ensure_block) or a plain-matrix
@@ -522,9 +512,8 @@ int matmul_diagonal_fused(hhe_ctx *c, const DiagSched &sch, const u64 *const *d_
     const int nsteps = sch.steps;
     u64 *state = c->w->ws_ct[0];
     if (sch.pre_step) {
-        int rc = op_rotate_rows(c, state, sch.pre_step, c->w->ws_ct[2], B);
+        int rc = op_prep_rows(c, state, sch.pre_step, c->w->ws_ct[2], B);
         if (rc) return rc;
-        op_add(c, state, c->w->ws_ct[2], state, B, 2);
     }
     const u32 g = galois_elt_from_step(c, sch.rot_step);
     auto it = c->gks->gk.find(g);
@@ -675,24 +664,14 @@ int shared_l0_chain(hhe_ctx *c, const u64 *enc_key, const u64 *const *h_pdiag_pt
     if (rc) return rc;
     const size_t ln = (size_t)c->L * c->n;
     const size_t S = std::max<size_t>(2, std::min<size_t>(PASTA_T, c->l0_budget / (3 * ln * 8)));
-    if (c->l0_tab_steps != S || !c->l0_tab || c->l0_ptr_cap < B) sync_ctx(c);
-    if (c->l0_tab_steps != S || !c->l0_tab) {
-        rt_free(c->l0_tab);
-        c->l0_tab_steps = 0;
-        if (!(c->l0_tab = (u64 *)rt_malloc(S * 3 * ln * 8))) return dev_fail("shared first layer: operand table");
-        c->l0_tab_steps = S;
-    }
-    if (c->l0_ptr_cap < B) {
-        rt_free((void *)c->l0_ptrs);
-        c->l0_ptr_cap = 0;
-        if (!(c->l0_ptrs = (const u64 **)rt_malloc(B * sizeof(u64 *)))) return dev_fail("shared first layer: pointer table");
-        c->l0_ptr_cap = B;
-    }
-    rt_h2d(c->l0_ptrs, h_pdiag_ptrs, B * sizeof(u64 *), main.stream);  // the caller's array outlives the call's final sync
+    if (c->l0_tab.cap > S * 3 * ln) { sync_ctx(c); c->l0_tab.release(); }  // the table holds exactly S steps (hhe_ctx::l0_steps)
+    if ((rc = c->l0_tab.reserve(c, S * 3 * ln, "shared first layer: operand table"))) return rc;
+    if ((rc = c->l0_ptrs.reserve(c, B, "shared first layer: pointer table"))) return rc;
+    rt_h2d(c->l0_ptrs.p, h_pdiag_ptrs, B * sizeof(u64 *), main.stream);  // the caller's array outlives the call's final sync
     rt_d2d(main.ws_ct[0], enc_key, c->ct_words() * 8, main.stream);
     L0Capture cap;
-    cap.c0 = c->l0_tab; cap.r0 = cap.c0 + S * ln; cap.d = cap.r0 + S * ln; cap.S = (int)S; cap.out = out; cap.B = B;
-    return matmul_diagonal_fused(c, pasta_sched(c, 0), c->l0_ptrs, 1, &cap);
+    cap.c0 = c->l0_tab.p; cap.r0 = cap.c0 + S * ln; cap.d = cap.r0 + S * ln; cap.S = (int)S; cap.out = out; cap.B = B;
+    return matmul_diagonal_fused(c, pasta_sched(c, 0), c->l0_ptrs.p, 1, &cap);
 }
 // ... and per chunk: the sums go back to the unrotated frame and to coefficient form, as at the end of matmul_diagonal_fused
 void shared_l0_tail(hhe_ctx *c, const u64 *sums, size_t B)
@@ -710,6 +689,47 @@ void shared_l0_tail(hhe_ctx *c, const u64 *sums, size_t B)
     p.in = sums + ln; p.out = state + ln;
     k_perm(p, c->w->stream);
     op_ntt(c, state, B * 2 * L, 0, L, true);
+}
+
+// ------------------------------------------------------------------ chunk scheduler of the batched calls
+// hhe_pasta3_transcipher, hhe_fc_row and hhe_packed_affine cut a batch into independent chunks of `per` items (the last one may be
+// shorter): a chunk's working set stays cache resident, and chunks on concurrent streams de-phase the load / butterfly / store phases
+// of the transforms.  Chunk idx runs on internal lane 1 + idx % ns; with ns = 0 every chunk runs on the main lane, in order.
+struct ChunkPlan {
+    size_t B = 0, per = 0, nch = 0;
+    int ns = 0;  // internal lanes that receive a chunk
+    ChunkPlan(size_t B_, size_t per_, int streams) : B(B_), per(per_), nch((B_ + per_ - 1) / per_), ns((int)std::min<size_t>(streams, nch)) {}
+    int first_lane() const { return ns ? 1 : 0; }  // the lanes to reserve for `per` items before anything is enqueued:
+    int last_lane() const { return ns; }           // [first_lane(), last_lane()]
+    size_t count(size_t idx) const { return std::min(per, B - idx * per); }
+};
+// transciphering and the affine layer: as many chunks as HHE_CHUNK demands, rounded up to a multiple of the stream count, balanced
+ChunkPlan plan_balanced(const hhe_ctx *c, size_t B)
+{
+    const int ns = c->nstreams;
+    if (ns == 0) return ChunkPlan(B, B, 0);
+    size_t nch = (B + c->chunk - 1) / c->chunk;
+    if (nch > 1) nch = (nch + ns - 1) / ns * ns;
+    return ChunkPlan(B, (B + nch - 1) / nch, ns);
+}
+// chunk(lane, idx, b0, count) enqueues items [b0, b0 + count) on `lane` (= *c->w while it runs).  The internal lanes fork from the
+// main stream and join it again, whatever the chunks returned; no chunk is issued after the first error.  The caller syncs.
+int run_chunks(hhe_ctx *c, const ChunkPlan &pl, const std::function<int(Lane &, size_t, size_t, size_t)> &chunk)
+{
+    Lane &main = c->lanes[0];
+    if (pl.ns) rt_event_record(c->ev_fork, main.stream);
+    for (int s = 1; s <= pl.ns; ++s) rt_stream_wait_event(c->lanes[s].stream, c->ev_fork);
+    int rc = HHE_OK;
+    for (size_t idx = 0; idx < pl.nch && !rc; ++idx) {
+        c->w = &c->lanes[pl.ns ? 1 + idx % pl.ns : 0];
+        rc = chunk(*c->w, idx, idx * pl.per, pl.count(idx));
+    }
+    for (int s = 1; s <= pl.ns; ++s) {
+        rt_event_record(c->lanes[s].ev_done, c->lanes[s].stream);
+        rt_stream_wait_event(main.stream, c->lanes[s].ev_done);
+    }
+    c->w = &main;
+    return rc;
 }
 
 }  // namespace
@@ -918,48 +938,23 @@ static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t 
         ptrs[B + b] = bt->rc;
         memcpy(&cwp[b * PASTA_T], cw + b * PASTA_T, ncw[b] * 8);
     }
-    const int ns = c->nstreams;
     // fused diagonal method: layer 0 acts on the same ciphertext for every item -- its chain runs once, here (HHE_SHARED_L0)
     const bool shared = c->matmul_mode == 1 && !use_bsgs && c->shared_l0 > 0 && B >= (size_t)c->shared_l0;
-    if (ns == 0) {
-        if (!(rc = lane_reserve(c, main, B)) && !(shared && (rc = shared_l0_chain(c, enc_key, ptrs.data(), B, out)))) {
-            std::vector<const u64 *> lp(2 * main.ptr_cap, nullptr);
-            for (size_t b = 0; b < B; ++b) { lp[b] = ptrs[b]; lp[main.ptr_cap + b] = ptrs[B + b]; }
-            rt_h2d(main.d_ptrs, lp.data(), lp.size() * sizeof(u64 *), main.stream);
-            rc = transcipher_chunk(c, enc_key, main.d_ptrs, main.d_ptrs + main.ptr_cap, cwp.data(), out, B, use_bsgs != 0, shared);
-        }
-    } else {
-        // independent chunks round-robin over the internal streams: a chunk's working set stays cache resident and
-        // concurrent streams de-phase the load / butterfly / store phases of the transforms
-        // balanced chunks: as many as the chunk size demands, rounded up to a multiple of the stream count
-        size_t nch = (B + c->chunk - 1) / c->chunk;
-        if (nch > 1) nch = (nch + ns - 1) / ns * ns;
-        const size_t per = (B + nch - 1) / nch;
-        for (int s = 1; s <= ns && !rc; ++s) rc = lane_reserve(c, c->lanes[s], per);
-        if (!rc && shared) rc = shared_l0_chain(c, enc_key, ptrs.data(), B, out);
-        if (!rc) {
-            rt_event_record(c->ev_fork, main.stream);
-            for (int s = 1; s <= ns; ++s) rt_stream_wait_event(c->lanes[s].stream, c->ev_fork);
-            size_t idx = 0;
-            std::vector<std::vector<const u64 *>> keep;  // host staging must outlive the asynchronous copies
-            for (size_t b0 = 0; b0 < B && !rc; b0 += per, ++idx) {
-                const size_t bc = std::min(per, B - b0);
-                Lane &ln = c->lanes[1 + idx % ns];
-                c->w = &ln;
-                keep.emplace_back(2 * ln.ptr_cap, nullptr);
-                std::vector<const u64 *> &lp = keep.back();
-                for (size_t b = 0; b < bc; ++b) { lp[b] = ptrs[b0 + b]; lp[ln.ptr_cap + b] = ptrs[B + b0 + b]; }
-                rt_h2d(ln.d_ptrs, lp.data(), lp.size() * sizeof(u64 *), ln.stream);
-                rc = transcipher_chunk(c, enc_key, ln.d_ptrs, ln.d_ptrs + ln.ptr_cap, &cwp[b0 * PASTA_T], out + b0 * c->ct_words(), bc, use_bsgs != 0, shared);
-            }
-            for (int s = 1; s <= ns; ++s) {
-                rt_event_record(c->lanes[s].ev_done, c->lanes[s].stream);
-                rt_stream_wait_event(main.stream, c->lanes[s].ev_done);
-            }
-            if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_pasta3_transcipher");
-        }
-        c->w = &main;
+    const ChunkPlan plan = plan_balanced(c, B);
+    for (int s = plan.first_lane(); s <= plan.last_lane(); ++s) {
+        if ((rc = lane_reserve(c, c->lanes[s], plan.per))) return rc;
+        if (use_bsgs && (rc = c->lanes[s].ws_rot.reserve(c, plan.per * ROT_SLOTS * c->ct_words(), "bsgs workspace"))) return rc;
     }
+    // from here on work is enqueued that reads host staging (ptrs, cwp, keep): every path ends in the final sync
+    if (shared) rc = shared_l0_chain(c, enc_key, ptrs.data(), B, out);
+    std::vector<std::vector<const u64 *>> keep(plan.nch);  // per chunk: its pointer table
+    if (!rc) rc = run_chunks(c, plan, [&](Lane &ln, size_t idx, size_t b0, size_t bc) {
+        std::vector<const u64 *> &lp = keep[idx];
+        lp.assign(2 * ln.ptr_cap, nullptr);
+        for (size_t b = 0; b < bc; ++b) { lp[b] = ptrs[b0 + b]; lp[ln.ptr_cap + b] = ptrs[B + b0 + b]; }
+        rt_h2d(ln.d_ptrs, lp.data(), lp.size() * sizeof(u64 *), ln.stream);
+        return transcipher_chunk(c, enc_key, ln.d_ptrs, ln.d_ptrs + ln.ptr_cap, &cwp[b0 * PASTA_T], out + b0 * c->ct_words(), bc, use_bsgs != 0, shared);
+    });
     if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_pasta3_transcipher");
     return rc;
 }
@@ -1057,15 +1052,9 @@ extern "C" int hhe_decompose_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keys
             ncw[s * nb + b] = (uint32_t)(hi - lo);
             bidx[s * nb + b] = b;
         }
-    if (c->blocks_cap < S * nb * ctw) {  // grow-only scratch for the decompositions of all blocks
-        sync_ctx(c);
-        rt_free(c->d_blocks);
-        c->blocks_cap = 0;
-        if (!(c->d_blocks = (u64 *)rt_malloc(S * nb * ctw * 8))) return dev_fail("hhe_decompose");
-        c->blocks_cap = S * nb * ctw;
-    }
-    u64 *blocks = c->d_blocks;
-    int rc;
+    int rc = c->d_blocks.reserve(c, S * nb * ctw, "hhe_decompose");  // the decompositions of all blocks
+    if (rc) return rc;
+    u64 *blocks = c->d_blocks.p;
     {   // PASTA_SEAL HHE(context, pk, sk, analyst rk, analyst gk).decomposition(...) (CSP.cpp:238-252)
         KeyScope keys(c, gk, rk);
         rc = transcipher_impl(c, enc_key, cw.data(), ncw.data(), bidx.data(), S * nb, 0, blocks);
@@ -1382,10 +1371,10 @@ struct FcWalk {
                 einv[l] = (u32)nt_invmod(q[l].elt, 2 * c->n);
                 parents[l] = csum ? nullptr : q[l].parent;   // the c0 terms of the leaves come from the per-element sums
             }
-            a.S_sp = ln.ws_leaf; a.s_acc = acc->accS; a.mods = c->d_mods; a.logn = c->logn; a.B = (int)B; a.L = L; a.K = K; a.m = m;
+            a.S_sp = ln.ws_leaf.p; a.s_acc = acc->accS; a.mods = c->d_mods; a.logn = c->logn; a.B = (int)B; a.L = L; a.K = K; a.m = m;
             a.sp_only = csum ? 1 : 0;
             if (k_ks_mac_leaves(a, ln.stream)) return fail(HHE_ERR_INVALID, "fc: leaf group");
-            fc_leaf_round(c, ln.ws_leaf, true, parents, einv, m, *acc, B);
+            fc_leaf_round(c, ln.ws_leaf.p, true, parents, einv, m, *acc, B);
         }
         for (int l = 0; l < m; l++) ln.fc_slots[q[l].slot].refs--;
         m = 0;
@@ -1518,99 +1507,12 @@ int fc_dfs(hhe_ctx *c, const std::vector<NafNode> &trie, int node, int depth, co
 }
 }  // namespace
 
-// one chunk on lane `ln`, enqueued asynchronously; shared = the shared-digit evaluation (raises *ln.zero_flag when it is not exact)
-static int fc_row_chunk(hhe_ctx *c, Lane &ln, bool shared, const uint64_t *vi, const uint64_t *w, size_t W, size_t n_inputs,
-                        int default_galois_only, uint64_t *out, size_t B);
-
-// hhe_fc_row with the key objects already named: c->rks relinearizes the product, c->gks serves the rotation sum
-static int fc_row_impl(hhe_ctx *c, const uint64_t *vi, const uint64_t *w, size_t W, size_t n_inputs, int default_galois_only, uint64_t *out, size_t B)
+// trie of the NAF term sequences of steps -1 .. -(n_inputs - 1) over the named Galois keys (terms equal to +-N/2 are skipped,
+// evaluator.h rotate_internal); depends on n_inputs, the key set and default_galois_only alone: built once per call
+static int fc_build_trie(const hhe_ctx *c, size_t n_inputs, int default_galois_only, std::vector<NafNode> &trie, int &max_depth)
 {
-    if (!c || !vi || !w || !out || W == 0 || B == 0 || n_inputs == 0 || n_inputs > c->n / 2)
-        return fail(HHE_ERR_INVALID, "hhe_fc_row: bad arguments");
-    if (!c->rks->rk) return fail(HHE_ERR_NO_RELIN_KEY, "relinearization key not set");
-    // chunks bound the key-switch working set (digit transforms per trie level); a chunk is a multiple of W so that item i
-    // of a chunk still uses weight row i % W.  Chunks are independent: with more than one internal stream (HHE_STREAMS)
-    // they run round-robin on the streams, as in hhe_pasta3_transcipher.
-    size_t per = c->fc_chunk ? c->fc_chunk : B;
-    if (per < B) per = std::max<size_t>(W, per / W * W);
-    per = std::min(per, B);
-    const size_t nch = (B + per - 1) / per, ctw = c->ct_words();
-    const int ns = nch > 1 ? c->nstreams : 0;
-    Lane &main = c->lanes[0];
-    const bool shared = c->fc_shared != 0;
-    u32 *flags = nullptr;
-    if (shared) {
-        if (c->flags_cap < nch) {  // grow-only per-chunk flags
-            sync_ctx(c);
-            rt_free(c->d_flags);
-            c->flags_cap = 0;
-            if (!(c->d_flags = (u32 *)rt_malloc(nch * 4))) return dev_fail("hhe_fc_row");
-            c->flags_cap = nch;
-        }
-        flags = c->d_flags;
-        rt_memset(flags, 0, nch * 4, main.stream);
-    }
-    int rc = HHE_OK;
-    if (ns) {
-        rt_event_record(c->ev_fork, main.stream);
-        for (int s = 1; s <= ns; ++s) rt_stream_wait_event(c->lanes[s].stream, c->ev_fork);
-    }
-    size_t idx = 0;
-    for (size_t b0 = 0; b0 < B && !rc; b0 += per, ++idx) {
-        Lane &ln = ns ? c->lanes[1 + idx % ns] : main;
-        ln.zero_flag = shared ? flags + idx : nullptr;
-        rc = fc_row_chunk(c, ln, shared, vi + b0 * ctw, w, W, n_inputs, default_galois_only, out + b0 * ctw, std::min(per, B - b0));
-    }
-    for (int s = 1; s <= ns; ++s) {
-        rt_event_record(c->lanes[s].ev_done, c->lanes[s].stream);
-        rt_stream_wait_event(main.stream, c->lanes[s].ev_done);
-    }
-    c->w = &main;
-    if (shared && !rc) {
-        std::vector<u32> h(nch, 0);
-        if (rt_d2h(h.data(), flags, nch * 4, main.stream) || rt_sync(main.stream)) rc = dev_fail("hhe_fc_row");
-        // a zero coefficient in some c1 (probability ~ N/q per ciphertext): that chunk is recomputed with per-child transforms
-        idx = 0;
-        for (size_t b0 = 0; b0 < B && !rc; b0 += per, ++idx)
-            if (h[idx] || c->fc_shared == 2) {
-                c->fc_fallbacks++;
-                main.zero_flag = nullptr;
-                rc = fc_row_chunk(c, main, false, vi + b0 * ctw, w, W, n_inputs, default_galois_only, out + b0 * ctw, std::min(per, B - b0));
-            }
-    }
-    if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_fc_row");
-    return rc;
-}
-extern "C" int hhe_fc_row_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const uint64_t *vi, const uint64_t *w, size_t W, size_t n_inputs,
-                             uint64_t *out, size_t B)
-{
-    HHE_LOCK(c);
-    if (!c) return fail(HHE_ERR_INVALID, "hhe_fc_row: null context");
-    int rc = check_sets(c, rk, gk);
-    if (rc) return rc;
-    KeyScope keys(c, gk, rk);
-    return fc_row_impl(c, vi, w, W, n_inputs, 0, out, B);  // the set IS the GaloisKeys object: every key it holds is visible to rotate_rows
-}
-extern "C" int hhe_fc_row(hhe_ctx *c, const uint64_t *vi, const uint64_t *w, size_t W, size_t n_inputs, int relin_slot,
-                          int default_galois_only, uint64_t *out, size_t B)
-{
-    HHE_LOCK(c);
-    if (!c || relin_slot < 0 || relin_slot >= HHE_RELIN_SLOTS) return fail(HHE_ERR_INVALID, "hhe_fc_row: bad arguments");
-    KeyScope keys(c, nullptr, c->relin_set(relin_slot));
-    return fc_row_impl(c, vi, w, W, n_inputs, default_galois_only, out, B);
-}
-
-static int fc_row_chunk(hhe_ctx *c, Lane &lane, bool shared, const uint64_t *vi, const uint64_t *w, size_t W, size_t n_inputs,
-                        int default_galois_only, uint64_t *out, size_t B)
-{
-    c->w = &lane;
-    int rc = lane_reserve(c, lane, B);
-    if (rc) return rc;
-    const int L = c->L;
-    const size_t ctw = c->ct_words();
-    // trie of NAF term sequences (terms equal to +-N/2 are skipped, evaluator.h rotate_internal)
-    std::vector<NafNode> trie(1);
-    int max_depth = 0;
+    trie.assign(1, NafNode());
+    max_depth = 0;
     for (size_t i = 1; i < n_inputs; ++i) {
         const int step = -(int)i;
         std::vector<int> terms;
@@ -1638,52 +1540,113 @@ static int fc_row_chunk(hhe_ctx *c, Lane &lane, bool shared, const uint64_t *vi,
         trie[node].mult++;
         max_depth = std::max(max_depth, (int)terms.size());
     }
+    if (max_depth + 1 > ROT_SLOTS) return fail(HHE_ERR_INVALID, "hhe_fc_row: NAF depth");  // the unshared walk keeps one ciphertext per depth in ws_rot
+    return HHE_OK;
+}
+
+// one chunk on the current lane (c->w, workspaces reserved by the caller), enqueued asynchronously; shared = the shared-digit
+// evaluation (raises the lane's zero_flag when it is not exact)
+static int fc_row_chunk(hhe_ctx *c, bool shared, const std::vector<NafNode> &trie, int max_depth, const uint64_t *vi, const uint64_t *w,
+                        size_t W, uint64_t *out, size_t B)
+{
     Lane &ln = *c->w;
-    if (ln.rot_cap < B || max_depth + 1 > 16) {
-        if (max_depth + 1 > 16) return fail(HHE_ERR_INVALID, "hhe_fc_row: NAF depth");
-        rt_sync(ln.stream);
-        rt_free(ln.ws_rot);
-        ln.ws_rot = (u64 *)rt_malloc(B * 16 * ctw * 8);
-        if (!ln.ws_rot) return dev_fail("hhe_fc_row workspace");
-        ln.rot_cap = B;
-    }
-    u64 *wb = ln.ws_ct[0], *prod = ln.ws_rot;  // depth-0 buffer holds the product
+    const int L = c->L;
+    const size_t ctw = c->ct_words();
+    u64 *wb = ln.ws_ct[0], *prod = ln.ws_rot.p;  // depth-0 buffer holds the product
     op_elt(c, ELT_BCAST, nullptr, w, wb, B * 2 * L, 0, L, (int)(W * 2 * L));
     op_multiply(c, vi, wb, ln.ws_ct3, B);                                  // packed_enc_multiply
-    rc = op_relinearize(c, ln.ws_ct3, prod, B);                            // CSP.cpp:306 (the RelinKeys object the call names: c->rks)
+    int rc = op_relinearize(c, ln.ws_ct3, prod, B);                        // CSP.cpp:306 (the RelinKeys object the call names: c->rks)
     if (rc) return rc;
     const size_t bln = B * (size_t)L * c->n;
     // one evaluation of the rotation trie; shared = children of a node reuse the digit transforms of its c1
-    auto run = [&](bool shared) -> int {
-        rt_d2d(out, prod, B * ctw * 8, ln.stream);
-        auto dfs = [&](const FcLeafAcc *acc) {
-            return shared ? fc_dfs_shared(c, trie, max_depth, prod, out, acc, B) : fc_dfs(c, trie, 0, 1, prod, ln.ws_rot, out, acc, B);
-        };
-        if (!c->fc_leaf_sums) return dfs(nullptr);
-        FcLeafAcc acc;
-        const size_t leaf_words = B * 2 * (size_t)HHE_LEAF_GROUP * c->n;
-        if (ln.leaf_cap < B) {
-            rt_sync(ln.stream);
-            rt_free(ln.ws_leaf);
-            ln.leaf_cap = 0;
-            if (!(ln.ws_leaf = (u64 *)rt_malloc(2 * leaf_words * 8))) return dev_fail("hhe_fc_row workspace");
-            ln.leaf_cap = B;
-        }
-        acc.accS = ln.ws_ct[0]; acc.accH = ln.ws_ct[1]; acc.rscr = ln.ws_leaf + ln.leaf_cap * 2 * (size_t)HHE_LEAF_GROUP * c->n;
-        rt_memset(acc.accS, 0, 2 * bln * 8, ln.stream);
-        rt_memset(acc.accH, 0, 2 * bln * 8, ln.stream);
-        int r = dfs(&acc);
-        if (r) return r;
-        op_ntt(c, acc.accS, B * 2 * L, 0, L, true);
-        LeafSumArgs ls;
-        memset(&ls, 0, sizeof(ls));
-        ls.accS = acc.accS; ls.accH = acc.accH; ls.out = out; ls.mods = c->d_mods; ls.logn = c->logn;
-        ls.B = (int)B; ls.L = L; ls.ks = c->ksc;
-        k_leaf_sum(ls, ln.stream);
-        return HHE_OK;
+    if (max_depth == 0) shared = false;
+    rt_d2d(out, prod, B * ctw * 8, ln.stream);
+    auto dfs = [&](const FcLeafAcc *acc) {
+        return shared ? fc_dfs_shared(c, trie, max_depth, prod, out, acc, B) : fc_dfs(c, trie, 0, 1, prod, ln.ws_rot.p, out, acc, B);
     };
-    if (!shared || max_depth == 0) return run(false);
-    return run(true);
+    if (!c->fc_leaf_sums) return dfs(nullptr);
+    FcLeafAcc acc;
+    acc.accS = ln.ws_ct[0]; acc.accH = ln.ws_ct[1]; acc.rscr = ln.ws_leaf.p + B * 2 * (size_t)HHE_LEAF_GROUP * c->n;
+    rt_memset(acc.accS, 0, 2 * bln * 8, ln.stream);
+    rt_memset(acc.accH, 0, 2 * bln * 8, ln.stream);
+    if ((rc = dfs(&acc))) return rc;
+    op_ntt(c, acc.accS, B * 2 * L, 0, L, true);
+    LeafSumArgs ls;
+    memset(&ls, 0, sizeof(ls));
+    ls.accS = acc.accS; ls.accH = acc.accH; ls.out = out; ls.mods = c->d_mods; ls.logn = c->logn;
+    ls.B = (int)B; ls.L = L; ls.ks = c->ksc;
+    k_leaf_sum(ls, ln.stream);
+    return HHE_OK;
+}
+
+// hhe_fc_row with the key objects already named: c->rks relinearizes the product, c->gks serves the rotation sum
+static int fc_row_impl(hhe_ctx *c, const uint64_t *vi, const uint64_t *w, size_t W, size_t n_inputs, int default_galois_only, uint64_t *out, size_t B)
+{
+    if (!c || !vi || !w || !out || W == 0 || B == 0 || n_inputs == 0 || n_inputs > c->n / 2)
+        return fail(HHE_ERR_INVALID, "hhe_fc_row: bad arguments");
+    if (!c->rks->rk) return fail(HHE_ERR_NO_RELIN_KEY, "relinearization key not set");
+    std::vector<NafNode> trie;
+    int max_depth = 0, rc = fc_build_trie(c, n_inputs, default_galois_only, trie, max_depth);
+    if (rc) return rc;
+    // chunks bound the key-switch working set (digit transforms per trie level); a chunk is a multiple of W so that item i
+    // of a chunk still uses weight row i % W.  A single chunk runs on the main lane, without a fork.
+    size_t per = c->fc_chunk ? c->fc_chunk : B;
+    if (per < B) per = std::max<size_t>(W, per / W * W);
+    ChunkPlan plan(B, std::min(per, B), c->nstreams);
+    if (plan.nch == 1) plan.ns = 0;
+    const size_t ctw = c->ct_words();
+    Lane &main = c->lanes[0];
+    const bool shared = c->fc_shared != 0;
+    auto reserve = [&](Lane &ln) {
+        int r = lane_reserve(c, ln, plan.per);
+        if (!r) r = ln.ws_rot.reserve(c, plan.per * ROT_SLOTS * ctw, "hhe_fc_row workspace");
+        if (!r && c->fc_leaf_sums) r = ln.ws_leaf.reserve(c, plan.per * 4 * (size_t)HHE_LEAF_GROUP * c->n, "hhe_fc_row workspace");
+        return r;
+    };
+    for (int s = plan.first_lane(); s <= plan.last_lane(); ++s)
+        if ((rc = reserve(c->lanes[s]))) return rc;
+    u32 *flags = nullptr;
+    if (shared) {
+        if ((rc = c->d_flags.reserve(c, plan.nch, "hhe_fc_row"))) return rc;  // one flag per chunk
+        flags = c->d_flags.p;
+        rt_memset(flags, 0, plan.nch * 4, main.stream);
+    }
+    auto chunk = [&](Lane &ln, size_t idx, size_t b0, size_t bc, bool sh) {
+        ln.zero_flag = sh ? flags + idx : nullptr;
+        return fc_row_chunk(c, sh, trie, max_depth, vi + b0 * ctw, w, W, out + b0 * ctw, bc);
+    };
+    rc = run_chunks(c, plan, [&](Lane &ln, size_t idx, size_t b0, size_t bc) { return chunk(ln, idx, b0, bc, shared); });
+    if (shared && !rc) {
+        std::vector<u32> h(plan.nch, 0);
+        if (rt_d2h(h.data(), flags, plan.nch * 4, main.stream) || rt_sync(main.stream)) rc = dev_fail("hhe_fc_row");
+        // a zero coefficient in some c1 (probability ~ N/q per ciphertext): that chunk is recomputed with per-child transforms, on the
+        // main lane (which grows, if it must, before the first of them: everything has completed by then)
+        for (size_t idx = 0; idx < plan.nch && !rc; ++idx)
+            if (h[idx] || c->fc_shared == 2) {
+                c->fc_fallbacks++;
+                if (!(rc = reserve(main))) rc = chunk(main, idx, idx * plan.per, plan.count(idx), false);
+            }
+    }
+    if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_fc_row");
+    return rc;
+}
+extern "C" int hhe_fc_row_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const uint64_t *vi, const uint64_t *w, size_t W, size_t n_inputs,
+                             uint64_t *out, size_t B)
+{
+    HHE_LOCK(c);
+    if (!c) return fail(HHE_ERR_INVALID, "hhe_fc_row: null context");
+    int rc = check_sets(c, rk, gk);
+    if (rc) return rc;
+    KeyScope keys(c, gk, rk);
+    return fc_row_impl(c, vi, w, W, n_inputs, 0, out, B);  // the set IS the GaloisKeys object: every key it holds is visible to rotate_rows
+}
+extern "C" int hhe_fc_row(hhe_ctx *c, const uint64_t *vi, const uint64_t *w, size_t W, size_t n_inputs, int relin_slot,
+                          int default_galois_only, uint64_t *out, size_t B)
+{
+    HHE_LOCK(c);
+    if (!c || relin_slot < 0 || relin_slot >= HHE_RELIN_SLOTS) return fail(HHE_ERR_INVALID, "hhe_fc_row: bad arguments");
+    KeyScope keys(c, nullptr, c->relin_set(relin_slot));
+    return fc_row_impl(c, vi, w, W, n_inputs, default_galois_only, out, B);
 }
 
 // ====================================================================== packed plain-matrix affine layers
@@ -1732,18 +1695,15 @@ int affine_chunk(hhe_ctx *c, const hhe_matrix *m, const u64 *in, u64 *out, size_
         // diagonal (:271-313): the fused loop of the PASTA layers with dim steps of rotate_rows(+1) and the one table for every item
         rt_d2d(w.ws_ct[0], in, B * ctw * 8, w.stream);
         const DiagSched sch{(int)m->dim, 1, pre, 0, m->dim * ln};
-        if ((rc = matmul_diagonal_fused(c, sch, m->self, B))) return rc;
+        if ((rc = matmul_diagonal_fused(c, sch, m->self.p, B))) return rc;
         res = w.ws_ct[0];
     } else {
         // babystep_giantstep (:185-267).  The baby steps are a sequential chain (each key switch's rounding feeds the next); then ONE
         // forward transform over all of them, all n2 inner sums in one kernel, ONE inverse transform, and the giant rotations
         const size_t n1 = (size_t)m->n1, n2 = (size_t)m->n2;
-        u64 *rot = w.ws_aff, *inner = rot + n1 * B * ctw;  // [n1][B][2][L][N] | [n2][B][2][L][N]
+        u64 *rot = w.ws_aff.p, *inner = rot + n1 * B * ctw;  // [n1][B][2][L][N] | [n2][B][2][L][N]
         rt_d2d(rot, in, B * ctw * 8, w.stream);
-        if (pre) {
-            if ((rc = op_rotate_rows(c, rot, pre, w.ws_ct[2], B))) return rc;
-            op_add(c, rot, w.ws_ct[2], rot, B, 2);
-        }
+        if (pre && (rc = op_prep_rows(c, rot, pre, w.ws_ct[2], B))) return rc;
         for (size_t j = 1; j < n1; ++j)
             if ((rc = op_rotate_rows(c, rot + (j - 1) * B * ctw, 1, rot + j * B * ctw, B))) return rc;
         op_ntt(c, rot, n1 * B * 2 * L, 0, L, false);
@@ -1752,7 +1712,7 @@ int affine_chunk(hhe_ctx *c, const hhe_matrix *m, const u64 *in, u64 *out, size_
         p.bsgs_n1 = (int)n1; p.bsgs_n2 = (int)n2;
         p.in = rot; p.in_step_stride = B * ctw; p.in_item_stride = ctw;
         p.out = inner; p.out_step_stride = B * ctw; p.out_item_stride = ctw;
-        p.mul_ptrs = m->self; p.mul_step_stride = ln;
+        p.mul_ptrs = m->self.p; p.mul_step_stride = ln;
         p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(B * 2 * L); p.L = L;
         k_perm(p, w.stream);
         op_ntt(c, inner, n2 * B * 2 * L, 0, L, true);
@@ -1768,27 +1728,18 @@ int affine_chunk(hhe_ctx *c, const hhe_matrix *m, const u64 *in, u64 *out, size_
     else rt_d2d(out, res, B * ctw * 8, w.stream);
     return HHE_OK;
 }
-// grow-only per-call state: the handle's pointer array and the lane's BSGS workspace for chunks of `per` items
-int affine_reserve(hhe_ctx *c, hhe_matrix *m, Lane &ln, size_t per)
+// the handle's pointer array for chunks of `per` items: every entry names the one table
+int matrix_reserve_self(hhe_ctx *c, hhe_matrix *m, size_t per)
 {
-    int rc = lane_reserve(c, ln, per);
-    if (rc) return rc;
-    if (m->self_cap < per) {
-        sync_ctx(c);
-        rt_free((void *)m->self);
-        m->self_cap = 0;
-        if (!(m->self = (const u64 **)rt_malloc(per * sizeof(u64 *)))) return dev_fail("hhe_packed_affine: pointer table");
-        std::vector<const u64 *> h(per, m->tab);
-        if (rt_h2d((void *)m->self, h.data(), per * sizeof(u64 *), ln.stream) || rt_sync(ln.stream)) return dev_fail("hhe_packed_affine: pointer table");
-        m->self_cap = per;
-    }
-    const size_t need_words = m->n1 ? (size_t)(m->n1 + m->n2) * per * c->ct_words() : 0;
-    if (ln.aff_cap < need_words) {
-        sync_ctx(c);
-        rt_free(ln.ws_aff);
-        ln.aff_cap = 0;
-        if (!(ln.ws_aff = (u64 *)rt_malloc(need_words * 8))) return dev_fail("hhe_packed_affine: babystep-giantstep workspace");
-        ln.aff_cap = need_words;
+    bool grew = false;
+    int rc = m->self.reserve(c, per, "hhe_packed_affine: pointer table", &grew);
+    if (rc || !grew) return rc;
+    rt_stream st = c->lanes[0].stream;
+    std::vector<const u64 *> h(m->self.cap, m->tab);
+    if (rt_h2d((void *)m->self.p, h.data(), h.size() * sizeof(u64 *), st) || rt_sync(st)) {
+        rc = dev_fail("hhe_packed_affine: pointer table");
+        m->self.release();  // never leave an unfilled array behind
+        return rc;
     }
     return HHE_OK;
 }
@@ -1797,7 +1748,7 @@ int affine_reserve(hhe_ctx *c, hhe_matrix *m, Lane &ln, size_t per)
 void matrix_free(hhe_matrix *m)
 {
     if (!m) return;
-    rt_free(m->tab); rt_free(m->bias); rt_free((void *)m->self);
+    rt_free(m->tab); rt_free(m->bias); m->self.release();
     delete m;
 }
 
@@ -1900,30 +1851,14 @@ extern "C" int hhe_packed_affine_ks(hhe_ctx *c, const hhe_keyset *gk, const hhe_
         if (s == 1 ? (m->dim > 1 && !c->gks->gk.count(galois_elt_from_step(c, 1))) : !rot_reachable(c, s)) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
     Lane &main = c->lanes[0];
     c->w = &main;
-    const int ns = c->nstreams;
-    if (ns == 0) {
-        if (!(rc = affine_reserve(c, m, main, B))) rc = affine_chunk(c, m, ct, out, B);
-    } else {
-        // chunks round-robin over the internal streams, as hhe_pasta3_transcipher forms them
-        size_t nch = (B + c->chunk - 1) / c->chunk;
-        if (nch > 1) nch = (nch + ns - 1) / ns * ns;
-        const size_t per = (B + nch - 1) / nch;
-        for (int s = 1; s <= ns && !rc; ++s) rc = affine_reserve(c, m, c->lanes[s], per);
-        if (!rc) {
-            rt_event_record(c->ev_fork, main.stream);
-            for (int s = 1; s <= ns; ++s) rt_stream_wait_event(c->lanes[s].stream, c->ev_fork);
-            size_t idx = 0;
-            for (size_t b0 = 0; b0 < B && !rc; b0 += per, ++idx) {
-                c->w = &c->lanes[1 + idx % ns];
-                rc = affine_chunk(c, m, ct + b0 * c->ct_words(), out + b0 * c->ct_words(), std::min(per, B - b0));
-            }
-            for (int s = 1; s <= ns; ++s) {
-                rt_event_record(c->lanes[s].ev_done, c->lanes[s].stream);
-                rt_stream_wait_event(main.stream, c->lanes[s].ev_done);
-            }
-        }
-        c->w = &main;
+    const ChunkPlan plan = plan_balanced(c, B);
+    const size_t ctw = c->ct_words();
+    for (int s = plan.first_lane(); s <= plan.last_lane(); ++s) {
+        if ((rc = lane_reserve(c, c->lanes[s], plan.per))) return rc;
+        if (m->n1 && (rc = c->lanes[s].ws_aff.reserve(c, (size_t)(m->n1 + m->n2) * plan.per * ctw, "hhe_packed_affine: babystep-giantstep workspace"))) return rc;
     }
+    if ((rc = matrix_reserve_self(c, m, plan.per))) return rc;
+    rc = run_chunks(c, plan, [&](Lane &, size_t, size_t b0, size_t bc) { return affine_chunk(c, m, ct + b0 * ctw, out + b0 * ctw, bc); });
     if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_packed_affine");
     return rc;
 }

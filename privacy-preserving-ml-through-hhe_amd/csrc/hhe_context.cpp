@@ -365,13 +365,11 @@ static void free_lane(Lane &ln)
 {
     rt_free(ln.ws_T); rt_free(ln.ws_S); rt_free(ln.ws_d); rt_free(ln.ws_ct3); rt_free(ln.ws_plain); rt_free(ln.ws_vals);
     for (auto &p : ln.ws_ct) { rt_free(p); p = nullptr; }
-    rt_free(ln.ws_rot); ln.ws_rot = nullptr; ln.rot_cap = 0;
-    rt_free(ln.ws_aff); ln.ws_aff = nullptr; ln.aff_cap = 0;
+    ln.ws_rot.release(); ln.ws_aff.release(); ln.ws_leaf.release();
     for (auto &sl : ln.fc_slots) { rt_free(sl.tp); rt_free(sl.ct); rt_free(sl.c0hat); }
     ln.fc_slots.clear(); ln.fc_slot_cap = 0;
     for (u64 *p : ln.csum_bufs) rt_free(p);
     ln.csum_bufs.clear();
-    rt_free(ln.ws_leaf); ln.ws_leaf = nullptr; ln.leaf_cap = 0;
     rt_free((void *)ln.d_ptrs); ln.d_ptrs = nullptr; ln.ptr_cap = 0;
     for (auto &pr : ln.prof_ev) { rt_event_destroy(pr.first); rt_event_destroy(pr.second); }
     ln.prof_ev.clear(); ln.prof_used = 0;
@@ -446,8 +444,8 @@ extern "C" void hhe_ctx_destroy(hhe_ctx *c)
     rt_free(c->d_feistel_mask);
     rt_free(c->d_zero_corr);
     rt_free(c->d_qsp_poly);
-    rt_free(c->d_blocks); rt_free(c->d_flags);
-    rt_free(c->l0_tab); rt_free((void *)c->l0_ptrs);
+    c->d_blocks.release(); c->d_flags.release();
+    c->l0_tab.release(); c->l0_ptrs.release();
     rt_free(c->d_tables); rt_free(c->d_mods); rt_free(c->d_behz); rt_free(c->d_slot_map);
     delete c;
 }
@@ -538,7 +536,7 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "block_cache_entries") return c->blocks.size();
     if (w == "row_kernel") return use_row_kernel(c) ? 1 : 0;
     if (w == "shared_l0") return (u64)c->shared_l0;       // smallest batch that takes the shared first layer (0: none)
-    if (w == "shared_l0_steps") return c->l0_tab_steps;   // steps per block of the operand table of the last shared first layer (0: none ran)
+    if (w == "shared_l0_steps") return c->l0_steps();   // steps per block of the operand table of the last shared first layer (0: none ran)
     if (w == "pm_ok" && i >= 0 && i < c->K) return (u64)c->pm_ok[i];
     if (w == "digit_reduce") return (u64)c->digit_reduce;
     return 0;

@@ -6,6 +6,44 @@
 #include <vector>
 #include "hhe_common.h"
 #include "hhe_launch.h"
+#include "../../include/hhe_gfx950.h"
+
+struct hhe_ctx;
+void hhe_set_error(const std::string &msg);
+void sync_ctx(hhe_ctx *c);  // waits for every stream of the context
+
+struct DevBuf {  // scoped device allocation (freed on every exit path unless released)
+    void *p = nullptr;
+    explicit DevBuf(size_t bytes) { p = rt_malloc(bytes ? bytes : 8); }
+    ~DevBuf() { if (p) rt_free(p); }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    u64 *w() const { return (u64 *)p; }
+    u64 *release() { u64 *r = (u64 *)p; p = nullptr; return r; }
+};
+// Grow-only device workspace of a context, a lane or a handle; `cap` counts elements of T.  A request within the capacity costs
+// nothing.  Growth waits for every stream of the context (something in flight may still read the old buffer), frees, allocates;
+// when the allocation fails the buffer is left empty ({nullptr, 0}), so the next request of any size allocates again.
+template <class T> struct GrowBuf {
+    T *p = nullptr;
+    size_t cap = 0;
+    // HHE_OK, or HHE_ERR_DEVICE with the error text "<what>: <runtime message>"; *grew: the buffer is a new one (contents undefined)
+    int reserve(hhe_ctx *c, size_t count, const char *what, bool *grew = nullptr)
+    {
+        if (grew) *grew = false;
+        if (count <= cap) return HHE_OK;
+        sync_ctx(c);
+        release();
+        if (!(p = (T *)rt_malloc(count * sizeof(T)))) {
+            hhe_set_error(std::string(what) + ": " + rt_last_error());
+            return HHE_ERR_DEVICE;
+        }
+        cap = count;
+        if (grew) *grew = true;
+        return HHE_OK;
+    }
+    void release() { rt_free((void *)p); p = nullptr; cap = 0; }  // the caller has waited for the readers
+};
 
 struct BlockTables {   // public per-(nonce, block index) data of one PASTA block, device resident
     u64 *diag = nullptr;  // [4][128][L][N] lifted + NTT'd diagonals (multiply_plain operands)
@@ -18,7 +56,6 @@ struct BlockTables {   // public per-(nonce, block index) data of one PASTA bloc
 
 constexpr int HHE_MAX_STREAMS = 4;
 constexpr int HHE_RELIN_SLOTS = 4;
-struct hhe_ctx;
 // One seal::RelinKeys / seal::GaloisKeys object with its identity: the reference's CSP holds several made by the same key
 // generator with different randomness (analyst_he_gk with all default elements, csp_he_gk with the flatten steps, two RelinKeys;
 // Analyst.cpp:62-94) and names the one it uses at every call (CSP.cpp:238-242, 271-278, 306, 312-316); which keys a rotation
@@ -38,11 +75,12 @@ struct hhe_matrix {
     int n1 = 0, n2 = 0;          // babystep-giantstep split; 0 / 0: diagonal method
     u64 *tab = nullptr;          // diagonal: [dim][L][N] multipliers in the frame of rotate_rows(+1) | their Shoup quotients; BSGS: [dim][L][N]
     u64 *bias = nullptr;         // [N] plaintext of the bias (coefficients mod t), or null
-    const u64 **self = nullptr;  // [self_cap] device pointers, all = tab: the per-item pointer array the kernels take
-    size_t self_cap = 0;
+    GrowBuf<const u64 *> self;   // device pointers, all = tab: the per-item pointer array the kernels take (refilled when it grows)
     size_t bytes = 0;            // device footprint of tab + bias
 };
-struct Lane {   // one stream + the per-batch workspaces of the ops (capacity `cap` ciphertexts)
+// one stream + the per-batch workspaces of the ops: lane_reserve allocates the fixed set for `cap` ciphertexts under that one
+// capacity; the GrowBuf members belong to single schedules, grow on their own and go with the lane's workspaces (free_lane)
+struct Lane {
     rt_stream stream = nullptr;
     void *ev_done = nullptr;
     bool own_stream = false;
@@ -60,18 +98,15 @@ struct Lane {   // one stream + the per-batch workspaces of the ops (capacity `c
     u64 *bz_db = nullptr;    // [B][3][L+1][N]
     const u64 **d_ptrs = nullptr;  // [2*cap] per-item public-table pointers (diag | rc)
     size_t ptr_cap = 0;
-    u64 *ws_rot = nullptr;   // [B][16][2][L][N] babystep rotations (allocated on first BSGS use)
-    size_t rot_cap = 0;
-    u64 *ws_aff = nullptr;   // [n1 + n2][B][2][L][N] baby-step ciphertexts | inner sums of hhe_packed_affine (BSGS; grow-only)
-    size_t aff_cap = 0;      // words
+    GrowBuf<u64> ws_rot;     // [16][B][2][L][N]: PASTA's babystep rotations, and the FC's product + per-depth buffers of the unshared walk
+    GrowBuf<u64> ws_aff;     // [n1 + n2][B][2][L][N] baby-step ciphertexts | inner sums of hhe_packed_affine (BSGS)
     // FC shared digits: one slot per trie node that is still needed -- the digit transforms of its un-rotated c1 (tp [B][L][K][N]) and its
     // ciphertext (ct [B][2][L][N]); refs = 1 while the depth-first walk is below the node + 1 per queued leaf key switch that reads it
     struct FcSlot { u64 *tp = nullptr, *ct = nullptr, *c0hat = nullptr; int refs = 0; int tp_polys = 0; };  // c0hat [B][L][N]: NTT form of the node's c0 (nodes with a non-leaf child)  // tp_polys: K, or 1 when tp holds the special-prime transforms only
     std::vector<FcSlot> fc_slots;
     std::vector<u64 *> csum_bufs;  // FC leaves: integer sums of parents' c1 per Galois element, [B][L][N] each (sized like the slots)
     size_t fc_slot_cap = 0;  // items the slots were sized for
-    u64 *ws_leaf = nullptr;  // FC leaf groups: special-limb sums [B][2][G][N] | their inverse transforms [B][2][G][N], G = HHE_LEAF_GROUP
-    size_t leaf_cap = 0;
+    GrowBuf<u64> ws_leaf;    // FC leaf groups: special-limb sums [B][2][G][N] | their inverse transforms [B][2][G][N], G = HHE_LEAF_GROUP
     u32 *zero_flag = nullptr; // device flag of the chunk this lane is evaluating (shared-digit FC)
     // host staging of small per-call inputs (mask values, pointer tables): it outlives the asynchronous copy, and the next
     // user waits for that copy (ev_stage) before overwriting it
@@ -120,10 +155,9 @@ struct hhe_ctx {
                                    // (HHE_SHARED_L0; 1: every call, 0: never = per-item chain).  A few items cost what one costs (latency-bound either
                                    // way), so below the threshold sharing saves nothing and adds the sum launches: ms per call shared / per item at 4, 8, 12, 16, 32 items: 38.4 / 36.3, 44.5 / 44.1, 54.7 / 58.2, 61.7 / 66.8, 98.5 / 113.4
     size_t l0_budget = (size_t)512 << 20;  // bytes the operand table of that chain may take (HHE_SHARED_L0_MB); a chain that needs more runs in blocks of steps
-    u64 *l0_tab = nullptr;         // [S][2][L][N] operands of S chain steps (workspace, allocated on first use, freed with the context)
-    size_t l0_tab_steps = 0;
-    const u64 **l0_ptrs = nullptr; // [l0_ptr_cap] per-item diagonal tables of the running call
-    size_t l0_ptr_cap = 0;
+    GrowBuf<u64> l0_tab;           // [3][S][L][N] operands of S chain steps (L0Capture), exactly that size (allocated on first use, freed with the context)
+    GrowBuf<const u64 *> l0_ptrs;  // per-item diagonal tables of the running call
+    size_t l0_steps() const { return l0_tab.cap / ((size_t)3 * L * n); }
     KsConsts ksc{};
 
     // device tables
@@ -147,11 +181,9 @@ struct hhe_ctx {
     std::map<const u64 *, u64 *> d_key_shoup;  // per key-switch key (by device address): Shoup quotients of its words (fused row kernel), built on first use
     hhe_keyset *relin_set(int slot) { return slot == 0 ? &keys0 : &rk_slots[slot]; }
 
-    // grow-only device scratch of hhe_decompose (all blocks of the records) and hhe_fc_row (per-chunk flags)
-    u64 *d_blocks = nullptr;
-    size_t blocks_cap = 0;   // words
-    u32 *d_flags = nullptr;
-    size_t flags_cap = 0;    // entries
+    // device scratch of hhe_decompose (all blocks of the records) and hhe_fc_row (one flag per chunk)
+    GrowBuf<u64> d_blocks;
+    GrowBuf<u32> d_flags;
 
     // PASTA public tables
     std::map<u64, BlockTables> blocks;
@@ -160,14 +192,15 @@ struct hhe_ctx {
     u64 block_call = 0;                          // running number of the transciphering calls
     u64 *d_feistel_mask = nullptr;  // [L][N] NTT form of the sbox_feistel mask plaintext
 
-    // execution lanes: lane 0 runs on the caller's stream (generic ops); lanes 1.. are internal streams that
-    // the transciphering path uses to process chunks of a batch concurrently (each with its own workspace)
+    // execution lanes: lane 0 runs on the caller's stream (generic ops); lanes 1.. are internal streams on which the batched
+    // calls (transciphering, FC row, packed affine layer) process chunks of a batch concurrently, each with its own workspace
+    // (ChunkPlan / run_chunks in hhe_api.cpp)
     Lane lanes[1 + HHE_MAX_STREAMS];
     Lane *w = &lanes[0];
     int nstreams = 1;      // internal streams used by hhe_pasta3_transcipher (0 = caller's stream only).  One: since the row kernel lost its
                            // exposed round trips two overlapping chunks give the same throughput (289 vs 289 /s) and make every kernel's duration depend on its neighbour
     size_t chunk = 128;    // items per chunk (HHE_CHUNK); measured 211 /s at 32, 221 at 64, 225 at 128 items (round 1)
-    void *ev_fork = nullptr;
+    void *ev_fork = nullptr; // recorded on the main stream when the chunks fork; every used lane waits for it
 
     size_t ct_words() const { return (size_t)2 * L * n; }
     size_t ksk_words() const { return (size_t)L * 2 * K * n; }
@@ -201,16 +234,6 @@ inline int ntt_lazy8(const hhe_ctx *c, int mod_base, int mod_cycle)
 // below a power of two do not.  hhe_ctx_query("row_kernel") reports the decision.
 inline bool use_row_kernel(const hhe_ctx *c) { return k_ks_row_supported(c->logn) && ntt_lazy8(c, 0, c->K); }
 
-struct DevBuf {  // scoped device allocation (freed on every exit path unless released)
-    void *p = nullptr;
-    explicit DevBuf(size_t bytes) { p = rt_malloc(bytes ? bytes : 8); }
-    ~DevBuf() { if (p) rt_free(p); }
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    u64 *w() const { return (u64 *)p; }
-    u64 *release() { u64 *r = (u64 *)p; p = nullptr; return r; }
-};
-
 struct CtxLock {  // null-safe scoped lock of a context (entry points check their arguments after taking it)
     std::unique_lock<std::recursive_mutex> l;
     explicit CtxLock(const hhe_ctx *c) { if (c) l = std::unique_lock<std::recursive_mutex>(const_cast<hhe_ctx *>(c)->mu); }
@@ -233,7 +256,5 @@ int keyset_put_galois(hhe_keyset *ks, u32 elt, const u64 *ksk);
 int keyset_put_relin(hhe_keyset *ks, const u64 *ksk);
 void keyset_clear(hhe_keyset *ks);
 
-void hhe_set_error(const std::string &msg);
 int lane_reserve(hhe_ctx *c, Lane &ln, size_t B);
-void sync_ctx(hhe_ctx *c);  // waits for every stream of the context
 void matrix_free(hhe_matrix *m);  // hhe_api.cpp: device memory of a handle and the handle

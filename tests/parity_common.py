@@ -205,6 +205,66 @@ def check_transcipher(X, S, orc, mem, pt, block_ids=None, check_decrypt=True, or
     return res
 
 
+def check_batched_calls_regrow(make_ctx, S, orc, mem, n_in=37, dim=16, bsgs=(4, 4)):
+    """The three batched entry points on ONE context whose internal streams have been used, every grow-only workspace reallocated
+    in between: hhe_pasta3_transcipher (use_bsgs = 1), hhe_packed_affine_ks (BSGS handle) and hhe_fc_row_ks (W = 1) with 1 item,
+    then 5 (with 2 items per chunk: three chunks on two lanes, the last one ragged), then 1 again.  Every output word equals the
+    same call on a fresh context that saw that batch size first; item 0 of every first call equals the oracle.  make_ctx() returns
+    a fresh context created under the knobs the caller set (HHE_STREAMS, HHE_CHUNK, HHE_FC_CHUNK); S holds every default Galois
+    key plus steps -16k (k = 1..7) and the affine layer's (affine_common.hand_steps)."""
+    import affine_common as ac
+    O = S.O
+    small, large = 1, 5
+    pt = np.array([(11 * i + 5) % 256 for i in range(128 * large)], dtype=np.uint64)
+    cw, ncw = S.sym_blocks(orc, pt[:128 * large - 30])   # the last block is short
+    M, bias = ac.seeded_matrix(S.t, dim, 77)
+    cts, _ = ac.inputs(S, dim, large, 7)
+    rng = np.random.default_rng(21)
+    v, w = rng.integers(0, 4, (large, n_in)), rng.integers(-8, 9, n_in)
+    vi = np.stack([O.encrypt(S.pk, O.encode(v[b]), 141 + b) for b in range(large)])
+    wc = O.encrypt(S.pk, O.encode(w % S.t), 143)
+
+    def open_ctx():
+        X = make_ctx()
+        S.load_keys(X)
+        ks = X.keyset()   # hhe_fc_row_ks names its key objects
+        ks.set_relin(S.rk)
+        for e, k in zip(S.gk.elts, S.gk.keys):
+            ks.set_galois(int(e), k)
+        return X, ks, X.matrix(M, bias=bias, bsgs=bsgs)
+
+    def calls(ctx, B):
+        X, ks, mat = ctx
+        o_t, o_a, o_f = (mem.empty((B,) + O.ct_shape) for _ in range(3))
+        X.transcipher(mem.to_dev(S.enc_key), cw[:B], ncw[:B], list(range(B)), o_t, use_bsgs=True)
+        X.packed_affine(mem.to_dev(cts[:B]), mat, o_a, B)
+        X.fc_row(mem.to_dev(vi[:B]), mem.to_dev(wc[None]), 1, n_in, o_f, B, rk=ks, gk=ks)
+        return [mem.to_host(o) for o in (o_t, o_a, o_f)]
+
+    def close(ctx):
+        X, ks, mat = ctx
+        mat.close(); ks.close(); X.close()
+
+    fresh = {}
+    for B in (small, large):
+        ctx = open_ctx()
+        fresh[B] = calls(ctx, B)
+        close(ctx)
+    ctx = open_ctx()
+    for B in (small, large, small):
+        got = calls(ctx, B)
+        for name, g, f in zip(("transcipher", "packed_affine", "fc_row"), got, fresh[B]):
+            assert g.shape == f.shape and (g == f).all(), (name, B, "differs from a fresh context", np.argwhere((g != f).reshape(B, -1).any(axis=1)).ravel())
+    assert ctx[0].query("fc_fallbacks") == 0
+    close(ctx)
+    ref_t = O.transcipher_block(S.enc_key, S.rk, S.gk, cw[0, :ncw[0]], 0, use_bsgs=True)
+    ref_a = ac.packed_affine_ref(O, S.gk, M, cts[0], bias, bsgs)
+    ref_f = O.fc_row(vi[0], wc, S.rk, S.gk, n_in)[0]
+    for B in (small, large):
+        for name, g, ref in zip(("transcipher", "packed_affine", "fc_row"), fresh[B], (ref_t, ref_a, ref_f)):
+            assert (g[0] == ref).all(), (name, B, "item 0 differs from the oracle")
+
+
 def golden_key(t):
     return np.array([(i * 2654435761 + 12345) % t for i in range(256)], dtype=np.uint64)
 
@@ -598,7 +658,7 @@ def default_galois_elts_py(n):
 
 
 class FcTrie:
-    """Model of the rotation trie of one hhe_fc_row chunk, built by the rule of fc_row_chunk (csrc/hhe_api.cpp) and nothing else of
+    """Model of the rotation trie of one hhe_fc_row chunk, built by the rule of fc_build_trie (csrc/hhe_api.cpp) and nothing else of
     the library: for i = 1 .. n_in-1, step -i is ONE term [-i] if the key set holds its element and (i is a power of two, or the
     call sees the whole set: hhe_fc_row_ks, or default_galois_only = 0); otherwise its terms are naf(-i) without those equal to
     +-N/2.  Node 0 is the root (the relinearized product); term[k] / parent[k] / kids[k] / mult[k] describe node k, mult = how many
