@@ -49,7 +49,10 @@ const char *hhe_backend(void);
 /* ---- context: replaces SEALZpCipher::create_context / sealhelper::get_seal_context
  *      (src/pasta/SEAL_Cipher.cpp:38-68, src/util/sealhelper.cpp:8-41) with an explicit
  *      prime list: q[K] = coeff_modulus (last = special key-switch prime), t = plain_modulus.
- *      Derives NTT tables, BatchEncoder map, BEHZ base exactly as SEAL 4.0.0 does. ---- */
+ *      Derives NTT tables, BatchEncoder map, BEHZ base exactly as SEAL 4.0.0 does.
+ *      t may be any batching prime below 2^61, on either side of the coefficient primes: the reference's 65537,
+ *      8088322049 and 1096486890805657601 (configs/config.cpp:19-26), the last one above every prime of
+ *      BFVDefault(32768).  What that means for plaintexts is stated at hhe_multiply_plain. ---- */
 int hhe_ctx_create(int logn, int K, const uint64_t *q_hptr, uint64_t t, int device, hhe_ctx **out);
 /* the prime chain SEALZpCipher::create_context picks: CoeffModulus::BFVDefault(N) for N <= 32768 and the hard-coded
  * 29-prime chain for N = 65536 (src/pasta/SEAL_Cipher.cpp:47-65).  *count: in = capacity, out = number of primes. */
@@ -115,7 +118,11 @@ int hhe_negate(hhe_ctx *c, const uint64_t *a_dptr, uint64_t *out_dptr, size_t B,
 /* Evaluator::add_plain / sub_plain (seal/evaluator.h:665-680); plain [B][N] or [1][N] if bcast */
 int hhe_add_plain(hhe_ctx *c, const uint64_t *ct_dptr, const uint64_t *plain_dptr, int plain_bcast,
                   int subtract, uint64_t *out_dptr, size_t B);
-/* Evaluator::multiply_plain (seal/evaluator.h:729-747) */
+/* Evaluator::multiply_plain (seal/evaluator.h:729-747).  Plaintext lift, per limb j and for any t < 2^61 and any q_j: a
+ * coefficient x in [0, t) becomes x mod q_j below (t + 1) / 2 and (x - t) mod q_j from there on, the residue of its centred
+ * representative.  Where t < q_j that is SEAL's fast branch x + (q_j - t), no reduction; where t > q_j it is the per-prime
+ * decomposition of x + (Q - t) (seal/context.h:359-372).  The same lift feeds hhe_mask, hhe_matrix_create and the public
+ * tables of the transciphering. */
 int hhe_multiply_plain(hhe_ctx *c, const uint64_t *ct_dptr, const uint64_t *plain_dptr, int plain_bcast,
                        uint64_t *out_dptr, size_t B);
 /* Evaluator::apply_galois (seal/evaluator.h:889) */

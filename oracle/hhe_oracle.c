@@ -282,7 +282,7 @@ orc_ctx *orc_ctx_create(int logn, int K, const u64 *q, u64 t)
     c->q_mod_t = prod_mod_except(dq, L, -1, t);
     c->up_thr = (t + 1) >> 1;
     for (int j = 0; j < L; j++) {
-        c->up_inc[j] = q[j] - t;
+        c->up_inc[j] = t < q[j] ? q[j] - t : 0;   /* used by the fast lift only (orc_multiply_plain) */
         /* floor(Q/t) = (Q - Q mod t)/t  ==  -(Q mod t) * t^-1  (mod q_j) */
         u64 tinv = invmod(t % q[j], q[j]);
         c->delta[j] = negmod(mulmod_slow(c->q_mod_t % q[j], tinv, q[j]), q[j]);
@@ -757,7 +757,11 @@ void orc_multiply_plain(const orc_ctx *c, const u64 *a, const u64 *plain, u64 *o
     u64 *pl = (u64 *)malloc(8 * n), *tmp = (u64 *)malloc(8 * n);
     for (int j = 0; j < L; j++) {
         const modtab *m = &c->m[j];
-        for (size_t i = 0; i < n; i++) pl[i] = plain[i] >= c->up_thr ? plain[i] + c->up_inc[j] : plain[i];
+        if (c->t < m->q)   /* fast lift: x + (q_j - t) needs no reduction */
+            for (size_t i = 0; i < n; i++) pl[i] = plain[i] >= c->up_thr ? plain[i] + c->up_inc[j] : plain[i];
+        else               /* x + (Q - t) decomposed per prime (seal/context.h:359-372): (x - t) mod q_j from the threshold on */
+            for (size_t i = 0; i < n; i++)
+                pl[i] = plain[i] >= c->up_thr ? negmod((c->t - plain[i]) % m->q, m->q) : plain[i] % m->q;
         ntt_fwd(m, c->logn, pl);
         for (int k = 0; k < 2; k++) {
             size_t o = ((size_t)k * L + j) * n;

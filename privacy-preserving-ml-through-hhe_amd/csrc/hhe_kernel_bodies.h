@@ -172,9 +172,16 @@ template <bool FIRST> HD U2 ntt_load_op(const NttArgs &a, const ModDev &m, int p
             if (a.digit_reduce) { v.a = reduce64(v.a, m); v.b = reduce64(v.b, m); }
         }
         else if (a.load_op == LOAD_LIFT) {
-            const u64 thr = (a.t + 1) >> 1, inc = m.q - a.t;
-            v.a = (v.a >= thr) ? v.a + inc : v.a;
-            v.b = (v.b >= thr) ? v.b + inc : v.b;
+            // centred lift of x in [0,t) to the residue of x (below (t+1)/2) or of x - t (from there on) mod q
+            const u64 thr = (a.t + 1) >> 1;
+            if (a.t < m.q) {   // SEAL's fast branch: x + (q - t) is below q already.  Uniform over the workgroup (one modulus each)
+                const u64 inc = m.q - a.t;
+                v.a = (v.a >= thr) ? v.a + inc : v.a;
+                v.b = (v.b >= thr) ? v.b + inc : v.b;
+            } else {           // t above this prime: the decomposition of x + (Q - t), i.e. -((t - x) mod q), with 0 < t - x < t/2
+                v.a = (v.a >= thr) ? negmod(reduce64(a.t - v.a, m), m.q) : reduce64(v.a, m);
+                v.b = (v.b >= thr) ? negmod(reduce64(a.t - v.b, m), m.q) : reduce64(v.b, m);
+            }
         } else if (a.load_op == LOAD_RNEG) {
             const u64 h = a.ks.half_mod[poly % a.L];
             v.a = submod(reduce64(v.a, m), h, m.q);
