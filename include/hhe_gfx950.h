@@ -164,7 +164,14 @@ int hhe_pasta3_transcipher_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset
  * N = 2^15, L = 3; 1.07 / 2.1 GiB at the reference defaults N = 2^14, L = 8 -- and the babystep-giantstep variant adds (4 x 128 x L) x N.
  * The cache is bounded: beyond `bytes` (default 32 GiB; HHE_BLOCK_CACHE_MB) the least recently used counters are dropped, never
  * one the running call uses (a single call that needs more than the limit is served).  hhe_ctx_query("block_cache_bytes" /
- * "block_cache_entries") report its state; hhe_pasta3_clear_block_cache drops everything. */
+ * "block_cache_entries") report its state; hhe_pasta3_clear_block_cache drops everything.
+ * One keystream per counter (HHE_DEDUP, default 1): everything a transciphering does before it adds the item's own words -- the
+ * homomorphic keystream, res[b] = Enc(c_b) - state (pasta_3_seal.cpp:161-169) -- depends on enc_key, the key objects and the block
+ * counter only.  A call in which counters repeat (every record starts at counter 0: a batch of S records of nb blocks has nb
+ * distinct counters) evaluates each distinct counter once and finishes every item with one encode + add_plain against its counter's
+ * keystream; the output words are those of the per-item evaluation.  A call whose counters are all distinct runs as before, and
+ * HHE_DEDUP=0 makes every item evaluate its own keystream.  Nothing is kept from one call to the next (the ABI has no identity for
+ * enc_key).  hhe_ctx_query("dedup") reports the knob, "transcipher_unique" the keystream evaluations of the last call. */
 int hhe_pasta3_set_block_cache_limit(hhe_ctx *c, size_t bytes);
 void hhe_pasta3_clear_block_cache(hhe_ctx *c);
 /* SEALZpCipher::mask (src/pasta/SEAL_Cipher.cpp:161-166): mask_vals_hptr[count], shared by the batch */

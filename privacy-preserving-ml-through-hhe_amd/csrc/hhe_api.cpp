@@ -62,10 +62,10 @@ void op_elt(hhe_ctx *c, int op, const u64 *x, const u64 *y, u64 *out, size_t cou
 void op_add(hhe_ctx *c, const u64 *x, const u64 *y, u64 *out, size_t B, int size) { op_elt(c, ELT_ADD, x, y, out, B * size * c->L, 0, c->L); }
 
 void op_add_plain(hhe_ctx *c, const u64 *ct, const u64 *plain, const u64 *const *plain_ptrs, size_t shift, bool bcast,
-                  bool subtract, bool negate, u64 *out, size_t B)
+                  bool subtract, bool negate, u64 *out, size_t B, const u32 *ct_map = nullptr)
 {
     AddPlainArgs a = c->apl;
-    a.ct = ct; a.plain = plain; a.plain_ptrs = plain_ptrs; a.plain_shift = shift; a.out = out; a.B = (int)B;
+    a.ct = ct; a.ct_map = ct_map; a.plain = plain; a.plain_ptrs = plain_ptrs; a.plain_shift = shift; a.out = out; a.B = (int)B;
     a.plain_bcast = bcast; a.subtract = subtract; a.negate_ct = negate;
     k_add_plain(a, c->w->stream);
 }
@@ -655,7 +655,7 @@ int matmul_diagonal_fused(hhe_ctx *c, const DiagSched &sch, const u64 *const *d_
 
 // Shared first layer, once per transciphering call on lane 0 before the chunks fork: the rotation chain of layer 0 on the ONE key
 // ciphertext and, per block of S steps, the diagonal sums of all B items into `out` (which nothing else touches before a chunk's
-// last kernel).  The operand table is a workspace of the context: S = 128 states when 128 * 3 * L * N words fit the budget.
+// last kernel: the call's output, or its keystream table when items share counters).  The operand table is a workspace of the context: S = 128 states when 128 * 3 * L * N words fit the budget.
 int shared_l0_chain(hhe_ctx *c, const u64 *enc_key, const u64 *const *h_pdiag_ptrs, size_t B, u64 *out)
 {
     Lane &main = c->lanes[0];
@@ -863,6 +863,7 @@ extern "C" int hhe_relinearize_slot(hhe_ctx *c, int slot, const uint64_t *a3, ui
 
 // one chunk of the batch on the current lane (c->w): the schedule of PASTA_SEAL::decomposition (pasta_3_seal.cpp:123-170)
 // shared_l0: `out` holds the items' first-layer sums (shared_l0_chain)
+// cw_padded_host null: the keystream only -- the chunk stops before res = Enc(c_b) - KS and its last addition leaves the state in `out`
 static int transcipher_chunk(hhe_ctx *c, const u64 *enc_key, const u64 *const *d_diag, const u64 *const *d_rc,
                              const u64 *cw_padded_host, u64 *out, size_t B, bool bsgs, bool shared_l0)
 {
@@ -870,7 +871,7 @@ static int transcipher_chunk(hhe_ctx *c, const u64 *enc_key, const u64 *const *d
     const int L = c->L;
     const bool fused = c->matmul_mode == 1;
     int rc = HHE_OK;
-    rt_h2d(c->w->ws_vals, cw_padded_host, B * PASTA_T * 8, c->w->stream);
+    if (cw_padded_host) rt_h2d(c->w->ws_vals, cw_padded_host, B * PASTA_T * 8, c->w->stream);
     u64 *state = c->w->ws_ct[0], *tmp = c->w->ws_ct[1], *t3 = c->w->ws_ct3;
     // state <- enc_ssk[0] for every item (pasta_3_seal.cpp:126)
     if (!shared_l0) op_elt(c, ELT_BCAST, nullptr, enc_key, state, B * 2 * L, 0, L, 2 * L);
@@ -882,7 +883,7 @@ static int transcipher_chunk(hhe_ctx *c, const u64 *enc_key, const u64 *const *d
         // mix (:417-423)
         if ((rc = op_apply_galois(c, state, (u32)(2 * n - 1), tmp, B))) break;
         op_add(c, tmp, state, tmp, B, 2);
-        op_add(c, state, tmp, state, B, 2);
+        op_add(c, state, tmp, r == PASTA_R && !cw_padded_host ? out : state, B, 2);
         if (r == PASTA_R) break;
         if (r == PASTA_R - 1) {
             // sbox_cube (:215-218): exponentiate_inplace(x,3) == relin(mul(relin(mul(x,x)), x))
@@ -899,7 +900,7 @@ static int transcipher_chunk(hhe_ctx *c, const u64 *enc_key, const u64 *const *d
             op_add(c, state, tmp, state, B, 2);
         }
     }
-    if (!rc) {
+    if (!rc && cw_padded_host) {
         // res = Enc(c_b) - KS : encode, negate, add_plain (:161-169)
         op_encode(c, c->w->ws_vals, B, PASTA_T, PASTA_T, -1, c->w->ws_plain);
         op_add_plain(c, state, c->w->ws_plain, nullptr, 0, false, false, true, out, B);
@@ -908,11 +909,16 @@ static int transcipher_chunk(hhe_ctx *c, const u64 *enc_key, const u64 *const *d
 }
 
 // hhe_pasta3_transcipher with the key objects already named (c->rks / c->gks)
+// Everything before res = Enc(c_b) - KS is a function of the key ciphertext, the named key sets and the item's block counter only, so
+// items of one call with the same counter share one keystream ciphertext, word for word (HHE_DEDUP, DESIGN.md "one keystream per
+// counter").  A call in which counters repeat runs in two phases: the chunk schedule over its U distinct counters, which leaves the
+// keystreams in ks_tab, then a finishing pass over all B items (encode, one add_plain that reads slot umap[b]).  A call of distinct
+// counters (U == B) runs as one phase, with no table and no map.
 static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t *cw, const uint32_t *ncw,
                             const uint64_t *block_index, size_t B, int use_bsgs, uint64_t *out)
 {
     if (!c || !enc_key || !cw || !ncw || !block_index || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_pasta3_transcipher: null argument or empty batch");
-    const size_t n = c->n, half = n / 2;
+    const size_t n = c->n, half = n / 2, ctw = c->ct_words();
     // pasta_3_seal.cpp:376-377
     if ((size_t)PASTA_T * 2 != n && (size_t)PASTA_T * 4 > n) return fail(HHE_ERR_TOO_FEW_SLOTS, "too little slots for matmul implementation!");
     if (!c->rks->rk) return fail(HHE_ERR_NO_RELIN_KEY, "relinearization key not set");
@@ -926,35 +932,71 @@ static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t 
     int rc;
     if ((rc = ensure_feistel_mask(c))) return rc;
     ++c->block_call;
-    // per-item public tables
-    std::vector<const u64 *> ptrs(2 * B);
+    // the distinct counters in order of first appearance; umap[b]: where item b's counter stands among them
+    std::vector<u64> uniq;
+    std::vector<u32> umap;
+    if (c->dedup) {
+        std::map<u64, u32> seen;
+        umap.resize(B);
+        for (size_t b = 0; b < B; ++b) {
+            auto ins = seen.emplace(block_index[b], (u32)uniq.size());
+            if (ins.second) uniq.push_back(block_index[b]);
+            umap[b] = ins.first->second;
+        }
+    }
+    const bool dedup = c->dedup && uniq.size() < B;
+    const size_t U = dedup ? uniq.size() : B;  // keystream evaluations
+    const uint64_t *counters = dedup ? uniq.data() : block_index;
+    c->last_unique = U;
+    // per-evaluation public tables
+    std::vector<const u64 *> ptrs(2 * U);
     std::vector<u64> cwp(B * PASTA_T, 0);
     for (size_t b = 0; b < B; ++b) {
         if (ncw[b] > PASTA_T) return fail(HHE_ERR_INVALID, "hhe_pasta3_transcipher: more than 128 words in a block");
-        BlockTables *bt = nullptr;
-        if ((rc = ensure_block(c, block_index[b], &bt))) return rc;
-        if (use_bsgs && (rc = ensure_bsgs_tables(c, block_index[b], bt))) return rc;
-        ptrs[b] = use_bsgs ? bt->bsgs : c->matmul_mode == 1 ? bt->pdiag : bt->diag;
-        ptrs[B + b] = bt->rc;
         memcpy(&cwp[b * PASTA_T], cw + b * PASTA_T, ncw[b] * 8);
     }
+    for (size_t u = 0; u < U; ++u) {
+        BlockTables *bt = nullptr;
+        if ((rc = ensure_block(c, counters[u], &bt))) return rc;
+        if (use_bsgs && (rc = ensure_bsgs_tables(c, counters[u], bt))) return rc;
+        ptrs[u] = use_bsgs ? bt->bsgs : c->matmul_mode == 1 ? bt->pdiag : bt->diag;
+        ptrs[U + u] = bt->rc;
+    }
     // fused diagonal method: layer 0 acts on the same ciphertext for every item -- its chain runs once, here (HHE_SHARED_L0)
-    const bool shared = c->matmul_mode == 1 && !use_bsgs && c->shared_l0 > 0 && B >= (size_t)c->shared_l0;
-    const ChunkPlan plan = plan_balanced(c, B);
+    const bool shared = c->matmul_mode == 1 && !use_bsgs && c->shared_l0 > 0 && U >= (size_t)c->shared_l0;
+    const ChunkPlan plan = plan_balanced(c, U), fin = plan_balanced(c, B);
     for (int s = plan.first_lane(); s <= plan.last_lane(); ++s) {
         if ((rc = lane_reserve(c, c->lanes[s], plan.per))) return rc;
-        if (use_bsgs && (rc = c->lanes[s].ws_rot.reserve(c, plan.per * ROT_SLOTS * c->ct_words(), "bsgs workspace"))) return rc;
+        if (use_bsgs && (rc = c->lanes[s].ws_rot.reserve(c, plan.per * ROT_SLOTS * ctw, "bsgs workspace"))) return rc;
     }
-    // from here on work is enqueued that reads host staging (ptrs, cwp, keep): every path ends in the final sync
-    if (shared) rc = shared_l0_chain(c, enc_key, ptrs.data(), B, out);
+    if (dedup) {  // the finishing pass needs its items' words, plaintexts and map only, not the ciphertext workspaces of a lane
+        if ((rc = c->ks_tab.reserve(c, U * ctw, "transciphering: keystream table"))) return rc;
+        if ((rc = c->ks_map.reserve(c, B, "transciphering: keystream map"))) return rc;
+        for (int s = fin.first_lane(); s <= fin.last_lane(); ++s)
+            if ((rc = c->lanes[s].ws_fin.reserve(c, fin.per * (PASTA_T + n), "transciphering: finishing pass"))) return rc;
+    }
+    u64 *ks = dedup ? c->ks_tab.p : out;  // where an evaluation leaves its result
+    // from here on work is enqueued that reads host staging (ptrs, cwp, umap, keep): every path ends in the final sync
+    if (shared) rc = shared_l0_chain(c, enc_key, ptrs.data(), U, ks);
     std::vector<std::vector<const u64 *>> keep(plan.nch);  // per chunk: its pointer table
     if (!rc) rc = run_chunks(c, plan, [&](Lane &ln, size_t idx, size_t b0, size_t bc) {
         std::vector<const u64 *> &lp = keep[idx];
         lp.assign(2 * ln.ptr_cap, nullptr);
-        for (size_t b = 0; b < bc; ++b) { lp[b] = ptrs[b0 + b]; lp[ln.ptr_cap + b] = ptrs[B + b0 + b]; }
+        for (size_t b = 0; b < bc; ++b) { lp[b] = ptrs[b0 + b]; lp[ln.ptr_cap + b] = ptrs[U + b0 + b]; }
         rt_h2d(ln.d_ptrs, lp.data(), lp.size() * sizeof(u64 *), ln.stream);
-        return transcipher_chunk(c, enc_key, ln.d_ptrs, ln.d_ptrs + ln.ptr_cap, &cwp[b0 * PASTA_T], out + b0 * c->ct_words(), bc, use_bsgs != 0, shared);
+        return transcipher_chunk(c, enc_key, ln.d_ptrs, ln.d_ptrs + ln.ptr_cap, dedup ? nullptr : &cwp[b0 * PASTA_T], ks + b0 * ctw, bc, use_bsgs != 0, shared);
     });
+    if (!rc && dedup) {
+        // res = Enc(c_b) - KS for every item (:161-169), after the join of the keystream chunks on the main stream
+        rt_h2d(c->ks_map.p, umap.data(), B * sizeof(u32), main.stream);
+        rc = run_chunks(c, fin, [&](Lane &ln, size_t, size_t b0, size_t bc) {
+            u64 *vals = ln.ws_fin.p, *plain = vals + fin.per * PASTA_T;
+            rt_h2d(vals, &cwp[b0 * PASTA_T], bc * PASTA_T * 8, ln.stream);
+            op_encode(c, vals, bc, PASTA_T, PASTA_T, -1, plain);
+            op_add_plain(c, ks, plain, nullptr, 0, false, false, true, out + b0 * ctw, bc, c->ks_map.p + b0);
+            return (int)HHE_OK;
+        });
+    }
     if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_pasta3_transcipher");
     return rc;
 }

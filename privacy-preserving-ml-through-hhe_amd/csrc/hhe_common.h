@@ -337,6 +337,7 @@ struct KsFinishArgs {  // SURVEY A.4 mod-down; S already INTT'd (coefficient for
 
 struct AddPlainArgs {
     const u64 *ct;     // [B][2][L][N]
+    const u32 *ct_map; // if set: item b reads ciphertext ct_map[b] of `ct` (several items on one operand); out stays [B][2][L][N]
     const u64 *plain;  // [B or 1][N] coefficients mod t
     const u64 *const *plain_ptrs;  // if set: item b reads plain_ptrs[b] + plain_shift
     size_t plain_shift;

@@ -331,6 +331,7 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
     }
     if (const char *mm = getenv("HHE_MATMUL")) c->matmul_mode = atoi(mm);
     if (const char *e = getenv("HHE_SHARED_L0")) c->shared_l0 = std::max(0, atoi(e));
+    if (const char *e = getenv("HHE_DEDUP")) c->dedup = atoi(e) != 0;
     if (const char *e = getenv("HHE_SHARED_L0_MB")) c->l0_budget = (size_t)(std::max(0.0, atof(e)) * (double)(1 << 20));
     if (const char *e = getenv("HHE_BLOCK_CACHE_MB")) c->block_cache_limit = (size_t)std::max(0, atoi(e)) << 20;
     if (const char *e = getenv("HHE_FC_ROWFUSED")) c->fc_row_fused = atoi(e);
@@ -365,7 +366,7 @@ static void free_lane(Lane &ln)
 {
     rt_free(ln.ws_T); rt_free(ln.ws_S); rt_free(ln.ws_d); rt_free(ln.ws_ct3); rt_free(ln.ws_plain); rt_free(ln.ws_vals);
     for (auto &p : ln.ws_ct) { rt_free(p); p = nullptr; }
-    ln.ws_rot.release(); ln.ws_aff.release(); ln.ws_leaf.release();
+    ln.ws_rot.release(); ln.ws_fin.release(); ln.ws_aff.release(); ln.ws_leaf.release();
     for (auto &sl : ln.fc_slots) { rt_free(sl.tp); rt_free(sl.ct); rt_free(sl.c0hat); }
     ln.fc_slots.clear(); ln.fc_slot_cap = 0;
     for (u64 *p : ln.csum_bufs) rt_free(p);
@@ -446,6 +447,7 @@ extern "C" void hhe_ctx_destroy(hhe_ctx *c)
     rt_free(c->d_qsp_poly);
     c->d_blocks.release(); c->d_flags.release();
     c->l0_tab.release(); c->l0_ptrs.release();
+    c->ks_tab.release(); c->ks_map.release();
     rt_free(c->d_tables); rt_free(c->d_mods); rt_free(c->d_behz); rt_free(c->d_slot_map);
     delete c;
 }
@@ -537,6 +539,8 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "row_kernel") return use_row_kernel(c) ? 1 : 0;
     if (w == "shared_l0") return (u64)c->shared_l0;       // smallest batch that takes the shared first layer (0: none)
     if (w == "shared_l0_steps") return c->l0_steps();   // steps per block of the operand table of the last shared first layer (0: none ran)
+    if (w == "dedup") return (u64)c->dedup;               // 1: one keystream evaluation per distinct block counter of a call
+    if (w == "transcipher_unique") return c->last_unique; // keystream evaluations of the last transciphering call (its item count when it ran per item)
     if (w == "pm_ok" && i >= 0 && i < c->K) return (u64)c->pm_ok[i];
     if (w == "digit_reduce") return (u64)c->digit_reduce;
     return 0;

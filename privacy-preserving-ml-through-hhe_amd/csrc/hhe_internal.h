@@ -99,6 +99,8 @@ struct Lane {
     const u64 **d_ptrs = nullptr;  // [2*cap] per-item public-table pointers (diag | rc)
     size_t ptr_cap = 0;
     GrowBuf<u64> ws_rot;     // [16][B][2][L][N]: PASTA's babystep rotations, and the FC's product + per-depth buffers of the unshared walk
+    GrowBuf<u64> ws_fin;     // [B][128] symmetric ciphertext words | [B][N] their plaintexts: the finishing pass of a transciphering call with repeated
+                             // counters, whose chunks are larger than the lane's ciphertext workspaces (B counts items of that pass)
     GrowBuf<u64> ws_aff;     // [n1 + n2][B][2][L][N] baby-step ciphertexts | inner sums of hhe_packed_affine (BSGS)
     // FC shared digits: one slot per trie node that is still needed -- the digit transforms of its un-rotated c1 (tp [B][L][K][N]) and its
     // ciphertext (ct [B][2][L][N]); refs = 1 while the depth-first walk is below the node + 1 per queued leaf key switch that reads it
@@ -158,6 +160,11 @@ struct hhe_ctx {
     GrowBuf<u64> l0_tab;           // [3][S][L][N] operands of S chain steps (L0Capture), exactly that size (allocated on first use, freed with the context)
     GrowBuf<const u64 *> l0_ptrs;  // per-item diagonal tables of the running call
     size_t l0_steps() const { return l0_tab.cap / ((size_t)3 * L * n); }
+    int dedup = 1;                 // transciphering: the keystream ciphertext of a block counter is evaluated once per call and every item with that counter
+                                   // only subtracts it from its own encoded words (HHE_DEDUP; 0: every item evaluates its own).  Nothing is kept across calls
+    GrowBuf<u64> ks_tab;           // [U][2][L][N]: the keystream ciphertexts of the running call's U distinct counters, in order of first appearance
+    GrowBuf<u32> ks_map;           // [B]: the slot of ks_tab item b reads
+    size_t last_unique = 0;        // keystream evaluations of the last transciphering call: U, or B when it ran per item
     KsConsts ksc{};
 
     // device tables

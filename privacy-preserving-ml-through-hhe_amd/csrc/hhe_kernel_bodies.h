@@ -1309,6 +1309,7 @@ HD void add_plain_body(const AddPlainArgs &a, size_t gid)
     const size_t b = gid >> a.logn;
     if (b >= (size_t)a.B) return;
     const u64 mval = a.plain_ptrs ? a.plain_ptrs[b][a.plain_shift + i] : a.plain[(a.plain_bcast ? 0 : b * n) + i];
+    const size_t cb = a.ct_map ? a.ct_map[b] : b;  // the ciphertext operand of item b
     // fix = floor((m * (Q mod t) + (t+1)/2) / t)
     u64 lo = mval * a.q_mod_t, hi = mulhi64(mval, a.q_mod_t);
     lo += a.thr; hi += (lo < a.thr);
@@ -1322,7 +1323,7 @@ HD void add_plain_body(const AddPlainArgs &a, size_t gid)
         acc_add(s, fix);
         const u64 sc = barrett128(s.lo, s.hi, m);
         const size_t o0 = ((b * 2 + 0) * a.L + j) * n + i, o1 = ((b * 2 + 1) * a.L + j) * n + i;
-        u64 c0 = a.ct[o0], c1 = a.ct[o1];
+        u64 c0 = a.ct[((cb * 2 + 0) * a.L + j) * n + i], c1 = a.ct[((cb * 2 + 1) * a.L + j) * n + i];
         if (a.negate_ct) { c0 = negmod(c0, m.q); c1 = negmod(c1, m.q); }
         a.out[o0] = a.subtract ? submod(c0, sc, m.q) : addmod(c0, sc, m.q);
         a.out[o1] = c1;
