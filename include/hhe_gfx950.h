@@ -170,10 +170,23 @@ int hhe_pasta3_transcipher_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset
  * counter only.  A call in which counters repeat (every record starts at counter 0: a batch of S records of nb blocks has nb
  * distinct counters) evaluates each distinct counter once and finishes every item with one encode + add_plain against its counter's
  * keystream; the output words are those of the per-item evaluation.  A call whose counters are all distinct runs as before, and
- * HHE_DEDUP=0 makes every item evaluate its own keystream.  Nothing is kept from one call to the next (the ABI has no identity for
- * enc_key).  hhe_ctx_query("dedup") reports the knob, "transcipher_unique" the keystream evaluations of the last call. */
+ * HHE_DEDUP=0 makes every item evaluate its own keystream.  hhe_ctx_query("dedup") reports the knob, "transcipher_unique" the
+ * distinct counters of the last call (its item count when it ran per item).
+ * One keystream per key (HHE_KS_CACHE, default 1): the keystream ciphertext of a counter is also the same from call to call while
+ * the words of enc_key, the key objects the call names and use_bsgs stay what they were -- a service under one analyst key evaluates
+ * counter i once, not once per record.  The context keeps the keystream ciphertexts it has evaluated (ciphertexts under the analyst's
+ * key, 2 L N words each; nothing else) with its counter's public tables and drops them with those tables (the limit below,
+ * hhe_pasta3_clear_block_cache, hhe_ctx_destroy), beyond HHE_KS_CACHE_MB (default 256) of them, least recently used first, and on
+ * hhe_pasta3_clear_keystream_cache.  What makes a kept keystream valid for a call: enc_key equals, word for word, a device copy taken
+ * when the keystream was evaluated (compared on the device on the context's stream at every call, so the buffer may be overwritten in
+ * place between calls; copies of up to 4 different key ciphertexts are kept); the key sets are the ones it was evaluated under and no key
+ * of them has been uploaded, replaced or cleared since; same use_bsgs; same counter.  A call evaluates only the counters it finds no
+ * keystream for; the output words are those of a call that evaluates everything.  The cache stands aside (no lookup, nothing kept)
+ * under HHE_KS_CACHE=0 or HHE_DEDUP=0, and while hhe_ctx_profile is enabled.  hhe_ctx_query: "ks_cache" (the knob),
+ * "transcipher_evaluated" / "ks_cache_hits" (keystreams the last call evaluated / found), "ks_cache_entries", "ks_cache_bytes". */
 int hhe_pasta3_set_block_cache_limit(hhe_ctx *c, size_t bytes);
 void hhe_pasta3_clear_block_cache(hhe_ctx *c);
+void hhe_pasta3_clear_keystream_cache(hhe_ctx *c);
 /* SEALZpCipher::mask (src/pasta/SEAL_Cipher.cpp:161-166): mask_vals_hptr[count], shared by the batch */
 int hhe_mask(hhe_ctx *c, const uint64_t *ct_dptr, const uint64_t *mask_vals_hptr, size_t count,
              uint64_t *out_dptr, size_t B);

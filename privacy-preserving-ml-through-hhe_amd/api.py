@@ -39,7 +39,13 @@ _SYMBOLS = [
     "hhe_apply_galois_ks", "hhe_rotate_rows_ks", "hhe_rotate_columns_ks", "hhe_relinearize_ks", "hhe_pasta3_transcipher_ks",
     "hhe_flatten_ks", "hhe_decompose_ks", "hhe_fc_row_ks", "hhe_seal_load_relin_keys_ks", "hhe_seal_load_galois_keys_ks",
     "hhe_matrix_create", "hhe_matrix_destroy", "hhe_matrix_bytes", "hhe_packed_affine_ks", "hhe_affine_galois_steps",
+    "hhe_pasta3_clear_keystream_cache",
 ]
+
+
+# exports a library built from an earlier commit may lack (HHE_LIB selects such a build for A/B runs): bound when present, and the method
+# that needs one raises when it is not
+_OPTIONAL = {"hhe_pasta3_clear_keystream_cache"}
 
 
 def exported_symbols():
@@ -60,7 +66,8 @@ def load_library(path=None):
         import torch  # noqa: F401
     lib = C.CDLL(path)
     for s in _SYMBOLS:
-        getattr(lib, s)  # AttributeError if the ABI is incomplete
+        if s not in _OPTIONAL or hasattr(lib, s):
+            getattr(lib, s)  # AttributeError if the ABI is incomplete
     lib.hhe_last_error.restype = C.c_char_p
     lib.hhe_backend.restype = C.c_char_p
     lib.hhe_ctx_query.restype = C.c_uint64
@@ -70,6 +77,9 @@ def load_library(path=None):
     lib.hhe_free.argtypes = [C.c_void_p]
     lib.hhe_ctx_destroy.argtypes = [C.c_void_p]
     lib.hhe_pasta3_clear_block_cache.argtypes = [C.c_void_p]
+    if hasattr(lib, "hhe_pasta3_clear_keystream_cache"):
+        lib.hhe_pasta3_clear_keystream_cache.argtypes = [C.c_void_p]
+        lib.hhe_pasta3_clear_keystream_cache.restype = None
     lib.hhe_keyset_destroy.argtypes = [C.c_void_p]
     lib.hhe_keyset_destroy.restype = None
     lib.hhe_matrix_destroy.argtypes = [C.c_void_p]
@@ -311,6 +321,12 @@ class Context:
 
     def clear_block_cache(self):
         self.lib.hhe_pasta3_clear_block_cache(self.h)
+
+    def clear_keystream_cache(self):
+        """drop the keystream ciphertexts kept across transciphering calls (the block tables stay)"""
+        if not hasattr(self.lib, "hhe_pasta3_clear_keystream_cache"):
+            raise RuntimeError("this library keeps no keystreams across calls (no hhe_pasta3_clear_keystream_cache)")
+        self.lib.hhe_pasta3_clear_keystream_cache(self.h)
 
     def set_block_cache_limit(self, nbytes):
         self._chk(self.lib.hhe_pasta3_set_block_cache_limit(self.h, C.c_size_t(nbytes)))

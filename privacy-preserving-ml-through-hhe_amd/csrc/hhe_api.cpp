@@ -293,6 +293,7 @@ void evict_blocks(hhe_ctx *c, size_t need)
         sync_ctx(c);  // earlier calls have completed (every entry point waits for its work), but a caller's stream may lag
         c->block_bytes -= victim->second.bytes;
         free_block(victim->second);
+        c->ks_cache.drop_counter(c, victim->first);  // a kept keystream goes with its counter's tables
         c->blocks.erase(victim);
     }
 }
@@ -908,12 +909,58 @@ static int transcipher_chunk(hhe_ctx *c, const u64 *enc_key, const u64 *const *d
     return rc;
 }
 
+// Keystream cache, lookup side: which resident snapshot holds the words of enc_key (*snap = its number, 0: none).  The comparison
+// runs on the main lane's stream -- the caller's, so it is ordered behind whatever produced enc_key -- word for word against every
+// snapshot: a launch raises its flag where a word differs, and the host reads the flags after one wait.
+static int ks_match_snapshot(hhe_ctx *c, const u64 *enc_key, u64 *snap)
+{
+    KsCache &kc = c->ks_cache;
+    *snap = 0;
+    const size_t ns = kc.snaps.size();
+    if (!ns) return HHE_OK;
+    int rc = c->ks_flags.reserve(c, KsCache::MAX_SNAPSHOTS, "transciphering: key comparison");
+    if (rc) return rc;
+    c->w = &c->lanes[0];  // op_elt launches on the current lane: the main one, like the clear and the read around it
+    rt_stream st = c->w->stream;
+    u64 *flags = c->ks_flags.p, h[KsCache::MAX_SNAPSHOTS];
+    rt_memset(flags, 0, ns * 8, st);
+    for (size_t i = 0; i < ns; ++i) op_elt(c, ELT_DIFF, enc_key, kc.snaps[i].words, flags + i, (size_t)2 * c->L, 0, c->L);
+    if (rt_d2h(h, flags, ns * 8, st) || rt_sync(st)) return dev_fail("hhe_pasta3_transcipher: key comparison");
+    for (size_t i = 0; i < ns && !*snap; ++i)
+        if (!h[i]) { *snap = kc.snaps[i].id; kc.snaps[i].last_use = c->block_call; }
+    return HHE_OK;
+}
+// ... insertion side: the device copies a call has made for the cache and not handed over yet.  They are handed over after the call's
+// final wait has succeeded (commit); on every other path they are freed when the call returns, which is after that wait as well
+struct KsPending {
+    u64 *snap = nullptr;                       // copy of enc_key (no resident snapshot equals it)
+    std::vector<std::pair<u64, u64 *>> cts;    // (counter, copy of its new keystream)
+    ~KsPending()
+    {
+        rt_free(snap);
+        for (auto &p : cts) rt_free(p.second);
+    }
+    void commit(hhe_ctx *c, KsCache::Entry key)
+    {
+        KsCache &kc = c->ks_cache;
+        if (cts.empty()) return;
+        if (snap) { key.snap = kc.add_snapshot(c, snap, c->block_call); snap = nullptr; }
+        for (auto &p : cts)
+            if (c->blocks.count(p.first)) { key.ct = p.second; kc.insert(c, p.first, key); }  // insert takes the copy either way
+            else rt_free(p.second);
+        cts.clear();
+    }
+};
+
 // hhe_pasta3_transcipher with the key objects already named (c->rks / c->gks)
 // Everything before res = Enc(c_b) - KS is a function of the key ciphertext, the named key sets and the item's block counter only, so
 // items of one call with the same counter share one keystream ciphertext, word for word (HHE_DEDUP, DESIGN.md "one keystream per
-// counter").  A call in which counters repeat runs in two phases: the chunk schedule over its U distinct counters, which leaves the
-// keystreams in ks_tab, then a finishing pass over all B items (encode, one add_plain that reads slot umap[b]).  A call of distinct
-// counters (U == B) runs as one phase, with no table and no map.
+// counter").  Such a call runs in two phases: the chunk schedule over its distinct counters, which leaves the keystreams in ks_tab,
+// then a finishing pass over all B items (encode, one add_plain that reads slot ks_map[b]).
+// The keystreams are kept from call to call (KsCache, DESIGN.md "one keystream per key"): every call then takes the two-phase shape,
+// phase 1 runs over the counters no kept keystream was found for, the kept ones are copied into their slots of ks_tab, and the new
+// ones are copied out of it.  Slots: the M evaluated counters first, in order of first appearance, then the found ones.
+// Without the cache (HHE_KS_CACHE=0, or a profiled call) a call of distinct counters (U == B) runs as one phase, with no table and no map.
 static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t *cw, const uint32_t *ncw,
                             const uint64_t *block_index, size_t B, int use_bsgs, uint64_t *out)
 {
@@ -944,31 +991,56 @@ static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t 
             umap[b] = ins.first->second;
         }
     }
-    const bool dedup = c->dedup && uniq.size() < B;
-    const size_t U = dedup ? uniq.size() : B;  // keystream evaluations
+    const bool cache = c->dedup && c->ks_cache.enabled && !c->profile;
+    const bool dedup = c->dedup && (cache || uniq.size() < B);
+    const size_t U = dedup ? uniq.size() : B;  // keystreams the call needs
     const uint64_t *counters = dedup ? uniq.data() : block_index;
-    c->last_unique = U;
-    // per-evaluation public tables
-    std::vector<const u64 *> ptrs(2 * U);
+    c->last_unique = c->last_evaluated = U;
+    c->last_hits = 0;
     std::vector<u64> cwp(B * PASTA_T, 0);
     for (size_t b = 0; b < B; ++b) {
         if (ncw[b] > PASTA_T) return fail(HHE_ERR_INVALID, "hhe_pasta3_transcipher: more than 128 words in a block");
         memcpy(&cwp[b * PASTA_T], cw + b * PASTA_T, ncw[b] * 8);
     }
+    // public tables of every counter of the call (pinned for its duration), kept keystreams or not
+    std::vector<BlockTables *> tabs(U);
     for (size_t u = 0; u < U; ++u) {
-        BlockTables *bt = nullptr;
-        if ((rc = ensure_block(c, counters[u], &bt))) return rc;
-        if (use_bsgs && (rc = ensure_bsgs_tables(c, counters[u], bt))) return rc;
-        ptrs[u] = use_bsgs ? bt->bsgs : c->matmul_mode == 1 ? bt->pdiag : bt->diag;
-        ptrs[U + u] = bt->rc;
+        if ((rc = ensure_block(c, counters[u], &tabs[u]))) return rc;
+        if (use_bsgs && (rc = ensure_bsgs_tables(c, counters[u], tabs[u]))) return rc;
+    }
+    // kept keystreams: found[u], or null = counter u is evaluated
+    std::vector<const u64 *> found(U, nullptr);
+    KsCache::Entry kkey{nullptr, 0, c->gks->serial, c->rks->serial, use_bsgs != 0, c->block_call};
+    if (cache) {
+        if ((rc = ks_match_snapshot(c, enc_key, &kkey.snap))) return rc;
+        if (kkey.snap)
+            for (size_t u = 0; u < U; ++u)
+                if ((found[u] = c->ks_cache.find(counters[u], kkey, c->block_call))) ++c->last_hits;
+    }
+    const size_t M = U - c->last_hits;  // keystream evaluations
+    c->last_evaluated = M;
+    std::vector<size_t> eval, slot(U);  // eval[m]: the counter (index u) evaluation m is for; slot[u]: its place in ks_tab
+    for (size_t u = 0, h = M; u < U; ++u) {
+        if (found[u]) slot[u] = h++;
+        else { slot[u] = eval.size(); eval.push_back(u); }
+    }
+    if (dedup)
+        for (size_t b = 0; b < B; ++b) umap[b] = (u32)slot[umap[b]];
+    // per-evaluation public tables
+    std::vector<const u64 *> ptrs(2 * M);
+    for (size_t m = 0; m < M; ++m) {
+        const BlockTables *bt = tabs[eval[m]];
+        ptrs[m] = use_bsgs ? bt->bsgs : c->matmul_mode == 1 ? bt->pdiag : bt->diag;
+        ptrs[M + m] = bt->rc;
     }
     // fused diagonal method: layer 0 acts on the same ciphertext for every item -- its chain runs once, here (HHE_SHARED_L0)
-    const bool shared = c->matmul_mode == 1 && !use_bsgs && c->shared_l0 > 0 && U >= (size_t)c->shared_l0;
-    const ChunkPlan plan = plan_balanced(c, U), fin = plan_balanced(c, B);
-    for (int s = plan.first_lane(); s <= plan.last_lane(); ++s) {
-        if ((rc = lane_reserve(c, c->lanes[s], plan.per))) return rc;
-        if (use_bsgs && (rc = c->lanes[s].ws_rot.reserve(c, plan.per * ROT_SLOTS * ctw, "bsgs workspace"))) return rc;
-    }
+    const bool shared = c->matmul_mode == 1 && !use_bsgs && c->shared_l0 > 0 && M >= (size_t)c->shared_l0;
+    const ChunkPlan plan = plan_balanced(c, std::max<size_t>(M, 1)), fin = plan_balanced(c, B);
+    if (M)
+        for (int s = plan.first_lane(); s <= plan.last_lane(); ++s) {
+            if ((rc = lane_reserve(c, c->lanes[s], plan.per))) return rc;
+            if (use_bsgs && (rc = c->lanes[s].ws_rot.reserve(c, plan.per * ROT_SLOTS * ctw, "bsgs workspace"))) return rc;
+        }
     if (dedup) {  // the finishing pass needs its items' words, plaintexts and map only, not the ciphertext workspaces of a lane
         if ((rc = c->ks_tab.reserve(c, U * ctw, "transciphering: keystream table"))) return rc;
         if ((rc = c->ks_map.reserve(c, B, "transciphering: keystream map"))) return rc;
@@ -976,16 +1048,29 @@ static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t 
             if ((rc = c->lanes[s].ws_fin.reserve(c, fin.per * (PASTA_T + n), "transciphering: finishing pass"))) return rc;
     }
     u64 *ks = dedup ? c->ks_tab.p : out;  // where an evaluation leaves its result
-    // from here on work is enqueued that reads host staging (ptrs, cwp, umap, keep): every path ends in the final sync
-    if (shared) rc = shared_l0_chain(c, enc_key, ptrs.data(), U, ks);
+    // from here on work is enqueued that reads host staging (ptrs, cwp, umap, keep) and the pending copies: every path ends in the final sync
+    KsPending pend;
+    if (cache) {
+        for (size_t u = 0; u < U; ++u)
+            if (found[u]) rt_d2d(ks + slot[u] * ctw, found[u], ctw * 8, main.stream);
+        // a copy that cannot be allocated is a keystream that is not kept, nothing more
+        if (M && !kkey.snap && (pend.snap = (u64 *)rt_malloc(ctw * 8))) rt_d2d(pend.snap, enc_key, ctw * 8, main.stream);
+    }
+    if (M && shared) rc = shared_l0_chain(c, enc_key, ptrs.data(), M, ks);
     std::vector<std::vector<const u64 *>> keep(plan.nch);  // per chunk: its pointer table
-    if (!rc) rc = run_chunks(c, plan, [&](Lane &ln, size_t idx, size_t b0, size_t bc) {
+    if (M && !rc) rc = run_chunks(c, plan, [&](Lane &ln, size_t idx, size_t b0, size_t bc) {
         std::vector<const u64 *> &lp = keep[idx];
         lp.assign(2 * ln.ptr_cap, nullptr);
-        for (size_t b = 0; b < bc; ++b) { lp[b] = ptrs[b0 + b]; lp[ln.ptr_cap + b] = ptrs[U + b0 + b]; }
+        for (size_t b = 0; b < bc; ++b) { lp[b] = ptrs[b0 + b]; lp[ln.ptr_cap + b] = ptrs[M + b0 + b]; }
         rt_h2d(ln.d_ptrs, lp.data(), lp.size() * sizeof(u64 *), ln.stream);
         return transcipher_chunk(c, enc_key, ln.d_ptrs, ln.d_ptrs + ln.ptr_cap, dedup ? nullptr : &cwp[b0 * PASTA_T], ks + b0 * ctw, bc, use_bsgs != 0, shared);
     });
+    if (!rc && cache && (kkey.snap || pend.snap))  // the new keystreams, after the join of their chunks on the main stream
+        for (size_t m = 0; m < M; ++m)
+            if (u64 *copy = (u64 *)rt_malloc(ctw * 8)) {
+                rt_d2d(copy, ks + m * ctw, ctw * 8, main.stream);
+                pend.cts.emplace_back(counters[eval[m]], copy);
+            }
     if (!rc && dedup) {
         // res = Enc(c_b) - KS for every item (:161-169), after the join of the keystream chunks on the main stream
         rt_h2d(c->ks_map.p, umap.data(), B * sizeof(u32), main.stream);
@@ -998,6 +1083,7 @@ static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t 
         });
     }
     if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_pasta3_transcipher");
+    if (!rc) pend.commit(c, kkey);  // a failed call leaves nothing behind
     return rc;
 }
 extern "C" int hhe_pasta3_transcipher_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const uint64_t *enc_key, const uint64_t *cw,

@@ -139,7 +139,8 @@ struct NttArgs {
     KsConsts ks;
 };
 
-enum EltOp { ELT_ADD = 0, ELT_SUB = 1, ELT_NEG = 2, ELT_MUL = 3, ELT_MAC = 4, ELT_COPY = 5, ELT_BCAST = 6, ELT_SHOUP = 7 };
+enum EltOp { ELT_ADD = 0, ELT_SUB = 1, ELT_NEG = 2, ELT_MUL = 3, ELT_MAC = 4, ELT_COPY = 5, ELT_BCAST = 6, ELT_SHOUP = 7,
+             ELT_DIFF = 8 };  // ELT_DIFF writes no polynomial: out[0] = 1 when a word of a differs from its word of b (out[0] cleared by the caller)
 
 struct EltArgs {  // element-wise kernels over [count][N] polys, modulus = mod_base + p % mod_cycle
     const u64 *a, *b;

@@ -222,6 +222,8 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
     hhe_ctx *c = new hhe_ctx();
     c->keys0.ctx = c;
     for (auto &ks : c->rk_slots) ks.ctx = c;
+    keyset_new_serial(&c->keys0);
+    for (auto &ks : c->rk_slots) keyset_new_serial(&ks);
     c->logn = logn; c->n = n; c->K = K; c->L = K - 1; c->t = t; c->device = device;
     c->q.assign(q, q + K);
     const int L = c->L;
@@ -332,6 +334,9 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
     if (const char *mm = getenv("HHE_MATMUL")) c->matmul_mode = atoi(mm);
     if (const char *e = getenv("HHE_SHARED_L0")) c->shared_l0 = std::max(0, atoi(e));
     if (const char *e = getenv("HHE_DEDUP")) c->dedup = atoi(e) != 0;
+    if (const char *e = getenv("HHE_KS_CACHE")) c->ks_cache.enabled = atoi(e) != 0;
+    if (const char *e = getenv("HHE_KS_CACHE_MB")) c->ks_cache.budget = (size_t)(std::max(0.0, atof(e)) * (double)(1 << 20));
+    c->ks_cache.entry_bytes = c->ct_words() * 8;
     if (const char *e = getenv("HHE_SHARED_L0_MB")) c->l0_budget = (size_t)(std::max(0.0, atof(e)) * (double)(1 << 20));
     if (const char *e = getenv("HHE_BLOCK_CACHE_MB")) c->block_cache_limit = (size_t)std::max(0, atoi(e)) << 20;
     if (const char *e = getenv("HHE_FC_ROWFUSED")) c->fc_row_fused = atoi(e);
@@ -423,6 +428,14 @@ extern "C" void hhe_pasta3_clear_block_cache(hhe_ctx *c)
     for (auto &kv : c->blocks) { rt_free(kv.second.diag); rt_free(kv.second.pdiag); rt_free(kv.second.rc); rt_free(kv.second.bsgs); }
     c->blocks.clear();
     c->block_bytes = 0;
+    c->ks_cache.clear(c);  // a kept keystream belongs to its counter's tables
+}
+// the keystream ciphertexts kept across transciphering calls, and the copies of the key ciphertexts they belong to; the block tables stay
+extern "C" void hhe_pasta3_clear_keystream_cache(hhe_ctx *c)
+{
+    HHE_LOCK(c);
+    if (!c) return;
+    c->ks_cache.clear(c);
 }
 
 extern "C" void hhe_ctx_destroy(hhe_ctx *c)
@@ -447,7 +460,7 @@ extern "C" void hhe_ctx_destroy(hhe_ctx *c)
     rt_free(c->d_qsp_poly);
     c->d_blocks.release(); c->d_flags.release();
     c->l0_tab.release(); c->l0_ptrs.release();
-    c->ks_tab.release(); c->ks_map.release();
+    c->ks_tab.release(); c->ks_map.release(); c->ks_flags.release();
     rt_free(c->d_tables); rt_free(c->d_mods); rt_free(c->d_behz); rt_free(c->d_slot_map);
     delete c;
 }
@@ -540,7 +553,12 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "shared_l0") return (u64)c->shared_l0;       // smallest batch that takes the shared first layer (0: none)
     if (w == "shared_l0_steps") return c->l0_steps();   // steps per block of the operand table of the last shared first layer (0: none ran)
     if (w == "dedup") return (u64)c->dedup;               // 1: one keystream evaluation per distinct block counter of a call
-    if (w == "transcipher_unique") return c->last_unique; // keystream evaluations of the last transciphering call (its item count when it ran per item)
+    if (w == "transcipher_unique") return c->last_unique; // distinct counters of the last transciphering call (its item count when it ran per item)
+    if (w == "transcipher_evaluated") return c->last_evaluated;  // keystream chains the last call ran: the counters it found no kept keystream for
+    if (w == "ks_cache") return c->ks_cache.enabled ? 1 : 0;      // keystreams are kept across calls (HHE_KS_CACHE)
+    if (w == "ks_cache_hits") return c->last_hits;                // counters of the last call served from a kept keystream
+    if (w == "ks_cache_entries") return c->ks_cache.entries();
+    if (w == "ks_cache_bytes") return c->ks_cache.bytes;
     if (w == "pm_ok" && i >= 0 && i < c->K) return (u64)c->pm_ok[i];
     if (w == "digit_reduce") return (u64)c->digit_reduce;
     return 0;
@@ -580,7 +598,17 @@ static int upload_key(hhe_ctx *c, u64 *&slot, const uint64_t *ksk)
     }
     return HHE_OK;
 }
-int keyset_put_relin(hhe_keyset *ks, const u64 *ksk) { return upload_key(ks->ctx, ks->rk, ksk); }
+void keyset_new_serial(hhe_keyset *ks)
+{
+    hhe_ctx *c = ks->ctx;
+    if (ks->serial) c->ks_cache.drop_serial(c, ks->serial);
+    ks->serial = ++c->next_serial;
+}
+int keyset_put_relin(hhe_keyset *ks, const u64 *ksk)
+{
+    keyset_new_serial(ks);
+    return upload_key(ks->ctx, ks->rk, ksk);
+}
 int keyset_put_galois(hhe_keyset *ks, u32 elt, const u64 *ksk)
 {
     hhe_ctx *c = ks->ctx;
@@ -592,6 +620,7 @@ int keyset_put_galois(hhe_keyset *ks, u32 elt, const u64 *ksk)
     auto it = ks->gk.find(elt);
     u64 *slot = it == ks->gk.end() ? nullptr : it->second;
     const bool fresh = slot == nullptr;
+    keyset_new_serial(ks);
     rc = upload_key(c, slot, ksk);
     if (rc && fresh) { rt_free(slot); return rc; }  // a key that did not arrive is not registered
     ks->gk[elt] = slot;
@@ -600,6 +629,7 @@ int keyset_put_galois(hhe_keyset *ks, u32 elt, const u64 *ksk)
 void keyset_clear(hhe_keyset *ks)
 {
     hhe_ctx *c = ks->ctx;
+    keyset_new_serial(ks);
     if (ks->rk) { forget_key(c, ks->rk); rt_free(ks->rk); ks->rk = nullptr; }
     for (auto &kv : ks->gk) { forget_key(c, kv.second); rt_free(kv.second); }
     for (auto &kv : ks->gk_corr) rt_free(kv.second);
@@ -612,6 +642,7 @@ extern "C" int hhe_keyset_create(hhe_ctx *c, hhe_keyset **out)
     if (!c || !out) { hhe_set_error("hhe_keyset_create: null argument"); return HHE_ERR_INVALID; }
     hhe_keyset *ks = new hhe_keyset();
     ks->ctx = c;
+    keyset_new_serial(ks);
     c->sets.push_back(ks);
     *out = ks;
     return HHE_OK;

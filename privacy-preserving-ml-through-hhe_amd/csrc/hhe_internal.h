@@ -6,6 +6,7 @@
 #include <vector>
 #include "hhe_common.h"
 #include "hhe_launch.h"
+#include "hhe_kscache.h"
 #include "../../include/hhe_gfx950.h"
 
 struct hhe_ctx;
@@ -63,6 +64,8 @@ constexpr int HHE_RELIN_SLOTS = 4;
 // are keyed by the key's device address (hhe_ctx::d_key_shoup), so two sets never share one.
 struct hhe_keyset {
     hhe_ctx *ctx = nullptr;
+    u64 serial = 0;                    // identity of the set's present content (hhe_ctx::next_serial): re-drawn whenever a key of the set is uploaded,
+                                       // replaced or cleared, never reused; what a kept keystream records of the key sets it was evaluated under (KsCache)
     u64 *rk = nullptr;                 // RelinKeys::key(2): [L][2][K][N]
     std::map<u32, u64 *> gk;           // by Galois element: [L][2][K][N] each
     std::map<u32, u64 *> gk_corr;      // per Galois key of THIS set: shared-digit correction [2][K][N] (KsCorrArgs), built on first FC use
@@ -161,10 +164,15 @@ struct hhe_ctx {
     GrowBuf<const u64 *> l0_ptrs;  // per-item diagonal tables of the running call
     size_t l0_steps() const { return l0_tab.cap / ((size_t)3 * L * n); }
     int dedup = 1;                 // transciphering: the keystream ciphertext of a block counter is evaluated once per call and every item with that counter
-                                   // only subtracts it from its own encoded words (HHE_DEDUP; 0: every item evaluates its own).  Nothing is kept across calls
+                                   // only subtracts it from its own encoded words (HHE_DEDUP; 0: every item evaluates its own).  What is kept across calls: ks_cache
     GrowBuf<u64> ks_tab;           // [U][2][L][N]: the keystream ciphertexts of the running call's U distinct counters, in order of first appearance
     GrowBuf<u32> ks_map;           // [B]: the slot of ks_tab item b reads
-    size_t last_unique = 0;        // keystream evaluations of the last transciphering call: U, or B when it ran per item
+    size_t last_unique = 0;        // distinct counters of the last transciphering call: U, or B when it ran per item
+    size_t last_evaluated = 0;     // keystream chains the last call ran (= last_unique unless kept keystreams were found), and
+    size_t last_hits = 0;          // the counters it found a kept keystream for
+    KsCache ks_cache;              // keystream ciphertexts kept across calls, per counter (hhe_kscache.h; HHE_KS_CACHE, HHE_KS_CACHE_MB); it stands aside
+                                   // under HHE_DEDUP=0 and while hhe_ctx_profile is enabled (a profiled call exists to time the chain)
+    GrowBuf<u64> ks_flags;         // [KsCache::MAX_SNAPSHOTS]: raised where enc_key differs from a snapshot (ELT_DIFF)
     KsConsts ksc{};
 
     // device tables
@@ -185,6 +193,7 @@ struct hhe_ctx {
     std::vector<hhe_keyset *> sets;
     std::vector<hhe_matrix *> mats;            // plain-matrix handles created on this context
     hhe_keyset *gks = &keys0, *rks = &keys0;
+    u64 next_serial = 0;                       // the last hhe_keyset::serial handed out
     std::map<const u64 *, u64 *> d_key_shoup;  // per key-switch key (by device address): Shoup quotients of its words (fused row kernel), built on first use
     hhe_keyset *relin_set(int slot) { return slot == 0 ? &keys0 : &rk_slots[slot]; }
 
@@ -262,6 +271,7 @@ struct KeyScope {
 int keyset_put_galois(hhe_keyset *ks, u32 elt, const u64 *ksk);
 int keyset_put_relin(hhe_keyset *ks, const u64 *ksk);
 void keyset_clear(hhe_keyset *ks);
+void keyset_new_serial(hhe_keyset *ks);  // the set's content changes: keystreams kept under its old serial go
 
 int lane_reserve(hhe_ctx *c, Lane &ln, size_t B);
 void matrix_free(hhe_matrix *m);  // hhe_api.cpp: device memory of a handle and the handle

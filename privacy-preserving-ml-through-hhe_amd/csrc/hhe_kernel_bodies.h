@@ -523,6 +523,7 @@ HD void elt_body(const EltArgs &a, int op, size_t gid)
     const size_t bp = a.b_cycle ? p % a.b_cycle : p;
     const u64 x = op == ELT_BCAST ? 0 : a.a[gid];
     if (op == ELT_SHOUP) { a.out[gid] = shoup_quotient(x, m); return; }
+    if (op == ELT_DIFF) { if (x != a.b[bp * n + i]) a.out[0] = 1; return; }
     u64 r;
     switch (op) {
     case ELT_BCAST: r = a.b[bp * n + i]; break;
