@@ -409,6 +409,68 @@ public:
         check(hhe_pasta3_plain_crypt(h(), key, d.u64(), 1, count, dec ? 1 : 0, d.u64()));
         check(hhe_copy_d2h(h(), v, d.p, count * 8));
     }
+    // ---- keys and ciphertexts from a seed, on the device (hhe_gfx950.h "key generation and encryption").  seed: 32 bytes, THE ONLY
+    // ENTROPY: fresh from the caller's generator for every call below; the same seed for the same call repeats the randomness.
+    size_t key_limbs() const { return L_ + 1; }
+    size_t ksk_words() const { return L_ * 2 * (L_ + 1) * n_; }
+    // KeyGenerator::secret_key + create_public_key: sk [K][N], pk [2][K][N], NTT form at the key level
+    void generate_keys(const uint8_t *seed, std::vector<uint64_t> &sk, std::vector<uint64_t> &pk)
+    {
+        const size_t kn = key_limbs() * n_;
+        DevBuf s(kn * 8), p(2 * kn * 8);
+        check(hhe_keygen_secret(h(), seed, s.u64()));
+        check(hhe_keygen_public(h(), s.u64(), seed, p.u64()));
+        sk.resize(kn);
+        pk.resize(2 * kn);
+        check(hhe_copy_d2h(h(), sk.data(), s.p, kn * 8));
+        check(hhe_copy_d2h(h(), pk.data(), p.p, 2 * kn * 8));
+    }
+    // KeyGenerator::create_relin_keys: RelinKeys::key(2) words
+    void generate_relin(const uint64_t *sk, const uint8_t *seed, std::vector<uint64_t> &key)
+    {
+        const KeySet ks = keys_.new_set();
+        DevBuf s(key_limbs() * n_ * 8);
+        check(hhe_copy_h2d(h(), s.p, sk, key_limbs() * n_ * 8));
+        check(hhe_keyset_generate_relin(ks.get(), s.u64(), seed));
+        key.resize(ksk_words());
+        check(hhe_keyset_get_relin(ks.get(), key.data()));
+    }
+    // KeyGenerator::create_galois_keys(steps, gk) (SEALZpCipher::create_gk, SEAL_Cipher.cpp:359); no steps: create_galois_keys(gk), the
+    // default elements.  Words by Galois element.
+    void generate_galois(const uint64_t *sk, const std::vector<int> &steps, const uint8_t *seed, std::map<uint32_t, std::vector<uint64_t>> &keys)
+    {
+        std::vector<uint32_t> elts;
+        for (int s : steps) {
+            const uint32_t e = (uint32_t)hhe_ctx_query(h(), "galois_elt", s);
+            if (!e) throw std::invalid_argument("step count too large");  // GaloisTool::get_elt_from_step
+            if (std::find(elts.begin(), elts.end(), e) == elts.end()) elts.push_back(e);
+        }
+        const KeySet ks = keys_.new_set();
+        DevBuf s(key_limbs() * n_ * 8);
+        check(hhe_copy_h2d(h(), s.p, sk, key_limbs() * n_ * 8));
+        check(hhe_keyset_generate_galois(ks.get(), s.u64(), elts.empty() ? nullptr : elts.data(), elts.size(), seed));
+        if (elts.empty())  // the default set: every odd element the set now holds
+            for (uint32_t e = 1; e < 2 * n_; e += 2)
+                if (hhe_keyset_has_galois(ks.get(), e)) elts.push_back(e);
+        keys.clear();
+        for (uint32_t e : elts) {
+            std::vector<uint64_t> &k = keys[e];
+            k.resize(ksk_words());
+            check(hhe_keyset_get_galois(ks.get(), e, k.data()));
+        }
+    }
+    // BatchEncoder::encode + Encryptor::encrypt of `count` slot values (the rest are zero) under the public key pk [2][K][N]
+    template <class Sink> void encrypt(const uint64_t *pk, const uint64_t *vals, size_t count, const uint8_t *seed, Sink dst)
+    {
+        if (!count || count > n_) throw std::invalid_argument("encrypt: values do not fit the slots");
+        DevBuf p(2 * key_limbs() * n_ * 8), v(count * 8), plain(n_ * 8), ct(ct_words() * 8);
+        check(hhe_copy_h2d(h(), p.p, pk, 2 * key_limbs() * n_ * 8));
+        check(hhe_copy_h2d(h(), v.p, vals, count * 8));
+        check(hhe_encode(h(), v.u64(), 1, count, plain.u64()));
+        check(hhe_encrypt(h(), p.u64(), plain.u64(), 0, seed, 1, ct.u64()));
+        download(ct.u64(), 1, 2, dst);
+    }
+
     // analyst end: Decryptor::decrypt + BatchEncoder::decode; sk: [K][N] NTT form; vals: N slot values < t
     void decrypt(const uint64_t *sk, const uint64_t *ct, uint64_t *vals)
     {

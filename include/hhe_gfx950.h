@@ -266,6 +266,48 @@ int hhe_pasta3_plain_crypt(hhe_ctx *c, const uint64_t *key_hptr, const uint64_t 
  * sk_hptr: the secret key polynomial at the key level, NTT form [K][N] (SecretKey::data().data()). */
 int hhe_decrypt(hhe_ctx *c, const uint64_t *sk_hptr, const uint64_t *ct_dptr, size_t B, uint64_t *vals_dptr);
 
+/* ---- key generation and encryption on the device, from a seed.
+ *      THE SEED IS THE ONLY ENTROPY.  seed_hptr is 32 bytes on the host; every random word is SHAKE128 of the seed and a position
+ *      (purpose, Galois element, digit or batch item, kind, limb, chunk of 64 coefficients; the definition is in
+ *      csrc/hhe_keygen_bodies.h and DESIGN.md section 4), so the same seed for the same purpose repeats the randomness: the caller
+ *      supplies 32 FRESH bytes from its own generator per key-generation call and per encryption batch, and keeps them as secret as
+ *      the key they make.  Purposes and Galois elements are separate domains, so one seed may serve one call of each kind.
+ *      Neither SEAL's nor any other library's random stream is reproduced: keys and ciphertexts are valid BFV objects of the context,
+ *      not the words a seal::KeyGenerator would have drawn. ---- */
+/* The sampler alone (the test seam of its definition, as hhe_ntt is for the transforms): one polynomial at position
+ * (purpose < 256, elt, index) of kind 1 ternary / 2 noise / 3 uniform, out_dptr [mod_count][N] under the moduli
+ * mod_base .. mod_base + mod_count - 1 of the table hhe_ntt indexes.  Ternary and noise: residues of one small polynomial;
+ * uniform: an independent polynomial per limb (limb = the modulus index).  Shape of util::sample_poly_ternary / sample_poly_cbd /
+ * sample_poly_uniform (seal/util/rlwe.h:31-66). */
+int hhe_sample_poly(hhe_ctx *c, const uint8_t *seed_hptr, uint32_t purpose, uint32_t elt, uint32_t index, int kind, int mod_base,
+                    int mod_count, uint64_t *out_dptr);
+/* KeyGenerator::KeyGenerator / secret_key (src/examples/Analyst/Analyst.cpp:38-40, src/examples/hhe_pktnn_examples.cpp:435-437):
+ * sk_dptr [K][N], the ternary secret in NTT form under every key-level prime (SecretKey::data() layout, what hhe_decrypt takes
+ * once copied to the host) */
+int hhe_keygen_secret(hhe_ctx *c, const uint8_t *seed_hptr, uint64_t *sk_dptr);
+/* KeyGenerator::create_public_key (Analyst.cpp:41-42, hhe_pktnn_examples.cpp:438-439): pk_dptr [2][K][N] = (-(a s + e), a) at the
+ * key level in NTT form (PublicKey::data() layout) */
+int hhe_keygen_public(hhe_ctx *c, const uint64_t *sk_dptr, const uint8_t *seed_hptr, uint64_t *pk_dptr);
+/* KeyGenerator::create_relin_keys (Analyst.cpp:62-66, hhe_pktnn_examples.cpp:440-441) into a key set.  A generated key enters the set
+ * as an uploaded one does: what was derived from a replaced key is dropped and keystreams kept under the set's old content go. */
+int hhe_keyset_generate_relin(hhe_keyset *ks, const uint64_t *sk_dptr, const uint8_t *seed_hptr);
+/* KeyGenerator::create_galois_keys (Analyst.cpp:68-93, hhe_pktnn_examples.cpp:442-443, 615-617) for the `count` Galois elements
+ * elts_hptr (from steps: hhe_ctx_query "galois_elt", as for hhe_keyset_set_galois); count == 0 with elts_hptr == NULL: the default
+ * set create_galois_keys(gk) makes without indices (GaloisTool::get_elts_all, seal/util/galois.h:131, one key per element).
+ * All-or-nothing: an even element or one >= 2N returns HHE_ERR_INVALID with the set exactly as it was. */
+int hhe_keyset_generate_galois(hhe_keyset *ks, const uint64_t *sk_dptr, const uint32_t *elts_hptr, size_t count, const uint8_t *seed_hptr);
+/* reading a set back (the analyst ships its RelinKeys / GaloisKeys to the CSP, Analyst.cpp:96-130): ksk_hptr [L][2][K][N];
+ * HHE_ERR_NO_RELIN_KEY / HHE_ERR_NO_GALOIS_KEY when the set does not hold the key */
+int hhe_keyset_get_relin(const hhe_keyset *ks, uint64_t *ksk_hptr);
+int hhe_keyset_get_galois(const hhe_keyset *ks, uint32_t galois_elt, uint64_t *ksk_hptr);
+/* Encryptor::encrypt with the public key (the client's PASTA key, src/util/pastahelper.cpp:355-377; the analyst's weight rows,
+ * src/util/sealhelper.cpp:123-142) for B plaintexts plain_dptr [B][N] (or [1][N] if plain_bcast; coefficients mod t, from hhe_encode):
+ * item b draws u (ternary), e_0, e_1 (noise) at index b; c_k = INTT(NTT(u) pk_k) + e_k on the data-level primes, then the scaled
+ * plaintext is added as hhe_add_plain adds it.  out_dptr [B][2][L][N].  (SEAL encrypts at the key level and drops the special
+ * prime; the noise is the same to a fraction of a bit.) */
+int hhe_encrypt(hhe_ctx *c, const uint64_t *pk_dptr, const uint64_t *plain_dptr, int plain_bcast, const uint8_t *seed_hptr, size_t B,
+                uint64_t *out_dptr);
+
 /* ---- SEAL 4.0 binary serialization at the boundary: the blobs the reference moves over gRPC and spills to
  *      disk (src/examples/CSP/CSP.cpp:328-490 `*.load(*context, bytes, size)`, :495-547 spill file = size_t count followed by
  *      Ciphertext::save streams, :552-605 concatenated stream, protos/hhe.proto:21-24) decoded straight into HBM.

@@ -7,6 +7,9 @@
 //   sealhelper::packed_enc_multiply / encrypted_vec_sum   src/util/sealhelper.h:84-129
 //   pasta::PASTA          src/pasta/pasta_3_plain.h:17-30  (client side: encrypt / decrypt)
 //   sealhelper::decrypting                                 src/util/sealhelper.cpp:252-266 (analyst side)
+//   KeyGenerator as the parties use it (Analyst.cpp:38-93), SEALZpCipher::create_gk (SEAL_Cipher.cpp:359) and
+//   PASTA_SEAL::encrypt_key_2 (pasta_3_seal.cpp:23-38): keys and the encrypted PASTA key made on the device from a 32-byte seed the
+//   caller supplies -- the only entropy, fresh for every call (include/hhe_gfx950.h)
 // The reference passes seal:: objects; SEAL is not linked here, so the boundary types below are plain
 // word containers with SEAL's in-memory layouts (what Ciphertext::data(), KSwitchKeys::data() hold).
 // Only the conversions between those containers and plain words live here: every call body is hhe::AdapterCore
@@ -38,8 +41,9 @@ struct Ciphertext {
 typedef std::vector<uint64_t> KSwitchKey;
 struct RelinKeys { KSwitchKey key; };                       // RelinKeys::key(2)
 struct GaloisKeys { std::map<uint32_t, KSwitchKey> keys; }; // by Galois element (GaloisKeys::get_index = (elt-1)/2)
-struct PublicKey { std::vector<uint64_t> words; };          // unused on the CSP path (kept for signature parity)
-struct SecretKey { std::vector<uint64_t> words; };
+struct PublicKey { std::vector<uint64_t> words; };          // PublicKey::data(): [2][K][N], NTT form (read by encrypt_key_2 only)
+struct SecretKey { std::vector<uint64_t> words; };          // SecretKey::data(): [K][N], NTT form
+typedef const uint8_t *Seed;                                // 32 bytes: the only entropy of a key-generation call / an encryption
 
 // seal::SEALContext stand-in: (N, coeff_modulus incl. the special prime, plain_modulus) plus everything the adapter core keeps per
 // context (keys(): the key-set cache, key_uploads); max_key_sets is the cache's capacity
@@ -115,6 +119,15 @@ public:
     void add_bsgs_indices(uint64_t n1, uint64_t n2) { hhe::bsgs_indices(mod_degree, n1, n2, gk_indices); }   // SEAL_Cipher.cpp:337-346
     void add_diagonal_indices(size_t size) { hhe::diagonal_indices(mod_degree, size, gk_indices); }          // :350-355
     const std::vector<int> &get_gk_indices() const { return gk_indices; }
+    // SEALZpCipher::create_gk (SEAL_Cipher.cpp:359): keygen.create_galois_keys(gk_indices, he_gk) with this object's secret key, on the
+    // device; the object then rotates with these keys.  get_galois_keys(): what the analyst ships to the CSP
+    void create_gk(Seed seed)
+    {
+        if (he_sk.words.size() != context->key_limbs() * context->poly_modulus_degree()) throw std::invalid_argument("create_gk: no secret key");
+        context->generate_galois(he_sk.words.data(), gk_indices, seed, he_gk.keys);
+        gk_set = context->keys().galois(detail::words(he_gk));
+    }
+    const GaloisKeys &get_galois_keys() const { return he_gk; }
 
     // SEALZpCipher::mask (SEAL_Cipher.cpp:161-166)
     void mask(Ciphertext &cipher, std::vector<uint64_t> &mask_vec)
@@ -168,6 +181,7 @@ protected:
     std::shared_ptr<HheContext> context;
     PublicKey he_pk;
     SecretKey he_sk;
+    GaloisKeys he_gk;  // filled by create_gk only
     std::vector<int> gk_indices;
     bool use_bsgs = false;
     size_t bsgs_n1 = 0, bsgs_n2 = 0;
@@ -197,6 +211,22 @@ public:
     // supply the BFV encryption of the PASTA key that HE_decrypt reads (secret_key_encrypted[0],
     // pasta_3_seal.cpp:58; filled by encrypt_key() on the client side of the reference)
     void set_encrypted_key(const Ciphertext &enc_key) { secret_key_encrypted.assign(1, enc_key); }
+
+    // PASTA_SEAL::encrypt_key_2 (pasta_3_seal.cpp:23-38): the BFV encryption of the 256-word PASTA key ssk under this object's public
+    // key, packed as the reference packs it (words 0..127 at slots 0.., words 128..255 at slots N/2..)
+    std::vector<Ciphertext> encrypt_key_2(const std::vector<uint64_t> &ssk, Seed seed)
+    {
+        if (ssk.size() != PASTA_PARAMS.key_size) throw std::runtime_error("Invalid Key length");
+        if (he_pk.words.size() != 2 * context->key_limbs() * slots) throw std::invalid_argument("encrypt_key_2: no public key");
+        std::vector<uint64_t> key_tmp(halfslots + PASTA_PARAMS.plain_size, 0);
+        for (size_t i = 0; i < PASTA_PARAMS.plain_size; i++) {
+            key_tmp[i] = ssk[i];
+            key_tmp[i + halfslots] = ssk[i + PASTA_PARAMS.plain_size];
+        }
+        std::vector<Ciphertext> enc_sk(1);
+        context->encrypt(he_pk.words.data(), key_tmp.data(), key_tmp.size(), seed, detail::into(*context, enc_sk[0]));
+        return enc_sk;
+    }
 
     // PASTA_SEAL::HE_decrypt (pasta_3_seal.cpp:42-104) == decomposition(ciphertexts, secret_key_encrypted)
     virtual std::vector<Ciphertext> HE_decrypt(std::vector<uint64_t> &ciphertexts, bool batch_encoder = false)
@@ -265,6 +295,15 @@ private:
     uint64_t modulus;
     ZpCipherParams params;
 };
+
+// seal::KeyGenerator as the parties use it (Analyst.cpp:38-66, hhe_pktnn_examples.cpp:435-441): secret + public key, and
+// create_relin_keys, on the device
+inline void keygen(HheContext &ctx, Seed seed, SecretKey &sk, PublicKey &pk) { ctx.generate_keys(seed, sk.words, pk.words); }
+inline void create_relin_keys(HheContext &ctx, const SecretKey &sk, Seed seed, RelinKeys &rk)
+{
+    if (sk.words.size() != ctx.key_limbs() * ctx.poly_modulus_degree()) throw std::invalid_argument("create_relin_keys: no secret key");
+    ctx.generate_relin(sk.words.data(), seed, rk.key);
+}
 
 }  // namespace pasta
 

@@ -40,12 +40,15 @@ _SYMBOLS = [
     "hhe_flatten_ks", "hhe_decompose_ks", "hhe_fc_row_ks", "hhe_seal_load_relin_keys_ks", "hhe_seal_load_galois_keys_ks",
     "hhe_matrix_create", "hhe_matrix_destroy", "hhe_matrix_bytes", "hhe_packed_affine_ks", "hhe_affine_galois_steps",
     "hhe_pasta3_clear_keystream_cache",
+    "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin", "hhe_keyset_generate_galois",
+    "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
 ]
 
 
 # exports a library built from an earlier commit may lack (HHE_LIB selects such a build for A/B runs): bound when present, and the method
 # that needs one raises when it is not
-_OPTIONAL = {"hhe_pasta3_clear_keystream_cache"}
+_OPTIONAL = {"hhe_pasta3_clear_keystream_cache", "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin",
+             "hhe_keyset_generate_galois", "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt"}
 
 
 def exported_symbols():
@@ -102,6 +105,13 @@ def _ptr(x):
     return C.c_void_p(x.data_ptr())
 
 
+def _seed(seed):
+    """the 32 seed bytes of a key-generation call or an encryption batch (the only entropy: fresh per call)"""
+    seed = bytes(seed)
+    assert len(seed) == 32
+    return (C.c_uint8 * 32).from_buffer_copy(seed)
+
+
 def _ks(keyset):
     """handle of a KeySet, or NULL = the context's default set"""
     return keyset.h if keyset is not None else C.c_void_p(0)
@@ -144,6 +154,30 @@ class KeySet:
 
     def has_relin(self):
         return bool(self.ctx.lib.hhe_keyset_has_relin(self.h))
+
+    def generate_relin(self, sk, seed):
+        """sk: device uint64 [K][N] (Context.keygen_secret); seed: 32 fresh bytes"""
+        self.ctx._chk(self.ctx.lib.hhe_keyset_generate_relin(self.h, _ptr(sk), _seed(seed)))
+        return self
+
+    def generate_galois(self, sk, seed, elts=None):
+        """elts: Galois elements, or None for the default set of create_galois_keys(); all-or-nothing"""
+        if elts is None:
+            self.ctx._chk(self.ctx.lib.hhe_keyset_generate_galois(self.h, _ptr(sk), C.c_void_p(0), C.c_size_t(0), _seed(seed)))
+        else:
+            e = np.ascontiguousarray(elts, dtype=np.uint32)
+            self.ctx._chk(self.ctx.lib.hhe_keyset_generate_galois(self.h, _ptr(sk), _ptr(e), C.c_size_t(len(e)), _seed(seed)))
+        return self
+
+    def get_relin(self):
+        ksk = np.zeros((self.ctx.L, 2, self.ctx.K, self.ctx.n), np.uint64)
+        self.ctx._chk(self.ctx.lib.hhe_keyset_get_relin(self.h, _ptr(ksk)))
+        return ksk
+
+    def get_galois(self, elt):
+        ksk = np.zeros((self.ctx.L, 2, self.ctx.K, self.ctx.n), np.uint64)
+        self.ctx._chk(self.ctx.lib.hhe_keyset_get_galois(self.h, C.c_uint32(elt), _ptr(ksk)))
+        return ksk
 
     def seal_load_relin_keys(self, blob):
         buf = (C.c_uint8 * len(blob)).from_buffer_copy(bytes(blob))
@@ -408,6 +442,24 @@ class Context:
         sk = np.ascontiguousarray(sk, dtype=np.uint64)
         assert sk.size >= self.L * self.n
         self._chk(self.lib.hhe_decrypt(self.h, _ptr(sk), _ptr(ct), C.c_size_t(B), _ptr(vals_out)))
+
+    # ---- keys and ciphertexts from a seed (32 fresh bytes per call: the only entropy) ----
+    def sample_poly(self, seed, purpose, elt, index, kind, mod_base, mod_count, out):
+        """the sampler alone: out device [mod_count][N]; kind 1 ternary, 2 noise, 3 uniform"""
+        self._chk(self.lib.hhe_sample_poly(self.h, _seed(seed), C.c_uint32(purpose), C.c_uint32(elt), C.c_uint32(index), C.c_int(kind),
+                                           C.c_int(mod_base), C.c_int(mod_count), _ptr(out)))
+
+    def keygen_secret(self, seed, sk_out):
+        """sk_out: device [K][N] (NTT form, key level)"""
+        self._chk(self.lib.hhe_keygen_secret(self.h, _seed(seed), _ptr(sk_out)))
+
+    def keygen_public(self, sk, seed, pk_out):
+        """sk device [K][N]; pk_out device [2][K][N]"""
+        self._chk(self.lib.hhe_keygen_public(self.h, _ptr(sk), _seed(seed), _ptr(pk_out)))
+
+    def encrypt(self, pk, plain, seed, B, out, bcast=False):
+        """pk device [2][K][N]; plain device [B][N] ([1][N] if bcast); out device [B][2][L][N]"""
+        self._chk(self.lib.hhe_encrypt(self.h, _ptr(pk), _ptr(plain), C.c_int(int(bcast)), _seed(seed), C.c_size_t(B), _ptr(out)))
 
 
 def bfv_default_coeff_modulus(n, lib=None):

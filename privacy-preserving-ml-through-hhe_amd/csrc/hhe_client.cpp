@@ -2,6 +2,7 @@
 // (pasta::PASTA::encrypt / decrypt, pasta::Pasta::keystream -- src/pasta/pasta_3_plain.cpp:9-46,156-178) and batched
 // BFV result decryption (sealhelper::decrypting, src/util/sealhelper.cpp:252-266).  Host code only sets up constants and
 // launches; the arithmetic is in hhe_client_bodies.h.
+#include <algorithm>
 #include <cstring>
 #include <vector>
 #include "hhe_internal.h"
@@ -26,6 +27,7 @@ int keystream_into(hhe_ctx *c, const uint64_t *key, uint64_t first_block, size_t
     if (!rnd.p || !dkey.p) return dev_fail("hhe_pasta3_plain_keystream");
     if (rt_h2d(dkey.p, key, 2 * PASTA_T * 8, st)) return dev_fail("hhe_pasta3_plain_keystream");
     PastaXofArgs x;
+    x.mode = XOF_PASTA;
     x.t = c->t; x.nonce = PASTA_NONCE; x.first_block = first_block; x.nblocks = (int)nblocks; x.rand = rnd.w();
     int bits = 0;
     for (u64 v = c->t; v; v >>= 1) ++bits;
@@ -132,5 +134,246 @@ extern "C" int hhe_decrypt(hhe_ctx *c, const uint64_t *sk, const uint64_t *ct, s
     g2.in = plain.w(); g2.vals = vals; g2.slot_map = c->d_slot_map; g2.logn = c->logn; g2.B = B;
     k_decode_gather(g2, st);
     if (rt_sync(st)) return dev_fail("hhe_decrypt");
+    return HHE_OK;
+}
+
+// ------------------------------------------------------------------ key generation and public-key encryption from a seed
+// (KeyGenerator::create_public_key / create_relin_keys / create_galois_keys, Analyst.cpp:38-93, hhe_pktnn_examples.cpp:435-443,
+// 615-617; Encryptor::encrypt, pastahelper.cpp:355-377, sealhelper.cpp:123-142).  The randomness is the sampler of
+// hhe_keygen_bodies.h; host code only names the positions and launches.
+namespace {
+enum { PUR_SECRET = 1, PUR_PUBLIC = 2, PUR_RELIN = 3, PUR_GALOIS = 4, PUR_ENCRYPT = 5 };
+
+PastaXofArgs sample_args(const hhe_ctx *c, const uint8_t *seed, u32 purpose, u32 elt, u32 first_index)
+{
+    PastaXofArgs x;
+    memset(&x, 0, sizeof(x));
+    x.mode = XOF_SAMPLE;
+    for (int w = 0; w < 4; ++w)
+        for (int b = 0; b < 8; ++b) x.seed[w] |= (u64)seed[8 * w + b] << (8 * b);
+    x.purpose = purpose; x.elt = elt; x.first_index = first_index; x.logn = c->logn; x.mods = c->d_mods;
+    return x;
+}
+void seg_small(SampleSeg &g, int kind, int nidx, int ncomp, int nres, int mod_cycle, u64 *out, size_t idx_stride, size_t comp_stride)
+{
+    g.kind = kind; g.nidx = nidx; g.ncomp = ncomp; g.nres = nres; g.mod_base = 0; g.mod_cycle = mod_cycle;
+    g.out = out; g.idx_stride = idx_stride; g.comp_stride = comp_stride;
+}
+void seg_uniform(SampleSeg &g, int nidx, int nlimbs, int mod_base, u64 *out, size_t idx_stride, size_t n)
+{
+    g.kind = SMP_UNIFORM; g.nidx = nidx; g.ncomp = nlimbs; g.nres = 0; g.mod_base = mod_base; g.mod_cycle = nlimbs;
+    g.out = out; g.idx_stride = idx_stride; g.comp_stride = n;
+}
+void sample_launch(const hhe_ctx *c, PastaXofArgs &x, rt_stream st)
+{
+    const size_t polys = (size_t)x.seg[0].nidx * x.seg[0].ncomp + (size_t)x.seg[1].nidx * x.seg[1].ncomp;
+    x.nblocks = (int)(polys << (c->logn - 6));  // one lane per 64-coefficient chunk
+    k_pasta_xof(x, st);
+}
+NttArgs plain_ntt(const hhe_ctx *c, u64 *polys, size_t count, int mod_cycle)
+{
+    NttArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = polys; a.dst = polys; a.mods = c->d_mods; a.logn = c->logn; a.count = (int)count;
+    a.mod_base = 0; a.mod_cycle = mod_cycle; a.src_div = 1; a.t = c->t;
+    a.load_op = LOAD_PLAIN; a.store_op = STORE_PLAIN; a.mul_cycle = 1; a.mul_item_polys = 1;
+    a.L = c->L; a.K = c->K; a.ks = c->ksc; a.lazy8 = ntt_lazy8(c, 0, mod_cycle);
+    return a;
+}
+EltArgs elt_args(const hhe_ctx *c, const u64 *x, const u64 *y, u64 *out, size_t count, int mod_cycle, int b_cycle)
+{
+    EltArgs a;
+    memset(&a, 0, sizeof(a));
+    a.a = x; a.b = y; a.out = out; a.mods = c->d_mods; a.logn = c->logn; a.count = (int)count;
+    a.mod_base = 0; a.mod_cycle = mod_cycle; a.b_cycle = b_cycle;
+    return a;
+}
+// D encryptions of zero under the secret key at the key level, NTT form, into key [D][2][K][N] (generate_one_kswitch_key; D = 1 without
+// new_key: a public key): one sampler launch (a into the c1 slots, e into noise [D][K][N]), one forward transform, one fused launch.
+// with_key: new_key [K][N] (NTT form) sits behind the noise, at noise + D * K * N (new_key_of)
+u64 *new_key_of(const hhe_ctx *c, u64 *noise, int D) { return noise + (size_t)D * c->K * c->n; }
+void gen_enc_zero(hhe_ctx *c, const u64 *sk, bool with_key, const uint8_t *seed, u32 purpose, u32 elt, int D, u64 *key, u64 *noise, rt_stream st)
+{
+    const int K = c->K;
+    const size_t n = c->n;
+    PastaXofArgs x = sample_args(c, seed, purpose, elt, 0);
+    seg_uniform(x.seg[0], D, K, 0, key + (size_t)K * n, (size_t)2 * K * n, n);
+    seg_small(x.seg[1], SMP_NOISE, D, 1, K, K, noise, (size_t)K * n, 0);
+    sample_launch(c, x, st);
+    k_ntt(plain_ntt(c, noise, (size_t)D * K, K), false, st);
+    EltArgs e = elt_args(c, noise, sk, key, (size_t)D * K, K, K);
+    e.with_key = with_key ? 1 : 0;
+    k_elt(e, ELT_ENCZ, st);
+}
+int seed_check(const hhe_ctx *c, const char *who)
+{
+    if (c->logn < 6) return fail(HHE_ERR_INVALID, std::string(who) + ": the sampler needs N >= 64");
+    return HHE_OK;
+}
+}  // namespace
+
+extern "C" int hhe_sample_poly(hhe_ctx *c, const uint8_t *seed, uint32_t purpose, uint32_t elt, uint32_t index, int kind, int mod_base,
+                               int mod_count, uint64_t *out)
+{
+    HHE_LOCK(c);
+    if (!c || !seed || !out || purpose > 255 || kind < SMP_TERNARY || kind > SMP_UNIFORM || mod_base < 0 || mod_count < 1 ||
+        mod_base + mod_count > c->nmod)
+        return fail(HHE_ERR_INVALID, "hhe_sample_poly: bad arguments");
+    if (int rc = seed_check(c, "hhe_sample_poly")) return rc;
+    rt_stream st = c->lanes[0].stream;
+    PastaXofArgs x = sample_args(c, seed, purpose, elt, index);
+    if (kind == SMP_UNIFORM) seg_uniform(x.seg[0], 1, mod_count, mod_base, out, 0, c->n);
+    else {
+        seg_small(x.seg[0], kind, 1, 1, mod_count, mod_count, out, 0, 0);
+        x.seg[0].mod_base = mod_base;
+    }
+    sample_launch(c, x, st);
+    if (rt_sync(st)) return dev_fail("hhe_sample_poly");
+    return HHE_OK;
+}
+
+extern "C" int hhe_keygen_secret(hhe_ctx *c, const uint8_t *seed, uint64_t *sk)
+{
+    HHE_LOCK(c);
+    if (!c || !seed || !sk) return fail(HHE_ERR_INVALID, "hhe_keygen_secret: null argument");
+    if (int rc = seed_check(c, "hhe_keygen_secret")) return rc;
+    rt_stream st = c->lanes[0].stream;
+    PastaXofArgs x = sample_args(c, seed, PUR_SECRET, 0, 0);
+    seg_small(x.seg[0], SMP_TERNARY, 1, 1, c->K, c->K, sk, 0, 0);
+    sample_launch(c, x, st);
+    k_ntt(plain_ntt(c, sk, c->K, c->K), false, st);
+    if (rt_sync(st)) return dev_fail("hhe_keygen_secret");
+    return HHE_OK;
+}
+
+extern "C" int hhe_keygen_public(hhe_ctx *c, const uint64_t *sk, const uint8_t *seed, uint64_t *pk)
+{
+    HHE_LOCK(c);
+    if (!c || !sk || !seed || !pk) return fail(HHE_ERR_INVALID, "hhe_keygen_public: null argument");
+    if (int rc = seed_check(c, "hhe_keygen_public")) return rc;
+    rt_stream st = c->lanes[0].stream;
+    DevBuf noise((size_t)c->K * c->n * 8);
+    if (!noise.p) return dev_fail("hhe_keygen_public");
+    gen_enc_zero(c, sk, false, seed, PUR_PUBLIC, 0, 1, pk, noise.w(), st);
+    if (rt_sync(st)) return dev_fail("hhe_keygen_public");
+    return HHE_OK;
+}
+
+extern "C" int hhe_keyset_generate_relin(hhe_keyset *ks, const uint64_t *sk, const uint8_t *seed)
+{
+    if (!ks || !sk || !seed) return fail(HHE_ERR_INVALID, "hhe_keyset_generate_relin: null argument");
+    hhe_ctx *c = ks->ctx;
+    HHE_LOCK(c);
+    if (int rc = seed_check(c, "hhe_keyset_generate_relin")) return rc;
+    rt_stream st = c->lanes[0].stream;
+    const size_t kn = (size_t)c->K * c->n;
+    DevBuf key(c->ksk_words() * 8), noise((size_t)(c->L + 1) * kn * 8);
+    if (!key.p || !noise.p) return dev_fail("hhe_keyset_generate_relin");
+    k_elt(elt_args(c, sk, sk, new_key_of(c, noise.w(), c->L), c->K, c->K, 0), ELT_MUL, st);  // new_key = s^2 (NTT form)
+    gen_enc_zero(c, sk, true, seed, PUR_RELIN, 0, c->L, key.w(), noise.w(), st);
+    if (rt_sync(st)) return dev_fail("hhe_keyset_generate_relin");
+    keyset_adopt_relin(ks, key.release());
+    return HHE_OK;
+}
+
+extern "C" int hhe_keyset_generate_galois(hhe_keyset *ks, const uint64_t *sk, const uint32_t *elts, size_t count, const uint8_t *seed)
+{
+    if (!ks || !sk || !seed || (count == 0) != (elts == nullptr)) return fail(HHE_ERR_INVALID, "hhe_keyset_generate_galois: bad arguments");
+    hhe_ctx *c = ks->ctx;
+    HHE_LOCK(c);
+    if (int rc = seed_check(c, "hhe_keyset_generate_galois")) return rc;
+    const size_t n = c->n, kn = (size_t)c->K * n;
+    std::vector<u32> list;
+    if (count == 0) {  // GaloisTool::get_elts_all (seal/util/galois.h:131): 3^(2^i), 3^-(2^i), then 2N-1
+        u64 pos = 3, neg = nt_invmod(3, 2 * n);
+        for (int i = 0; i < c->logn - 1; ++i) {
+            list.push_back((u32)pos); list.push_back((u32)neg);
+            pos = pos * pos % (2 * n); neg = neg * neg % (2 * n);
+        }
+        list.push_back((u32)(2 * n - 1));
+    } else list.assign(elts, elts + count);
+    std::vector<u32> uniq;  // one key per element (get_elts_all repeats 3^(N/4))
+    for (u32 e : list) {
+        if (!(e & 1) || e >= 2 * n) return fail(HHE_ERR_INVALID, "invalid Galois element");  // nothing has been touched
+        if (std::find(uniq.begin(), uniq.end(), e) == uniq.end()) uniq.push_back(e);
+    }
+    rt_stream st = c->lanes[0].stream;
+    DevBuf noise((size_t)(c->L + 1) * kn * 8), scoef(kn * 8);
+    u64 *const sg = new_key_of(c, noise.w(), c->L);
+    std::vector<u64 *> keys;
+    auto drop = [&]() { for (u64 *k : keys) rt_free(k); };
+    if (!noise.p || !scoef.p) return dev_fail("hhe_keyset_generate_galois");
+    if (rt_d2d(scoef.p, sk, kn * 8, st)) return dev_fail("hhe_keyset_generate_galois");
+    k_ntt(plain_ntt(c, scoef.w(), c->K, c->K), true, st);  // s in coefficient form, once
+    for (u32 e : uniq) {
+        u64 *key = (u64 *)rt_malloc(c->ksk_words() * 8);
+        if (!key) { rt_sync(st); drop(); return dev_fail("hhe_keyset_generate_galois"); }
+        keys.push_back(key);
+        GaloisArgs g;  // new_key = sigma_e(s): GaloisTool::apply_galois between the transforms
+        memset(&g, 0, sizeof(g));
+        g.mods = c->d_mods; g.logn = c->logn; g.count = c->K; g.L = c->K; g.einv = (u32)nt_invmod(e, 2 * n);
+        g.in = scoef.w(); g.out = sg; g.in_item_stride = kn; g.out_item_stride = kn;
+        k_galois(g, st);
+        k_ntt(plain_ntt(c, sg, c->K, c->K), false, st);
+        gen_enc_zero(c, sk, true, seed, PUR_GALOIS, e, c->L, key, noise.w(), st);
+    }
+    if (rt_sync(st)) { drop(); return dev_fail("hhe_keyset_generate_galois"); }
+    for (size_t i = 0; i < uniq.size(); ++i) keyset_adopt_galois(ks, uniq[i], keys[i]);
+    return HHE_OK;
+}
+
+extern "C" int hhe_keyset_get_relin(const hhe_keyset *ks, uint64_t *ksk)
+{
+    if (!ks || !ksk) return fail(HHE_ERR_INVALID, "hhe_keyset_get_relin: null argument");
+    hhe_ctx *c = ks->ctx;
+    HHE_LOCK(c);
+    if (!ks->rk) return fail(HHE_ERR_NO_RELIN_KEY, "relinearization key not present");
+    rt_stream st = c->lanes[0].stream;
+    if (rt_d2h(ksk, ks->rk, c->ksk_words() * 8, st) || rt_sync(st)) return dev_fail("hhe_keyset_get_relin");
+    return HHE_OK;
+}
+
+extern "C" int hhe_keyset_get_galois(const hhe_keyset *ks, uint32_t elt, uint64_t *ksk)
+{
+    if (!ks || !ksk) return fail(HHE_ERR_INVALID, "hhe_keyset_get_galois: null argument");
+    hhe_ctx *c = ks->ctx;
+    HHE_LOCK(c);
+    auto it = ks->gk.find(elt);
+    if (it == ks->gk.end()) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+    rt_stream st = c->lanes[0].stream;
+    if (rt_d2h(ksk, it->second, c->ksk_words() * 8, st) || rt_sync(st)) return dev_fail("hhe_keyset_get_galois");
+    return HHE_OK;
+}
+
+extern "C" int hhe_encrypt(hhe_ctx *c, const uint64_t *pk, const uint64_t *plain, int plain_bcast, const uint8_t *seed, size_t B, uint64_t *out)
+{
+    HHE_LOCK(c);
+    if (!c || !pk || !plain || !seed || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_encrypt: bad arguments");
+    if (int rc = seed_check(c, "hhe_encrypt")) return rc;
+    const int L = c->L, K = c->K;
+    const size_t n = c->n, ln = (size_t)L * n;
+    if (B * 3 * (n >> 6) > ((size_t)1 << 30) || B * 2 * L > ((size_t)1 << 30)) return fail(HHE_ERR_INVALID, "hhe_encrypt: batch too large");
+    rt_stream st = c->lanes[0].stream;
+    DevBuf e(B * 2 * ln * 8), pkd(2 * ln * 8);
+    if (!e.p || !pkd.p) return dev_fail("hhe_encrypt");
+    // item b: u (ternary) as 2L residue polynomials straight into out [B][2][L][N], e_0 / e_1 (noise) into e [B][2][L][N]
+    PastaXofArgs x = sample_args(c, seed, PUR_ENCRYPT, 0, 0);
+    seg_small(x.seg[0], SMP_TERNARY, (int)B, 1, 2 * L, L, out, 2 * ln, 0);
+    seg_small(x.seg[1], SMP_NOISE, (int)B, 2, L, L, e.w(), 2 * ln, ln);
+    sample_launch(c, x, st);
+    for (int k = 0; k < 2; ++k)  // the data-level limbs of the key-level public key, contiguous: [2][L][N]
+        if (rt_d2d(pkd.w() + k * ln, pk + (size_t)k * K * n, ln * 8, st)) return dev_fail("hhe_encrypt");
+    // c_k = INTT(NTT(u) * pk_k) + e_k
+    NttArgs a = plain_ntt(c, out, B * 2 * L, L);
+    a.store_op = STORE_MUL; a.mul = pkd.w(); a.mul_cycle = 2 * L; a.mul_item_polys = 1;
+    k_ntt(a, false, st);
+    k_ntt(plain_ntt(c, out, B * 2 * L, L), true, st);
+    k_elt(elt_args(c, out, e.w(), out, B * 2 * L, L, 0), ELT_ADD, st);
+    // + the scaled plaintext (multiply_add_plain_with_scaling_variant), as hhe_add_plain does
+    AddPlainArgs p = c->apl;
+    p.ct = out; p.ct_map = nullptr; p.plain = plain; p.plain_ptrs = nullptr; p.plain_shift = 0; p.out = out; p.B = (int)B;
+    p.plain_bcast = plain_bcast != 0; p.subtract = 0; p.negate_ct = 0;
+    k_add_plain(p, st);
+    if (rt_sync(st)) return dev_fail("hhe_encrypt");
     return HHE_OK;
 }

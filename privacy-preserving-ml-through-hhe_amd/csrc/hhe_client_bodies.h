@@ -2,7 +2,7 @@
 // (1) The plain PASTA-3 cipher:
 // keystream blocks of pasta::Pasta::gen_keystream (src/pasta/pasta_3_plain.cpp:156-173) for many block counters at once,
 // and PASTA::encrypt / decrypt (:9-46) over batches of records.  Two kernels:
-//   pasta_xof_body    one lane per block counter: SHAKE128(BE64(nonce) || BE64(counter)) squeezed as big-endian 64-bit
+//   pasta_xof_fields_body  one lane per block counter: SHAKE128(BE64(nonce) || BE64(counter)) squeezed as big-endian 64-bit
 //                     words, masked to bitlen(t), rejection-sampled (:56-84) into the 4 x 512 field elements a block
 //                     consumes (per affine layer: first row of matrix 1, of matrix 2, rc 1, rc 2 -- the draw order of
 //                     linear_layer, :205-211)
@@ -17,10 +17,30 @@
 constexpr int PASTA_RAND_PER_BLOCK = (PASTA_R + 1) * 4 * PASTA_T;  // 2048 field elements per block
 constexpr int PASTA_PLAIN_THREADS = 2 * PASTA_T;
 
+// The XOF launch has two bodies behind it: the PASTA field elements below, and the seeded BFV sampler of key generation and
+// encryption (hhe_keygen_bodies.h).  One segment of a sampler launch = polynomials of one kind: index first_index + i (i < nidx),
+// component c (c < ncomp), polynomial p = i * ncomp + c of the segment, written at out + i * idx_stride + c * comp_stride.
+enum XofMode { XOF_PASTA = 0, XOF_SAMPLE = 1 };
+enum SampleKind { SMP_TERNARY = 1, SMP_NOISE = 2, SMP_UNIFORM = 3 };
+struct SampleSeg {
+    int kind;
+    int nidx, ncomp;
+    int nres;                  // ternary / noise: residue r < nres of the one small polynomial goes to out + r * N, modulus mod_base + r % mod_cycle
+    int mod_base, mod_cycle;   // uniform: modulus of component c = mod_base + c (one word range per limb), nres unused
+    u64 *out;
+    size_t idx_stride, comp_stride;
+};
 struct PastaXofArgs {
     u64 t, mask, nonce, first_block;
-    int nblocks;
+    int nblocks;  // lanes: block counters (XOF_PASTA) or 64-coefficient chunks (XOF_SAMPLE)
     u64 *rand;  // [nblocks][4][4][128]
+    int mode;     // XofMode
+    // XOF_SAMPLE
+    u64 seed[4];  // the 32 seed bytes as little-endian words
+    u32 purpose, elt, first_index;
+    int logn;
+    const ModDev *mods;
+    SampleSeg seg[2];  // lanes of seg[0] first; an unused segment has nidx = 0
 };
 struct PastaPlainArgs {
     u64 t, r_lo, r_hi;
@@ -83,7 +103,7 @@ HD void keccak_f1600(u64 *A)
 
 // Pasta::init_shake + generate_random_field_element (pasta_3_plain.cpp:56-84) for the whole block: element p of the
 // block is drawn with "zero allowed" iff it is a round constant (p % 512 >= 256); first-row elements reject zero (:286-295)
-HD void pasta_xof_body(const PastaXofArgs &a, size_t gid)
+HD void pasta_xof_fields_body(const PastaXofArgs &a, size_t gid)
 {
     if (gid >= (size_t)a.nblocks) return;
     u64 A[25];
@@ -268,3 +288,6 @@ HD void decode_gather_body(const DecodeArgs &a, size_t gid)
     const size_t b = gid >> a.logn, i = gid & (n - 1);
     a.vals[gid] = a.in[b * n + a.slot_map[i]];
 }
+
+// the seeded BFV sampler and the dispatch of the XOF launch between its two bodies
+#include "hhe_keygen_bodies.h"

@@ -140,7 +140,8 @@ struct NttArgs {
 };
 
 enum EltOp { ELT_ADD = 0, ELT_SUB = 1, ELT_NEG = 2, ELT_MUL = 3, ELT_MAC = 4, ELT_COPY = 5, ELT_BCAST = 6, ELT_SHOUP = 7,
-             ELT_DIFF = 8 };  // ELT_DIFF writes no polynomial: out[0] = 1 when a word of a differs from its word of b (out[0] cleared by the caller)
+             ELT_DIFF = 8,    // ELT_DIFF writes no polynomial: out[0] = 1 when a word of a differs from its word of b (out[0] cleared by the caller)
+             ELT_ENCZ = 9 };  // key generation: c0 = -(a s + e) (+ f new_key) of an encryption of zero under the secret key (elt_encz_body; a kernel of its own)
 
 struct EltArgs {  // element-wise kernels over [count][N] polys, modulus = mod_base + p % mod_cycle
     const u64 *a, *b;
@@ -148,6 +149,8 @@ struct EltArgs {  // element-wise kernels over [count][N] polys, modulus = mod_b
     const ModDev *mods;
     int logn, count, mod_base, mod_cycle;
     int b_cycle;  // poly of b = p % b_cycle (broadcast over the batch), 0 => same index
+    int with_key;  // ELT_ENCZ: 1 => new_key [K][N] (NTT form) of a key-switching key follows the `count` polynomials of a (fills the
+                   // struct's tail padding: the argument block of the older ops keeps its size and offsets)
 };
 
 struct CopyItemsArgs {  // dst item (s * dst_stride + dst_off) <- src item (s * src_stride + src_off), `words` words each, s < count

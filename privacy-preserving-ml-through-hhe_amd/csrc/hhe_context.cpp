@@ -626,6 +626,29 @@ int keyset_put_galois(hhe_keyset *ks, u32 elt, const u64 *ksk)
     ks->gk[elt] = slot;
     return rc;
 }
+static void adopt_key(hhe_ctx *c, u64 *&slot, u64 *key)
+{
+    sync_ctx(c);  // a resident key may still be read by work in flight on any lane
+    if (slot) { forget_key(c, slot); rt_free(slot); }
+    slot = key;
+}
+void keyset_adopt_relin(hhe_keyset *ks, u64 *key)
+{
+    keyset_new_serial(ks);
+    adopt_key(ks->ctx, ks->rk, key);
+}
+void keyset_adopt_galois(hhe_keyset *ks, u32 elt, u64 *key)
+{
+    hhe_ctx *c = ks->ctx;
+    auto corr = ks->gk_corr.find(elt);  // derived from the key being replaced
+    if (corr != ks->gk_corr.end()) { sync_ctx(c); rt_free(corr->second); ks->gk_corr.erase(corr); }
+    keyset_new_serial(ks);
+    u64 *slot = nullptr;
+    auto it = ks->gk.find(elt);
+    if (it != ks->gk.end()) slot = it->second;
+    adopt_key(c, slot, key);
+    ks->gk[elt] = slot;
+}
 void keyset_clear(hhe_keyset *ks)
 {
     hhe_ctx *c = ks->ctx;

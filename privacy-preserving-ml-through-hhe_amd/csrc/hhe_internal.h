@@ -271,6 +271,10 @@ struct KeyScope {
 int keyset_put_galois(hhe_keyset *ks, u32 elt, const u64 *ksk);
 int keyset_put_relin(hhe_keyset *ks, const u64 *ksk);
 void keyset_clear(hhe_keyset *ks);
+// a key generated on the device enters a set under the rules of the uploads (serial re-drawn, tables derived from a replaced key dropped);
+// the set takes ownership of `key` ([L][2][K][N] device words, reduced by construction).  elt is valid (the caller checked the whole list)
+void keyset_adopt_relin(hhe_keyset *ks, u64 *key);
+void keyset_adopt_galois(hhe_keyset *ks, u32 elt, u64 *key);
 void keyset_new_serial(hhe_keyset *ks);  // the set's content changes: keystreams kept under its old serial go
 
 int lane_reserve(hhe_ctx *c, Lane &ln, size_t B);

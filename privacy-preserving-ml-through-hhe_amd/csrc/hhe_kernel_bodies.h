@@ -11,6 +11,7 @@
 // lanes in LDS and runs radix-16/8/4 register rounds over it.
 #pragma once
 #include "hhe_modarith.h"
+#include "hhe_client_bodies.h"
 
 constexpr int NTT_THREADS = 256;
 // 4096-point tiles, radix-16/8 register rounds (16 points per lane).  (A 2048-point / radix-8 geometry at 5-8 waves per SIMD
@@ -513,7 +514,7 @@ HD void ntt_body_store(const NttArgs &a, int bx, int by, int tid, const u64 *lds
 
 // ------------------------------------------------------------------ element-wise
 
-HD void elt_body(const EltArgs &a, int op, size_t gid)
+HD void elt_base_body(const EltArgs &a, int op, size_t gid)
 {
     const int n = 1 << a.logn;
     const size_t p = gid >> a.logn;
@@ -535,6 +536,12 @@ HD void elt_body(const EltArgs &a, int op, size_t gid)
     default: r = x; break;
     }
     a.out[gid] = r;
+}
+// the element-wise launch as the tests-only emulator loops it; on the device the fused key-generation epilogue is a kernel of its own
+HD void elt_body(const EltArgs &a, int op, size_t gid)
+{
+    if (op == ELT_ENCZ) elt_encz_body(a, gid);
+    else elt_base_body(a, op, gid);
 }
 
 // strided gather / scatter of whole ciphertexts (16 bytes per lane): gid over [count][words / 2]

@@ -488,7 +488,8 @@ constexpr int ELT_THREADS = 256;
 static inline unsigned nblocks(size_t total) { return (unsigned)((total + ELT_THREADS - 1) / ELT_THREADS); }
 #define GID ((size_t)blockIdx.x * ELT_THREADS + threadIdx.x)
 
-__global__ void __launch_bounds__(ELT_THREADS) elt_kernel(EltArgs a, int op) { elt_body(a, op, GID); }
+__global__ void __launch_bounds__(ELT_THREADS) elt_kernel(EltArgs a, int op) { elt_base_body(a, op, GID); }
+__global__ void __launch_bounds__(ELT_THREADS) elt_encz_kernel(EltArgs a) { elt_encz_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) copy_items_kernel(CopyItemsArgs a) { copy_items_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) galois_kernel(GaloisArgs a) { galois_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) perm_kernel(PermArgs a) { perm_body(a, GID); }
@@ -539,7 +540,11 @@ __global__ void __launch_bounds__(ELT_THREADS) behz_floor_kernel(BehzFloorArgs a
         if (_t) hipLaunchKernelGGL(kern, dim3(nblocks(_t)), dim3(ELT_THREADS), 0, (hipStream_t)(s), __VA_ARGS__); \
     } while (0)
 
-void k_elt(const EltArgs &a, int op, rt_stream s) { LAUNCH1D(elt_kernel, (size_t)a.count << a.logn, s, a, op); }
+void k_elt(const EltArgs &a, int op, rt_stream s)
+{
+    if (op == ELT_ENCZ) LAUNCH1D(elt_encz_kernel, (size_t)a.count << a.logn, s, a);
+    else LAUNCH1D(elt_kernel, (size_t)a.count << a.logn, s, a, op);
+}
 void k_copy_items(const CopyItemsArgs &a, rt_stream s) { LAUNCH1D(copy_items_kernel, a.count * (a.words >> 1), s, a); }
 void k_galois(const GaloisArgs &a, rt_stream s) { LAUNCH1D(galois_kernel, (size_t)a.count << (a.logn - 1), s, a); }
 void k_perm(const PermArgs &a, rt_stream s)
@@ -609,7 +614,9 @@ void k_tensor(const TensorArgs &a, rt_stream s) { LAUNCH1D(tensor_kernel, ((size
 void k_behz_floor(const BehzFloorArgs &a, rt_stream s) { LAUNCH1D(behz_floor_kernel, (size_t)a.P << a.logn, s, a); }
 
 // ---------------------------------------------------------------- plain PASTA-3 (client / analyst side)
-__global__ void __launch_bounds__(64) pasta_xof_kernel(PastaXofArgs a) { pasta_xof_body(a, (size_t)blockIdx.x * 64 + threadIdx.x); }
+__global__ void __launch_bounds__(64) pasta_xof_kernel(PastaXofArgs a) { pasta_xof_fields_body(a, (size_t)blockIdx.x * 64 + threadIdx.x); }
+// the seeded BFV sampler (hhe_keygen_bodies.h): one lane per 64-coefficient chunk, the sponge state in registers
+__global__ void __launch_bounds__(64) sample_kernel(PastaXofArgs a) { sample_body(a, (size_t)blockIdx.x * 64 + threadIdx.x); }
 __global__ void __launch_bounds__(PASTA_PLAIN_THREADS) pasta_plain_kernel(PastaPlainArgs a)
 {
     __shared__ u64 lds[PASTA_PLAIN_LDS];
@@ -621,7 +628,9 @@ __global__ void __launch_bounds__(PASTA_PLAIN_THREADS) pasta_plain_kernel(PastaP
 __global__ void __launch_bounds__(ELT_THREADS) pasta_crypt_kernel(PastaCryptArgs a) { pasta_crypt_body(a, GID); }
 void k_pasta_xof(const PastaXofArgs &a, rt_stream s)
 {
-    if (a.nblocks > 0) hipLaunchKernelGGL(pasta_xof_kernel, dim3((a.nblocks + 63) / 64), dim3(64), 0, (hipStream_t)s, a);
+    if (a.nblocks <= 0) return;
+    if (a.mode == XOF_SAMPLE) hipLaunchKernelGGL(sample_kernel, dim3((a.nblocks + 63) / 64), dim3(64), 0, (hipStream_t)s, a);
+    else hipLaunchKernelGGL(pasta_xof_kernel, dim3((a.nblocks + 63) / 64), dim3(64), 0, (hipStream_t)s, a);
 }
 void k_pasta_plain(const PastaPlainArgs &a, rt_stream s)
 {
