@@ -82,6 +82,27 @@ void op_encode(hhe_ctx *c, const u64 *vals, size_t B, int stride, int count, int
     op_ntt(c, plain, B, c->mod_t, 1, true);
 }
 
+// res = Enc(c_b) - KS of a transciphering call (pasta_3_seal.cpp:161-169) for B items, in two halves on the current lane:
+//   front: vals [B][128] (zero padded) -> tmp [B][N]; it does not depend on the keystreams
+//   back:  out [B][2][L][N] from tmp and the items' keystream ciphertexts
+// Fused (fin_fused_on): the first inverse pass mod t gathers its tile from the words (LOAD_ENCODE) and the last one ends in the
+// add_plain epilogue (STORE_ADD_PLAIN), which reads item b's keystream at ks_ptrs[b], or at ks + b * 2LN without a table; the
+// plaintexts are never written.  Else launch for launch: clear, scatter, transform; add_plain on ks through ks_map (or item for item).
+void op_finish_front(hhe_ctx *c, const u64 *vals, u64 *tmp, size_t B)
+{
+    if (!fin_fused_on(c)) { op_encode(c, vals, B, PASTA_T, PASTA_T, -1, tmp); return; }
+    NttArgs a = ntt_args(c, vals, tmp, B, c->mod_t, 1);
+    a.load_op = LOAD_ENCODE; a.src_item_polys = 1; a.src_item_stride = PASTA_T; a.fin = c->d_fin;
+    k_ntt_pass(a, true, false, c->w->stream);
+}
+void op_finish_back(hhe_ctx *c, u64 *tmp, const u64 *ks, const u64 *const *ks_ptrs, const u32 *ks_map, u64 *out, size_t B)
+{
+    if (!fin_fused_on(c)) { op_add_plain(c, ks, tmp, nullptr, 0, false, false, true, out, B, ks_map); return; }
+    NttArgs a = ntt_args(c, tmp, tmp, B, c->mod_t, 1);
+    a.store_op = STORE_ADD_PLAIN; a.mul = ks; a.mul_ptrs = ks_ptrs; a.aux_out = out; a.fin = c->d_fin;
+    k_ntt_pass(a, true, true, c->w->stream);
+}
+
 // plain [P][N] (coefficients mod t) -> lifted NTT form [P][L][N]   
 void op_lift_ntt(hhe_ctx *c, const u64 *plain, size_t P, u64 *out)
 {
@@ -865,6 +886,7 @@ extern "C" int hhe_relinearize_slot(hhe_ctx *c, int slot, const uint64_t *a3, ui
 // one chunk of the batch on the current lane (c->w): the schedule of PASTA_SEAL::decomposition (pasta_3_seal.cpp:123-170)
 // shared_l0: `out` holds the items' first-layer sums (shared_l0_chain)
 // cw_padded_host null: the keystream only -- the chunk stops before res = Enc(c_b) - KS and its last addition leaves the state in `out`
+// (else the items' words, zero padded, in the context's host staging)
 static int transcipher_chunk(hhe_ctx *c, const u64 *enc_key, const u64 *const *d_diag, const u64 *const *d_rc,
                              const u64 *cw_padded_host, u64 *out, size_t B, bool bsgs, bool shared_l0)
 {
@@ -903,29 +925,40 @@ static int transcipher_chunk(hhe_ctx *c, const u64 *enc_key, const u64 *const *d
     }
     if (!rc && cw_padded_host) {
         // res = Enc(c_b) - KS : encode, negate, add_plain (:161-169)
-        op_encode(c, c->w->ws_vals, B, PASTA_T, PASTA_T, -1, c->w->ws_plain);
-        op_add_plain(c, state, c->w->ws_plain, nullptr, 0, false, false, true, out, B);
+        op_finish_front(c, c->w->ws_vals, c->w->ws_plain, B);
+        op_finish_back(c, c->w->ws_plain, state, nullptr, nullptr, out, B);
     }
     return rc;
 }
 
-// Keystream cache, lookup side: which resident snapshot holds the words of enc_key (*snap = its number, 0: none).  The comparison
-// runs on the main lane's stream -- the caller's, so it is ordered behind whatever produced enc_key -- word for word against every
-// snapshot: a launch raises its flag where a word differs, and the host reads the flags after one wait.
-static int ks_match_snapshot(hhe_ctx *c, const u64 *enc_key, u64 *snap)
+// Keystream cache, lookup side: which resident snapshot holds the words of enc_key.  The comparison runs on the main lane's stream --
+// the caller's, so it is ordered behind whatever produced enc_key -- word for word against every snapshot: a launch raises its flag
+// where a word differs.  ks_match_enqueue enqueues the clear, the launches, the read-back into the context's page-locked staging and
+// an event; the caller goes on preparing and enqueueing what does not depend on the answer, and ks_match_resolve waits for the event
+// (*snap = the snapshot's number, 0: none).
+static int ks_match_enqueue(hhe_ctx *c, const u64 *enc_key)
 {
     KsCache &kc = c->ks_cache;
-    *snap = 0;
     const size_t ns = kc.snaps.size();
     if (!ns) return HHE_OK;
     int rc = c->ks_flags.reserve(c, KsCache::MAX_SNAPSHOTS, "transciphering: key comparison");
     if (rc) return rc;
     c->w = &c->lanes[0];  // op_elt launches on the current lane: the main one, like the clear and the read around it
     rt_stream st = c->w->stream;
-    u64 *flags = c->ks_flags.p, h[KsCache::MAX_SNAPSHOTS];
+    u64 *flags = c->ks_flags.p;
     rt_memset(flags, 0, ns * 8, st);
     for (size_t i = 0; i < ns; ++i) op_elt(c, ELT_DIFF, enc_key, kc.snaps[i].words, flags + i, (size_t)2 * c->L, 0, c->L);
-    if (rt_d2h(h, flags, ns * 8, st) || rt_sync(st)) return dev_fail("hhe_pasta3_transcipher: key comparison");
+    if (rt_d2h(c->fin_host.p, flags, ns * 8, st) || rt_event_record(c->ev_cmp, st)) return dev_fail("hhe_pasta3_transcipher: key comparison");
+    return HHE_OK;
+}
+static int ks_match_resolve(hhe_ctx *c, u64 *snap)
+{
+    KsCache &kc = c->ks_cache;
+    *snap = 0;
+    const size_t ns = kc.snaps.size();
+    if (!ns) return HHE_OK;
+    if (rt_event_sync(c->ev_cmp)) return dev_fail("hhe_pasta3_transcipher: key comparison");
+    const u64 *h = c->fin_host.p;
     for (size_t i = 0; i < ns && !*snap; ++i)
         if (!h[i]) { *snap = kc.snaps[i].id; kc.snaps[i].last_use = c->block_call; }
     return HHE_OK;
@@ -956,30 +989,27 @@ struct KsPending {
 // Everything before res = Enc(c_b) - KS is a function of the key ciphertext, the named key sets and the item's block counter only, so
 // items of one call with the same counter share one keystream ciphertext, word for word (HHE_DEDUP, DESIGN.md "one keystream per
 // counter").  Such a call runs in two phases: the chunk schedule over its distinct counters, which leaves the keystreams in ks_tab,
-// then a finishing pass over all B items (encode, one add_plain that reads slot ks_map[b]).
-// The keystreams are kept from call to call (KsCache, DESIGN.md "one keystream per key"): every call then takes the two-phase shape,
-// phase 1 runs over the counters no kept keystream was found for, the kept ones are copied into their slots of ks_tab, and the new
-// ones are copied out of it.  Slots: the M evaluated counters first, in order of first appearance, then the found ones.
+// then a finishing pass over all B items (op_finish_front / op_finish_back).
+// The keystreams are kept from call to call (KsCache, DESIGN.md "one keystream per key"): every call then takes the two-phase shape and
+// phase 1 runs over the counters no kept keystream was found for.  The fused finishing pass reads every item's keystream where it is,
+// through a table of B pointers: a kept one in the cache (entries only go in commit, after the final wait, under the context's lock),
+// an evaluated one in ks_tab.  The unfused one reads ks_tab through a map: the M evaluated counters first, in order of first
+// appearance, then copies of the kept ones.
+// Order of a call: the key comparison is enqueued first and the host does not wait for it until it has prepared the call and
+// enqueued the half of the finishing pass that does not depend on the keystreams (upload of the words, first pass).
 // Without the cache (HHE_KS_CACHE=0, or a profiled call) a call of distinct counters (U == B) runs as one phase, with no table and no map.
-static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t *cw, const uint32_t *ncw,
-                            const uint64_t *block_index, size_t B, int use_bsgs, uint64_t *out)
+// transcipher_enqueue returns after enqueueing; whatever it returns, its caller waits for the main stream before anything it staged goes.
+static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64_t *cw, const uint32_t *ncw,
+                               const uint64_t *block_index, size_t B, int use_bsgs, uint64_t *out, KsPending &pend, KsCache::Entry &kkey)
 {
-    if (!c || !enc_key || !cw || !ncw || !block_index || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_pasta3_transcipher: null argument or empty batch");
-    const size_t n = c->n, half = n / 2, ctw = c->ct_words();
-    // pasta_3_seal.cpp:376-377
-    if ((size_t)PASTA_T * 2 != n && (size_t)PASTA_T * 4 > n) return fail(HHE_ERR_TOO_FEW_SLOTS, "too little slots for matmul implementation!");
-    if (!c->rks->rk) return fail(HHE_ERR_NO_RELIN_KEY, "relinearization key not set");
-    for (int step : {-1, half != PASTA_T ? PASTA_T : -1, 0})
-        if (!c->gks->gk.count(galois_elt_from_step(c, step))) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
-    if (use_bsgs)  // add_gk_indices (:196-200): -k*BSGS_N1, k = 1..7
-        for (int k = 1; k < 8; ++k)
-            if (!c->gks->gk.count(galois_elt_from_step(c, -16 * k))) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+    const size_t n = c->n, ctw = c->ct_words();
     Lane &main = c->lanes[0];
-    c->w = &main;
     int rc;
-    if ((rc = ensure_feistel_mask(c))) return rc;
-    ++c->block_call;
-    // the distinct counters in order of first appearance; umap[b]: where item b's counter stands among them
+    if ((rc = fin_reserve(c, B))) return rc;  // before anything reads the staging: growth replaces it
+    const bool cache = c->dedup && c->ks_cache.enabled && !c->profile;
+    // 1. the key comparison
+    if (cache && (rc = ks_match_enqueue(c, enc_key))) return rc;
+    // 2. host preparation.  The distinct counters in order of first appearance; umap[b]: where item b's counter stands among them
     std::vector<u64> uniq;
     std::vector<u32> umap;
     if (c->dedup) {
@@ -991,16 +1021,16 @@ static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t 
             umap[b] = ins.first->second;
         }
     }
-    const bool cache = c->dedup && c->ks_cache.enabled && !c->profile;
     const bool dedup = c->dedup && (cache || uniq.size() < B);
     const size_t U = dedup ? uniq.size() : B;  // keystreams the call needs
     const uint64_t *counters = dedup ? uniq.data() : block_index;
     c->last_unique = c->last_evaluated = U;
-    c->last_hits = 0;
-    std::vector<u64> cwp(B * PASTA_T, 0);
+    // staging: [MAX_SNAPSHOTS] flags | [B] pointers or map | [B][128] words.  Every word of the last part is written: nothing of an earlier call stays
+    u64 *const h_tab = c->fin_host.p + KsCache::MAX_SNAPSHOTS, *const h_words = h_tab + fin_tab_words(B);
+    u64 *const d_tab = c->fin_dev.p, *const d_words = d_tab + fin_tab_words(B), *const d_tmp = d_words + B * PASTA_T;
     for (size_t b = 0; b < B; ++b) {
-        if (ncw[b] > PASTA_T) return fail(HHE_ERR_INVALID, "hhe_pasta3_transcipher: more than 128 words in a block");
-        memcpy(&cwp[b * PASTA_T], cw + b * PASTA_T, ncw[b] * 8);
+        memcpy(h_words + b * PASTA_T, cw + b * PASTA_T, ncw[b] * 8);
+        memset(h_words + b * PASTA_T + ncw[b], 0, (PASTA_T - ncw[b]) * 8);
     }
     // public tables of every counter of the call (pinned for its duration), kept keystreams or not
     std::vector<BlockTables *> tabs(U);
@@ -1008,24 +1038,32 @@ static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t 
         if ((rc = ensure_block(c, counters[u], &tabs[u]))) return rc;
         if (use_bsgs && (rc = ensure_bsgs_tables(c, counters[u], tabs[u]))) return rc;
     }
-    // kept keystreams: found[u], or null = counter u is evaluated
+    // 3. the half of the finishing pass that does not depend on the keystreams
+    const ChunkPlan fin = plan_balanced(c, B);
+    if (dedup) {
+        rt_h2d(d_words, h_words, B * PASTA_T * 8, main.stream);
+        rc = run_chunks(c, fin, [&](Lane &, size_t, size_t b0, size_t bc) {
+            op_finish_front(c, d_words + b0 * PASTA_T, d_tmp + b0 * n, bc);
+            return (int)HHE_OK;
+        });
+        if (rc) return rc;
+    }
+    // 4. kept keystreams: found[u], or null = counter u is evaluated
     std::vector<const u64 *> found(U, nullptr);
-    KsCache::Entry kkey{nullptr, 0, c->gks->serial, c->rks->serial, use_bsgs != 0, c->block_call};
     if (cache) {
-        if ((rc = ks_match_snapshot(c, enc_key, &kkey.snap))) return rc;
+        if ((rc = ks_match_resolve(c, &kkey.snap))) return rc;
         if (kkey.snap)
             for (size_t u = 0; u < U; ++u)
                 if ((found[u] = c->ks_cache.find(counters[u], kkey, c->block_call))) ++c->last_hits;
     }
     const size_t M = U - c->last_hits;  // keystream evaluations
     c->last_evaluated = M;
+    const bool by_ptr = dedup && fin_fused_on(c);  // the finishing pass reads kept keystreams in place
     std::vector<size_t> eval, slot(U);  // eval[m]: the counter (index u) evaluation m is for; slot[u]: its place in ks_tab
     for (size_t u = 0, h = M; u < U; ++u) {
         if (found[u]) slot[u] = h++;
         else { slot[u] = eval.size(); eval.push_back(u); }
     }
-    if (dedup)
-        for (size_t b = 0; b < B; ++b) umap[b] = (u32)slot[umap[b]];
     // per-evaluation public tables
     std::vector<const u64 *> ptrs(2 * M);
     for (size_t m = 0; m < M; ++m) {
@@ -1035,24 +1073,19 @@ static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t 
     }
     // fused diagonal method: layer 0 acts on the same ciphertext for every item -- its chain runs once, here (HHE_SHARED_L0)
     const bool shared = c->matmul_mode == 1 && !use_bsgs && c->shared_l0 > 0 && M >= (size_t)c->shared_l0;
-    const ChunkPlan plan = plan_balanced(c, std::max<size_t>(M, 1)), fin = plan_balanced(c, B);
+    const ChunkPlan plan = plan_balanced(c, std::max<size_t>(M, 1));
     if (M)
         for (int s = plan.first_lane(); s <= plan.last_lane(); ++s) {
             if ((rc = lane_reserve(c, c->lanes[s], plan.per))) return rc;
             if (use_bsgs && (rc = c->lanes[s].ws_rot.reserve(c, plan.per * ROT_SLOTS * ctw, "bsgs workspace"))) return rc;
         }
-    if (dedup) {  // the finishing pass needs its items' words, plaintexts and map only, not the ciphertext workspaces of a lane
-        if ((rc = c->ks_tab.reserve(c, U * ctw, "transciphering: keystream table"))) return rc;
-        if ((rc = c->ks_map.reserve(c, B, "transciphering: keystream map"))) return rc;
-        for (int s = fin.first_lane(); s <= fin.last_lane(); ++s)
-            if ((rc = c->lanes[s].ws_fin.reserve(c, fin.per * (PASTA_T + n), "transciphering: finishing pass"))) return rc;
-    }
+    if (dedup && (rc = c->ks_tab.reserve(c, (by_ptr ? M : U) * ctw, "transciphering: keystream table"))) return rc;
     u64 *ks = dedup ? c->ks_tab.p : out;  // where an evaluation leaves its result
-    // from here on work is enqueued that reads host staging (ptrs, cwp, umap, keep) and the pending copies: every path ends in the final sync
-    KsPending pend;
+    // 5. the chain over the counters that are evaluated
     if (cache) {
-        for (size_t u = 0; u < U; ++u)
-            if (found[u]) rt_d2d(ks + slot[u] * ctw, found[u], ctw * 8, main.stream);
+        if (!by_ptr)
+            for (size_t u = 0; u < U; ++u)
+                if (found[u]) rt_d2d(ks + slot[u] * ctw, found[u], ctw * 8, main.stream);
         // a copy that cannot be allocated is a keystream that is not kept, nothing more
         if (M && !kkey.snap && (pend.snap = (u64 *)rt_malloc(ctw * 8))) rt_d2d(pend.snap, enc_key, ctw * 8, main.stream);
     }
@@ -1063,25 +1096,61 @@ static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t 
         lp.assign(2 * ln.ptr_cap, nullptr);
         for (size_t b = 0; b < bc; ++b) { lp[b] = ptrs[b0 + b]; lp[ln.ptr_cap + b] = ptrs[M + b0 + b]; }
         rt_h2d(ln.d_ptrs, lp.data(), lp.size() * sizeof(u64 *), ln.stream);
-        return transcipher_chunk(c, enc_key, ln.d_ptrs, ln.d_ptrs + ln.ptr_cap, dedup ? nullptr : &cwp[b0 * PASTA_T], ks + b0 * ctw, bc, use_bsgs != 0, shared);
+        return transcipher_chunk(c, enc_key, ln.d_ptrs, ln.d_ptrs + ln.ptr_cap, dedup ? nullptr : h_words + b0 * PASTA_T, ks + b0 * ctw, bc, use_bsgs != 0, shared);
     });
-    if (!rc && cache && (kkey.snap || pend.snap))  // the new keystreams, after the join of their chunks on the main stream
+    if (rc) {  // the pointer tables in `keep` are read by copies in flight
+        rt_sync(main.stream);
+        return rc;
+    }
+    if (cache && (kkey.snap || pend.snap))  // the new keystreams, after the join of their chunks on the main stream
         for (size_t m = 0; m < M; ++m)
             if (u64 *copy = (u64 *)rt_malloc(ctw * 8)) {
                 rt_d2d(copy, ks + m * ctw, ctw * 8, main.stream);
                 pend.cts.emplace_back(counters[eval[m]], copy);
             }
-    if (!rc && dedup) {
-        // res = Enc(c_b) - KS for every item (:161-169), after the join of the keystream chunks on the main stream
-        rt_h2d(c->ks_map.p, umap.data(), B * sizeof(u32), main.stream);
-        rc = run_chunks(c, fin, [&](Lane &ln, size_t, size_t b0, size_t bc) {
-            u64 *vals = ln.ws_fin.p, *plain = vals + fin.per * PASTA_T;
-            rt_h2d(vals, &cwp[b0 * PASTA_T], bc * PASTA_T * 8, ln.stream);
-            op_encode(c, vals, bc, PASTA_T, PASTA_T, -1, plain);
-            op_add_plain(c, ks, plain, nullptr, 0, false, false, true, out + b0 * ctw, bc, c->ks_map.p + b0);
+    // 6. res = Enc(c_b) - KS for every item (:161-169), after the join of the keystream chunks on the main stream
+    if (dedup) {
+        if (by_ptr)
+            for (size_t b = 0; b < B; ++b) {
+                const size_t u = umap[b];
+                h_tab[b] = (u64)(found[u] ? found[u] : ks + slot[u] * ctw);
+            }
+        else
+            for (size_t b = 0; b < B; ++b) ((u32 *)h_tab)[b] = (u32)slot[umap[b]];
+        rt_h2d(d_tab, h_tab, B * (by_ptr ? sizeof(u64) : sizeof(u32)), main.stream);
+        rc = run_chunks(c, fin, [&](Lane &, size_t, size_t b0, size_t bc) {
+            op_finish_back(c, d_tmp + b0 * n, ks, by_ptr ? (const u64 *const *)d_tab + b0 : nullptr, by_ptr ? nullptr : (const u32 *)d_tab + b0, out + b0 * ctw, bc);
             return (int)HHE_OK;
         });
     }
+    if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_pasta3_transcipher");  // `keep` and the host vectors above go with this frame
+    return rc;
+}
+static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t *cw, const uint32_t *ncw,
+                            const uint64_t *block_index, size_t B, int use_bsgs, uint64_t *out)
+{
+    if (!c || !enc_key || !cw || !ncw || !block_index || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_pasta3_transcipher: null argument or empty batch");
+    const size_t n = c->n, half = n / 2;
+    // pasta_3_seal.cpp:376-377
+    if ((size_t)PASTA_T * 2 != n && (size_t)PASTA_T * 4 > n) return fail(HHE_ERR_TOO_FEW_SLOTS, "too little slots for matmul implementation!");
+    if (!c->rks->rk) return fail(HHE_ERR_NO_RELIN_KEY, "relinearization key not set");
+    for (int step : {-1, half != PASTA_T ? PASTA_T : -1, 0})
+        if (!c->gks->gk.count(galois_elt_from_step(c, step))) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+    if (use_bsgs)  // add_gk_indices (:196-200): -k*BSGS_N1, k = 1..7
+        for (int k = 1; k < 8; ++k)
+            if (!c->gks->gk.count(galois_elt_from_step(c, -16 * k))) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+    for (size_t b = 0; b < B; ++b)
+        if (ncw[b] > PASTA_T) return fail(HHE_ERR_INVALID, "hhe_pasta3_transcipher: more than 128 words in a block");
+    Lane &main = c->lanes[0];
+    c->w = &main;
+    int rc;
+    if ((rc = ensure_feistel_mask(c))) return rc;
+    ++c->block_call;
+    c->last_hits = 0;
+    // from here on work is enqueued that reads host staging and the pending copies: every path ends in the final wait
+    KsPending pend;
+    KsCache::Entry kkey{nullptr, 0, c->gks->serial, c->rks->serial, use_bsgs != 0, c->block_call};
+    rc = transcipher_enqueue(c, enc_key, cw, ncw, block_index, B, use_bsgs, out, pend, kkey);
     if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_pasta3_transcipher");
     if (!rc) pend.commit(c, kkey);  // a failed call leaves nothing behind
     return rc;

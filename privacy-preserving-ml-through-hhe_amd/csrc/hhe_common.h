@@ -74,14 +74,27 @@ HD ModDev mod_at_u(const ModDev *mods, int i)
 // Modulus indices inside ModDev[]: 0..K-1 coefficient primes (K-1 = special),
 // K..K+L Bsk = {B_0..B_{L-1}, m_sk}, K+L+1 = plain modulus t.
 
-enum NttLoadOp { LOAD_PLAIN = 0, LOAD_DIGIT = 1, LOAD_LIFT = 2, LOAD_RNEG = 3 };
+enum NttLoadOp { LOAD_PLAIN = 0, LOAD_DIGIT = 1, LOAD_LIFT = 2, LOAD_RNEG = 3,
+                 LOAD_ENCODE = 4 };  // inv, mod t: the tile is gathered from the items' words through FinArgs::slot_inv (BatchEncoder::encode without a plaintext buffer)
 enum NttStoreOp {
     STORE_PLAIN = 0, STORE_MUL = 1, STORE_SCALE_T = 2, STORE_MAC = 3,
     STORE_RSP = 5,         // inv (special limb): v + floor(q_sp/2) mod q_sp
     STORE_KS1 = 6,         // inv: (v - r_1 + half) * q_sp^-1, written through the Galois map into aux_out
     STORE_KS0 = 7,         // fwd: NTT-domain key-switch finish of c0 + permuted-frame diagonal MAC
     STORE_KSF = 10,        // inv, polys [B][2][L]: generic key-switch finish (v - r_k + half) * q_sp^-1 (+ base poly k) into aux_out
-    STORE_LAZY = 8         // fwd: leave the result in the lazy range [0,4q) (consumer reduces: key-switch inner product)
+    STORE_LAZY = 8,        // fwd: leave the result in the lazy range [0,4q) (consumer reduces: key-switch inner product)
+    STORE_ADD_PLAIN = 11   // inv, mod t, one polynomial per item: aux_out[b] = scaled plaintext - operand ciphertext of item b (add_plain on a negated operand)
+};
+
+// Constants of the fused finishing pass of a transciphering call (LOAD_ENCODE / STORE_ADD_PLAIN), written to device memory once
+// per context: NttArgs carries a pointer, not a copy of delta[].
+struct FinArgs {
+    const u32 *slot_inv;       // [N]: slot_inv[slot_map[s]] = s
+    int count;                 // LOAD_ENCODE: words per item placed at slots [0, count); every other coefficient slot is 0
+    int L;
+    u64 t, q_mod_t, thr;       // as in AddPlainArgs
+    u64 t_r_lo, t_r_hi;
+    u64 delta[HHE_MAXL];
 };
 
 // key-switch mod-down constants, passed by value to the kernels that finish a key switch
@@ -137,6 +150,9 @@ struct NttArgs {
     size_t base_stride; // KSF: words between the items of aux_in
     int base_mask;      // KSF: bit k set => add base poly k
     KsConsts ks;
+    // fused finishing pass.  LOAD_ENCODE: src = the items' words (item b at src + b * src_item_stride, src_item_polys = 1).
+    // STORE_ADD_PLAIN: the operand ciphertext of item b is mul_ptrs[b] if mul_ptrs is set, else mul + b * 2LN; aux_out = out [B][2][L][N]
+    const FinArgs *fin;
 };
 
 enum EltOp { ELT_ADD = 0, ELT_SUB = 1, ELT_NEG = 2, ELT_MUL = 3, ELT_MAC = 4, ELT_COPY = 5, ELT_BCAST = 6, ELT_SHOUP = 7,

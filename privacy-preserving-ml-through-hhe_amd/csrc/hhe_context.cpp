@@ -261,6 +261,10 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
         }
     }
     c->d_slot_map = (u32 *)rt_malloc(4 * n);
+    c->d_slot_inv = (u32 *)rt_malloc(4 * n);
+    c->d_fin = (FinArgs *)rt_malloc(sizeof(FinArgs));
+    std::vector<u32> slot_inv(n);
+    for (size_t i = 0; i < n; ++i) slot_inv[c->slot_map[i]] = (u32)i;
 
     std::vector<u64> dq(c->q.begin(), c->q.begin() + L), Bq(c->bsk.begin(), c->bsk.begin() + L);
     const u64 msk = c->bsk[L], MT = (u64)1 << 32;
@@ -313,8 +317,15 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
     }
     bz.inv_B_msk = nt_invmod(product_mod(Bq, -1, msk), msk);
     c->d_behz = (BehzDev *)rt_malloc(sizeof(BehzDev));
+    // the fused finishing pass of a transciphering call reads the add_plain constants from device memory
+    FinArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    fa.slot_inv = c->d_slot_inv; fa.count = PASTA_T; fa.L = L;
+    fa.t = ap.t; fa.q_mod_t = ap.q_mod_t; fa.thr = ap.thr; fa.t_r_lo = ap.t_r_lo; fa.t_r_hi = ap.t_r_hi;
+    for (int j = 0; j < L; ++j) fa.delta[j] = ap.delta[j];
 
-    if (!c->d_tables || !c->d_mods || !c->d_slot_map || !c->d_behz ||
+    if (!c->d_tables || !c->d_mods || !c->d_slot_map || !c->d_behz || !c->d_slot_inv || !c->d_fin ||
+        rt_h2d(c->d_slot_inv, slot_inv.data(), 4 * n, nullptr) || rt_h2d(c->d_fin, &fa, sizeof(fa), nullptr) ||
         rt_h2d(c->d_tables, host_tab.data(), host_tab.size() * 8, nullptr) ||
         rt_h2d(c->d_mods, mods.data(), sizeof(ModDev) * c->nmod, nullptr) ||
         rt_h2d(c->d_slot_map, c->slot_map.data(), 4 * n, nullptr) ||
@@ -335,6 +346,7 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
     if (const char *e = getenv("HHE_SHARED_L0")) c->shared_l0 = std::max(0, atoi(e));
     if (const char *e = getenv("HHE_DEDUP")) c->dedup = atoi(e) != 0;
     if (const char *e = getenv("HHE_KS_CACHE")) c->ks_cache.enabled = atoi(e) != 0;
+    if (const char *e = getenv("HHE_FIN_FUSED")) c->fin_fused = atoi(e) != 0;
     if (const char *e = getenv("HHE_KS_CACHE_MB")) c->ks_cache.budget = (size_t)(std::max(0.0, atof(e)) * (double)(1 << 20));
     c->ks_cache.entry_bytes = c->ct_words() * 8;
     if (const char *e = getenv("HHE_SHARED_L0_MB")) c->l0_budget = (size_t)(std::max(0.0, atof(e)) * (double)(1 << 20));
@@ -355,6 +367,7 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
         c->lanes[s].ev_done = rt_event_create();
     }
     c->ev_fork = rt_event_create();
+    c->ev_cmp = rt_event_create();
     {   // a digit d_I < q_I may enter NTT_J unreduced when q_I < 4 q_J (butterfly inputs live in [0,4q))
         u64 qmax = 0, qmin = ~(u64)0;
         for (int i = 0; i < L; ++i) qmax = std::max(qmax, c->q[i]);
@@ -371,7 +384,7 @@ static void free_lane(Lane &ln)
 {
     rt_free(ln.ws_T); rt_free(ln.ws_S); rt_free(ln.ws_d); rt_free(ln.ws_ct3); rt_free(ln.ws_plain); rt_free(ln.ws_vals);
     for (auto &p : ln.ws_ct) { rt_free(p); p = nullptr; }
-    ln.ws_rot.release(); ln.ws_fin.release(); ln.ws_aff.release(); ln.ws_leaf.release();
+    ln.ws_rot.release(); ln.ws_aff.release(); ln.ws_leaf.release();
     for (auto &sl : ln.fc_slots) { rt_free(sl.tp); rt_free(sl.ct); rt_free(sl.c0hat); }
     ln.fc_slots.clear(); ln.fc_slot_cap = 0;
     for (u64 *p : ln.csum_bufs) rt_free(p);
@@ -389,6 +402,14 @@ void sync_ctx(hhe_ctx *c)
     for (auto &ln : c->lanes) {
         if (&ln == &c->lanes[0] || ln.own_stream) rt_sync(ln.stream);
     }
+}
+
+// device block and host staging of the finishing pass of a transciphering call of B items
+int fin_reserve(hhe_ctx *c, size_t B)
+{
+    int rc = c->fin_dev.reserve(c, fin_tab_words(B) + B * (PASTA_T + c->n), "transciphering: finishing pass");
+    if (!rc) rc = c->fin_host.reserve(c, KsCache::MAX_SNAPSHOTS + fin_tab_words(B) + B * PASTA_T, "transciphering: finishing pass");
+    return rc;
 }
 
 int lane_reserve(hhe_ctx *c, Lane &ln, size_t B)
@@ -450,6 +471,7 @@ extern "C" void hhe_ctx_destroy(hhe_ctx *c)
         if (ln.own_stream) rt_stream_destroy(ln.stream);
     }
     rt_event_destroy(c->ev_fork);
+    rt_event_destroy(c->ev_cmp);
     keyset_clear(&c->keys0);
     for (auto &ks : c->rk_slots) keyset_clear(&ks);
     for (hhe_keyset *ks : c->sets) { keyset_clear(ks); delete ks; }  // sets the caller did not destroy
@@ -460,8 +482,8 @@ extern "C" void hhe_ctx_destroy(hhe_ctx *c)
     rt_free(c->d_qsp_poly);
     c->d_blocks.release(); c->d_flags.release();
     c->l0_tab.release(); c->l0_ptrs.release();
-    c->ks_tab.release(); c->ks_map.release(); c->ks_flags.release();
-    rt_free(c->d_tables); rt_free(c->d_mods); rt_free(c->d_behz); rt_free(c->d_slot_map);
+    c->ks_tab.release(); c->ks_flags.release(); c->fin_dev.release(); c->fin_host.release();
+    rt_free(c->d_tables); rt_free(c->d_mods); rt_free(c->d_behz); rt_free(c->d_slot_map); rt_free(c->d_slot_inv); rt_free(c->d_fin);
     delete c;
 }
 
@@ -522,6 +544,7 @@ extern "C" int hhe_ctx_reserve(hhe_ctx *c, size_t B)
 {
     HHE_LOCK(c);
     if (!c || B == 0) return HHE_ERR_INVALID;
+    if (int rc = fin_reserve(c, B)) return rc;
     // generic ops run whole batches on lane 0; the transciphering path works in chunks on the internal lanes
     if (c->nstreams > 0) {
         const size_t per = std::min(B, c->chunk);
@@ -555,6 +578,7 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "dedup") return (u64)c->dedup;               // 1: one keystream evaluation per distinct block counter of a call
     if (w == "transcipher_unique") return c->last_unique; // distinct counters of the last transciphering call (its item count when it ran per item)
     if (w == "transcipher_evaluated") return c->last_evaluated;  // keystream chains the last call ran: the counters it found no kept keystream for
+    if (w == "fin_fused") return fin_fused_on(c) ? 1 : 0;        // the finishing pass of a transciphering call runs as two fused kernels (HHE_FIN_FUSED)
     if (w == "ks_cache") return c->ks_cache.enabled ? 1 : 0;      // keystreams are kept across calls (HHE_KS_CACHE)
     if (w == "ks_cache_hits") return c->last_hits;                // counters of the last call served from a kept keystream
     if (w == "ks_cache_entries") return c->ks_cache.entries();

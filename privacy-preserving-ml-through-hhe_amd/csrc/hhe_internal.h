@@ -1,5 +1,6 @@
 // hhe_internal.h -- host-side context of libhhe_gfx950.so (not part of the C ABI).
 #pragma once
+#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <string>
@@ -44,6 +45,30 @@ template <class T> struct GrowBuf {
         return HHE_OK;
     }
     void release() { rt_free((void *)p); p = nullptr; cap = 0; }  // the caller has waited for the readers
+};
+
+// Grow-only host staging of a context: page-locked where the runtime offers it (rt_host_malloc), else from malloc; `cap` counts words.
+// The caller has waited for every copy that reads the old block before it grows (GrowBuf's rule; contents are not kept).
+struct HostStage {
+    u64 *p = nullptr;
+    size_t cap = 0;
+    bool pinned = false;
+    int reserve(hhe_ctx *c, size_t words, const char *what)
+    {
+        if (words <= cap) return HHE_OK;
+        sync_ctx(c);
+        release();
+        pinned = rt_host_malloc && rt_host_free;
+        p = (u64 *)(pinned ? rt_host_malloc(words * 8) : malloc(words * 8));
+        if (!p) { hhe_set_error(std::string(what) + ": host staging allocation failed"); return HHE_ERR_DEVICE; }
+        cap = words;
+        return HHE_OK;
+    }
+    void release()
+    {
+        if (p) { if (pinned) rt_host_free(p); else free(p); }
+        p = nullptr; cap = 0;
+    }
 };
 
 struct BlockTables {   // public per-(nonce, block index) data of one PASTA block, device resident
@@ -102,8 +127,6 @@ struct Lane {
     const u64 **d_ptrs = nullptr;  // [2*cap] per-item public-table pointers (diag | rc)
     size_t ptr_cap = 0;
     GrowBuf<u64> ws_rot;     // [16][B][2][L][N]: PASTA's babystep rotations, and the FC's product + per-depth buffers of the unshared walk
-    GrowBuf<u64> ws_fin;     // [B][128] symmetric ciphertext words | [B][N] their plaintexts: the finishing pass of a transciphering call with repeated
-                             // counters, whose chunks are larger than the lane's ciphertext workspaces (B counts items of that pass)
     GrowBuf<u64> ws_aff;     // [n1 + n2][B][2][L][N] baby-step ciphertexts | inner sums of hhe_packed_affine (BSGS)
     // FC shared digits: one slot per trie node that is still needed -- the digit transforms of its un-rotated c1 (tp [B][L][K][N]) and its
     // ciphertext (ct [B][2][L][N]); refs = 1 while the depth-first walk is below the node + 1 per queued leaf key switch that reads it
@@ -165,8 +188,16 @@ struct hhe_ctx {
     size_t l0_steps() const { return l0_tab.cap / ((size_t)3 * L * n); }
     int dedup = 1;                 // transciphering: the keystream ciphertext of a block counter is evaluated once per call and every item with that counter
                                    // only subtracts it from its own encoded words (HHE_DEDUP; 0: every item evaluates its own).  What is kept across calls: ks_cache
-    GrowBuf<u64> ks_tab;           // [U][2][L][N]: the keystream ciphertexts of the running call's U distinct counters, in order of first appearance
-    GrowBuf<u32> ks_map;           // [B]: the slot of ks_tab item b reads
+    GrowBuf<u64> ks_tab;           // [M][2][L][N]: the keystream ciphertexts the running call evaluates, in order of first appearance ([U]: with copies of the kept ones behind them, unfused finishing pass)
+    // the finishing pass res = Enc(c_b) - KS over all B items of a call (its chunks are larger than the lanes' ciphertext workspaces):
+    int fin_fused = 1;             // two kernels (LOAD_ENCODE row pass, STORE_ADD_PLAIN strided pass) instead of clear + scatter + transform + add_plain
+                                   // (HHE_FIN_FUSED; 0: launch for launch).  Off where no test runs the fused kernels' geometry (N = 2^16: fin_fused_ok)
+    FinArgs *d_fin = nullptr;      // the fused kernels' constants, written once
+    u32 *d_slot_inv = nullptr;     // [N] inverse of slot_map (FinArgs::slot_inv)
+    GrowBuf<u64> fin_dev;          // [B] per item: pointer to its keystream (fused) or its slot of ks_tab as u32 (unfused) | [B][128] the items' words,
+                                   // zero padded | [B][N] the intermediate of the transform mod t (unfused: the plaintexts)
+    HostStage fin_host;            // [KsCache::MAX_SNAPSHOTS] flags of the key comparison, read back | the first two parts of fin_dev as they are uploaded
+    void *ev_cmp = nullptr;        // recorded behind the read-back of the flags
     size_t last_unique = 0;        // distinct counters of the last transciphering call: U, or B when it ran per item
     size_t last_evaluated = 0;     // keystream chains the last call ran (= last_unique unless kept keystreams were found), and
     size_t last_hits = 0;          // the counters it found a kept keystream for
@@ -278,4 +309,9 @@ void keyset_adopt_galois(hhe_keyset *ks, u32 elt, u64 *key);
 void keyset_new_serial(hhe_keyset *ks);  // the set's content changes: keystreams kept under its old serial go
 
 int lane_reserve(hhe_ctx *c, Lane &ln, size_t B);
+int fin_reserve(hhe_ctx *c, size_t B);  // fin_dev and fin_host for a transciphering call of B items
+inline size_t fin_tab_words(size_t B) { return (B + 1) & ~(size_t)1; }  // the table part of both, padded: what follows it is read and written 16 bytes at a time
+// The fused finishing kernels run where a test runs their geometry: every N up to 2^15.  At N = 2^16 the strided pass has 256 points, a
+// size no other N gives it, and the setup of a test there does not fit the suite's budget -- that size takes the separate launches.
+inline bool fin_fused_on(const hhe_ctx *c) { return c->fin_fused && c->logn <= 15; }
 void matrix_free(hhe_matrix *m);  // hhe_api.cpp: device memory of a handle and the handle

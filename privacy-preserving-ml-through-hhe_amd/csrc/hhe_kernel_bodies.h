@@ -164,6 +164,37 @@ template <bool STRIDED> HD void ntt_pair(const NttArgs &a, const NttGeom &g, int
     gi = ntt_gidx<STRIDED>(g, x, lane);
 }
 
+// The ops of the fused finishing pass (LOAD_ENCODE, STORE_ADD_PLAIN) are a compile-time matter on the device: the bodies below are
+// compiled into every transform kernel, and a runtime test would put the ops' code and registers into all of them.  FIN_ABSENT:
+// the launch never carries them (every kernel but the two of the finishing pass; the code is what it was without them);
+// FIN_PRESENT: the launch carries the op of its pass and nothing else (launch_pass selects by load_op / store_op);
+// FIN_RUNTIME: tested at run time -- the default, which only the tests-only emulator takes.
+enum { FIN_RUNTIME = -1, FIN_ABSENT = 0, FIN_PRESENT = 1 };
+template <int FIN> HD bool fin_op(int op, int which) { return FIN == FIN_PRESENT ? true : FIN == FIN_ABSENT ? false : op == which; }
+// a field of a table that is written once per context (FinArgs), read as mod_at reads ModDev: through the constant address space
+template <class T> HD T ld_const(const T *p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return *(const __attribute__((address_space(4))) T *)p;
+#else
+    return *p;
+#endif
+}
+// LOAD_ENCODE: coefficients (gi, gi + 1) of the slot image of one item (BatchEncoder::encode as a gather): word s of the
+// item where slot_inv[gi] = s < count, reduced as encode_scatter_body reduces it, else 0.  gi is even.
+HD U2 ld2_encode(const NttArgs &a, const u64 *vals, int gi)
+{
+    const u32 *sinv = ld_const(&a.fin->slot_inv);
+    const u32 cnt = (u32)ld_const(&a.fin->count);
+    const u64 t = ld_const(&a.fin->t);
+    const u64 w = *as_global(reinterpret_cast<const u64 *>(sinv + gi));  // both slot numbers with one 8-byte load
+    const u32 s0 = (u32)w, s1 = (u32)(w >> 32);
+    U2 v = {0, 0};
+    if (s0 < cnt) { const u64 x = vals[s0]; v.a = x >= t ? x % t : x; }
+    if (s1 < cnt) { const u64 x = vals[s1]; v.b = x >= t ? x % t : x; }
+    return v;
+}
+
 // load op of the first pass applied to one 16-byte pair
 template <bool FIRST> HD U2 ntt_load_op(const NttArgs &a, const ModDev &m, int poly, U2 v)
 {
@@ -193,31 +224,34 @@ template <bool FIRST> HD U2 ntt_load_op(const NttArgs &a, const ModDev &m, int p
 }
 // full tiles (every launch with N >= 4096): all NP global loads of a lane are issued before the first LDS write, so
 // a workgroup's load phase costs one memory round trip instead of NP
-template <bool STRIDED, bool INVERSE, int NP, int T = NTT_THREADS>
+template <bool STRIDED, bool INVERSE, int NP, int T = NTT_THREADS, int FIN = FIN_RUNTIME>
 HD void ntt_load_full(const NttArgs &a, const NttGeom &g, const ModDev &m, const u64 *src, int tid, u64 *lds)
 {
     constexpr bool FIRST = (STRIDED != INVERSE);
+    const bool enc = FIRST && INVERSE && fin_op<FIN>(a.load_op, LOAD_ENCODE);
     U2 v[NP];
     int l0[NP], l1[NP];
 #pragma unroll
     for (int k = 0; k < NP; k++) {
         int x, lane, gi;
         ntt_pair<STRIDED>(a, g, tid + k * T, x, lane, gi, l0[k], l1[k]);
-        if (FIRST && a.load_einv) v[k] = ld2_galois(src, (u32)gi, a.logn, a.load_einv, ntt_src_q(a, g));
+        if (enc) v[k] = ld2_encode(a, src, gi);
+        else if (FIRST && a.load_einv) v[k] = ld2_galois(src, (u32)gi, a.logn, a.load_einv, ntt_src_q(a, g));
         else v[k] = ld2_stream(src + gi);
     }
 #pragma unroll
     for (int k = 0; k < NP; k++) {
-        const U2 w = ntt_load_op<FIRST>(a, m, g.poly, v[k]);
+        const U2 w = enc ? v[k] : ntt_load_op<FIRST>(a, m, g.poly, v[k]);
         lds[l0[k]] = w.a;
         lds[l1[k]] = w.b;
     }
 }
 
-template <bool STRIDED, bool INVERSE, int CM = -1, int CC = -1, int T = NTT_THREADS>
+template <bool STRIDED, bool INVERSE, int CM = -1, int CC = -1, int T = NTT_THREADS, int FIN = FIN_RUNTIME>
 HD void ntt_body_load(const NttArgs &a, int bx, int by, int tid, u64 *lds)
 {
     constexpr bool FIRST = (STRIDED != INVERSE);
+    const bool enc = FIRST && INVERSE && fin_op<FIN>(a.load_op, LOAD_ENCODE);
     const NttGeom g = ntt_geom<CM, CC>(a, bx, by);
     const ModDev m = mod_at_u(a.mods, g.mod_index);
     const u64 *src;
@@ -226,13 +260,13 @@ HD void ntt_body_load(const NttArgs &a, int bx, int by, int tid, u64 *lds)
         src = a.src + (size_t)(g.poly / ip) * a.src_item_stride + (size_t)((g.poly % ip) / a.src_div) * g.n;
     } else src = a.dst + (size_t)g.poly * g.n;
     const int E2 = (g.M * g.C) >> 1;
-    if (E2 == 8 * T) { ntt_load_full<STRIDED, INVERSE, 8, T>(a, g, m, src, tid, lds); return; }
-    if (E2 == 4 * T) { ntt_load_full<STRIDED, INVERSE, 4, T>(a, g, m, src, tid, lds); return; }
+    if (E2 == 8 * T) { ntt_load_full<STRIDED, INVERSE, 8, T, FIN>(a, g, m, src, tid, lds); return; }
+    if (E2 == 4 * T) { ntt_load_full<STRIDED, INVERSE, 4, T, FIN>(a, g, m, src, tid, lds); return; }
     for (int e2 = tid; e2 < E2; e2 += T) {
         int x, lane, gi, l0, l1;
         ntt_pair<STRIDED>(a, g, e2, x, lane, gi, l0, l1);
-        const U2 raw = (FIRST && a.load_einv) ? ld2_galois(src, (u32)gi, a.logn, a.load_einv, ntt_src_q(a, g)) : ld2(src + gi);
-        const U2 v = ntt_load_op<FIRST>(a, m, g.poly, raw);
+        const U2 raw = enc ? ld2_encode(a, src, gi) : (FIRST && a.load_einv) ? ld2_galois(src, (u32)gi, a.logn, a.load_einv, ntt_src_q(a, g)) : ld2(src + gi);
+        const U2 v = enc ? raw : ntt_load_op<FIRST>(a, m, g.poly, raw);
         lds[l0] = v.a;
         lds[l1] = v.b;
     }
@@ -350,6 +384,92 @@ HD void ntt_body_round(const NttArgs &a, int bx, int by, int tid, u64 *lds, cons
 // put the loads of several pairs in flight before the first store (stores to acc / aux_out may alias them as far as the
 // compiler knows, which would otherwise serialise one memory round trip per pair).
 struct StorePre { U2 d, s, acc, gp; };
+// STORE_ADD_PLAIN has a prefetch struct of its own (the operand ciphertext's limbs; kept out of StorePre so that the kernels
+// without the op keep their registers): FIN_PRE limbs of both polynomials are fetched ahead, further limbs where they are used
+constexpr int FIN_PRE = 3;
+struct FinPre { U2 k0[FIN_PRE], k1[FIN_PRE]; gptr kp; };
+
+// add_plain with the BFV scaling variant (seal/util/scalingvariant.h:23), per coefficient, for add_plain_body and the
+// STORE_ADD_PLAIN epilogue (A = AddPlainArgs or FinArgs, read into registers by the caller):
+// fix = floor((m * (Q mod t) + (t+1)/2) / t), and the value added to limb j is (m * delta_j + fix) mod q_j
+struct PlainScale { u64 t, q_mod_t, thr, t_r_lo, t_r_hi; };
+HD u64 plain_fix(const PlainScale &a, u64 mval)
+{
+    u64 lo = mval * a.q_mod_t, hi = mulhi64(mval, a.q_mod_t);
+    lo += a.thr; hi += (lo < a.thr);
+    u64 fix = barrett_quo(lo, hi, a.t_r_lo, a.t_r_hi);
+    u64 rem = lo - fix * a.t;
+    while (rem >= a.t) { rem -= a.t; fix++; }
+    return fix;
+}
+HD u64 plain_scaled(u64 mval, u64 fix, u64 delta, const ModDev &m)
+{
+    Acc128 s = {0, 0};
+    acc_mac(s, mval, delta);
+    acc_add(s, fix);
+    return barrett128(s.lo, s.hi, m);
+}
+// STORE_ADD_PLAIN, limb j of one pair: out[b][0][j] = plaintext - c0, out[b][1][j] = -c1 (op_add_plain with negate_ct = 1, subtract = 0)
+HD void fin_store_limb(const NttArgs &a, const NttGeom &g, int gi, int j, const u64 *mv, const u64 *fix, U2 c0, U2 c1)
+{
+    const ModDev m = mod_at_u(a.mods, j);
+    const u64 d = ld_const(&a.fin->delta[j]);
+    u64 *o = a.aux_out + ((size_t)g.poly * 2 * a.L + j) * g.n + gi;
+    U2 o0, o1;
+    o0.a = addmod(negmod(c0.a, m.q), plain_scaled(mv[0], fix[0], d, m), m.q);
+    o0.b = addmod(negmod(c0.b, m.q), plain_scaled(mv[1], fix[1], d, m), m.q);
+    o1.a = negmod(c1.a, m.q);
+    o1.b = negmod(c1.b, m.q);
+    st2_stream(o, o0);
+    st2_stream(o + (size_t)a.L * g.n, o1);
+}
+HD FinPre fin_store_fetch(const NttArgs &a, const NttGeom &g, int gi)
+{
+    FinPre p = {};
+    p.kp = as_global(a.mul_ptrs ? a.mul_ptrs[g.poly] : a.mul + (size_t)g.poly * 2 * a.L * g.n);
+#pragma unroll
+    for (int j = 0; j < FIN_PRE; j++)
+        if (j < a.L) { p.k0[j] = ld2g(p.kp + (size_t)j * g.n + gi); p.k1[j] = ld2g(p.kp + (size_t)(a.L + j) * g.n + gi); }
+    return p;
+}
+// (v0, v1): the pair out of the last inverse pass mod t, before the N^-1 scaling
+HD void fin_store_pair(const NttArgs &a, const NttGeom &g, const ModDev &mt, int gi, u64 v0, u64 v1, const FinPre &pre)
+{
+    const u64 mv[2] = {csub(shoup_lazy_n(v0, mt.ninv, mt.ninv_s, mt.nq), mt.nq), csub(shoup_lazy_n(v1, mt.ninv, mt.ninv_s, mt.nq), mt.nq)};  // as STORE_PLAIN scales
+    const FinArgs *f = a.fin;
+    const PlainScale sc = {ld_const(&f->t), ld_const(&f->q_mod_t), ld_const(&f->thr), ld_const(&f->t_r_lo), ld_const(&f->t_r_hi)};
+    const u64 fix[2] = {plain_fix(sc, mv[0]), plain_fix(sc, mv[1])};
+#pragma unroll
+    for (int j = 0; j < FIN_PRE; j++)
+        if (j < a.L) fin_store_limb(a, g, gi, j, mv, fix, pre.k0[j], pre.k1[j]);
+    for (int j = FIN_PRE; j < a.L; j++)
+        fin_store_limb(a, g, gi, j, mv, fix, ld2g(pre.kp + (size_t)j * g.n + gi), ld2g(pre.kp + (size_t)(a.L + j) * g.n + gi));
+}
+
+// the whole store phase of a STORE_ADD_PLAIN tile (the last inverse pass mod t: strided); the plaintext coefficients stay in registers
+template <int T> HD void fin_body_store(const NttArgs &a, const NttGeom &g, const ModDev &mt, int tid, const u64 *lds)
+{
+#ifndef NTT_FIN_G
+#define NTT_FIN_G 2    // the operands of two pairs (2 x 2 x FIN_PRE 16-byte loads) are in flight before the first store
+#endif
+    constexpr int G = NTT_FIN_G;
+    const int E2 = (g.M * g.C) >> 1;  // a multiple of G * T for every tile of 2^10 points and more (N >= 1024); smaller tiles are guarded
+    for (int e0 = tid; e0 < E2; e0 += G * T) {
+        FinPre pre[G];
+        int gi[G], l0[G], l1[G];
+#pragma unroll
+        for (int k = 0; k < G; k++) {
+            if (e0 + k * T >= E2) continue;
+            int x, lane;
+            ntt_pair<true>(a, g, e0 + k * T, x, lane, gi[k], l0[k], l1[k]);
+            pre[k] = fin_store_fetch(a, g, gi[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < G; k++)
+            if (e0 + k * T < E2) fin_store_pair(a, g, mt, gi[k], lds[l0[k]], lds[l1[k]], pre[k]);
+    }
+}
+
 template <bool STRIDED, bool INVERSE>
 HD StorePre ntt_store_fetch(const NttArgs &a, const NttGeom &g, size_t pbase, int gi)
 {
@@ -494,13 +614,16 @@ HD void ntt_store_full(const NttArgs &a, const NttGeom &g, const ModDev &m, u64 
         for (int k = 0; k < G; k++) ntt_store_pair<STRIDED, INVERSE>(a, g, m, dst, pbase, gi[k], l0[k], l1[k], pre[k], lds);
     }
 }
-template <bool STRIDED, bool INVERSE, int CM = -1, int CC = -1, int T = NTT_THREADS>
+template <bool STRIDED, bool INVERSE, int CM = -1, int CC = -1, int T = NTT_THREADS, int FIN = FIN_RUNTIME>
 HD void ntt_body_store(const NttArgs &a, int bx, int by, int tid, const u64 *lds)
 {
     const NttGeom g = ntt_geom<CM, CC>(a, bx, by);
     const ModDev m = mod_at_u(a.mods, g.mod_index);
     u64 *dst = a.dst + (size_t)g.poly * g.n;
     const size_t pbase = (size_t)g.poly * g.n;
+    if constexpr (STRIDED && INVERSE && FIN != FIN_ABSENT) {
+        if (fin_op<FIN>(a.store_op, STORE_ADD_PLAIN)) { fin_body_store<T>(a, g, m, tid, lds); return; }
+    }
     const int E2 = (g.M * g.C) >> 1;
     if (E2 == 8 * T) { ntt_store_full<STRIDED, INVERSE, 8, T>(a, g, m, dst, pbase, tid, lds); return; }  // full tiles
     if (E2 == 4 * T) { ntt_store_full<STRIDED, INVERSE, 4, T>(a, g, m, dst, pbase, tid, lds); return; }
@@ -1318,18 +1441,10 @@ HD void add_plain_body(const AddPlainArgs &a, size_t gid)
     if (b >= (size_t)a.B) return;
     const u64 mval = a.plain_ptrs ? a.plain_ptrs[b][a.plain_shift + i] : a.plain[(a.plain_bcast ? 0 : b * n) + i];
     const size_t cb = a.ct_map ? a.ct_map[b] : b;  // the ciphertext operand of item b
-    // fix = floor((m * (Q mod t) + (t+1)/2) / t)
-    u64 lo = mval * a.q_mod_t, hi = mulhi64(mval, a.q_mod_t);
-    lo += a.thr; hi += (lo < a.thr);
-    u64 fix = barrett_quo(lo, hi, a.t_r_lo, a.t_r_hi);
-    u64 rem = lo - fix * a.t;
-    while (rem >= a.t) { rem -= a.t; fix++; }
+    const u64 fix = plain_fix(PlainScale{a.t, a.q_mod_t, a.thr, a.t_r_lo, a.t_r_hi}, mval);
     for (int j = 0; j < a.L; j++) {
         const ModDev m = mod_at(a.mods, j);
-        Acc128 s = {0, 0};
-        acc_mac(s, mval, a.delta[j]);
-        acc_add(s, fix);
-        const u64 sc = barrett128(s.lo, s.hi, m);
+        const u64 sc = plain_scaled(mval, fix, a.delta[j], m);
         const size_t o0 = ((b * 2 + 0) * a.L + j) * n + i, o1 = ((b * 2 + 1) * a.L + j) * n + i;
         u64 c0 = a.ct[((cb * 2 + 0) * a.L + j) * n + i], c1 = a.ct[((cb * 2 + 1) * a.L + j) * n + i];
         if (a.negate_ct) { c0 = negmod(c0, m.q); c1 = negmod(c1, m.q); }

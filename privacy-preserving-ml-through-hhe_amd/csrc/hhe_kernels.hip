@@ -43,6 +43,13 @@ rt_stream rt_stream_create()
     return (rt_stream)s;
 }
 void rt_stream_destroy(rt_stream s) { if (s) (void)hipStreamDestroy((hipStream_t)s); }
+void *rt_host_malloc(size_t bytes)
+{
+    void *p = nullptr;
+    if (rt_check(hipHostMalloc(&p, bytes ? bytes : 8, hipHostMallocDefault), "hipHostMalloc")) return nullptr;
+    return p;
+}
+void rt_host_free(void *p) { if (p) (void)hipHostFree(p); }
 void *rt_event_create()
 {
     hipEvent_t e = nullptr;
@@ -128,15 +135,16 @@ static __device__ __forceinline__ void ntt_tile_rounds(const NttArgs &a, int bx,
 }
 
 // one pass of one tile: load phase, register rounds through LDS, store phase
-template <int LOGM, bool STRIDED, bool INVERSE, bool FULL, int T = NTT_THREADS, int SCH = T, int TL = NttTile::LOG, bool TWL = false, bool PM = false>
+// FIN: the ops of the fused finishing pass are known absent (every kernel but its two) or known present (hhe_kernel_bodies.h, fin_op)
+template <int LOGM, bool STRIDED, bool INVERSE, bool FULL, int T = NTT_THREADS, int SCH = T, int TL = NttTile::LOG, bool TWL = false, bool PM = false, int FIN = FIN_ABSENT>
 static __device__ __forceinline__ void ntt_pass_tile(const NttArgs &a, int bx, int by, u64 *lds, u64 *twl = nullptr)
 {
     constexpr int CM = FULL ? LOGM : -1, CC = FULL ? TL - LOGM : -1;
     if constexpr (TWL) ks_row_twiddle_fill<CM, CC>(a, bx, by, INVERSE, threadIdx.x, twl);
-    ntt_body_load<STRIDED, INVERSE, CM, CC, T>(a, bx, by, threadIdx.x, lds);
+    ntt_body_load<STRIDED, INVERSE, CM, CC, T, FIN>(a, bx, by, threadIdx.x, lds);
     tile_sync<T>();
     ntt_tile_rounds<LOGM, STRIDED, INVERSE, CC, T, SCH, TWL, PM>(a, bx, by, lds, twl);
-    ntt_body_store<STRIDED, INVERSE, CM, CC, T>(a, bx, by, threadIdx.x, lds);
+    ntt_body_store<STRIDED, INVERSE, CM, CC, T, FIN>(a, bx, by, threadIdx.x, lds);
 }
 
 // FULL: the tile is 2^LOGM points x 2^(12 - LOGM) columns (every launch with N >= 4096) -> geometry folds into constants
@@ -145,6 +153,14 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) ntt_pass_kernel(NttArgs a)
 {
     __shared__ u64 lds[NttLds::ELEMS];
     ntt_pass_tile<LOGM, STRIDED, INVERSE, FULL>(a, NTT_BX(a), NTT_BY(a), lds);
+}
+// the two kernels of the fused finishing pass of a transciphering call, mod t: the row pass gathers its tile from the items' words
+// (LOAD_ENCODE), the strided pass ends in the add_plain epilogue (STORE_ADD_PLAIN)
+template <int LOGM, bool STRIDED, bool FULL>
+__global__ void __launch_bounds__(NTT_THREADS, 4) ntt_fin_kernel(NttArgs a)
+{
+    __shared__ u64 lds[NttLds::ELEMS];
+    ntt_pass_tile<LOGM, STRIDED, true, FULL, NTT_THREADS, NTT_THREADS, NttTile::LOG, false, false, FIN_PRESENT>(a, NTT_BX(a), NTT_BY(a), lds);
 }
 // Two independent batches of the same pass in ONE grid (polynomials [0, a1.count) use a1, the rest a2): a small batch
 // rides in the tail of a big one instead of paying a launch of its own that cannot fill the 1024 workgroup slots.
@@ -174,6 +190,25 @@ static void launch_pass(NttArgs a, int logm, int other, hipStream_t st)
     a.tiles_log = other - logc;
     dim3 grid((unsigned)(((size_t)a.count) << a.tiles_log));
     const bool full = logc == NttTile::LOG - logm;
+    if constexpr (INVERSE) {
+        // first (row) pass: its load op; second (strided) pass: its store op.  The other field may carry the op of the other pass.
+        const bool fin = STRIDED ? a.store_op == STORE_ADD_PLAIN : a.load_op == LOAD_ENCODE;
+        if (fin) {
+            // a ragged tile (N < 4096) has a pass of at most 2^6 points
+#define NTT_LAUNCH_FIN(M_, RAGGED_)                                                                                        \
+    case M_:                                                                                                               \
+        if (full) hipLaunchKernelGGL((ntt_fin_kernel<M_, STRIDED, true>), grid, dim3(NTT_THREADS), 0, st, a);              \
+        else hipLaunchKernelGGL((ntt_fin_kernel<RAGGED_, STRIDED, false>), grid, dim3(NTT_THREADS), 0, st, a);             \
+        break;
+            if (!full && logm > 6) { snprintf(g_rt_err, sizeof(g_rt_err), "unsupported ragged NTT pass size 2^%d", logm); return; }
+            switch (logm) {
+                NTT_LAUNCH_FIN(5, 5) NTT_LAUNCH_FIN(6, 6) NTT_LAUNCH_FIN(7, 6) NTT_LAUNCH_FIN(8, 6)
+            default: snprintf(g_rt_err, sizeof(g_rt_err), "unsupported NTT pass size 2^%d", logm); break;
+            }
+#undef NTT_LAUNCH_FIN
+            return;
+        }
+    }
 #define NTT_LAUNCH(M_)                                                                                                     \
     case M_:                                                                                                               \
         if (full) hipLaunchKernelGGL((ntt_pass_kernel<M_, STRIDED, INVERSE, true>), grid, dim3(NTT_THREADS), 0, st, a);    \

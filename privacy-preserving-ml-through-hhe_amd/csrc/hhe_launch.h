@@ -27,6 +27,11 @@ int rt_event_record(void *ev, rt_stream s);
 int rt_event_sync(void *ev);                         // host waits for the event
 int rt_stream_wait_event(rt_stream s, void *ev);
 const char *rt_last_error();
+// Page-locked host memory, optional at link time: a runtime without it (the tests-only emulator) leaves the symbols undefined, they
+// are then null and the host driver takes malloc / free (HostStage, hhe_internal.h).  A copy out of page-locked memory is
+// enqueued without the staging copy that holds the host for one out of pageable memory.
+void *rt_host_malloc(size_t bytes) __attribute__((weak));
+void rt_host_free(void *p) __attribute__((weak));
 
 // kernels (all asynchronous on `s`)
 void k_ntt(const NttArgs &a, bool inverse, rt_stream s);  // runs both passes; a.logm/logc ignored
