@@ -103,6 +103,18 @@ void op_finish_back(hhe_ctx *c, u64 *tmp, const u64 *ks, const u64 *const *ks_pt
     k_ntt_pass(a, true, true, c->w->stream);
 }
 
+// Both halves for B items in one launch with one workgroup per item (fin_item_for; fin_item_kernel, hhe_fin_bodies.h): the plaintext
+// stays in LDS.  The launch is k_ntt's with both ops set; the kernel does not touch `tmp`, the two-pass form of the same launch
+// (the tests-only emulator) goes through it.
+void op_finish_item(hhe_ctx *c, const u64 *vals, u64 *tmp, const u64 *ks, const u64 *const *ks_ptrs, u64 *out, size_t B)
+{
+    NttArgs a = ntt_args(c, vals, tmp, B, c->mod_t, 1);
+    a.load_op = LOAD_ENCODE; a.src_item_polys = 1; a.src_item_stride = PASTA_T;
+    a.store_op = STORE_ADD_PLAIN; a.mul = ks; a.mul_ptrs = ks_ptrs; a.aux_out = out; a.fin = c->d_fin;
+    k_ntt(a, true, c->w->stream);
+    ++c->fin_item_launches;
+}
+
 // plain [P][N] (coefficients mod t) -> lifted NTT form [P][L][N]   
 void op_lift_ntt(hhe_ctx *c, const u64 *plain, size_t P, u64 *out)
 {
@@ -1007,8 +1019,10 @@ static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64
     int rc;
     if ((rc = fin_reserve(c, B))) return rc;  // before anything reads the staging: growth replaces it
     const bool cache = c->dedup && c->ks_cache.enabled && !c->profile;
-    // 1. the key comparison
-    if (cache && (rc = ks_match_enqueue(c, enc_key))) return rc;
+    const bool item = c->dedup && fin_item_for(c, B);  // the finishing pass of a two-phase call is one launch, one workgroup per item
+    // 1. the key comparison.  Where the item kernel may be enqueued on a prediction (2b) the comparison goes right in front of it
+    const bool may_predict = cache && item && !c->ks_cache.snaps.empty();
+    if (cache && !may_predict && (rc = ks_match_enqueue(c, enc_key))) return rc;
     // 2. host preparation.  The distinct counters in order of first appearance; umap[b]: where item b's counter stands among them
     std::vector<u64> uniq;
     std::vector<u32> umap;
@@ -1038,11 +1052,35 @@ static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64
         if ((rc = ensure_block(c, counters[u], &tabs[u]))) return rc;
         if (use_bsgs && (rc = ensure_bsgs_tables(c, counters[u], tabs[u]))) return rc;
     }
+    // 2b. The item kernel has no half that runs ahead of the keystreams, so nothing would hide the wait for the comparison: predict
+    // its answer -- the snapshot used last -- and, if every counter of the call has a kept keystream under it, enqueue the whole
+    // finishing pass behind the comparison before waiting.  The probe touches no stamp.  A call the flags do not confirm goes on as
+    // it would have without the prediction and finishes over `out` again, behind the stale launch on the same stream; what that
+    // launch read are cache entries, which go only behind a wait for the context's streams.
+    u64 predicted = 0;
+    if (may_predict) {
+        const KsCache &kc = c->ks_cache;
+        size_t best = 0;
+        for (size_t i = 1; i < kc.snaps.size(); ++i)
+            if (kc.snaps[i].last_use > kc.snaps[best].last_use) best = i;
+        KsCache::Entry probe = kkey;
+        probe.snap = kc.snaps[best].id;
+        std::vector<const u64 *> kept(U);
+        bool all = true;
+        for (size_t u = 0; u < U && all; ++u) all = (kept[u] = kc.peek(counters[u], probe)) != nullptr;
+        if (all) {
+            for (size_t b = 0; b < B; ++b) h_tab[b] = (u64)kept[umap[b]];
+            rt_h2d(d_tab, h_tab, (fin_tab_words(B) + B * PASTA_T) * 8, main.stream);  // table and words: one block
+            predicted = probe.snap;
+        }
+        if ((rc = ks_match_enqueue(c, enc_key))) return rc;
+        if (predicted) op_finish_item(c, d_words, d_tmp, nullptr, (const u64 *const *)d_tab, out, B);
+    }
     // 3. the half of the finishing pass that does not depend on the keystreams
-    const ChunkPlan fin = plan_balanced(c, B);
-    if (dedup) {
+    const ChunkPlan fin = item ? ChunkPlan(B, B, 0) : plan_balanced(c, B);  // the item kernel takes the batch whole
+    if (dedup && !predicted) {
         rt_h2d(d_words, h_words, B * PASTA_T * 8, main.stream);
-        rc = run_chunks(c, fin, [&](Lane &, size_t, size_t b0, size_t bc) {
+        if (!item) rc = run_chunks(c, fin, [&](Lane &, size_t, size_t b0, size_t bc) {
             op_finish_front(c, d_words + b0 * PASTA_T, d_tmp + b0 * n, bc);
             return (int)HHE_OK;
         });
@@ -1109,7 +1147,8 @@ static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64
                 pend.cts.emplace_back(counters[eval[m]], copy);
             }
     // 6. res = Enc(c_b) - KS for every item (:161-169), after the join of the keystream chunks on the main stream
-    if (dedup) {
+    if (predicted && predicted == kkey.snap && !M) {}  // confirmed: the finishing pass is enqueued already
+    else if (dedup) {
         if (by_ptr)
             for (size_t b = 0; b < B; ++b) {
                 const size_t u = umap[b];
@@ -1118,7 +1157,9 @@ static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64
         else
             for (size_t b = 0; b < B; ++b) ((u32 *)h_tab)[b] = (u32)slot[umap[b]];
         rt_h2d(d_tab, h_tab, B * (by_ptr ? sizeof(u64) : sizeof(u32)), main.stream);
-        rc = run_chunks(c, fin, [&](Lane &, size_t, size_t b0, size_t bc) {
+        c->w = &main;
+        if (item) op_finish_item(c, d_words, d_tmp, ks, (const u64 *const *)d_tab, out, B);
+        else rc = run_chunks(c, fin, [&](Lane &, size_t, size_t b0, size_t bc) {
             op_finish_back(c, d_tmp + b0 * n, ks, by_ptr ? (const u64 *const *)d_tab + b0 : nullptr, by_ptr ? nullptr : (const u32 *)d_tab + b0, out + b0 * ctw, bc);
             return (int)HHE_OK;
         });

@@ -95,7 +95,15 @@ struct FinArgs {
     u64 t, q_mod_t, thr;       // as in AddPlainArgs
     u64 t_r_lo, t_r_hi;
     u64 delta[HHE_MAXL];
+    // one workgroup per item (fin_item_kernel, hhe_fin_bodies.h); null where the context is not eligible
+    const u32 *slot_map;       // [N]: coefficient of slot s
+    const u32 *itw;            // [N][2]: the inverse powers mod t in the order of ModDev::iw, each with floor(w * 2^32 / t)
 };
+
+// where fin_item_kernel runs: N u32 words fit the LDS of one workgroup (4 N <= 128 KiB) and the lazy range [0, 4t) of its 32-bit
+// butterflies fits a word
+constexpr int FIN_ITEM_MIN_LOGN = 10, FIN_ITEM_MAX_LOGN = 15;
+inline bool fin_item_ok(int logn, u64 t) { return logn >= FIN_ITEM_MIN_LOGN && logn <= FIN_ITEM_MAX_LOGN && t < ((u64)1 << 30); }
 
 // key-switch mod-down constants, passed by value to the kernels that finish a key switch
 struct KsConsts {

@@ -323,8 +323,18 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
     fa.slot_inv = c->d_slot_inv; fa.count = PASTA_T; fa.L = L;
     fa.t = ap.t; fa.q_mod_t = ap.q_mod_t; fa.thr = ap.thr; fa.t_r_lo = ap.t_r_lo; fa.t_r_hi = ap.t_r_hi;
     for (int j = 0; j < L; ++j) fa.delta[j] = ap.delta[j];
+    // ... and, for the one-workgroup form, the inverse powers mod t as 32-bit words with 32-bit Shoup quotients
+    std::vector<u32> itw;
+    if (fin_item_ok(logn, t)) {
+        const u64 *iw = host_tab.data() + (size_t)c->mod_t * 6 * n + 2 * n;
+        itw.resize(2 * n);
+        for (size_t k = 0; k < n; ++k) { itw[2 * k] = (u32)iw[2 * k]; itw[2 * k + 1] = (u32)((iw[2 * k] << 32) / t); }
+        c->d_fin_itw = (u32 *)rt_malloc(8 * n);
+        fa.slot_map = c->d_slot_map; fa.itw = c->d_fin_itw;
+    }
 
     if (!c->d_tables || !c->d_mods || !c->d_slot_map || !c->d_behz || !c->d_slot_inv || !c->d_fin ||
+        (!itw.empty() && (!c->d_fin_itw || rt_h2d(c->d_fin_itw, itw.data(), 8 * n, nullptr))) ||
         rt_h2d(c->d_slot_inv, slot_inv.data(), 4 * n, nullptr) || rt_h2d(c->d_fin, &fa, sizeof(fa), nullptr) ||
         rt_h2d(c->d_tables, host_tab.data(), host_tab.size() * 8, nullptr) ||
         rt_h2d(c->d_mods, mods.data(), sizeof(ModDev) * c->nmod, nullptr) ||
@@ -347,6 +357,7 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
     if (const char *e = getenv("HHE_DEDUP")) c->dedup = atoi(e) != 0;
     if (const char *e = getenv("HHE_KS_CACHE")) c->ks_cache.enabled = atoi(e) != 0;
     if (const char *e = getenv("HHE_FIN_FUSED")) c->fin_fused = atoi(e) != 0;
+    if (const char *e = getenv("HHE_FIN_ITEM")) c->fin_item = atoi(e) != 0;
     if (const char *e = getenv("HHE_KS_CACHE_MB")) c->ks_cache.budget = (size_t)(std::max(0.0, atof(e)) * (double)(1 << 20));
     c->ks_cache.entry_bytes = c->ct_words() * 8;
     if (const char *e = getenv("HHE_SHARED_L0_MB")) c->l0_budget = (size_t)(std::max(0.0, atof(e)) * (double)(1 << 20));
@@ -483,7 +494,7 @@ extern "C" void hhe_ctx_destroy(hhe_ctx *c)
     c->d_blocks.release(); c->d_flags.release();
     c->l0_tab.release(); c->l0_ptrs.release();
     c->ks_tab.release(); c->ks_flags.release(); c->fin_dev.release(); c->fin_host.release();
-    rt_free(c->d_tables); rt_free(c->d_mods); rt_free(c->d_behz); rt_free(c->d_slot_map); rt_free(c->d_slot_inv); rt_free(c->d_fin);
+    rt_free(c->d_tables); rt_free(c->d_mods); rt_free(c->d_behz); rt_free(c->d_slot_map); rt_free(c->d_slot_inv); rt_free(c->d_fin); rt_free(c->d_fin_itw);
     delete c;
 }
 
@@ -579,6 +590,9 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "transcipher_unique") return c->last_unique; // distinct counters of the last transciphering call (its item count when it ran per item)
     if (w == "transcipher_evaluated") return c->last_evaluated;  // keystream chains the last call ran: the counters it found no kept keystream for
     if (w == "fin_fused") return fin_fused_on(c) ? 1 : 0;        // the finishing pass of a transciphering call runs as two fused kernels (HHE_FIN_FUSED)
+    if (w == "fin_item") return fin_item_on(c) ? 1 : 0;          // ... or as one kernel with one workgroup per item, from query("fin_item_min") items on (HHE_FIN_ITEM)
+    if (w == "fin_item_min") return fin_item_on(c) ? (c->fin_item > 0 ? 1 : (u64)c->fin_item_min) : 0;
+    if (w == "fin_item_launches") return c->fin_item_launches;
     if (w == "ks_cache") return c->ks_cache.enabled ? 1 : 0;      // keystreams are kept across calls (HHE_KS_CACHE)
     if (w == "ks_cache_hits") return c->last_hits;                // counters of the last call served from a kept keystream
     if (w == "ks_cache_entries") return c->ks_cache.entries();

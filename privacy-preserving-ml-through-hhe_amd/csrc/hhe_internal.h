@@ -193,6 +193,12 @@ struct hhe_ctx {
     int fin_fused = 1;             // two kernels (LOAD_ENCODE row pass, STORE_ADD_PLAIN strided pass) instead of clear + scatter + transform + add_plain
                                    // (HHE_FIN_FUSED; 0: launch for launch).  Off where no test runs the fused kernels' geometry (N = 2^16: fin_fused_ok)
     FinArgs *d_fin = nullptr;      // the fused kernels' constants, written once
+    int fin_item = -1;             // the whole finishing pass of an item in one workgroup, its plaintext kept in LDS (fin_item_kernel; HHE_FIN_ITEM): 0 never,
+                                   // 1 whenever the context is eligible (fin_item_on), -1 (unset) from fin_item_min items on
+    size_t fin_item_min = 64;      // an item occupies one CU whatever the batch: a small call is faster spread over the tiles of the two-pass kernels (measured: slower up to 32 items, level at 48, faster from 64)
+                                   // (DESIGN.md "Finishing pass in one workgroup")
+    u32 *d_fin_itw = nullptr;      // [N][2] u32 inverse twiddles mod t (FinArgs::itw); null where t needs more than 30 bits or N > 2^15
+    u64 fin_item_launches = 0;     // launches of fin_item_kernel (hhe_ctx_query("fin_item_launches"))
     u32 *d_slot_inv = nullptr;     // [N] inverse of slot_map (FinArgs::slot_inv)
     GrowBuf<u64> fin_dev;          // [B] per item: pointer to its keystream (fused) or its slot of ks_tab as u32 (unfused) | [B][128] the items' words,
                                    // zero padded | [B][N] the intermediate of the transform mod t (unfused: the plaintexts)
@@ -314,4 +320,7 @@ inline size_t fin_tab_words(size_t B) { return (B + 1) & ~(size_t)1; }  // the t
 // The fused finishing kernels run where a test runs their geometry: every N up to 2^15.  At N = 2^16 the strided pass has 256 points, a
 // size no other N gives it, and the setup of a test there does not fit the suite's budget -- that size takes the separate launches.
 inline bool fin_fused_on(const hhe_ctx *c) { return c->fin_fused && c->logn <= 15; }
+// ... and the one-workgroup form of them where the transform mod t fits 32-bit words and N words fit LDS (hhe_fin_bodies.h)
+inline bool fin_item_on(const hhe_ctx *c) { return c->fin_item != 0 && fin_fused_on(c) && c->d_fin_itw != nullptr; }
+inline bool fin_item_for(const hhe_ctx *c, size_t B) { return fin_item_on(c) && (c->fin_item > 0 || B >= c->fin_item_min); }
 void matrix_free(hhe_matrix *m);  // hhe_api.cpp: device memory of a handle and the handle

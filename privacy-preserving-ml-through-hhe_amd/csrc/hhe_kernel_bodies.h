@@ -432,10 +432,9 @@ HD FinPre fin_store_fetch(const NttArgs &a, const NttGeom &g, int gi)
         if (j < a.L) { p.k0[j] = ld2g(p.kp + (size_t)j * g.n + gi); p.k1[j] = ld2g(p.kp + (size_t)(a.L + j) * g.n + gi); }
     return p;
 }
-// (v0, v1): the pair out of the last inverse pass mod t, before the N^-1 scaling
-HD void fin_store_pair(const NttArgs &a, const NttGeom &g, const ModDev &mt, int gi, u64 v0, u64 v1, const FinPre &pre)
+// mv: the pair of plaintext coefficients, fully reduced mod t
+HD void fin_store_vals(const NttArgs &a, const NttGeom &g, int gi, const u64 *mv, const FinPre &pre)
 {
-    const u64 mv[2] = {csub(shoup_lazy_n(v0, mt.ninv, mt.ninv_s, mt.nq), mt.nq), csub(shoup_lazy_n(v1, mt.ninv, mt.ninv_s, mt.nq), mt.nq)};  // as STORE_PLAIN scales
     const FinArgs *f = a.fin;
     const PlainScale sc = {ld_const(&f->t), ld_const(&f->q_mod_t), ld_const(&f->thr), ld_const(&f->t_r_lo), ld_const(&f->t_r_hi)};
     const u64 fix[2] = {plain_fix(sc, mv[0]), plain_fix(sc, mv[1])};
@@ -444,6 +443,12 @@ HD void fin_store_pair(const NttArgs &a, const NttGeom &g, const ModDev &mt, int
         if (j < a.L) fin_store_limb(a, g, gi, j, mv, fix, pre.k0[j], pre.k1[j]);
     for (int j = FIN_PRE; j < a.L; j++)
         fin_store_limb(a, g, gi, j, mv, fix, ld2g(pre.kp + (size_t)j * g.n + gi), ld2g(pre.kp + (size_t)(a.L + j) * g.n + gi));
+}
+// (v0, v1): the pair out of the last inverse pass mod t, before the N^-1 scaling
+HD void fin_store_pair(const NttArgs &a, const NttGeom &g, const ModDev &mt, int gi, u64 v0, u64 v1, const FinPre &pre)
+{
+    const u64 mv[2] = {csub(shoup_lazy_n(v0, mt.ninv, mt.ninv_s, mt.nq), mt.nq), csub(shoup_lazy_n(v1, mt.ninv, mt.ninv_s, mt.nq), mt.nq)};  // as STORE_PLAIN scales
+    fin_store_vals(a, g, gi, mv, pre);
 }
 
 // the whole store phase of a STORE_ADD_PLAIN tile (the last inverse pass mod t: strided); the plaintext coefficients stay in registers

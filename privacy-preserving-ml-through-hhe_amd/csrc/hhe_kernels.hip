@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "hhe_kernel_bodies.h"
+#include "hhe_fin_bodies.h"
 #include "hhe_launch.h"
 
 static thread_local char g_rt_err[256] = "";
@@ -162,6 +163,43 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) ntt_fin_kernel(NttArgs a)
     __shared__ u64 lds[NttLds::ELEMS];
     ntt_pass_tile<LOGM, STRIDED, true, FULL, NTT_THREADS, NTT_THREADS, NttTile::LOG, false, false, FIN_PRESENT>(a, NTT_BX(a), NTT_BY(a), lds);
 }
+// the finishing pass with one workgroup per item (hhe_fin_bodies.h): encode into LDS, the whole inverse transform mod t in 32-bit
+// words there, add_plain epilogue.  LDS is 4 N bytes, so N = 2^15 takes one CU per item and N = 2^14 places two items on a CU.
+template <int LOGN, int R>
+static __device__ __forceinline__ void fin_item_rounds(const NttArgs &a, u32 *lds)
+{
+    if constexpr (R < FinItemSched<LOGN>::R) {
+        fin_item_round<LOGN, FinItemSched<LOGN>::s0(R), FinItemSched<LOGN>::rho(R), FIN_ITEM_THREADS>(a, threadIdx.x, lds);
+        __syncthreads();
+        fin_item_rounds<LOGN, R + 1>(a, lds);
+    }
+}
+template <int LOGN>
+__global__ void __launch_bounds__(FIN_ITEM_THREADS) fin_item_kernel(NttArgs a)
+{
+    __shared__ __attribute__((aligned(16))) u32 lds[1 << LOGN];
+    const int item = blockIdx.x;
+    fin_item_clear<FIN_ITEM_THREADS>(a, threadIdx.x, lds);
+    __syncthreads();
+    fin_item_encode<FIN_ITEM_THREADS>(a, item, threadIdx.x, lds);
+    __syncthreads();
+    fin_item_rounds<LOGN, 0>(a, lds);
+    fin_item_store<FIN_ITEM_THREADS>(a, item, threadIdx.x, lds);
+}
+static void launch_fin_item(const NttArgs &a, hipStream_t st)
+{
+    const dim3 grid((unsigned)a.count), block(FIN_ITEM_THREADS);
+    if (!a.fin) { snprintf(g_rt_err, sizeof(g_rt_err), "finishing pass per item: no constants"); return; }
+    switch (a.logn) {
+    case 10: hipLaunchKernelGGL(fin_item_kernel<10>, grid, block, 0, st, a); break;
+    case 11: hipLaunchKernelGGL(fin_item_kernel<11>, grid, block, 0, st, a); break;
+    case 12: hipLaunchKernelGGL(fin_item_kernel<12>, grid, block, 0, st, a); break;
+    case 13: hipLaunchKernelGGL(fin_item_kernel<13>, grid, block, 0, st, a); break;
+    case 14: hipLaunchKernelGGL(fin_item_kernel<14>, grid, block, 0, st, a); break;
+    case 15: hipLaunchKernelGGL(fin_item_kernel<15>, grid, block, 0, st, a); break;
+    default: snprintf(g_rt_err, sizeof(g_rt_err), "finishing pass per item: unsupported N = 2^%d", a.logn); break;
+    }
+}
 // Two independent batches of the same pass in ONE grid (polynomials [0, a1.count) use a1, the rest a2): a small batch
 // rides in the tail of a big one instead of paying a launch of its own that cannot fill the 1024 workgroup slots.
 // The argument block is selected per workgroup from the kernarg segment (uniform), the code is shared.
@@ -226,6 +264,8 @@ void k_ntt(const NttArgs &a, bool inverse, rt_stream s)
     int n1, n2;
     ntt_split(a.logn, n1, n2);
     hipStream_t st = (hipStream_t)s;
+    // both ops of the finishing pass in one launch: one workgroup per item; a.dst is not touched
+    if (inverse && a.load_op == LOAD_ENCODE && a.store_op == STORE_ADD_PLAIN) { launch_fin_item(a, st); return; }
     if (!inverse) {
         launch_pass<true, false>(a, n1, n2, st);   // strided pass: global stages 0..n1-1
         launch_pass<false, false>(a, n2, n1, st);  // row pass: stages n1..n-1

@@ -55,6 +55,15 @@ struct KsCache {
             if (e.same_key(key)) { e.last_use = now; return e.ct; }
         return nullptr;
     }
+    // the same without touching the hit: a call that predicts its key looks before it knows (hhe_api.cpp, transcipher_enqueue)
+    const u64 *peek(u64 counter, const Entry &key) const
+    {
+        auto it = by_counter.find(counter);
+        if (it == by_counter.end()) return nullptr;
+        for (const Entry &e : it->second)
+            if (e.same_key(key)) return e.ct;
+        return nullptr;
+    }
     // takes `words` (a device copy of a key ciphertext no resident snapshot equals); the least recently used snapshot makes room and
     // takes its entries with it.  Returns the new snapshot's number
     u64 add_snapshot(hhe_ctx *c, u64 *words, u64 now)
