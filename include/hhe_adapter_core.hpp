@@ -471,13 +471,52 @@ public:
         download(ct.u64(), 1, 2, dst);
     }
 
-    // analyst end: Decryptor::decrypt + BatchEncoder::decode; sk: [K][N] NTT form; vals: N slot values < t
-    void decrypt(const uint64_t *sk, const uint64_t *ct, uint64_t *vals)
+    // analyst end: Decryptor::decrypt + BatchEncoder::decode; sk: [K][N] NTT form; vals: N slot values < t.  limbs: the level of the
+    // ciphertext ([2][limbs][N] words; 0 = the data level)
+    void decrypt(const uint64_t *sk, const uint64_t *ct, uint64_t *vals, size_t limbs = 0)
     {
-        DevBuf c(ct_words() * 8), v(n_ * 8);
-        upload(c.u64(), ct);
-        check(hhe_decrypt(h(), sk, c.u64(), 1, v.u64()));
+        const size_t l = limbs_or_data(limbs), words = 2 * l * n_;
+        DevBuf c(words * 8), v(n_ * 8);
+        check(hhe_copy_h2d(h(), c.p, ct, words * 8));
+        check(hhe_decrypt_level(h(), sk, c.u64(), (int)l, 1, v.u64()));
         check(hhe_copy_d2h(h(), vals, v.p, n_ * 8));
+    }
+
+    // ---- levels (SEALZpCipher::get_cipher_size(ct, mod_switch, levels_from_last), SEAL_Cipher.cpp:363-378).  A ciphertext below the
+    // data level is a finished result: it can be switched further, measured and decrypted; every evaluation call refuses it.
+    size_t limbs_or_data(size_t limbs) const
+    {
+        if (limbs > L_) throw std::invalid_argument("encrypted is not valid for encryption parameters");
+        return limbs ? limbs : L_;
+    }
+    // limbs of the level `levels_from_last` steps above last_context_data(); the reference walks prev_context_data() off the chain
+    // (a null pointer) where this throws
+    size_t level_limbs(size_t levels_from_last) const
+    {
+        if (levels_from_last >= L_) throw std::invalid_argument("levels_from_last is beyond the first level of the modulus switching chain");
+        return 1 + levels_from_last;
+    }
+    // Evaluator::mod_switch_to_inplace: words [size][limbs_in][N] -> the sink's [size][limbs_out][N]; a switch to a higher level throws
+    // std::invalid_argument, as SEAL does
+    template <class Sink> void mod_switch(const uint64_t *words, size_t size, size_t limbs_in, size_t limbs_out, Sink dst)
+    {
+        limbs_or_data(limbs_in);
+        const size_t win = size * limbs_in * n_, wout = size * limbs_out * n_;
+        DevBuf a(win * 8), o((wout ? wout : 1) * 8);
+        check(hhe_copy_h2d(h(), a.p, words, win * 8));
+        check(hhe_mod_switch(h(), a.u64(), (int)size, 1, (int)limbs_in, (int)limbs_out, o.u64()));
+        check(hhe_copy_d2h(h(), dst(0), o.p, wout * 8));
+    }
+    // bytes of Ciphertext::save(stream, compr_mode_type::none) at that level.  The reference's ct.save(s) takes SEAL's default mode
+    // (zstd where SEAL was built with it): its figure is the compressed size, this one the uncompressed size it is bounded by
+    size_t saved_size(size_t size, size_t limbs)
+    {
+        static const uint8_t id[32] = {};
+        static const uint64_t none = 0;
+        size_t need = 0;
+        const int rc = hhe_seal_save_ciphertext_level(h(), &none, size, (int)limbs_or_data(limbs), id, nullptr, 0, &need);  // sizes only: nothing is read
+        if (rc != HHE_ERR_CAPACITY) check(rc);
+        return need;
     }
 
 private:

@@ -265,6 +265,22 @@ int hhe_pasta3_plain_crypt(hhe_ctx *c, const uint64_t *key_hptr, const uint64_t 
  * ciphertexts [B][2][L][N] -> slot values [B][N] (unsigned, < t; the signed view of decode_int64 is v > t/2 ? v - t : v).
  * sk_hptr: the secret key polynomial at the key level, NTT form [K][N] (SecretKey::data().data()). */
 int hhe_decrypt(hhe_ctx *c, const uint64_t *sk_hptr, const uint64_t *ct_dptr, size_t B, uint64_t *vals_dptr);
+/* hhe_decrypt for ciphertexts [B][2][limbs][N]; sk_hptr stays [K][N], its first `limbs` rows are used
+ * (Decryptor::decrypt on a ciphertext whose parms_id names a lower level of the modulus switching chain, seal/decryptor.h:70;
+ * 1 <= limbs <= L, hhe_decrypt is limbs = L).  The values are right exactly while the ciphertext's noise budget at that level
+ * (Decryptor::invariant_noise_budget, seal/decryptor.h:103) is positive: a switch that drops too many primes leaves noise above
+ * Q_level / 2t and the slots come back wrong, without an error, as in SEAL. */
+int hhe_decrypt_level(hhe_ctx *c, const uint64_t *sk_hptr, const uint64_t *ct_dptr, int limbs, size_t B, uint64_t *vals_dptr);
+
+/* ---- levels: modulus switching of finished results.  Evaluation (add, multiply, rotate, key switch, transciphering, affine
+ *      layers, FC rows) stays at the data level; a lower-level ciphertext can be switched further, saved, loaded and decrypted. ---- */
+/* Evaluator::mod_switch_to_inplace (seal/evaluator.h:426) on B coefficient-form ciphertexts:
+ * ct [B][size][limbs_in][N] under q_0..q_{limbs_in-1} -> out [B][size][limbs_out][N], dense.
+ * Every dropped prime q_m rounds on its own, floor((x + floor(q_m/2)) / q_m), as the chain of mod_switch_to_next does.  size is 2 or
+ * 3, 1 <= limbs_out <= limbs_in <= L (limbs_out == limbs_in copies), out must not overlap ct: a violation returns HHE_ERR_INVALID
+ * with out untouched (SEAL throws std::invalid_argument on a switch to a higher level).  One kernel launch per chunk of 2^30
+ * coefficients, i.e. one per call for any batch a service sends (hhe_ctx_query("mod_switch_launches") counts them).  Synchronous. */
+int hhe_mod_switch(hhe_ctx *c, const uint64_t *ct_dptr, int size, size_t B, int limbs_in, int limbs_out, uint64_t *out_dptr);
 
 /* ---- key generation and encryption on the device, from a seed.
  *      THE SEED IS THE ONLY ENTROPY.  seed_hptr is 32 bytes on the host; every random word is SHAKE128 of the seed and a position
@@ -325,6 +341,14 @@ int hhe_seal_load_ciphertext(hhe_ctx *c, const uint8_t *bytes_hptr, size_t nbyte
  * too small).  parms_id: 32 bytes taken from a loaded object of the same context (SEAL hashes the parameters into it) */
 int hhe_seal_save_ciphertext(hhe_ctx *c, const uint64_t *ct_dptr, size_t ct_size, const uint8_t *parms_id, uint8_t *out_hptr,
                              size_t out_cap, size_t *written);
+/* Ciphertext::save / Ciphertext::load of a ciphertext at any level of the chain: coeff_modulus_size = limbs, 1 <= limbs <= L, data
+ * [size][limbs][N] with every word checked against its prime q_j, j < limbs; the bounds and the all-or-nothing rule of the two entries
+ * above.  parms_id is carried, not computed: the caller passes the id of the target level (ContextData::parms_id of the level reached
+ * by walking last_context_data() -> prev_context_data()); the loader returns the stream's id and its limb count in *limbs. */
+int hhe_seal_save_ciphertext_level(hhe_ctx *c, const uint64_t *ct_dptr, size_t ct_size, int limbs, const uint8_t *parms_id,
+                                   uint8_t *out_hptr, size_t out_cap, size_t *written);
+int hhe_seal_load_ciphertext_level(hhe_ctx *c, const uint8_t *bytes_hptr, size_t nbytes, uint64_t *out_dptr, size_t out_cap_words,
+                                   size_t *ct_size, int *limbs, uint8_t *parms_id_out, size_t *consumed);
 /* RelinKeys::load / GaloisKeys::load: every key of the object is uploaded (relin key(2) into `slot`; Galois keys by element
  * 2*index+1, seal/galoiskeys.h:48-74) */
 int hhe_seal_load_relin_keys(hhe_ctx *c, int slot, const uint8_t *bytes_hptr, size_t nbytes, size_t *consumed);

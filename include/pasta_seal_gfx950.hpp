@@ -32,10 +32,12 @@ struct ZpCipherParams {  // src/pasta/Cipher.h:14-18
 };
 constexpr ZpCipherParams PASTA_PARAMS = {256, 128, 128};  // src/pasta/pasta_3_plain.h:15
 
-// seal::Ciphertext stand-in: data() words, [size][L][N], data level, non-NTT form
+// seal::Ciphertext stand-in: data() words, [size][L][N], data level, non-NTT form.  limbs: coeff_modulus_size() of a ciphertext that
+// get_cipher_size switched down ([size][limbs][N]); 0 = the data level, which is all that evaluation accepts
 struct Ciphertext {
     std::vector<uint64_t> words;
     size_t size = 0;
+    size_t limbs = 0;
 };
 // one KSwitchKeys::data()[index] entry: [L digits][2][K][N], NTT form
 typedef std::vector<uint64_t> KSwitchKey;
@@ -66,13 +68,14 @@ inline hhe::GaloisWords words(const GaloisKeys &gk)
 }
 inline const uint64_t *words(const HheContext &ctx, const Ciphertext &ct, size_t size = 2)
 {
-    if (ct.words.size() != ctx.ct_words(size)) throw std::invalid_argument("encrypted is not valid for encryption parameters");
+    if (ct.words.size() != ctx.ct_words(size) || (ct.limbs && ct.limbs != ctx.data_limbs()))
+        throw std::invalid_argument("encrypted is not valid for encryption parameters");
     return ct.words.data();
 }
 // output sinks: item i lands in a ciphertext of `size` polynomials
 inline auto into(const HheContext &ctx, Ciphertext &ct, size_t size = 2)
 {
-    return [&ctx, &ct, size](size_t) { ct.words.resize(ctx.ct_words(size)); ct.size = size; return ct.words.data(); };
+    return [&ctx, &ct, size](size_t) { ct.words.resize(ctx.ct_words(size)); ct.size = size; ct.limbs = 0; return ct.words.data(); };
 }
 inline auto into(const HheContext &ctx, std::vector<Ciphertext> &cts) { return [&ctx, &cts](size_t i) { return into(ctx, cts[i])(0); }; }
 }  // namespace detail
@@ -97,6 +100,26 @@ public:
     size_t get_key_size() const { return params.key_size; }
     size_t get_plain_size() const { return params.plain_size; }
     size_t get_cipher_size() const { return params.cipher_size; }
+    // SEALZpCipher::get_cipher_size(ct, mod_switch, levels_from_last) (SEAL_Cipher.cpp:363-378): with mod_switch, ct is switched in
+    // place (Evaluator::mod_switch_to_inplace) to the level `levels_from_last` steps above last_context_data(), i.e. to
+    // 1 + levels_from_last limbs; returns the byte size of the saved object.  Saves here are UNCOMPRESSED (compr_mode_type::none)
+    // where the reference's ct.save(s) takes SEAL's default, zstd: the figure is the bound of the reference's.  levels_from_last >= L
+    // throws std::invalid_argument (the reference walks off the chain there), and so does a switch to a higher level, as in SEAL.
+    size_t get_cipher_size(Ciphertext &ct, bool mod_switch = false, size_t levels_from_last = 0)
+    {
+        const size_t cur = context->limbs_or_data(ct.limbs);
+        if (ct.size < 2 || ct.words.size() != ct.size * cur * context->poly_modulus_degree())
+            throw std::invalid_argument("encrypted is not valid for encryption parameters");
+        if (mod_switch) {
+            const size_t target = context->level_limbs(levels_from_last);
+            context->mod_switch(ct.words.data(), ct.size, cur, target, [&](size_t) {
+                ct.words.resize(ct.size * target * context->poly_modulus_degree());
+                ct.limbs = target;
+                return ct.words.data();
+            });
+        }
+        return context->saved_size(ct.size, ct.limbs);
+    }
     virtual std::string get_cipher_name() const = 0;
     virtual std::vector<Ciphertext> HE_decrypt(std::vector<uint64_t> &ciphertext, bool batch_encoder = false) = 0;
     virtual void add_gk_indices() = 0;
@@ -313,11 +336,11 @@ namespace sealhelper {
 inline std::vector<int64_t> decrypting(const pasta::Ciphertext &enc_input, const pasta::SecretKey &he_sk, pasta::HheContext &ctx,
                                        size_t size)
 {
-    const size_t w = ctx.ct_words(), n = ctx.poly_modulus_degree();
+    const size_t n = ctx.poly_modulus_degree(), w = 2 * ctx.limbs_or_data(enc_input.limbs) * n;  // a switched-down result decrypts at its level
     if (enc_input.words.size() != w || he_sk.words.size() < ctx.data_limbs() * n || size > n)
         throw std::invalid_argument("decrypting: ciphertext / secret key do not match the context");
     std::vector<uint64_t> u(n);
-    ctx.decrypt(he_sk.words.data(), enc_input.words.data(), u.data());
+    ctx.decrypt(he_sk.words.data(), enc_input.words.data(), u.data(), enc_input.limbs);
     const uint64_t t = ctx.plain_modulus(), half = (t + 1) >> 1;
     std::vector<int64_t> out(size);
     for (size_t i = 0; i < size; i++) out[i] = u[i] > half ? (int64_t)u[i] - (int64_t)t : (int64_t)u[i];

@@ -86,6 +86,23 @@ public:
             throw std::invalid_argument("encrypted is not valid for encryption parameters");
         return ct.data();
     }
+    // a coefficient-form ciphertext at any level of the modulus switching chain (get_cipher_size): its words, [size][coeff_modulus_size][N]
+    const std::uint64_t *level_words(const seal::Ciphertext &ct) const
+    {
+        if (ct.is_ntt_form() || ct.poly_modulus_degree() != poly_modulus_degree() || ct.size() < 2) throw std::invalid_argument("encrypted is not valid for encryption parameters");
+        limbs_or_data(ct.coeff_modulus_size());
+        return ct.data();
+    }
+    // ... and the sink that resizes the destination at the level `id` names
+    static auto into_level(const seal::SEALContext &context, seal::Ciphertext &ct, seal::parms_id_type id, std::size_t size)
+    {
+        return [&context, &ct, id, size](std::size_t) {
+            ct.resize(context, id, size);
+            ct.is_ntt_form() = false;
+            ct.scale() = 1.0;
+            return ct.data();
+        };
+    }
     std::vector<const std::uint64_t *> words(const std::vector<seal::Ciphertext> &cts) const
     {
         std::vector<const std::uint64_t *> p;
@@ -213,6 +230,22 @@ public:
     size_t get_key_size() const { return params.key_size; }
     size_t get_plain_size() const { return params.plain_size; }
     size_t get_cipher_size() const { return params.cipher_size; }
+    // SEALZpCipher::get_cipher_size(ct, mod_switch, levels_from_last) (SEAL_Cipher.cpp:363-378): the switch runs on the device
+    // (hhe_mod_switch = Evaluator::mod_switch_to_inplace) and the destination takes the parms_id found by walking
+    // last_context_data() -> prev_context_data(), as the reference walks.  The size returned is that of an UNCOMPRESSED save
+    // (compr_mode_type::none); the reference's ct.save(s) takes SEAL's default, zstd.  levels_from_last beyond the chain throws
+    // std::invalid_argument (the reference dereferences a null pointer there).
+    size_t get_cipher_size(seal::Ciphertext &ct, bool mod_switch = false, size_t levels_from_last = 0)
+    {
+        if (mod_switch) {
+            const std::size_t target = device->level_limbs(levels_from_last);
+            auto c = context->last_context_data();
+            for (uint64_t _ = 0; _ < levels_from_last; _++) c = c->prev_context_data();
+            device->mod_switch(device->level_words(ct), ct.size(), ct.coeff_modulus_size(), target,
+                               gfx950::DeviceContext::into_level(*context, ct, c->parms_id(), ct.size()));
+        } else device->level_words(ct);
+        return device->saved_size(ct.size(), ct.coeff_modulus_size());
+    }
 
     void add_some_gk_indices(std::vector<int> &gk_ind)
     {

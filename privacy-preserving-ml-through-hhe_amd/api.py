@@ -42,13 +42,15 @@ _SYMBOLS = [
     "hhe_pasta3_clear_keystream_cache",
     "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin", "hhe_keyset_generate_galois",
     "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
+    "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level",
 ]
 
 
 # exports a library built from an earlier commit may lack (HHE_LIB selects such a build for A/B runs): bound when present, and the method
 # that needs one raises when it is not
 _OPTIONAL = {"hhe_pasta3_clear_keystream_cache", "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin",
-             "hhe_keyset_generate_galois", "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt"}
+             "hhe_keyset_generate_galois", "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
+             "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level"}
 
 
 def exported_symbols():
@@ -442,6 +444,36 @@ class Context:
         sk = np.ascontiguousarray(sk, dtype=np.uint64)
         assert sk.size >= self.L * self.n
         self._chk(self.lib.hhe_decrypt(self.h, _ptr(sk), _ptr(ct), C.c_size_t(B), _ptr(vals_out)))
+
+    # ---- levels: modulus switching of finished results, and the level-aware ends ----
+    def mod_switch(self, ct, size, B, limbs_in, limbs_out, out):
+        """ct device [B][size][limbs_in][N] -> out device [B][size][limbs_out][N] (Evaluator::mod_switch_to_inplace)"""
+        self._chk(self.lib.hhe_mod_switch(self.h, _ptr(ct), C.c_int(size), C.c_size_t(B), C.c_int(limbs_in), C.c_int(limbs_out), _ptr(out)))
+
+    def decrypt_level(self, sk, ct, limbs, B, vals_out):
+        """sk: host uint64 [K][N]; ct device [B][2][limbs][N]; vals_out device [B][N]"""
+        sk = np.ascontiguousarray(sk, dtype=np.uint64)
+        assert sk.size >= limbs * self.n
+        self._chk(self.lib.hhe_decrypt_level(self.h, _ptr(sk), _ptr(ct), C.c_int(limbs), C.c_size_t(B), _ptr(vals_out)))
+
+    def seal_save_ciphertext_level(self, ct, ct_size, limbs, parms_id):
+        need = C.c_size_t(0)
+        pid = (C.c_uint8 * 32).from_buffer_copy(parms_id)
+        cap = 16 + 32 + 1 + 40 + 16 + 8 + ct_size * max(limbs, 0) * self.n * 8
+        out = (C.c_uint8 * cap)()
+        self._chk(self.lib.hhe_seal_save_ciphertext_level(self.h, _ptr(ct), C.c_size_t(ct_size), C.c_int(limbs), pid, out, C.c_size_t(cap),
+                                                          C.byref(need)))
+        return bytes(out[:need.value])
+
+    def seal_load_ciphertext_level(self, blob, out, offset=0):
+        """Returns (ct_size, limbs, parms_id bytes, consumed)."""
+        buf = (C.c_uint8 * len(blob)).from_buffer_copy(bytes(blob))
+        size, used, limbs = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+        pid = (C.c_uint8 * 32)()
+        self._chk(self.lib.hhe_seal_load_ciphertext_level(self.h, C.byref(buf, offset), C.c_size_t(len(blob) - offset), _ptr(out),
+                                                          C.c_size_t(out.numel() if hasattr(out, "numel") else out.size),
+                                                          C.byref(size), C.byref(limbs), pid, C.byref(used)))
+        return int(size.value), int(limbs.value), bytes(pid), int(used.value)
 
     # ---- keys and ciphertexts from a seed (32 fresh bytes per call: the only entropy) ----
     def sample_poly(self, seed, purpose, elt, index, kind, mod_base, mod_count, out):

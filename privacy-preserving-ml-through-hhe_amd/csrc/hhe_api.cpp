@@ -797,6 +797,33 @@ extern "C" int hhe_negate(hhe_ctx *c, const uint64_t *a, uint64_t *out, size_t B
     op_elt(c, ELT_NEG, a, nullptr, out, B * size * c->L, 0, c->L);
     return HHE_OK;
 }
+// Evaluator::mod_switch_to_inplace on coefficient-form ciphertexts: one launch per chunk of items, every word read and written once
+extern "C" int hhe_mod_switch(hhe_ctx *c, const uint64_t *ct, int size, size_t B, int limbs_in, int limbs_out, uint64_t *out)
+{
+    HHE_LOCK(c);
+    if (!c || !ct || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_mod_switch: bad arguments");
+    if (size < 2 || size > 3) return fail(HHE_ERR_INVALID, "hhe_mod_switch: ciphertext size must be 2 or 3");
+    if (limbs_out < 1 || limbs_out > limbs_in || limbs_in > c->L)
+        return fail(HHE_ERR_INVALID, "hhe_mod_switch: need 1 <= limbs_out <= limbs_in <= L (a ciphertext cannot be switched to a higher level)");
+    const size_t n = c->n, in_item = (size_t)size * limbs_in * n, out_item = (size_t)size * limbs_out * n;
+    if (B > ((size_t)1 << 40) / in_item) return fail(HHE_ERR_INVALID, "hhe_mod_switch: batch too large");
+    if ((uintptr_t)ct < (uintptr_t)(out + B * out_item) && (uintptr_t)out < (uintptr_t)(ct + B * in_item))
+        return fail(HHE_ERR_INVALID, "hhe_mod_switch: out overlaps ct");
+    c->w = &c->lanes[0];
+    // a chunk: as many items as one grid of 2^30 lanes covers (N = 16384, size 2: 32768 items)
+    const size_t per = std::max<size_t>(1, (((size_t)1 << 30) >> c->logn) / size);
+    for (size_t b0 = 0; b0 < B; b0 += per) {
+        const size_t bc = std::min(per, B - b0);
+        EltArgs a;
+        memset(&a, 0, sizeof(a));
+        a.a = ct + b0 * in_item; a.b = c->d_moddown; a.out = out + b0 * out_item; a.mods = c->d_mods; a.logn = c->logn;
+        a.count = (int)(bc * size); a.mod_base = 0; a.mod_cycle = limbs_in; a.b_cycle = limbs_out;
+        k_elt(a, ELT_MODDOWN, c->w->stream);
+        ++c->mod_switch_launches;
+    }
+    if (rt_sync(c->w->stream)) return dev_fail("hhe_mod_switch");
+    return HHE_OK;
+}
 extern "C" int hhe_add_plain(hhe_ctx *c, const uint64_t *ct, const uint64_t *plain, int bcast, int subtract, uint64_t *out, size_t B)
 {
     HHE_LOCK(c);

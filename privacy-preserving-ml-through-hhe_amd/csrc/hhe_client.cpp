@@ -71,16 +71,15 @@ extern "C" int hhe_pasta3_plain_crypt(hhe_ctx *c, const uint64_t *key, const uin
     return HHE_OK;
 }
 
-extern "C" int hhe_decrypt(hhe_ctx *c, const uint64_t *sk, const uint64_t *ct, size_t B, uint64_t *vals)
+// Decryption under q_0 .. q_{L-1} for any 1 <= L <= c->L: every constant below is derived from the limb count of the call (a level of
+// the modulus chain is the context with its last data primes dropped; gamma and t do not change)
+static int decrypt_level(hhe_ctx *c, const uint64_t *sk, const uint64_t *ct, const int L, size_t B, uint64_t *vals)
 {
-    HHE_LOCK(c);
-    if (!c || !sk || !ct || !vals || B == 0) return fail(HHE_ERR_INVALID, "hhe_decrypt: bad arguments");
-    const int L = c->L;
     const size_t n = c->n, ln = (size_t)L * n;
     rt_stream st = c->lanes[0].stream;
     DevBuf dsk(ln * 8), c1s(B * ln * 8), plain(B * n * 8);
     if (!dsk.p || !c1s.p || !plain.p) return dev_fail("hhe_decrypt");
-    if (rt_h2d(dsk.p, sk, ln * 8, st)) return dev_fail("hhe_decrypt");  // data-level limbs of the key-level secret key
+    if (rt_h2d(dsk.p, sk, ln * 8, st)) return dev_fail("hhe_decrypt");  // the level's limbs of the key-level secret key
 
     // c1 * s: forward transform of c1 with the dyadic product fused into the store, inverse transform
     NttArgs a;
@@ -135,6 +134,18 @@ extern "C" int hhe_decrypt(hhe_ctx *c, const uint64_t *sk, const uint64_t *ct, s
     k_decode_gather(g2, st);
     if (rt_sync(st)) return dev_fail("hhe_decrypt");
     return HHE_OK;
+}
+extern "C" int hhe_decrypt(hhe_ctx *c, const uint64_t *sk, const uint64_t *ct, size_t B, uint64_t *vals)
+{
+    HHE_LOCK(c);
+    if (!c || !sk || !ct || !vals || B == 0) return fail(HHE_ERR_INVALID, "hhe_decrypt: bad arguments");
+    return decrypt_level(c, sk, ct, c->L, B, vals);
+}
+extern "C" int hhe_decrypt_level(hhe_ctx *c, const uint64_t *sk, const uint64_t *ct, int limbs, size_t B, uint64_t *vals)
+{
+    HHE_LOCK(c);
+    if (!c || !sk || !ct || !vals || B == 0 || limbs < 1 || limbs > c->L) return fail(HHE_ERR_INVALID, "hhe_decrypt_level: bad arguments (1 <= limbs <= L)");
+    return decrypt_level(c, sk, ct, limbs, B, vals);
 }
 
 // ------------------------------------------------------------------ key generation and public-key encryption from a seed

@@ -165,7 +165,8 @@ struct NttArgs {
 
 enum EltOp { ELT_ADD = 0, ELT_SUB = 1, ELT_NEG = 2, ELT_MUL = 3, ELT_MAC = 4, ELT_COPY = 5, ELT_BCAST = 6, ELT_SHOUP = 7,
              ELT_DIFF = 8,    // ELT_DIFF writes no polynomial: out[0] = 1 when a word of a differs from its word of b (out[0] cleared by the caller)
-             ELT_ENCZ = 9 };  // key generation: c0 = -(a s + e) (+ f new_key) of an encryption of zero under the secret key (elt_encz_body; a kernel of its own)
+             ELT_ENCZ = 9,    // key generation: c0 = -(a s + e) (+ f new_key) of an encryption of zero under the secret key (elt_encz_body; a kernel of its own)
+             ELT_MODDOWN = 10 };  // modulus switching: a [count][mod_cycle][N] -> out [count][b_cycle][N], b = the context's pair table (mod_down_body; kernels of its own)
 
 struct EltArgs {  // element-wise kernels over [count][N] polys, modulus = mod_base + p % mod_cycle
     const u64 *a, *b;
@@ -176,6 +177,15 @@ struct EltArgs {  // element-wise kernels over [count][N] polys, modulus = mod_b
     int with_key;  // ELT_ENCZ: 1 => new_key [K][N] (NTT form) of a key-switching key follows the `count` polynomials of a (fills the
                    // struct's tail padding: the argument block of the older ops keeps its size and offsets)
 };
+
+// ELT_MODDOWN (Evaluator::mod_switch_to_inplace on coefficient-form polynomials): `count` polynomials of mod_cycle = limbs_in residues
+// each, under q_0 .. q_{limbs_in-1} (mod_base = 0), leave with b_cycle = limbs_out residues; one lane owns one coefficient of one
+// polynomial, so the launch covers count << logn lanes like every other op of EltArgs.  b = the per-context table (hhe_ctx::d_moddown):
+// for every pair j < m three words at mod_down_pair(m, j) -- q_m^-1 mod q_j, its Shoup quotient, floor(q_m/2) mod q_j.
+// Up to MOD_DOWN_REGS input limbs the column lives in registers (one kernel per limb count); longer chains keep it in LDS.
+constexpr int MOD_DOWN_REGS = 8;
+HD size_t mod_down_pair(int m, int j) { return (size_t)3 * ((size_t)m * (m - 1) / 2 + j); }
+inline size_t mod_down_table_words(int L) { return mod_down_pair(L, 0) + 3; }  // never empty (L = 1 has no pair)
 
 struct CopyItemsArgs {  // dst item (s * dst_stride + dst_off) <- src item (s * src_stride + src_off), `words` words each, s < count
     const u64 *src;

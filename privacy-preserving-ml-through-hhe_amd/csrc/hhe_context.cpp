@@ -317,6 +317,16 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
     }
     bz.inv_B_msk = nt_invmod(product_mod(Bq, -1, msk), msk);
     c->d_behz = (BehzDev *)rt_malloc(sizeof(BehzDev));
+    // modulus switching (Evaluator::mod_switch_to_next): dropping q_m rescales every limb j < m by q_m^-1 mod q_j
+    std::vector<u64> moddown(mod_down_table_words(L), 0);
+    for (int m = 1; m < L; ++m)
+        for (int j = 0; j < m; ++j) {
+            u64 *e = moddown.data() + mod_down_pair(m, j);
+            e[0] = nt_invmod(dq[m] % dq[j], dq[j]);
+            e[1] = shoup_quot(e[0], dq[j]);
+            e[2] = (dq[m] >> 1) % dq[j];
+        }
+    c->d_moddown = (u64 *)rt_malloc(moddown.size() * 8);
     // the fused finishing pass of a transciphering call reads the add_plain constants from device memory
     FinArgs fa;
     memset(&fa, 0, sizeof(fa));
@@ -333,7 +343,8 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
         fa.slot_map = c->d_slot_map; fa.itw = c->d_fin_itw;
     }
 
-    if (!c->d_tables || !c->d_mods || !c->d_slot_map || !c->d_behz || !c->d_slot_inv || !c->d_fin ||
+    if (!c->d_tables || !c->d_mods || !c->d_slot_map || !c->d_behz || !c->d_slot_inv || !c->d_fin || !c->d_moddown ||
+        rt_h2d(c->d_moddown, moddown.data(), moddown.size() * 8, nullptr) ||
         (!itw.empty() && (!c->d_fin_itw || rt_h2d(c->d_fin_itw, itw.data(), 8 * n, nullptr))) ||
         rt_h2d(c->d_slot_inv, slot_inv.data(), 4 * n, nullptr) || rt_h2d(c->d_fin, &fa, sizeof(fa), nullptr) ||
         rt_h2d(c->d_tables, host_tab.data(), host_tab.size() * 8, nullptr) ||
@@ -495,6 +506,7 @@ extern "C" void hhe_ctx_destroy(hhe_ctx *c)
     c->l0_tab.release(); c->l0_ptrs.release();
     c->ks_tab.release(); c->ks_flags.release(); c->fin_dev.release(); c->fin_host.release();
     rt_free(c->d_tables); rt_free(c->d_mods); rt_free(c->d_behz); rt_free(c->d_slot_map); rt_free(c->d_slot_inv); rt_free(c->d_fin); rt_free(c->d_fin_itw);
+    rt_free(c->d_moddown);
     delete c;
 }
 
@@ -593,6 +605,7 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "fin_item") return fin_item_on(c) ? 1 : 0;          // ... or as one kernel with one workgroup per item, from query("fin_item_min") items on (HHE_FIN_ITEM)
     if (w == "fin_item_min") return fin_item_on(c) ? (c->fin_item > 0 ? 1 : (u64)c->fin_item_min) : 0;
     if (w == "fin_item_launches") return c->fin_item_launches;
+    if (w == "mod_switch_launches") return c->mod_switch_launches;  // kernel launches of hhe_mod_switch: one per call of up to one chunk
     if (w == "ks_cache") return c->ks_cache.enabled ? 1 : 0;      // keystreams are kept across calls (HHE_KS_CACHE)
     if (w == "ks_cache_hits") return c->last_hits;                // counters of the last call served from a kept keystream
     if (w == "ks_cache_entries") return c->ks_cache.entries();

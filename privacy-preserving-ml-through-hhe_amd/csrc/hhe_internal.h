@@ -211,6 +211,8 @@ struct hhe_ctx {
                                    // under HHE_DEDUP=0 and while hhe_ctx_profile is enabled (a profiled call exists to time the chain)
     GrowBuf<u64> ks_flags;         // [KsCache::MAX_SNAPSHOTS]: raised where enc_key differs from a snapshot (ELT_DIFF)
     KsConsts ksc{};
+    u64 *d_moddown = nullptr;      // modulus switching: per pair j < m < L three words at mod_down_pair(m, j) (hhe_common.h), written once
+    u64 mod_switch_launches = 0;   // kernel launches of hhe_mod_switch (hhe_ctx_query("mod_switch_launches"))
 
     // device tables
     ModDev *d_mods = nullptr;

@@ -665,10 +665,86 @@ HD void elt_base_body(const EltArgs &a, int op, size_t gid)
     }
     a.out[gid] = r;
 }
+// ------------------------------------------------------------------ modulus switching (ELT_MODDOWN)
+// One step m of Evaluator::mod_switch_to_next on a coefficient-form polynomial (divide_and_round_q_last_inplace, seal/util/rns.cpp):
+//   r = (x_m + floor(q_m/2)) mod q_m;   x_j <- (x_j - (r mod q_j) + (floor(q_m/2) mod q_j)) * q_m^-1 mod q_j   for j < m
+// i.e. floor((x + floor(q_m/2)) / q_m) mod q_j for the representative x in [0, Q_m+1).  Steps m = limbs_in - 1 .. limbs_out run in that
+// order and every one rounds on its own, as a chain of mod_switch_to_next does.  r < q_m may be far above q_j (and q_j above q_m): the
+// reduction is a full one.  The pair constants are workgroup uniform: read through the constant address space (mod_at's reason).
+struct ModDownPair { u64 inv, inv_s, half; };
+HD ModDownPair mod_down_at(const u64 *tab, int m, int j)
+{
+    ModDownPair c;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const __attribute__((address_space(4))) u64 *p = (const __attribute__((address_space(4))) u64 *)(tab + mod_down_pair(m, j));
+#else
+    const u64 *p = tab + mod_down_pair(m, j);
+#endif
+    c.inv = p[0]; c.inv_s = p[1]; c.half = p[2];
+    return c;
+}
+HD u64 mod_down_round(u64 xm, u64 qm) { return addmod(xm, qm >> 1, qm); }
+HD u64 mod_down_word(u64 xj, u64 r, const ModDev &mj, const ModDownPair &c)
+{
+    const u64 d = addmod(submod(xj, reduce64(r, mj), mj.q), c.half, mj.q);
+    return shoup_mul(d, c.inv, c.inv_s, mj.q);
+}
+// LIN > 0: the column of LIN residues in registers (every index is a compile-time constant).  LIN = 0: any limb count, the column at
+// col[j * cs] -- on the device the lane's own words of the workgroup's LDS block (cs = lanes: conflict-free 8-byte accesses, nobody
+// else touches them, so no barrier), in the tests-only emulator a local array.  Adjacent lanes own adjacent coefficients: every limb
+// row is read and written coalesced, each word once.
+template <int LIN> HD void mod_down_body(const EltArgs &a, size_t gid, u64 *col, int cs)
+{
+    const int lin = LIN ? LIN : a.mod_cycle, lout = a.b_cycle;
+    const size_t n = (size_t)1 << a.logn, p = gid >> a.logn, i = gid & (n - 1);
+    if (p >= (size_t)a.count) return;
+    const u64 *src = a.a + p * lin * n + i;
+    u64 *dst = a.out + p * lout * n + i;
+    if constexpr (LIN > 0) {
+        u64 x[LIN];
+#pragma unroll
+        for (int j = 0; j < LIN; j++) x[j] = src[(size_t)j * n];
+#pragma unroll
+        for (int m = LIN - 1; m >= 1; m--)
+            if (m >= lout) {
+                const u64 r = mod_down_round(x[m], mod_at(a.mods, a.mod_base + m).q);
+#pragma unroll
+                for (int j = 0; j < m; j++) x[j] = mod_down_word(x[j], r, mod_at(a.mods, a.mod_base + j), mod_down_at(a.b, m, j));
+            }
+#pragma unroll
+        for (int j = 0; j < LIN; j++)
+            if (j < lout) dst[(size_t)j * n] = x[j];
+    } else {
+        for (int j = 0; j < lin; j++) col[j * cs] = src[(size_t)j * n];
+        for (int m = lin - 1; m >= lout; m--) {
+            const u64 r = mod_down_round(col[m * cs], mod_at(a.mods, a.mod_base + m).q);
+            for (int j = 0; j < m; j++) col[j * cs] = mod_down_word(col[j * cs], r, mod_at(a.mods, a.mod_base + j), mod_down_at(a.b, m, j));
+        }
+        for (int j = 0; j < lout; j++) dst[(size_t)j * n] = col[j * cs];
+    }
+}
+// the form a launch of limbs_in residues takes, as k_elt picks the kernel on the device
+HD void mod_down_any(const EltArgs &a, size_t gid)
+{
+    u64 col[HHE_MAXL];
+    switch (a.mod_cycle <= MOD_DOWN_REGS ? a.mod_cycle : 0) {
+    case 1: mod_down_body<1>(a, gid, nullptr, 0); break;
+    case 2: mod_down_body<2>(a, gid, nullptr, 0); break;
+    case 3: mod_down_body<3>(a, gid, nullptr, 0); break;
+    case 4: mod_down_body<4>(a, gid, nullptr, 0); break;
+    case 5: mod_down_body<5>(a, gid, nullptr, 0); break;
+    case 6: mod_down_body<6>(a, gid, nullptr, 0); break;
+    case 7: mod_down_body<7>(a, gid, nullptr, 0); break;
+    case 8: mod_down_body<8>(a, gid, nullptr, 0); break;
+    default: mod_down_body<0>(a, gid, col, 1); break;
+    }
+}
 // the element-wise launch as the tests-only emulator loops it; on the device the fused key-generation epilogue is a kernel of its own
+// and so is every form of the modulus switch
 HD void elt_body(const EltArgs &a, int op, size_t gid)
 {
     if (op == ELT_ENCZ) elt_encz_body(a, gid);
+    else if (op == ELT_MODDOWN) mod_down_any(a, gid);
     else elt_base_body(a, op, gid);
 }
 

@@ -565,6 +565,14 @@ static inline unsigned nblocks(size_t total) { return (unsigned)((total + ELT_TH
 
 __global__ void __launch_bounds__(ELT_THREADS) elt_kernel(EltArgs a, int op) { elt_base_body(a, op, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) elt_encz_kernel(EltArgs a) { elt_encz_body(a, GID); }
+// ELT_MODDOWN: one kernel per register form (limbs_in <= MOD_DOWN_REGS), and the LDS form for longer chains -- limbs_in * ELT_THREADS
+// words of dynamic LDS (HHE_MAXL limbs: 64 KiB), lane t's column at words t, t + ELT_THREADS, ...
+template <int LIN> __global__ void __launch_bounds__(ELT_THREADS) mod_down_kernel(EltArgs a) { mod_down_body<LIN>(a, GID, nullptr, 0); }
+__global__ void __launch_bounds__(ELT_THREADS) mod_down_lds_kernel(EltArgs a)
+{
+    extern __shared__ u64 mod_down_cols[];
+    mod_down_body<0>(a, GID, mod_down_cols + threadIdx.x, ELT_THREADS);
+}
 __global__ void __launch_bounds__(ELT_THREADS) copy_items_kernel(CopyItemsArgs a) { copy_items_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) galois_kernel(GaloisArgs a) { galois_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) perm_kernel(PermArgs a) { perm_body(a, GID); }
@@ -615,9 +623,28 @@ __global__ void __launch_bounds__(ELT_THREADS) behz_floor_kernel(BehzFloorArgs a
         if (_t) hipLaunchKernelGGL(kern, dim3(nblocks(_t)), dim3(ELT_THREADS), 0, (hipStream_t)(s), __VA_ARGS__); \
     } while (0)
 
+static void launch_mod_down(const EltArgs &a, rt_stream s)
+{
+    const size_t total = (size_t)a.count << a.logn;
+    switch (a.mod_cycle <= MOD_DOWN_REGS ? a.mod_cycle : 0) {
+    case 1: LAUNCH1D(mod_down_kernel<1>, total, s, a); break;
+    case 2: LAUNCH1D(mod_down_kernel<2>, total, s, a); break;
+    case 3: LAUNCH1D(mod_down_kernel<3>, total, s, a); break;
+    case 4: LAUNCH1D(mod_down_kernel<4>, total, s, a); break;
+    case 5: LAUNCH1D(mod_down_kernel<5>, total, s, a); break;
+    case 6: LAUNCH1D(mod_down_kernel<6>, total, s, a); break;
+    case 7: LAUNCH1D(mod_down_kernel<7>, total, s, a); break;
+    case 8: LAUNCH1D(mod_down_kernel<8>, total, s, a); break;
+    default:
+        if (total && a.mod_cycle <= HHE_MAXL)
+            hipLaunchKernelGGL(mod_down_lds_kernel, dim3(nblocks(total)), dim3(ELT_THREADS), (size_t)a.mod_cycle * ELT_THREADS * sizeof(u64), (hipStream_t)s, a);
+        break;
+    }
+}
 void k_elt(const EltArgs &a, int op, rt_stream s)
 {
     if (op == ELT_ENCZ) LAUNCH1D(elt_encz_kernel, (size_t)a.count << a.logn, s, a);
+    else if (op == ELT_MODDOWN) launch_mod_down(a, s);
     else LAUNCH1D(elt_kernel, (size_t)a.count << a.logn, s, a, op);
 }
 void k_copy_items(const CopyItemsArgs &a, rt_stream s) { LAUNCH1D(copy_items_kernel, a.count * (a.words >> 1), s, a); }

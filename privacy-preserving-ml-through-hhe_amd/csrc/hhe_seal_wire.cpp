@@ -239,10 +239,10 @@ template <typename F> int guarded(F &&f)
 }  // namespace
 
 // ====================================================================== C ABI
-extern "C" int hhe_seal_load_ciphertext(hhe_ctx *c, const uint8_t *bytes, size_t nbytes, uint64_t *out_dptr, size_t out_cap_words,
-                                        size_t *ct_size, uint8_t *parms_id_out, size_t *consumed)
+// limbs_out null: the data level only (hhe_seal_load_ciphertext); else any level 1 <= coeff_modulus_size <= L, returned in *limbs_out
+static int load_ciphertext(hhe_ctx *c, const uint8_t *bytes, size_t nbytes, uint64_t *out_dptr, size_t out_cap_words,
+                           size_t *ct_size, int *limbs_out, uint8_t *parms_id_out, size_t *consumed)
 {
-    HHE_LOCK(c);
     if (!c || !bytes || !out_dptr) return wfail(HHE_ERR_INVALID, "null argument");
     return guarded([&]() -> int {
     std::vector<uint8_t> storage;
@@ -253,7 +253,9 @@ extern "C" int hhe_seal_load_ciphertext(hhe_ctx *c, const uint8_t *bytes, size_t
     Reader r(body, body_n);
     CtMembers m;
     if ((rc = parse_ct_members(r, m))) return rc;
-    if (m.n != c->n || m.cms != (uint64_t)c->L) return wfail(HHE_ERR_INVALID, "ciphertext is not at the data level of this context (encrypted is not valid for encryption parameters)");
+    if (m.n != c->n || (limbs_out ? m.cms > (uint64_t)c->L : m.cms != (uint64_t)c->L))
+        return wfail(HHE_ERR_INVALID, limbs_out ? "ciphertext is not at a level of this context's modulus chain (encrypted is not valid for encryption parameters)"
+                                                : "ciphertext is not at the data level of this context (encrypted is not valid for encryption parameters)");
     if (m.is_ntt) return wfail(HHE_ERR_INVALID, "BFV ciphertext in NTT form");
     if (m.words > out_cap_words) return wfail(HHE_ERR_CAPACITY, "output buffer too small");
     // the safe load's is_data_valid_for: every coefficient below its prime (a foreign blob must not reach the lazy kernels)
@@ -268,18 +270,31 @@ extern "C" int hhe_seal_load_ciphertext(hhe_ctx *c, const uint8_t *bytes, size_t
     rt_stream st = c->lanes[0].stream;
     if (rt_h2d(out_dptr, m.data, m.words * 8, st) || rt_sync(st)) return wfail(HHE_ERR_DEVICE, rt_last_error());
     if (ct_size) *ct_size = (size_t)m.size;
+    if (limbs_out) *limbs_out = (int)m.cms;
     if (parms_id_out) memcpy(parms_id_out, m.parms_id, 32);
     if (consumed) *consumed = used;
     return HHE_OK;
     });
 }
-
-extern "C" int hhe_seal_save_ciphertext(hhe_ctx *c, const uint64_t *ct_dptr, size_t ct_size, const uint8_t *parms_id, uint8_t *out,
-                                        size_t out_cap, size_t *written)
+extern "C" int hhe_seal_load_ciphertext(hhe_ctx *c, const uint8_t *bytes, size_t nbytes, uint64_t *out_dptr, size_t out_cap_words,
+                                        size_t *ct_size, uint8_t *parms_id_out, size_t *consumed)
 {
     HHE_LOCK(c);
-    if (!c || !ct_dptr || !parms_id || !written || ct_size < 2 || ct_size > 3) return wfail(HHE_ERR_INVALID, "bad arguments");
-    const size_t words = ct_size * c->L * c->n;
+    return load_ciphertext(c, bytes, nbytes, out_dptr, out_cap_words, ct_size, nullptr, parms_id_out, consumed);
+}
+extern "C" int hhe_seal_load_ciphertext_level(hhe_ctx *c, const uint8_t *bytes, size_t nbytes, uint64_t *out_dptr, size_t out_cap_words,
+                                              size_t *ct_size, int *limbs, uint8_t *parms_id_out, size_t *consumed)
+{
+    HHE_LOCK(c);
+    if (!limbs) return wfail(HHE_ERR_INVALID, "null argument");
+    return load_ciphertext(c, bytes, nbytes, out_dptr, out_cap_words, ct_size, limbs, parms_id_out, consumed);
+}
+
+static int save_ciphertext(hhe_ctx *c, const uint64_t *ct_dptr, size_t ct_size, int limbs, const uint8_t *parms_id, uint8_t *out,
+                           size_t out_cap, size_t *written)
+{
+    if (!c || !ct_dptr || !parms_id || !written || ct_size < 2 || ct_size > 3 || limbs < 1 || limbs > c->L) return wfail(HHE_ERR_INVALID, "bad arguments");
+    const size_t words = ct_size * limbs * c->n;
     const size_t inner = HDR + 8 + words * 8;                 // DynArray object
     const size_t total = HDR + 32 + 1 + 8 * 5 + inner;        // header + members
     *written = total;
@@ -295,7 +310,7 @@ extern "C" int hhe_seal_save_ciphertext(hhe_ctx *c, const uint64_t *ct_dptr, siz
     header(p, total); p += HDR;
     memcpy(p, parms_id, 32); p += 32;
     *p++ = 0;  // is_ntt_form: BFV ciphertexts are kept in coefficient form
-    const uint64_t f[3] = {ct_size, c->n, (uint64_t)c->L};
+    const uint64_t f[3] = {ct_size, c->n, (uint64_t)limbs};
     memcpy(p, f, 24); p += 24;
     const double scale = 1.0;
     const uint64_t corr = 1;
@@ -307,6 +322,18 @@ extern "C" int hhe_seal_save_ciphertext(hhe_ctx *c, const uint64_t *ct_dptr, siz
     rt_stream st = c->lanes[0].stream;
     if (rt_d2h(p, ct_dptr, words * 8, st) || rt_sync(st)) return wfail(HHE_ERR_DEVICE, rt_last_error());
     return HHE_OK;
+}
+extern "C" int hhe_seal_save_ciphertext(hhe_ctx *c, const uint64_t *ct_dptr, size_t ct_size, const uint8_t *parms_id, uint8_t *out,
+                                        size_t out_cap, size_t *written)
+{
+    HHE_LOCK(c);
+    return save_ciphertext(c, ct_dptr, ct_size, c ? c->L : 0, parms_id, out, out_cap, written);
+}
+extern "C" int hhe_seal_save_ciphertext_level(hhe_ctx *c, const uint64_t *ct_dptr, size_t ct_size, int limbs, const uint8_t *parms_id,
+                                              uint8_t *out, size_t out_cap, size_t *written)
+{
+    HHE_LOCK(c);
+    return save_ciphertext(c, ct_dptr, ct_size, limbs, parms_id, out, out_cap, written);
 }
 
 // every key of the object, decoded and validated on the host; nothing is uploaded here
