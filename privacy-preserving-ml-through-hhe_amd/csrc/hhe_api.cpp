@@ -111,6 +111,7 @@ void op_finish_item(hhe_ctx *c, const u64 *vals, u64 *tmp, const u64 *ks, const 
     NttArgs a = ntt_args(c, vals, tmp, B, c->mod_t, 1);
     a.load_op = LOAD_ENCODE; a.src_item_polys = 1; a.src_item_stride = PASTA_T;
     a.store_op = STORE_ADD_PLAIN; a.mul = ks; a.mul_ptrs = ks_ptrs; a.aux_out = out; a.fin = c->d_fin;
+    a.base_mask = c->fin_scale32;  // which instantiation the launch takes
     k_ntt(a, true, c->w->stream);
     ++c->fin_item_launches;
 }

@@ -98,12 +98,32 @@ struct FinArgs {
     // one workgroup per item (fin_item_kernel, hhe_fin_bodies.h); null where the context is not eligible
     const u32 *slot_map;       // [N]: coefficient of slot s
     const u32 *itw;            // [N][2]: the inverse powers mod t in the order of ModDev::iw, each with floor(w * 2^32 / t)
+    // the 32-bit scaling of the item kernel (plain_fix32 / plain_scaled32, hhe_fin_bodies.h); zero where fin_scale32_ok does not hold
+    u32 q_mod_t_s;             // floor(q_mod_t * 2^32 / t)
+    u32 scale32;               // 1: q_mod_t_s and delta_s are set
+    u64 delta_s[HHE_MAXL];     // floor(delta[j] * 2^64 / q_j)
 };
 
 // where fin_item_kernel runs: N u32 words fit the LDS of one workgroup (4 N <= 128 KiB) and the lazy range [0, 4t) of its 32-bit
 // butterflies fits a word
 constexpr int FIN_ITEM_MIN_LOGN = 10, FIN_ITEM_MAX_LOGN = 15;
 inline bool fin_item_ok(int logn, u64 t) { return logn >= FIN_ITEM_MIN_LOGN && logn <= FIN_ITEM_MAX_LOGN && t < ((u64)1 << 30); }
+// where the item kernel scales its plaintext with 32-bit products: the coefficients are below t < 2^30 (fin_item_ok), and the fix
+// (below t) is added to a residue with ONE conditional subtraction, so every data prime q[0 .. L) must exceed t
+inline bool fin_scale32_ok(int logn, u64 t, const u64 *q, int L)
+{
+    if (!fin_item_ok(logn, t)) return false;
+    for (int j = 0; j < L; ++j)
+        if (q[j] <= t) return false;
+    return true;
+}
+// the constants of that scaling from t, q_mod_t and delta[] of `fa` (host only; call where fin_scale32_ok holds)
+inline void fin_scale32_fill(FinArgs &fa, const u64 *q, int L)
+{
+    fa.q_mod_t_s = (u32)((fa.q_mod_t << 32) / fa.t);  // q_mod_t < t < 2^30
+    for (int j = 0; j < L; ++j) fa.delta_s[j] = (u64)(((unsigned __int128)fa.delta[j] << 64) / q[j]);  // delta[j] < q[j]
+    fa.scale32 = 1;
+}
 
 // key-switch mod-down constants, passed by value to the kernels that finish a key switch
 struct KsConsts {
@@ -156,7 +176,8 @@ struct NttArgs {
     const u64 *aux_in;  // KS0: c0 (NTT form) of the current state [B][L][N];  KSF: base ciphertexts (item b at aux_in + b * base_stride) or null
     u64 *aux_out;       // KS1: d [B][L][N];  KS0: c0 (NTT form) of the next state [B][L][N];  KSF: out [B][2][L][N]
     size_t base_stride; // KSF: words between the items of aux_in
-    int base_mask;      // KSF: bit k set => add base poly k
+    int base_mask;      // KSF: bit k set => add base poly k.  Both ops of the finishing pass in one launch (the item kernel): 1 => the
+                        // launch takes the instantiation with the 32-bit scaling (FinArgs::scale32 is set); the two-pass kernels ignore it
     KsConsts ks;
     // fused finishing pass.  LOAD_ENCODE: src = the items' words (item b at src + b * src_item_stride, src_item_polys = 1).
     // STORE_ADD_PLAIN: the operand ciphertext of item b is mul_ptrs[b] if mul_ptrs is set, else mul + b * 2LN; aux_out = out [B][2][L][N]

@@ -341,6 +341,12 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
         for (size_t k = 0; k < n; ++k) { itw[2 * k] = (u32)iw[2 * k]; itw[2 * k + 1] = (u32)((iw[2 * k] << 32) / t); }
         c->d_fin_itw = (u32 *)rt_malloc(8 * n);
         fa.slot_map = c->d_slot_map; fa.itw = c->d_fin_itw;
+        // ... and the quotients of its 32-bit plaintext scaling (HHE_FIN_SCALE32=0: the shared 128-bit definition, as every ineligible context)
+        const char *e = getenv("HHE_FIN_SCALE32");
+        if (fin_scale32_ok(logn, t, dq.data(), L) && !(e && atoi(e) == 0)) {
+            fin_scale32_fill(fa, dq.data(), L);
+            c->fin_scale32 = true;
+        }
     }
 
     if (!c->d_tables || !c->d_mods || !c->d_slot_map || !c->d_behz || !c->d_slot_inv || !c->d_fin || !c->d_moddown ||
@@ -605,6 +611,7 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "fin_item") return fin_item_on(c) ? 1 : 0;          // ... or as one kernel with one workgroup per item, from query("fin_item_min") items on (HHE_FIN_ITEM)
     if (w == "fin_item_min") return fin_item_on(c) ? (c->fin_item > 0 ? 1 : (u64)c->fin_item_min) : 0;
     if (w == "fin_item_launches") return c->fin_item_launches;
+    if (w == "fin_scale32") return fin_item_on(c) && c->fin_scale32 ? 1 : 0;  // ... with the plaintext scaled by 32-bit products and -c1 written early (HHE_FIN_SCALE32; t < 2^30 below every data prime)
     if (w == "mod_switch_launches") return c->mod_switch_launches;  // kernel launches of hhe_mod_switch: one per call of up to one chunk
     if (w == "ks_cache") return c->ks_cache.enabled ? 1 : 0;      // keystreams are kept across calls (HHE_KS_CACHE)
     if (w == "ks_cache_hits") return c->last_hits;                // counters of the last call served from a kept keystream

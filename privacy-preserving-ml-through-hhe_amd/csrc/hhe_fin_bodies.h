@@ -8,7 +8,8 @@
 //   encode   the item's `count` words, reduced mod t and multiplied by N^-1, go to their coefficient slots (BatchEncoder::encode)
 //   rounds   the whole inverse negacyclic transform (Gentleman-Sande, SEAL's order: the stages ntt_body_round runs in two passes) in
 //            register rounds of radix 8 from stage log N - 1 down, a shorter last round where log N is no multiple of 3
-//   store    the add_plain epilogue of the two-pass kernels (fin_store_fetch / fin_store_vals), fed from LDS
+//   store    the add_plain epilogue of the two-pass kernels (fin_store_fetch / fin_store_vals), fed from LDS; in the instantiation
+//            with the 32-bit scaling (below) the c0 half only, the c1 half going out in slices in front of the other phases
 // The transform is linear, so the N^-1 scaling is applied to the at most 128 words that enter it instead of the N that leave it.
 //
 // 32-bit arithmetic: Harvey's lazy butterflies with values in [0, 2t).  X' = X + Y < 4t is folded below 2t; Y' = (X + 2t - Y) w
@@ -123,11 +124,69 @@ template <int LOGN> struct FinItemSched {
     static constexpr int rho(int r) { return LOGN - 3 * r >= 3 ? 3 : LOGN - 3 * r; }
 };
 
+// The 32-bit scaling (FinArgs::scale32; fin_scale32_ok: t < 2^30 and every data prime above t).  A coefficient m < t is a u32, so the
+// two values add_plain derives from it need no 128-bit product:
+//   fix = floor((m (Q mod t) + thr) / t):  est = mulhi32(m, q_mod_t_s) is the quotient of m (Q mod t) by t or one below it (Shoup,
+//         q_mod_t_s = floor((Q mod t) 2^32 / t)), so m (Q mod t) - est t lies in [0, 2t) and is exact in 32 bits; with thr = (t+1)/2
+//         added the sum is below 2.5 t + 1 < 2^32, and each of two conditional subtractions of t that is taken adds 1 to est.
+//   (m delta_j + fix) mod q_j:  H = floor(m delta_s / 2^64) with delta_s = floor(delta_j 2^64 / q_j) -- for a 32-bit m that is
+//         (m hi32(delta_s) + mulhi32(m, lo32(delta_s))) >> 32, exactly -- leaves m delta_j - H q_j in [0, 2 q_j) (low 64 bits; q_j < 2^61);
+//         a conditional subtraction, + fix (fix < t < q_j), and another one give the canonical residue.
+// Both are the words plain_fix / plain_scaled return (hhe_kernel_bodies.h), which keep the shared 128-bit definition everywhere else.
+struct FinScale32 { u32 t, q_mod_t, q_mod_t_s, thr; };
+HD FinScale32 fin_scale32_consts(const FinArgs *f)
+{
+    const FinScale32 s = {(u32)ld_const(&f->t), (u32)ld_const(&f->q_mod_t), ld_const(&f->q_mod_t_s), (u32)ld_const(&f->thr)};
+    return s;
+}
+HD u32 plain_fix32(const FinScale32 &s, u32 m)
+{
+    u32 fix = mulhi32(m, s.q_mod_t_s);
+    u32 r = m * s.q_mod_t - fix * s.t + s.thr;
+#if defined(HHE_RANGE_CHECK) && !defined(__HIP_DEVICE_COMPILE__)
+    if ((u64)m * s.q_mod_t - (u64)fix * s.t >= 2 * (u64)s.t) hhe_range_violation("32-bit fix: remainder not below 2t");
+#endif
+    u32 d = r - s.t;
+    if (d < r) { r = d; fix++; }
+    d = r - s.t;
+    if (d < r) { r = d; fix++; }
+    return fix;
+}
+HD u64 plain_scaled32(u32 m, u32 fix, u64 delta, u64 delta_s, u64 q)
+{
+    const u64 h = ((u64)m * (u32)(delta_s >> 32) + mulhi32(m, (u32)delta_s)) >> 32;
+    u64 r = (u64)m * delta - h * q;
+#if defined(HHE_RANGE_CHECK) && !defined(__HIP_DEVICE_COMPILE__)
+    if (r >= 2 * q) hhe_range_violation("32-bit scaling: remainder not below 2q");
+#endif
+    r = r >= q ? r - q : r;
+    r += fix;
+    return r >= q ? r - q : r;
+}
+
 // the epilogue: coefficient pairs (gi, gi + 1) out of LDS, the operands of G pairs in flight before the first store
 #ifndef FIN_ITEM_G
 #define FIN_ITEM_G 2
 #endif
-template <int T> HD void fin_item_store(const NttArgs &a, int item, int tid, const u32 *lds)
+// In the 32-bit instantiation out[b][1][j] = -c1[j], which needs nothing from LDS, is written by fin_item_c1 in slices ahead of the
+// other phases (FIN_ITEM_C1_EARLY 1), and the store phase writes c0 only; 0 leaves both halves to the store phase (A/B builds).
+#ifndef FIN_ITEM_C1_EARLY
+#define FIN_ITEM_C1_EARLY 1
+#endif
+// limb j of one pair with the 32-bit scaling: what fin_store_limb writes; C1: the c1 half too
+template <bool C1> HD void fin_store_limb32(const NttArgs &a, const NttGeom &g, int gi, int j, const u32 *mv, const u32 *fix, U2 c0, U2 c1)
+{
+    const u64 q = mod_at_u(a.mods, j).q;
+    const u64 d = ld_const(&a.fin->delta[j]), ds = ld_const(&a.fin->delta_s[j]);
+    u64 *o = a.aux_out + ((size_t)g.poly * 2 * a.L + j) * g.n + gi;
+    U2 o0;
+    o0.a = addmod(negmod(c0.a, q), plain_scaled32(mv[0], fix[0], d, ds, q), q);
+    o0.b = addmod(negmod(c0.b, q), plain_scaled32(mv[1], fix[1], d, ds, q), q);
+    st2_stream(o, o0);
+    if (C1) st2_stream(o + (size_t)a.L * g.n, U2{negmod(c1.a, q), negmod(c1.b, q)});
+}
+// SCALE32 = false (the default) is the shared definition: fin_store_fetch / fin_store_vals, both halves written here
+template <int T, bool SCALE32 = false, bool C1 = !FIN_ITEM_C1_EARLY> HD void fin_item_store(const NttArgs &a, int item, int tid, const u32 *lds)
 {
     constexpr int G = FIN_ITEM_G;
     NttGeom g = {};
@@ -135,23 +194,90 @@ template <int T> HD void fin_item_store(const NttArgs &a, int item, int tid, con
     g.poly = item;
     const u32 t = (u32)ld_const(&a.fin->t);
     const int E2 = g.n >> 1;  // a multiple of T for every N >= 2048; guarded below
-    for (int e0 = tid; e0 < E2; e0 += G * T) {
-        FinPre pre[G];
-        int gi[G];
+    if constexpr (!SCALE32) {
+        for (int e0 = tid; e0 < E2; e0 += G * T) {
+            FinPre pre[G];
+            int gi[G];
 #pragma unroll
-        for (int k = 0; k < G; k++) {
-            if (e0 + k * T >= E2) continue;
-            gi[k] = 2 * (e0 + k * T);
-            pre[k] = fin_store_fetch(a, g, gi[k]);
+            for (int k = 0; k < G; k++) {
+                if (e0 + k * T >= E2) continue;
+                gi[k] = 2 * (e0 + k * T);
+                pre[k] = fin_store_fetch(a, g, gi[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < G; k++) {
+                if (e0 + k * T >= E2) continue;
+                const u32 at = fin_lds_at((u32)gi[k]);
+                const u32 p0 = lds[at & ~1u], p1 = lds[at | 1u];
+                const bool sw = at & 1;
+                const u64 mv[2] = {csub32(sw ? p1 : p0, t), csub32(sw ? p0 : p1, t)};
+                fin_store_vals(a, g, gi[k], mv, pre[k]);
+            }
         }
+    } else {
+        const FinScale32 sc = fin_scale32_consts(a.fin);
+        const gptr kp = as_global(a.mul_ptrs ? a.mul_ptrs[item] : a.mul + (size_t)item * 2 * a.L * g.n);
+        for (int e0 = tid; e0 < E2; e0 += G * T) {
+            U2 k0[G][FIN_PRE], k1[G][FIN_PRE] = {};
+            int gi[G];
 #pragma unroll
-        for (int k = 0; k < G; k++) {
-            if (e0 + k * T >= E2) continue;
-            const u32 at = fin_lds_at((u32)gi[k]);
-            const u32 p0 = lds[at & ~1u], p1 = lds[at | 1u];
-            const bool sw = at & 1;
-            const u64 mv[2] = {csub32(sw ? p1 : p0, t), csub32(sw ? p0 : p1, t)};
-            fin_store_vals(a, g, gi[k], mv, pre[k]);
+            for (int k = 0; k < G; k++) {
+                if (e0 + k * T >= E2) continue;
+                gi[k] = 2 * (e0 + k * T);
+#pragma unroll
+                for (int j = 0; j < FIN_PRE; j++)
+                    if (j < a.L) {
+                        k0[k][j] = ld2g(kp + (size_t)j * g.n + gi[k]);
+                        if (C1) k1[k][j] = ld2g(kp + (size_t)(a.L + j) * g.n + gi[k]);
+                    }
+            }
+#pragma unroll
+            for (int k = 0; k < G; k++) {
+                if (e0 + k * T >= E2) continue;
+                const u32 at = fin_lds_at((u32)gi[k]);
+                const u32 p0 = lds[at & ~1u], p1 = lds[at | 1u];
+                const bool sw = at & 1;
+                const u32 mv[2] = {csub32(sw ? p1 : p0, t), csub32(sw ? p0 : p1, t)};
+                const u32 fix[2] = {plain_fix32(sc, mv[0]), plain_fix32(sc, mv[1])};
+#pragma unroll
+                for (int j = 0; j < FIN_PRE; j++)
+                    if (j < a.L) fin_store_limb32<C1>(a, g, gi[k], j, mv, fix, k0[k][j], k1[k][j]);
+                for (int j = FIN_PRE; j < a.L; j++)
+                    fin_store_limb32<C1>(a, g, gi[k], j, mv, fix, ld2g(kp + (size_t)j * g.n + gi[k]),
+                                         C1 ? ld2g(kp + (size_t)(a.L + j) * g.n + gi[k]) : U2{0, 0});
+            }
+        }
+    }
+}
+
+// slice `slice` of `nslices` of the item's c1 half, out[b][1][j] = -c1[j] (L N words as 16-byte pairs, limb j the pairs
+// [j N/2, (j+1) N/2)): loads of G pairs, then their stores.  The kernel issues one slice in front of each of its other phases --
+// clear, encode, every register round: fin_item_c1_slices -- so that memory drains it while the wave works in LDS; a barrier
+// waits for the wave's outstanding memory operations, which is why a slice is sized to one phase and the half is not hoisted whole.
+template <int LOGN> constexpr int fin_item_c1_slices() { return 2 + FinItemSched<LOGN>::R; }
+#ifndef FIN_ITEM_C1_G
+#define FIN_ITEM_C1_G 4
+#endif
+template <int T> HD void fin_item_c1(const NttArgs &a, int item, int tid, int slice, int nslices)
+{
+    constexpr int G = FIN_ITEM_C1_G;
+    const int n = 1 << a.logn, half = a.logn - 1;
+    const int P = a.L << half;  // at most 2^19 pairs: P * nslices fits an int
+    // slice boundaries on multiples of 8 pairs (128 bytes; P is one): no cache line is written in two parts by two phases or two waves
+    const int lo = (P * slice / nslices) & ~7, hi = slice + 1 == nslices ? P : (P * (slice + 1) / nslices) & ~7;
+    const gptr kp = as_global(a.mul_ptrs ? a.mul_ptrs[item] : a.mul + (size_t)item * 2 * a.L * n) + (size_t)a.L * n;
+    u64 *o = a.aux_out + ((size_t)item * 2 + 1) * a.L * n;
+    for (int j = lo >> half; (j << half) < hi; j++) {  // the limbs the slice touches: the prime is uniform over the workgroup
+        const u64 q = mod_at_u(a.mods, j).q;
+        const int p_lo = lo > (j << half) ? lo : (j << half), p_hi = hi < ((j + 1) << half) ? hi : ((j + 1) << half);
+        for (int p0 = p_lo + tid; p0 < p_hi; p0 += G * T) {
+            U2 v[G];
+#pragma unroll
+            for (int k = 0; k < G; k++)
+                if (p0 + k * T < p_hi) v[k] = ld2g(kp + 2 * (size_t)(p0 + k * T));
+#pragma unroll
+            for (int k = 0; k < G; k++)
+                if (p0 + k * T < p_hi) st2_stream(o + 2 * (size_t)(p0 + k * T), U2{negmod(v[k].a, q), negmod(v[k].b, q)});
         }
     }
 }

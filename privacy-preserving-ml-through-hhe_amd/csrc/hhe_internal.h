@@ -198,6 +198,7 @@ struct hhe_ctx {
     size_t fin_item_min = 64;      // an item occupies one CU whatever the batch: a small call is faster spread over the tiles of the two-pass kernels (measured: slower up to 32 items, level at 48, faster from 64)
                                    // (DESIGN.md "Finishing pass in one workgroup")
     u32 *d_fin_itw = nullptr;      // [N][2] u32 inverse twiddles mod t (FinArgs::itw); null where t needs more than 30 bits or N > 2^15
+    bool fin_scale32 = false;      // FinArgs carries the constants of the item kernel's 32-bit plaintext scaling (fin_scale32_ok and HHE_FIN_SCALE32 != 0): its launches take fin_item32_kernel
     u64 fin_item_launches = 0;     // launches of fin_item_kernel (hhe_ctx_query("fin_item_launches"))
     u32 *d_slot_inv = nullptr;     // [N] inverse of slot_map (FinArgs::slot_inv)
     GrowBuf<u64> fin_dev;          // [B] per item: pointer to its keystream (fused) or its slot of ks_tab as u32 (unfused) | [B][128] the items' words,

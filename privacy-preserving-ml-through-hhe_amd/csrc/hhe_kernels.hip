@@ -165,13 +165,15 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) ntt_fin_kernel(NttArgs a)
 }
 // the finishing pass with one workgroup per item (hhe_fin_bodies.h): encode into LDS, the whole inverse transform mod t in 32-bit
 // words there, add_plain epilogue.  LDS is 4 N bytes, so N = 2^15 takes one CU per item and N = 2^14 places two items on a CU.
-template <int LOGN, int R>
-static __device__ __forceinline__ void fin_item_rounds(const NttArgs &a, u32 *lds)
+// C1: fin_item_c1_slices<LOGN>() slices of the c1 half are issued, one in front of each phase; `slice` counts them (clear 0, encode 1)
+template <int LOGN, int R, bool C1 = false>
+static __device__ __forceinline__ void fin_item_rounds(const NttArgs &a, u32 *lds, int item = 0)
 {
     if constexpr (R < FinItemSched<LOGN>::R) {
+        if constexpr (C1) fin_item_c1<FIN_ITEM_THREADS>(a, item, threadIdx.x, 2 + R, fin_item_c1_slices<LOGN>());
         fin_item_round<LOGN, FinItemSched<LOGN>::s0(R), FinItemSched<LOGN>::rho(R), FIN_ITEM_THREADS>(a, threadIdx.x, lds);
         __syncthreads();
-        fin_item_rounds<LOGN, R + 1>(a, lds);
+        fin_item_rounds<LOGN, R + 1, C1>(a, lds, item);
     }
 }
 template <int LOGN>
@@ -186,19 +188,37 @@ __global__ void __launch_bounds__(FIN_ITEM_THREADS) fin_item_kernel(NttArgs a)
     fin_item_rounds<LOGN, 0>(a, lds);
     fin_item_store<FIN_ITEM_THREADS>(a, item, threadIdx.x, lds);
 }
+// the same with the 32-bit scaling of the plaintext (FinArgs::scale32) and the c1 half written ahead of and between the phases
+template <int LOGN>
+__global__ void __launch_bounds__(FIN_ITEM_THREADS) fin_item32_kernel(NttArgs a)
+{
+    __shared__ __attribute__((aligned(16))) u32 lds[1 << LOGN];
+    constexpr bool C1 = FIN_ITEM_C1_EARLY;
+    const int item = blockIdx.x;
+    if constexpr (C1) fin_item_c1<FIN_ITEM_THREADS>(a, item, threadIdx.x, 0, fin_item_c1_slices<LOGN>());
+    fin_item_clear<FIN_ITEM_THREADS>(a, threadIdx.x, lds);
+    __syncthreads();
+    if constexpr (C1) fin_item_c1<FIN_ITEM_THREADS>(a, item, threadIdx.x, 1, fin_item_c1_slices<LOGN>());
+    fin_item_encode<FIN_ITEM_THREADS>(a, item, threadIdx.x, lds);
+    __syncthreads();
+    fin_item_rounds<LOGN, 0, C1>(a, lds, item);
+    fin_item_store<FIN_ITEM_THREADS, true>(a, item, threadIdx.x, lds);
+}
 static void launch_fin_item(const NttArgs &a, hipStream_t st)
 {
     const dim3 grid((unsigned)a.count), block(FIN_ITEM_THREADS);
     if (!a.fin) { snprintf(g_rt_err, sizeof(g_rt_err), "finishing pass per item: no constants"); return; }
+    // a.base_mask: the context's FinArgs carries the constants of the 32-bit scaling (hhe_ctx::fin_scale32)
+#define FIN_ITEM_LAUNCH(N_)                                                                                                \
+    case N_:                                                                                                               \
+        if (a.base_mask) hipLaunchKernelGGL(fin_item32_kernel<N_>, grid, block, 0, st, a);                                 \
+        else hipLaunchKernelGGL(fin_item_kernel<N_>, grid, block, 0, st, a);                                               \
+        break;
     switch (a.logn) {
-    case 10: hipLaunchKernelGGL(fin_item_kernel<10>, grid, block, 0, st, a); break;
-    case 11: hipLaunchKernelGGL(fin_item_kernel<11>, grid, block, 0, st, a); break;
-    case 12: hipLaunchKernelGGL(fin_item_kernel<12>, grid, block, 0, st, a); break;
-    case 13: hipLaunchKernelGGL(fin_item_kernel<13>, grid, block, 0, st, a); break;
-    case 14: hipLaunchKernelGGL(fin_item_kernel<14>, grid, block, 0, st, a); break;
-    case 15: hipLaunchKernelGGL(fin_item_kernel<15>, grid, block, 0, st, a); break;
+        FIN_ITEM_LAUNCH(10) FIN_ITEM_LAUNCH(11) FIN_ITEM_LAUNCH(12) FIN_ITEM_LAUNCH(13) FIN_ITEM_LAUNCH(14) FIN_ITEM_LAUNCH(15)
     default: snprintf(g_rt_err, sizeof(g_rt_err), "finishing pass per item: unsupported N = 2^%d", a.logn); break;
     }
+#undef FIN_ITEM_LAUNCH
 }
 // Two independent batches of the same pass in ONE grid (polynomials [0, a1.count) use a1, the rest a2): a small batch
 // rides in the tail of a big one instead of paying a launch of its own that cannot fill the 1024 workgroup slots.
