@@ -58,7 +58,25 @@ int hhe_ctx_create(int logn, int K, const uint64_t *q_hptr, uint64_t t, int devi
  * 29-prime chain for N = 65536 (src/pasta/SEAL_Cipher.cpp:47-65).  *count: in = capacity, out = number of primes. */
 int hhe_bfv_default_coeff_modulus(size_t poly_modulus_degree, uint64_t *out_hptr, size_t *count);
 void hhe_ctx_destroy(hhe_ctx *c);
-/* run all work of this context on an existing HIP stream (hipStream_t); NULL = default stream */
+/* Run the work of this context on an existing HIP stream (hipStream_t, e.g. a torch.cuda.Stream's handle); NULL = the default
+ * stream.  The stream contract (tests/test_gpu_streams.py, and tests/test_stream_order_emu.py for the schedule behind it):
+ *  - Inputs are read in the order of the context's stream: every entry point enqueues its first read of a device input (ct, enc_key,
+ *    plain ...) on that stream, so it is ordered behind whatever the caller enqueued there before the call -- an upload still in
+ *    flight, a kernel that produces the input -- with no host synchronisation.  The key comparison of hhe_pasta3_transcipher runs
+ *    there too: enc_key is taken as what the buffer holds in stream order.  Work the caller has on OTHER streams is not waited for.
+ *    Host inputs (cw, ncw, block_index, records, keys, matrices, mask values) are read before the call returns.
+ *  - The batched calls return after their work has finished (hhe_pasta3_transcipher[_ks], hhe_decompose[_ks], hhe_fc_row[_ks],
+ *    hhe_packed_affine[_ks], hhe_mod_switch, every upload, read-back, key generation and matrix creation): they fork onto the
+ *    context's internal non-blocking streams (HHE_STREAMS), join the context's stream again and wait for it, so `out` may be read
+ *    from any stream when they return.  The generic evaluator ops (hhe_ntt, hhe_encode, hhe_add, hhe_negate, hhe_add_plain,
+ *    hhe_multiply_plain, hhe_multiply, hhe_relinearize, hhe_apply_galois, hhe_rotate_*, hhe_mask, hhe_flatten) only ENQUEUE on the
+ *    context's stream: their result is ordered for later work on that stream, and for the host after hhe_ctx_sync (or a wait for
+ *    the stream).  A non-blocking stream is not ordered with the default stream.
+ *  - hhe_ctx_create uploads its tables on the default stream and waits.  Key uploads, key generation and hhe_matrix_create use the
+ *    stream the context has at that call and wait: what they leave resident is complete, whichever stream later calls run on.
+ *  - Changing the stream waits for nothing.  Resident objects (keys, block tables, kept keystreams, matrices) stay valid, as they
+ *    were finished under a host wait.  Generic ops still in flight on the old stream are NOT ordered with calls on the new one,
+ *    and they share the context's workspaces: call hhe_ctx_sync before hhe_ctx_set_stream unless the last call was a batched one. */
 int hhe_ctx_set_stream(hhe_ctx *c, void *hip_stream);
 /* size per-batch workspaces for up to max_batch ciphertexts (allocated once, reused) */
 int hhe_ctx_reserve(hhe_ctx *c, size_t max_batch);

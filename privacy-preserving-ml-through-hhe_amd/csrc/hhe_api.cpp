@@ -324,7 +324,7 @@ void evict_blocks(hhe_ctx *c, size_t need)
         for (auto it = c->blocks.begin(); it != c->blocks.end(); ++it)
             if (it->second.last_call != c->block_call && (victim == c->blocks.end() || it->second.last_call < victim->second.last_call)) victim = it;
         if (victim == c->blocks.end()) return;
-        sync_ctx(c);  // earlier calls have completed (every entry point waits for its work), but a caller's stream may lag
+        sync_ctx(c);  // earlier batched calls have completed (they wait for their work), but generic ops enqueued on the caller's stream may lag
         c->block_bytes -= victim->second.bytes;
         free_block(victim->second);
         c->ks_cache.drop_counter(c, victim->first);  // a kept keystream goes with its counter's tables

@@ -27,9 +27,10 @@ int rt_event_record(void *ev, rt_stream s);
 int rt_event_sync(void *ev);                         // host waits for the event
 int rt_stream_wait_event(rt_stream s, void *ev);
 const char *rt_last_error();
-// Page-locked host memory, optional at link time: a runtime without it (the tests-only emulator) leaves the symbols undefined, they
-// are then null and the host driver takes malloc / free (HostStage, hhe_internal.h).  A copy out of page-locked memory is
-// enqueued without the staging copy that holds the host for one out of pageable memory.
+// Page-locked host memory, optional at link time: a runtime without it leaves the symbols undefined, they are then null and the
+// host driver takes malloc / free (HostStage, hhe_internal.h).  Both runtimes in the tree define them (the tests-only emulator
+// needs to tell page-locked from pageable sources for its stream model), so no test runs that fallback.  A copy out of
+// page-locked memory is enqueued without the staging copy that holds the host for one out of pageable memory.
 void *rt_host_malloc(size_t bytes) __attribute__((weak));
 void rt_host_free(void *p) __attribute__((weak));
 

@@ -2,7 +2,8 @@
 // kernel bodies of csrc/hhe_kernel_bodies.h over (block, thread) with a barrier between
 // phases, so the `-m "not gpu"` suite can check the kernels' index arithmetic and the host
 // schedule against the oracle without a GPU.  It is never built into or loaded by the
-// product library (libhhe_gfx950.so), which has no CPU path.
+// product library (libhhe_gfx950.so), which has no CPU path.  The device runtime (rt_*: memory, streams, events) and the order in
+// which enqueued work runs are emu_order.cpp's.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -10,6 +11,7 @@
 #include <vector>
 #include "hhe_kernel_bodies.h"
 #include "hhe_launch.h"
+#include "emu_order.h"
 
 // -DHHE_RANGE_CHECK (this build only): a lazy value left its 64-bit range -- a bug in the range analysis, never a data error
 void hhe_range_violation(const char *what)
@@ -18,25 +20,10 @@ void hhe_range_violation(const char *what)
     abort();
 }
 
-const char *rt_backend_name() { return "cpu-emulator(tests-only)"; }
-const char *rt_last_error() { return "emu"; }
-int rt_set_device(int) { return 0; }
-void *rt_malloc(size_t b) { return malloc(b ? b : 8); }
-void rt_free(void *p) { free(p); }
-int rt_h2d(void *d, const void *s, size_t n, rt_stream) { memcpy(d, s, n); return 0; }
-int rt_d2h(void *d, const void *s, size_t n, rt_stream) { memcpy(d, s, n); return 0; }
-int rt_d2d(void *d, const void *s, size_t n, rt_stream) { memmove(d, s, n); return 0; }
-int rt_memset(void *d, int v, size_t n, rt_stream) { memset(d, v, n); return 0; }
-int rt_sync(rt_stream) { return 0; }
-rt_stream rt_stream_create() { static int dummy[8]; static int n = 0; return (rt_stream)&dummy[(n++) & 7]; }
-void rt_stream_destroy(rt_stream) {}
-void *rt_event_create() { static int ev; return &ev; }
-void rt_event_destroy(void *) {}
-void *rt_event_create_timed() { static int ev; return &ev; }
-float rt_event_elapsed_ms(void *, void *) { return 0.f; }
-int rt_event_record(void *, rt_stream) { return 0; }
-int rt_event_sync(void *) { return 0; }
-int rt_stream_wait_event(rt_stream, void *) { return 0; }
+// The kernel launchers as they run: every one loops its body to completion inside the call.  The entry points of hhe_launch.h at the
+// end of this file hand them to the stream model of emu_order.cpp, which runs them at once (the default) or when their stream is
+// forced (HHE_EMU_ORDER=lazy).
+namespace eager {
 
 template <int LOGM, bool STRIDED, bool INVERSE, int CC, int T, int SCH, int I, int S0, bool LAZY8 = false, bool TWL = false>
 static void rounds_fwd(const NttArgs &a, int bx, int by, u64 *lds, const u64 *twl)
@@ -114,7 +101,7 @@ void k_ntt_pass(const NttArgs &a, bool inverse, bool second, rt_stream)
     if (!inverse) { if (!second) launch_pass<true, false>(a, n1, n2); else launch_pass<false, false>(a, n2, n1); }
     else { if (!second) launch_pass<false, true>(a, n2, n1); else launch_pass<true, true>(a, n1, n2); }
 }
-void k_ntt2_fwd_first(const NttArgs &a1, const NttArgs &a2, rt_stream s) { k_ntt_pass(a1, false, false, s); k_ntt_pass(a2, false, false, s); }
+void k_ntt2_fwd_first(const NttArgs &a1, const NttArgs &a2, rt_stream s) { eager::k_ntt_pass(a1, false, false, s); eager::k_ntt_pass(a2, false, false, s); }
 template <int LOGM>
 static void ks_row_emu(const NttArgs &a, const KsRowArgs &x, const NttArgs &c0, int gx, int gy)
 {
@@ -239,8 +226,8 @@ int k_ks_perm_row(const NttArgs &a0, const KsRowArgs &x, rt_stream)
     }
     return 0;
 }
-void k_ntt2_fwd(const NttArgs &a1, const NttArgs &a2, rt_stream s) { k_ntt(a1, false, s); k_ntt(a2, false, s); }
-void k_ntt2_inv(const NttArgs &a1, const NttArgs &a2, rt_stream s) { k_ntt(a1, true, s); k_ntt(a2, true, s); }
+void k_ntt2_fwd(const NttArgs &a1, const NttArgs &a2, rt_stream s) { eager::k_ntt(a1, false, s); eager::k_ntt(a2, false, s); }
+void k_ntt2_inv(const NttArgs &a1, const NttArgs &a2, rt_stream s) { eager::k_ntt(a1, true, s); eager::k_ntt(a2, true, s); }
 #define LOOP(total, call)                                         \
     do {                                                          \
         const long long _t = (long long)(total);                  \
@@ -311,3 +298,61 @@ void k_pasta_plain(const PastaPlainArgs &a, rt_stream)
 void k_pasta_crypt(const PastaCryptArgs &a, rt_stream) { LOOP(a.S * a.nwords, pasta_crypt_body(a, (size_t)g)); }
 void k_decrypt_round(const DecryptArgs &a, rt_stream) { LOOP(a.B << a.logn, decrypt_round_body(a, (size_t)g)); }
 void k_decode_gather(const DecodeArgs &a, rt_stream) { LOOP(a.B << a.logn, decode_gather_body(a, (size_t)g)); }
+
+}  // namespace eager
+
+// ---------------------------------------------------------------- hhe_launch.h: every launch is an operation of its stream
+// The argument block is captured by value, as a kernel launch copies it; so is the one host array an argument points to (c0_row).
+// A launcher with a status returns what the host can know when it enqueues: whether the geometry is supported.
+#define ENQ(s, call) emu_enqueue(s, [=] { eager::call; })
+void k_ntt(const NttArgs &a, bool inverse, rt_stream s) { ENQ(s, k_ntt(a, inverse, nullptr)); }
+void k_ntt_pass(const NttArgs &a, bool inverse, bool second, rt_stream s) { ENQ(s, k_ntt_pass(a, inverse, second, nullptr)); }
+void k_ntt2_fwd(const NttArgs &a1, const NttArgs &a2, rt_stream s) { ENQ(s, k_ntt2_fwd(a1, a2, nullptr)); }
+void k_ntt2_fwd_first(const NttArgs &a1, const NttArgs &a2, rt_stream s) { ENQ(s, k_ntt2_fwd_first(a1, a2, nullptr)); }
+void k_ntt2_inv(const NttArgs &a1, const NttArgs &a2, rt_stream s) { ENQ(s, k_ntt2_inv(a1, a2, nullptr)); }
+int k_ks_row(const NttArgs &a, const KsRowArgs &x, const NttArgs *c0_row, rt_stream s)
+{
+    if (!a.lazy8 || (c0_row && !c0_row->lazy8)) { fprintf(stderr, "emu: k_ks_row on a modulus without the pseudo-Mersenne form\n"); abort(); }
+    if (!k_ks_row_supported(a.logn)) return -1;
+    const bool has_c0 = c0_row != nullptr;
+    const NttArgs c0 = has_c0 ? *c0_row : a;  // the caller's copy may go when the launcher returns
+    emu_enqueue(s, [=] { eager::k_ks_row(a, x, has_c0 ? &c0 : nullptr, nullptr); });
+    return 0;
+}
+int k_ks_perm_row(const NttArgs &a, const KsRowArgs &x, rt_stream s)
+{
+    if (!a.lazy8) { fprintf(stderr, "emu: k_ks_perm_row on a modulus without the pseudo-Mersenne form\n"); abort(); }
+    if (!k_ks_row_supported(a.logn)) return -1;
+    ENQ(s, k_ks_perm_row(a, x, nullptr));
+    return 0;
+}
+void k_elt(const EltArgs &a, int op, rt_stream s) { ENQ(s, k_elt(a, op, nullptr)); }
+void k_copy_items(const CopyItemsArgs &a, rt_stream s) { ENQ(s, k_copy_items(a, nullptr)); }
+void k_galois(const GaloisArgs &a, rt_stream s) { ENQ(s, k_galois(a, nullptr)); }
+void k_perm(const PermArgs &a, rt_stream s) { ENQ(s, k_perm(a, nullptr)); }
+void k_ks_mac(const KsMacArgs &a, rt_stream s) { ENQ(s, k_ks_mac(a, nullptr)); }
+int k_ks_mac_leaves(const KsMacLeavesArgs &a, rt_stream s)
+{
+    if (a.L < 1 || a.L > 4) return -1;
+    ENQ(s, k_ks_mac_leaves(a, nullptr));
+    return 0;
+}
+void k_ks_corr(const KsCorrArgs &a, rt_stream s) { ENQ(s, k_ks_corr(a, nullptr)); }
+void k_ks_finish(const KsFinishArgs &a, rt_stream s) { ENQ(s, k_ks_finish(a, nullptr)); }
+void k_leaf_sum(const LeafSumArgs &a, rt_stream s) { ENQ(s, k_leaf_sum(a, nullptr)); }
+void k_leaf_round(const LeafRoundArgs &a, rt_stream s) { ENQ(s, k_leaf_round(a, nullptr)); }
+void k_csum_add(const CsumArgs &a, rt_stream s) { ENQ(s, k_csum_add(a, nullptr)); }
+void k_csum_c0(const CsumArgs &a, rt_stream s) { ENQ(s, k_csum_c0(a, nullptr)); }
+void k_csum_digits(const CsumArgs &a, rt_stream s) { ENQ(s, k_csum_digits(a, nullptr)); }
+void k_add_plain(const AddPlainArgs &a, rt_stream s) { ENQ(s, k_add_plain(a, nullptr)); }
+void k_encode_scatter(const EncodeArgs &a, rt_stream s) { ENQ(s, k_encode_scatter(a, nullptr)); }
+void k_diag(const DiagArgs &a, rt_stream s) { ENQ(s, k_diag(a, nullptr)); }
+void k_bsgs_diag(const BsgsDiagArgs &a, rt_stream s) { ENQ(s, k_bsgs_diag(a, nullptr)); }
+void k_behz_extend(const BehzExtendArgs &a, rt_stream s) { ENQ(s, k_behz_extend(a, nullptr)); }
+void k_tensor(const TensorArgs &a, rt_stream s) { ENQ(s, k_tensor(a, nullptr)); }
+void k_behz_floor(const BehzFloorArgs &a, rt_stream s) { ENQ(s, k_behz_floor(a, nullptr)); }
+void k_pasta_xof(const PastaXofArgs &a, rt_stream s) { ENQ(s, k_pasta_xof(a, nullptr)); }
+void k_pasta_plain(const PastaPlainArgs &a, rt_stream s) { ENQ(s, k_pasta_plain(a, nullptr)); }
+void k_pasta_crypt(const PastaCryptArgs &a, rt_stream s) { ENQ(s, k_pasta_crypt(a, nullptr)); }
+void k_decrypt_round(const DecryptArgs &a, rt_stream s) { ENQ(s, k_decrypt_round(a, nullptr)); }
+void k_decode_gather(const DecodeArgs &a, rt_stream s) { ENQ(s, k_decode_gather(a, nullptr)); }

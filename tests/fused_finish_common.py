@@ -111,3 +111,41 @@ def check_one_call(api, lib, S, mem, monkeypatch, oracle_items=(1,), seed=79):
     r = same(S, mem, X1, X0, cw, ncw, ids, oracle_items=oracle_items)
     assert (kc.run(X1, S, mem, cw, ncw, ids) == r).all() and kc.counts(X1) == (0, 2)
     X1.close(), X0.close()
+
+
+def check_prediction(api, lib, S, mem, monkeypatch, in_place=False):
+    """key A twice, key B over the same counters, A again, under HHE_FIN_ITEM=1 (set by the caller): the second call is enqueued on the
+    prediction and confirmed (one launch), the third is enqueued on the prediction of A, refuted and finished again (two launches), the
+    fourth predicts B -- the key used last -- and is refuted too; every result is the oracle's for its key and the counts are what they
+    are without the item kernel.  in_place (numpy-backed memory only): every call reads the key ciphertext from ONE buffer, overwritten
+    between the calls -- what the key comparison sees is what the buffer holds when the comparison runs"""
+    X = dc.make_ctx(api, lib, S, monkeypatch)
+    X0 = dc.make_ctx(api, lib, S, monkeypatch, HHE_FIN_ITEM=0)
+    assert X.query("fin_item") == 1 and X0.query("fin_item") == 0
+    cw, ncw, ids = kc.words(S, 3, 81), [128, 9, 128], [0, 2, 0]
+    enc_b = kc.other_enc_key(S, 0)
+    key_a, key_b = mem.to_dev(S.enc_key), mem.to_dev(enc_b)
+    buf = mem.to_dev(S.enc_key) if in_place else None
+
+    def held(key):
+        if not in_place:
+            return key
+        buf[...] = key
+        return buf
+
+    launches, results = [], []
+    for key, want in ((key_a, (2, 0)), (key_a, (0, 2)), (key_b, (2, 0)), (key_a, (0, 2))):
+        before = X.query("fin_item_launches")
+        results.append(kc.run(X, S, mem, cw, ncw, ids, key=held(key)))
+        launches.append(X.query("fin_item_launches") - before)
+        assert kc.counts(X) == want
+        assert (kc.run(X0, S, mem, cw, ncw, ids, key=held(key)) == results[-1]).all() and kc.counts(X0) == want
+        assert X.query("ks_cache_entries") == X0.query("ks_cache_entries")
+    assert launches == [1, 1, 2, 2] and X0.query("fin_item_launches") == 0
+    assert (results[0] == results[1]).all() and (results[0] == results[3]).all() and (results[0] != results[2]).any()
+    assert (results[1][1] == dc.oracle_block(S, cw, ncw, ids, 1)).all()
+    assert (results[2][1] == dc.oracle_block(S, cw, ncw, ids, 1, enc_key=enc_b)).all()
+    # the snapshot used last is now A's again: a call with A is confirmed
+    before = X.query("fin_item_launches")
+    assert (kc.run(X, S, mem, cw, ncw, ids, key=held(key_a)) == results[0]).all() and X.query("fin_item_launches") == before + 1
+    X.close(), X0.close()

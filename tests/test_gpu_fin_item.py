@@ -80,29 +80,7 @@ def test_gpu_prediction(orc, api, lib, mem, monkeypatch, request, item, shape):
     """key A twice, key B over the same counters, A again: the second call is enqueued on the prediction and confirmed (one launch), the
     third is enqueued on the prediction of A, refuted and finished again (two launches), the fourth predicts B -- the key used last --
     and is refuted too; every result is the oracle's for its key and the counts are what they are without the item kernel"""
-    S = request.getfixturevalue(shape)
-    X = dc.make_ctx(api, lib, S, monkeypatch)
-    X0 = dc.make_ctx(api, lib, S, monkeypatch, HHE_FIN_ITEM=0)
-    assert X.query("fin_item") == 1 and X0.query("fin_item") == 0
-    cw, ncw, ids = kc.words(S, 3, 81), [128, 9, 128], [0, 2, 0]
-    enc_b = kc.other_enc_key(S, 0)
-    key_a, key_b = mem.to_dev(S.enc_key), mem.to_dev(enc_b)
-    launches, results = [], []
-    for key, want in ((key_a, (2, 0)), (key_a, (0, 2)), (key_b, (2, 0)), (key_a, (0, 2))):
-        before = X.query("fin_item_launches")
-        results.append(kc.run(X, S, mem, cw, ncw, ids, key=key))
-        launches.append(X.query("fin_item_launches") - before)
-        assert kc.counts(X) == want
-        assert (kc.run(X0, S, mem, cw, ncw, ids, key=key) == results[-1]).all() and kc.counts(X0) == want
-        assert X.query("ks_cache_entries") == X0.query("ks_cache_entries")
-    assert launches == [1, 1, 2, 2] and X0.query("fin_item_launches") == 0
-    assert (results[0] == results[1]).all() and (results[0] == results[3]).all() and (results[0] != results[2]).any()
-    assert (results[1][1] == dc.oracle_block(S, cw, ncw, ids, 1)).all()
-    assert (results[2][1] == dc.oracle_block(S, cw, ncw, ids, 1, enc_key=enc_b)).all()
-    # the snapshot used last is now A's again: a call with A is confirmed
-    before = X.query("fin_item_launches")
-    assert (kc.run(X, S, mem, cw, ncw, ids, key=key_a) == results[0]).all() and X.query("fin_item_launches") == before + 1
-    X.close(), X0.close()
+    ff.check_prediction(api, lib, request.getfixturevalue(shape), mem, monkeypatch)
 
 
 @pytest.mark.gpu

@@ -80,94 +80,15 @@ def test_all_distinct_call(orc, api, emu_lib, mem, small, monkeypatch):
 
 
 def test_enc_key_overwritten_in_place(orc, api, emu_lib, mem, small, monkeypatch):
-    """the caller's buffer is identified by its words: refilled with another key ciphertext it misses, refilled with the first one it
-    hits the older snapshot; a fifth key ciphertext drops the least recently used snapshot with its keystreams"""
-    S, ids, ncw = small, [0, 0], [128, 40]
-    cw = kc.words(S, 2, 7)
-    encs = [S.enc_key] + [kc.other_enc_key(S, k) for k in range(4)]
-    X = kc.ctx_on(api, emu_lib, S, monkeypatch)
-    buf = mem.to_dev(encs[0])
-    ra = kc.run(X, S, mem, cw, ncw, ids, key=buf)
-    assert kc.counts(X) == (1, 0)
-    buf[...] = encs[1]
-    rb = kc.run(X, S, mem, cw, ncw, ids, key=buf)
-    assert kc.counts(X) == (1, 0) and X.query("ks_cache_entries") == 2
-    fresh = kc.run(kc.ctx_off(api, emu_lib, S, monkeypatch), S, mem, cw, ncw, ids, key=mem.to_dev(encs[1]))
-    assert (rb == fresh).all() and not (rb == ra).all()
-    assert (rb[1] == dc.oracle_block(S, cw, ncw, ids, 1, enc_key=encs[1])).all()
-    buf[...] = encs[0]
-    assert (kc.run(X, S, mem, cw, ncw, ids, key=buf) == ra).all() and kc.counts(X) == (0, 1)
-    # snapshots now, least recently used first: encs[1], encs[0]; three more fill the four, the last of them drops encs[1]
-    for k in (2, 3):
-        buf[...] = encs[k]
-        kc.run(X, S, mem, cw, ncw, ids, key=buf)
-        assert kc.counts(X) == (1, 0)
-    assert X.query("ks_cache_entries") == 4
-    buf[...] = encs[4]
-    r4 = kc.run(X, S, mem, cw, ncw, ids, key=buf)
-    assert kc.counts(X) == (1, 0) and X.query("ks_cache_entries") == 4
-    assert (r4[1] == dc.oracle_block(S, cw, ncw, ids, 1, enc_key=encs[4])).all()
-    buf[...] = encs[0]
-    assert (kc.run(X, S, mem, cw, ncw, ids, key=buf) == ra).all() and kc.counts(X) == (0, 1)
-    buf[...] = encs[1]  # the dropped one: evaluated again, the same words
-    assert (kc.run(X, S, mem, cw, ncw, ids, key=buf) == rb).all() and kc.counts(X) == (1, 0)
+    kc.check_enc_key_overwritten_in_place(orc, api, emu_lib, mem, small, monkeypatch)
 
 
 def test_key_replaced_or_added(orc, api, emu_lib, mem, small, monkeypatch):
-    """a key of the default set replaced (Galois key of step -1, then the relinearization key) or added: the set is another object"""
-    S, O, ids, ncw = small, small.O, [2, 2], [128, 50]
-    cw = kc.words(S, 2, 8)
-    rk2, gk2 = kc.other_keys(S, 41)
-    e1 = int(O.galois_elt(-1))
-    i1 = [int(e) for e in S.gk.elts].index(e1)
-    X = kc.ctx_on(api, emu_lib, S, monkeypatch)
-    ra = kc.run(X, S, mem, cw, ncw, ids)
-    assert kc.counts(X) == (1, 0)
-
-    def fresh(rk, g1):
-        Y = kc.ctx_off(api, emu_lib, S, monkeypatch)
-        Y.set_relin_key(rk)
-        Y.set_galois_key(e1, g1)
-        return kc.run(Y, S, mem, cw, ncw, ids)
-
-    X.set_galois_key(e1, gk2.keys[i1])
-    rb = kc.run(X, S, mem, cw, ncw, ids)
-    assert kc.counts(X) == (1, 0) and X.query("ks_cache_entries") == 1  # what was kept under the replaced key is gone
-    assert (rb == fresh(S.rk, gk2.keys[i1])).all() and not (rb == ra).all()
-    X.set_relin_key(rk2)
-    rc = kc.run(X, S, mem, cw, ncw, ids)
-    assert kc.counts(X) == (1, 0)
-    assert (rc == fresh(rk2, gk2.keys[i1])).all() and not (rc == rb).all()
-    assert (kc.run(X, S, mem, cw, ncw, ids) == rc).all() and kc.counts(X) == (0, 1)
-    e5 = int(O.galois_elt(5))  # a key no transciphering uses: the serial is the set's
-    X.set_galois_key(e5, O.keygen_galois(S.sk, [e5], 43).keys[0])
-    assert (kc.run(X, S, mem, cw, ncw, ids) == rc).all() and kc.counts(X) == (1, 0)
+    kc.check_key_replaced_or_added(orc, api, emu_lib, mem, small, monkeypatch)
 
 
 def test_two_key_sets_and_a_destroyed_one(orc, api, emu_lib, mem, small, monkeypatch):
-    S, ids, ncw = small, [1, 1], [128, 3]
-    cw = kc.words(S, 2, 9)
-    rk2, gk2 = kc.other_keys(S, 51)
-    X = kc.ctx_on(api, emu_lib, S, monkeypatch, load=False)
-    A, B = kc.load_set(X, S.rk, S.gk), kc.load_set(X, rk2, gk2)
-    ra = kc.run(X, S, mem, cw, ncw, ids, rk=A, gk=A)
-    rb = kc.run(X, S, mem, cw, ncw, ids, rk=B, gk=B)
-    assert kc.counts(X) == (1, 0) and X.query("ks_cache_entries") == 2
-    assert (kc.run(X, S, mem, cw, ncw, ids, rk=A, gk=A) == ra).all() and kc.counts(X) == (0, 1)
-    assert (kc.run(X, S, mem, cw, ncw, ids, rk=B, gk=B) == rb).all() and kc.counts(X) == (0, 1)
-    rab = kc.run(X, S, mem, cw, ncw, ids, rk=A, gk=B)  # the pair is the identity, not either set
-    assert kc.counts(X) == (1, 0) and X.query("ks_cache_entries") == 3
-    Y = kc.ctx_off(api, emu_lib, S, monkeypatch, load=False)
-    kc.load_default(Y, rk2, gk2)
-    assert (ra == kc.run(kc.ctx_off(api, emu_lib, S, monkeypatch), S, mem, cw, ncw, ids)).all()
-    assert (rb == kc.run(Y, S, mem, cw, ncw, ids)).all() and not (ra == rb).all() and not (rab == ra).all() and not (rab == rb).all()
-    assert (rb[1] == S.O.transcipher_block(S.enc_key, rk2, gk2, cw[1, :3], 1)).all()
-    # a destroyed set takes its keystreams with it, and a new set (here: at the keys of B) never finds the old one's
-    A.close()
-    assert X.query("ks_cache_entries") == 1
-    Cs = kc.load_set(X, rk2, gk2)
-    assert (kc.run(X, S, mem, cw, ncw, ids, rk=Cs, gk=Cs) == rb).all() and kc.counts(X) == (1, 0)
-    assert (kc.run(X, S, mem, cw, ncw, ids, rk=B, gk=B) == rb).all() and kc.counts(X) == (0, 1)
+    kc.check_two_key_sets_and_a_destroyed_one(orc, api, emu_lib, mem, small, monkeypatch)
 
 
 def test_bsgs_and_diagonal_do_not_share(orc, api, emu_lib, mem, monkeypatch):
@@ -189,39 +110,11 @@ def test_bsgs_and_diagonal_do_not_share(orc, api, emu_lib, mem, monkeypatch):
 
 
 def test_budget_of_two_entries(orc, api, emu_lib, mem, small, monkeypatch):
-    S, cw = small, kc.words(small, 1, 11)
-    X = kc.ctx_on(api, emu_lib, S, monkeypatch, HHE_KS_CACHE_MB=2 * kc.ct_bytes(S) / 2**20)
-    r = [kc.run(X, S, mem, cw, [128], [ctr]) for ctr in (0, 1, 2)]
-    assert X.query("ks_cache_entries") == 2 and X.query("ks_cache_bytes") == 2 * kc.ct_bytes(S) and X.query("block_cache_entries") == 3
-    assert (kc.run(X, S, mem, cw, [128], [2]) == r[2]).all() and kc.counts(X) == (0, 1)
-    assert (kc.run(X, S, mem, cw, [128], [0]) == r[0]).all() and kc.counts(X) == (1, 0)  # the least recently used one had gone
-    assert (kc.run(X, S, mem, cw, [128], [2]) == r[2]).all() and kc.counts(X) == (0, 1)  # ... and now counter 1 has
-    assert (kc.run(X, S, mem, cw, [128], [1]) == r[1]).all() and kc.counts(X) == (1, 0)
-    assert X.query("ks_cache_entries") == 2
-    assert (r[0][0] == dc.oracle_block(S, cw, [128], [0], 0)).all()
+    kc.check_budget_of_two_entries(orc, api, emu_lib, mem, small, monkeypatch)
 
 
 def test_goes_with_the_block_tables_and_clearing(orc, api, emu_lib, mem, small, monkeypatch):
-    S, cw = small, kc.words(small, 2, 12)
-    X = kc.ctx_on(api, emu_lib, S, monkeypatch)
-    ra = kc.run(X, S, mem, cw[:1], [128], [0])
-    rb = kc.run(X, S, mem, cw[1:], [60], [1])
-    assert X.query("ks_cache_entries") == 2 and X.query("block_cache_entries") == 2
-    limit = X.query("block_cache_bytes")
-    X.set_block_cache_limit(limit - 1)  # the tables of counter 0 (least recently used) go, and its keystream with them
-    assert X.query("block_cache_entries") == 1 and X.query("ks_cache_entries") == 1 and X.query("ks_cache_bytes") == kc.ct_bytes(S)
-    X.set_block_cache_limit(limit)
-    r = kc.run(X, S, mem, cw, [128, 60], [0, 1])
-    assert kc.counts(X) == (1, 1) and (r[0] == ra[0]).all() and (r[1] == rb[0]).all()
-    assert X.query("ks_cache_entries") == 2
-    X.clear_keystream_cache()
-    assert X.query("ks_cache_entries") == 0 and X.query("ks_cache_bytes") == 0 and X.query("block_cache_entries") == 2
-    assert (kc.run(X, S, mem, cw, [128, 60], [0, 1]) == r).all() and kc.counts(X) == (2, 0)
-    X.clear_block_cache()
-    assert X.query("ks_cache_entries") == 0 and X.query("block_cache_entries") == 0
-    assert (kc.run(X, S, mem, cw, [128, 60], [0, 1]) == r).all() and kc.counts(X) == (2, 0)
-    assert (kc.run(X, S, mem, cw, [128, 60], [0, 1]) == r).all() and kc.counts(X) == (0, 2)
-    X.close()  # with entries and a snapshot resident
+    kc.check_goes_with_the_block_tables_and_clearing(orc, api, emu_lib, mem, small, monkeypatch)
 
 
 def test_decompose_two_records_in_two_calls(orc, api, emu_lib, mem, monkeypatch):
