@@ -482,6 +482,39 @@ public:
         check(hhe_copy_d2h(h(), vals, v.p, n_ * 8));
     }
 
+    // Decryptor::invariant_noise_budget (seal/decryptor.h:103) of the ciphertexts words[i], all [size][limbs][N] (limbs 0 = the data
+    // level), in ONE device call; sk: [K][N] NTT form.  The budgets in the order of `words`
+    std::vector<int> noise_budget(const std::vector<const uint64_t *> &words, size_t size, size_t limbs, const uint64_t *sk)
+    {
+        if (words.empty()) throw std::invalid_argument("noise_budget: no ciphertext");
+        const size_t l = limbs_or_data(limbs), w = size * l * n_;
+        DevBuf c(words.size() * w * 8);
+        for (size_t i = 0; i < words.size(); i++) check(hhe_copy_h2d(h(), c.u64() + i * w, words[i], w * 8));
+        std::vector<int32_t> b(words.size());
+        check(hhe_noise_budget(h(), sk, c.u64(), (int)size, (int)l, words.size(), b.data(), nullptr));
+        return std::vector<int>(b.begin(), b.end());
+    }
+    // ... of ciphertexts that may differ in size or level: one device call per (size, limbs) among them, i.e. one for what a service holds
+    struct NoiseItem { const uint64_t *words; size_t size, limbs; };
+    std::vector<int> noise_budget(const std::vector<NoiseItem> &items, const uint64_t *sk)
+    {
+        if (items.empty()) throw std::invalid_argument("noise_budget: no ciphertext");
+        std::vector<int> out(items.size());
+        std::vector<char> done(items.size(), 0);
+        for (size_t i = 0; i < items.size(); i++) {
+            if (done[i]) continue;
+            std::vector<const uint64_t *> group;
+            std::vector<size_t> at;
+            for (size_t j = i; j < items.size(); j++)
+                if (!done[j] && items[j].size == items[i].size && limbs_or_data(items[j].limbs) == limbs_or_data(items[i].limbs)) {
+                    group.push_back(items[j].words); at.push_back(j); done[j] = 1;
+                }
+            const std::vector<int> b = noise_budget(group, items[i].size, items[i].limbs, sk);
+            for (size_t k = 0; k < at.size(); k++) out[at[k]] = b[k];
+        }
+        return out;
+    }
+
     // ---- levels (SEALZpCipher::get_cipher_size(ct, mod_switch, levels_from_last), SEAL_Cipher.cpp:363-378).  A ciphertext below the
     // data level is a finished result: it can be switched further, measured and decrypted; every evaluation call refuses it.
     size_t limbs_or_data(size_t limbs) const

@@ -289,6 +289,17 @@ int hhe_decrypt(hhe_ctx *c, const uint64_t *sk_hptr, const uint64_t *ct_dptr, si
  * (Decryptor::invariant_noise_budget, seal/decryptor.h:103) is positive: a switch that drops too many primes leaves noise above
  * Q_level / 2t and the slots come back wrong, without an error, as in SEAL. */
 int hhe_decrypt_level(hhe_ctx *c, const uint64_t *sk_hptr, const uint64_t *ct_dptr, int limbs, size_t B, uint64_t *vals_dptr);
+/* Decryptor::invariant_noise_budget (seal/decryptor.h:103) of B ciphertexts ct [B][size][limbs][N] (coefficient form, size 2 or 3,
+ * 1 <= limbs <= L; sk_hptr [K][N] as above).  With Q = q_0 ... q_{limbs-1} and m the largest centred magnitude over the coefficients
+ * of t * (c0 + c1 s [+ c2 s^2]) mod Q:  norm_bits = bit_length(m) (0 for a zero noise polynomial),
+ * budget = max(0, bit_length(Q) - norm_bits - 1).  budget_hptr [B] and norm_bits_hptr [B] (may be NULL) are host arrays; norm_bits is
+ * there because the clamp at 0 hides the magnitude exactly where decryption fails.  One launch after the phase: exact mixed-radix
+ * conversion of every coefficient's residue column and a multi-word comparison with (Q+1)/2, one lane per coefficient
+ * (hhe_ctx_query("noise_form"): the limb count of the register form the last call took, 0 = the LDS form of more than 8 limbs).
+ * A null pointer other than norm_bits_hptr, B == 0, a size other than 2 or 3 or limbs outside 1..L return HHE_ERR_INVALID with both
+ * outputs untouched.  Synchronous. */
+int hhe_noise_budget(hhe_ctx *c, const uint64_t *sk_hptr, const uint64_t *ct_dptr, int size, int limbs, size_t B, int32_t *budget_hptr,
+                     uint32_t *norm_bits_hptr);
 
 /* ---- levels: modulus switching of finished results.  Evaluation (add, multiply, rotate, key switch, transciphering, affine
  *      layers, FC rows) stays at the data level; a lower-level ciphertext can be switched further, saved, loaded and decrypted. ---- */

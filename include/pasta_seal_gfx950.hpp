@@ -18,6 +18,7 @@
 // std::invalid_argument, std::logic_error).
 #pragma once
 #include <cstdint>
+#include <iostream>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -78,6 +79,20 @@ inline auto into(const HheContext &ctx, Ciphertext &ct, size_t size = 2)
     return [&ctx, &ct, size](size_t) { ct.words.resize(ctx.ct_words(size)); ct.size = size; ct.limbs = 0; return ct.words.data(); };
 }
 inline auto into(const HheContext &ctx, std::vector<Ciphertext> &cts) { return [&ctx, &cts](size_t i) { return into(ctx, cts[i])(0); }; }
+// Decryptor::invariant_noise_budget of ciphertexts at any level (size 2 or 3, a switched-down result at its limbs): one device call
+// for ciphertexts of one size and level
+inline std::vector<int> noise_budgets(HheContext &ctx, const std::vector<const Ciphertext *> &cts, const SecretKey &he_sk)
+{
+    const size_t n = ctx.poly_modulus_degree();
+    if (he_sk.words.size() != ctx.key_limbs() * n) throw std::invalid_argument("invariant_noise_budget: no secret key");
+    std::vector<hhe::AdapterCore::NoiseItem> items;
+    for (const Ciphertext *ct : cts) {
+        if (ct->size < 2 || ct->words.size() != ct->size * ctx.limbs_or_data(ct->limbs) * n)
+            throw std::invalid_argument("encrypted is not valid for encryption parameters");
+        items.push_back({ct->words.data(), ct->size, ct->limbs});
+    }
+    return ctx.noise_budget(items, he_sk.words.data());
+}
 }  // namespace detail
 
 class SEALZpCipher {
@@ -119,6 +134,31 @@ public:
             });
         }
         return context->saved_size(ct.size, ct.limbs);
+    }
+    // SEALZpCipher::print_noise (SEAL_Cipher.cpp:71-99): Decryptor::invariant_noise_budget with this object's secret key, on the device
+    // (one batched call for the vector), the reference's lines on std::cout and its return values.  An empty vector, where the
+    // reference reads ciphs[0], and an object without a secret key throw std::invalid_argument
+    int print_noise() { return print_noise(secret_key_encrypted); }
+    int print_noise(std::vector<Ciphertext> &ciphs)
+    {
+        if (ciphs.empty()) throw std::invalid_argument("print_noise: no ciphertext");
+        std::vector<const Ciphertext *> p;
+        for (auto &ct : ciphs) p.push_back(&ct);
+        const std::vector<int> budget = detail::noise_budgets(*context, p, he_sk);
+        int min = budget[0], max = min;
+        for (int b : budget) {
+            if (b > max) max = b;
+            if (b < min) min = b;
+        }
+        std::cout << "min noise budget: " << min << std::endl;
+        std::cout << "max noise budget: " << max << std::endl;
+        return min;
+    }
+    int print_noise(Ciphertext &ciph)
+    {
+        const int noise = detail::noise_budgets(*context, {&ciph}, he_sk)[0];
+        std::cout << "noise budget: " << noise << std::endl;
+        return noise;
     }
     virtual std::string get_cipher_name() const = 0;
     virtual std::vector<Ciphertext> HE_decrypt(std::vector<uint64_t> &ciphertext, bool batch_encoder = false) = 0;
@@ -345,6 +385,13 @@ inline std::vector<int64_t> decrypting(const pasta::Ciphertext &enc_input, const
     std::vector<int64_t> out(size);
     for (size_t i = 0; i < size; i++) out[i] = u[i] > half ? (int64_t)u[i] - (int64_t)t : (int64_t)u[i];
     return out;
+}
+
+// Decryptor::invariant_noise_budget (seal/decryptor.h:103) of a ciphertext of size 2 or 3 at its level, on the device: what tells whether
+// `decrypting` returns the right slots (a budget of 0 means it does not)
+inline int invariant_noise_budget(const pasta::Ciphertext &enc_input, const pasta::SecretKey &he_sk, pasta::HheContext &ctx)
+{
+    return pasta::detail::noise_budgets(ctx, {&enc_input}, he_sk)[0];
 }
 
 // sealhelper::packed_enc_multiply, Evaluator::relinearize_inplace(record, csp_rk) and sealhelper::encrypted_vec_sum as

@@ -16,6 +16,7 @@
 // reference's SEAL 4.0.0 headers (g++ -fsyntax-only; the prebuilt libseal is never linked or loaded): it is not executed here.
 #pragma once
 
+#include <iostream>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -211,6 +212,14 @@ protected:
     // evicts them; null for an empty key object (declared after `device`: released while the context exists)
     hhe::KeySet rk_set, gk_set;
 
+    std::vector<int> noise_budgets(const std::vector<const seal::Ciphertext *> &cts)
+    {
+        if (he_sk.data().coeff_count() != device->key_limbs() * mod_degree) throw std::invalid_argument("invariant_noise_budget: no secret key");
+        std::vector<hhe::AdapterCore::NoiseItem> items;
+        for (const seal::Ciphertext *ct : cts) items.push_back({device->level_words(*ct), ct->size(), ct->coeff_modulus_size()});
+        return device->noise_budget(items, he_sk.data().data());
+    }
+
 public:
     // src/pasta/SEAL_Cipher.cpp:9-36 (all arguments by value, as the reference takes them)
     SEALZpCipher(ZpCipherParams params, std::shared_ptr<seal::SEALContext> con, seal::PublicKey pk, seal::SecretKey sk,
@@ -245,6 +254,32 @@ public:
                                gfx950::DeviceContext::into_level(*context, ct, c->parms_id(), ct.size()));
         } else device->level_words(ct);
         return device->saved_size(ct.size(), ct.coeff_modulus_size());
+    }
+
+    // SEALZpCipher::print_noise (SEAL_Cipher.cpp:71-99): Decryptor::invariant_noise_budget with he_sk, on the device (one batched call for
+    // the vector; a ciphertext below the data level at its coeff_modulus_size), the reference's lines on std::cout and its return
+    // values.  An empty vector, where the reference reads ciphs[0], and an object without a secret key throw std::invalid_argument
+    int print_noise() { return print_noise(secret_key_encrypted); }
+    int print_noise(std::vector<seal::Ciphertext> &ciphs)
+    {
+        if (ciphs.empty()) throw std::invalid_argument("print_noise: no ciphertext");
+        std::vector<const seal::Ciphertext *> p;
+        for (auto &ct : ciphs) p.push_back(&ct);
+        const std::vector<int> budget = noise_budgets(p);
+        int min = budget[0], max = min;
+        for (int b : budget) {
+            if (b > max) max = b;
+            if (b < min) min = b;
+        }
+        std::cout << "min noise budget: " << min << std::endl;
+        std::cout << "max noise budget: " << max << std::endl;
+        return min;
+    }
+    int print_noise(seal::Ciphertext &ciph)
+    {
+        const int noise = noise_budgets({&ciph})[0];
+        std::cout << "noise budget: " << noise << std::endl;
+        return noise;
     }
 
     void add_some_gk_indices(std::vector<int> &gk_ind)
@@ -359,7 +394,7 @@ public:
         return enc_sk;
     }
 
-    // pasta_3_seal.cpp:42-104 == decomposition(ciphertexts, secret_key_encrypted) without the debug noise printing (:73)
+    // pasta_3_seal.cpp:42-104 == decomposition(ciphertexts, secret_key_encrypted) without the debug noise printing (:73; print_noise() is there to call)
     virtual std::vector<seal::Ciphertext> HE_decrypt(std::vector<uint64_t> &ciphertext, bool batch_encoder = false)
     {
         return decomposition(ciphertext, secret_key_encrypted, batch_encoder);

@@ -43,6 +43,7 @@ _SYMBOLS = [
     "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin", "hhe_keyset_generate_galois",
     "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
     "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level",
+    "hhe_noise_budget",
 ]
 
 
@@ -50,7 +51,8 @@ _SYMBOLS = [
 # that needs one raises when it is not
 _OPTIONAL = {"hhe_pasta3_clear_keystream_cache", "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin",
              "hhe_keyset_generate_galois", "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
-             "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level"}
+             "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level",
+             "hhe_noise_budget"}
 
 
 def exported_symbols():
@@ -455,6 +457,18 @@ class Context:
         sk = np.ascontiguousarray(sk, dtype=np.uint64)
         assert sk.size >= limbs * self.n
         self._chk(self.lib.hhe_decrypt_level(self.h, _ptr(sk), _ptr(ct), C.c_int(limbs), C.c_size_t(B), _ptr(vals_out)))
+
+    def noise_budget(self, sk, ct, B, size=2, limbs=None, with_bits=False):
+        """Decryptor::invariant_noise_budget of B ciphertexts.  sk: host uint64 [K][N]; ct device [B][size][limbs][N] (limbs: L when
+        None).  Returns the budgets as an int32 array [B], or (budget, norm_bits) with the bit counts of the largest centred noise
+        coefficients (uint32 [B]) when with_bits is set"""
+        limbs = self.L if limbs is None else limbs
+        sk = np.ascontiguousarray(sk, dtype=np.uint64)
+        assert sk.size >= max(limbs, 0) * self.n
+        budget, bits = np.zeros(B, np.int32), np.zeros(B, np.uint32)
+        self._chk(self.lib.hhe_noise_budget(self.h, _ptr(sk), _ptr(ct), C.c_int(size), C.c_int(limbs), C.c_size_t(B), _ptr(budget),
+                                            _ptr(bits) if with_bits else _ptr(None)))
+        return (budget, bits) if with_bits else budget
 
     def seal_save_ciphertext_level(self, ct, ct_size, limbs, parms_id):
         need = C.c_size_t(0)

@@ -71,6 +71,35 @@ extern "C" int hhe_pasta3_plain_crypt(hhe_ctx *c, const uint64_t *key, const uin
     return HHE_OK;
 }
 
+// The phase of B ciphertexts [B][size][L][N] (coefficient form) under q_0 .. q_{L-1} without its c0: c1s [B][L][N] = c1 s (+ c2 s^2 for
+// size 3), coefficient form.  dsk [L][N] = the level's limbs of the key-level secret key on the device; s2 (size 3 only) is scratch:
+// [L][N] for s^2, then [B][L][N] for the transform of c2 between its passes (its last pass adds into c1s).  Forward transform of c1
+// with the dyadic product fused into the store, for size 3 the transform of c2 multiplied by s^2 and added in its store, one inverse
+// transform.  Enqueued on st.
+static void phase_c1s(hhe_ctx *c, const u64 *dsk, u64 *s2, const uint64_t *ct, int size, const int L, size_t B, u64 *c1s, rt_stream st)
+{
+    const size_t ln = (size_t)L * c->n;
+    NttArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = ct + ln; a.dst = c1s; a.mods = c->d_mods; a.logn = c->logn; a.count = (int)(B * L);
+    a.mod_base = 0; a.mod_cycle = L; a.src_div = 1; a.src_item_polys = L; a.src_item_stride = (size_t)size * ln; a.t = c->t;
+    a.load_op = LOAD_PLAIN; a.store_op = STORE_MUL; a.mul = dsk; a.mul_cycle = L; a.mul_item_polys = 1;
+    a.L = L; a.K = c->K; a.ks = c->ksc; a.lazy8 = ntt_lazy8(c, 0, L);
+    k_ntt(a, false, st);
+    if (size == 3) {
+        EltArgs e;
+        memset(&e, 0, sizeof(e));
+        e.a = dsk; e.b = dsk; e.out = s2; e.mods = c->d_mods; e.logn = c->logn; e.count = L; e.mod_base = 0; e.mod_cycle = L;
+        k_elt(e, ELT_MUL, st);  // s^2, a dyadic product of the uploaded key (NTT form)
+        NttArgs m = a;
+        m.src = ct + 2 * ln; m.dst = s2 + ln; m.store_op = STORE_MAC; m.mul = s2; m.acc = c1s;
+        k_ntt(m, false, st);
+    }
+    NttArgs inv = a;
+    inv.src = c1s; inv.src_item_polys = 0; inv.src_item_stride = 0; inv.store_op = STORE_PLAIN; inv.mul = nullptr;
+    k_ntt(inv, true, st);
+}
+
 // Decryption under q_0 .. q_{L-1} for any 1 <= L <= c->L: every constant below is derived from the limb count of the call (a level of
 // the modulus chain is the context with its last data primes dropped; gamma and t do not change)
 static int decrypt_level(hhe_ctx *c, const uint64_t *sk, const uint64_t *ct, const int L, size_t B, uint64_t *vals)
@@ -80,18 +109,7 @@ static int decrypt_level(hhe_ctx *c, const uint64_t *sk, const uint64_t *ct, con
     DevBuf dsk(ln * 8), c1s(B * ln * 8), plain(B * n * 8);
     if (!dsk.p || !c1s.p || !plain.p) return dev_fail("hhe_decrypt");
     if (rt_h2d(dsk.p, sk, ln * 8, st)) return dev_fail("hhe_decrypt");  // the level's limbs of the key-level secret key
-
-    // c1 * s: forward transform of c1 with the dyadic product fused into the store, inverse transform
-    NttArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = ct + ln; a.dst = c1s.w(); a.mods = c->d_mods; a.logn = c->logn; a.count = (int)(B * L);
-    a.mod_base = 0; a.mod_cycle = L; a.src_div = 1; a.src_item_polys = L; a.src_item_stride = 2 * ln; a.t = c->t;
-    a.load_op = LOAD_PLAIN; a.store_op = STORE_MUL; a.mul = dsk.w(); a.mul_cycle = L; a.mul_item_polys = 1;
-    a.L = L; a.K = c->K; a.ks = c->ksc; a.lazy8 = ntt_lazy8(c, 0, L);
-    k_ntt(a, false, st);
-    NttArgs inv = a;
-    inv.src = c1s.w(); inv.src_item_polys = 0; inv.src_item_stride = 0; inv.store_op = STORE_PLAIN; inv.mul = nullptr;
-    k_ntt(inv, true, st);
+    phase_c1s(c, dsk.w(), nullptr, ct, 2, L, B, c1s.w(), st);
 
     DecryptArgs d;
     memset(&d, 0, sizeof(d));
@@ -146,6 +164,61 @@ extern "C" int hhe_decrypt_level(hhe_ctx *c, const uint64_t *sk, const uint64_t 
     HHE_LOCK(c);
     if (!c || !sk || !ct || !vals || B == 0 || limbs < 1 || limbs > c->L) return fail(HHE_ERR_INVALID, "hhe_decrypt_level: bad arguments (1 <= limbs <= L)");
     return decrypt_level(c, sk, ct, limbs, B, vals);
+}
+
+// Decryptor::invariant_noise_budget (seal/decryptor.h:103) of B ciphertexts at one level: the phase as in decryption, then one launch
+// (noise_bits, hhe_client_bodies.h) that leaves the significant bits of the largest centred coefficient of t * phase mod Q per item.
+// Q and (Q+1)/2 for the call's level are made here, word by word, and travel in the argument block.
+extern "C" int hhe_noise_budget(hhe_ctx *c, const uint64_t *sk, const uint64_t *ct, int size, int limbs, size_t B, int32_t *budget,
+                                uint32_t *norm_bits)
+{
+    HHE_LOCK(c);
+    if (!c || !sk || !ct || !budget || B == 0) return fail(HHE_ERR_INVALID, "hhe_noise_budget: bad arguments");
+    if (size < 2 || size > 3) return fail(HHE_ERR_INVALID, "hhe_noise_budget: ciphertext size must be 2 or 3");
+    if (limbs < 1 || limbs > c->L) return fail(HHE_ERR_INVALID, "hhe_noise_budget: bad arguments (1 <= limbs <= L)");
+    const int L = limbs;
+    const size_t n = c->n, ln = (size_t)L * n;
+    if (B > ((size_t)1 << 30) / L) return fail(HHE_ERR_INVALID, "hhe_noise_budget: batch too large");
+    rt_stream st = c->lanes[0].stream;
+    DevBuf dsk((size == 3 ? 2 + B : 1) * ln * 8), c1s(B * ln * 8), dbits(B * 4);  // the key | size 3: phase_c1s' scratch
+    if (!dsk.p || !c1s.p || !dbits.p) return dev_fail("hhe_noise_budget");
+    if (rt_h2d(dsk.p, sk, ln * 8, st) || rt_memset(dbits.p, 0, B * 4, st)) return dev_fail("hhe_noise_budget");
+    phase_c1s(c, dsk.w(), dsk.w() + ln, ct, size, L, B, c1s.w(), st);
+
+    DecryptArgs d;
+    memset(&d, 0, sizeof(d));
+    d.mode = DEC_NOISE; d.size = size; d.mods = c->d_mods; d.ct = ct; d.c1s = c1s.w(); d.logn = c->logn; d.L = L; d.B = B;
+    d.t = c->t; d.pairs = c->d_moddown; d.bits = (u32 *)dbits.p;
+    d.cj[0] = 1;  // Q = q_0 ... q_{L-1} < 2^(64 L): L words
+    for (int j = 0; j < L; ++j) {
+        u64 carry = 0;
+        for (int w = 0; w < L; ++w) {
+            const u128 p = (u128)d.cj[w] * c->q[j] + carry;
+            d.cj[w] = (u64)p; carry = (u64)(p >> 64);
+        }
+        d.pg[j] = c->t % c->q[j];
+    }
+    int q_bits = 0;
+    for (int w = 0; w < L; ++w)
+        if (d.cj[w]) q_bits = 64 * w + 64 - __builtin_clzll(d.cj[w]);
+    {   // (Q+1)/2 = (Q >> 1) + (Q & 1)
+        u64 carry = d.cj[0] & 1;
+        for (int w = 0; w < L; ++w) {
+            const u64 sh = (d.cj[w] >> 1) | (w + 1 < L ? d.cj[w + 1] << 63 : 0);
+            d.pt[w] = sh + carry;
+            carry = d.pt[w] < sh;
+        }
+    }
+    k_decrypt_round(d, st);
+    c->noise_form = L <= NOISE_REGS ? L : 0;
+    std::vector<u32> bits(B);
+    if (rt_d2h(bits.data(), dbits.p, B * 4, st) || rt_sync(st)) return dev_fail("hhe_noise_budget");
+    for (size_t b = 0; b < B; ++b) {
+        const int v = q_bits - (int)bits[b] - 1;
+        budget[b] = v > 0 ? v : 0;
+        if (norm_bits) norm_bits[b] = bits[b];
+    }
+    return HHE_OK;
 }
 
 // ------------------------------------------------------------------ key generation and public-key encryption from a seed

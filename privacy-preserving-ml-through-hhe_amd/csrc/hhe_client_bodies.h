@@ -246,11 +246,18 @@ struct DecryptArgs {
     size_t B;
     u64 t, t_rlo, t_rhi, gamma, g_rlo, g_rhi;
     u64 neg_inv_q_t, neg_inv_q_g, inv_g_t;
-    u64 cj[HHE_MAXL];  // t*gamma * (Q/q_j)^-1 mod q_j
-    u64 pt[HHE_MAXL];  // Q/q_j mod t
-    u64 pg[HHE_MAXL];  // Q/q_j mod gamma
+    u64 cj[HHE_MAXL];  // t*gamma * (Q/q_j)^-1 mod q_j                  | noise mode: the words of Q = q_0 ... q_{L-1}, zero above
+    u64 pt[HHE_MAXL];  // Q/q_j mod t                                   | noise mode: the words of (Q+1)/2
+    u64 pg[HHE_MAXL];  // Q/q_j mod gamma                               | noise mode: t mod q_j
+    // DEC_NOISE (noise_body below): the launch writes no plaintext; size = polynomials per item of ct (c1s then holds c1 s + c2 s^2),
+    // pairs = the context's pair table (hhe_ctx::d_moddown: q_m^-1 mod q_j and its Shoup quotient at mod_down_pair(m, j)),
+    // bits [B] = the largest significant-bit count of the items' centred noise coefficients (cleared by the caller)
+    int mode, size;
+    const u64 *pairs;
+    u32 *bits;
 };
-HD void decrypt_round_body(const DecryptArgs &a, size_t gid)
+enum DecryptMode { DEC_ROUND = 0, DEC_NOISE = 1 };
+HD void decrypt_scale_body(const DecryptArgs &a, size_t gid)
 {
     const size_t n = (size_t)1 << a.logn;
     if (gid >= a.B * n) return;
@@ -272,6 +279,161 @@ HD void decrypt_round_body(const DecryptArgs &a, size_t gid)
     if (vg > (a.gamma >> 1)) d = addmod(vt, reduce64(a.gamma - vg, mt), a.t);
     else d = submod(vt, reduce64(vg, mt), a.t);
     a.plain[gid] = mulmod(d, a.inv_g_t, mt);
+}
+
+// ------------------------------------------------------------------ invariant noise budget (DecryptArgs::mode = DEC_NOISE)
+// Decryptor::invariant_noise_budget (seal/decryptor.h:103): the largest centred magnitude of t * (c0 + c1 s [+ c2 s^2]) mod Q over the
+// coefficients of an item, as a bit count.  One lane owns one coefficient.  Its column v_j = phase_j * (t mod q_j) is converted to mixed
+// radix from the top prime down -- the loop of mod_down_body without the rounding term:
+//   e_m = v_m;   v_j <- (v_j - (e_m mod q_j)) * q_m^-1 mod q_j   for j < m        (e_m may be far above q_j: a full reduction)
+// so that x = e_{L-1} + q_{L-1} (e_{L-2} + ... + q_1 e_0) is the representative in [0, Q).  Horner from e_0 upward builds it IN the column:
+// after step m the integer below q_0 ... q_m < 2^(64 (m + 1)) fills words 0 .. m, whose digits have been used, and the digits above m are
+// still there.  x >= (Q+1)/2 is replaced by Q - x, and only the bit count 64 k + 64 - clz(top non-zero word) leaves the lane: the
+// largest bit count is the bit count of the largest magnitude.
+// LIM > 0: the column in registers, every index a compile-time constant.  LIM = 0: any limb count, the column at col[j * cs] (the
+// lane's own words of the workgroup's LDS block, nobody else touches them: no barrier; in the tests-only emulator a local array).
+struct NoisePair { u64 inv, inv_s; };
+HD NoisePair noise_pair_at(const u64 *tab, int m, int j)
+{
+    NoisePair c;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const __attribute__((address_space(4))) u64 *p = (const __attribute__((address_space(4))) u64 *)(tab + mod_down_pair(m, j));
+#else
+    const u64 *p = tab + mod_down_pair(m, j);
+#endif
+    c.inv = p[0]; c.inv_s = p[1];
+    return c;
+}
+HD u64 noise_word(const DecryptArgs &a, size_t b, size_t i, int j)
+{
+    const ModDev m = mod_at(a.mods, j);
+    const u64 ph = addmod(a.ct[((b * a.size * a.L + j) << a.logn) + i], a.c1s[((b * a.L + j) << a.logn) + i], m.q);
+    return mulmod(ph, a.pg[j], m);
+}
+HD u64 noise_digit_step(u64 vj, u64 e, const ModDev &mj, const NoisePair &c)
+{
+    return shoup_mul(submod(vj, reduce64(e, mj), mj.q), c.inv, c.inv_s, mj.q);
+}
+// one word of X * q + carry; the new carry is below q (hi <= q - 1 with the carry-out of the low sum: (2^64 - 1) q + 2^64 - 1 < 2^64 (q + 1))
+HD u64 noise_horner_word(u64 &x, u64 q, u64 carry)
+{
+    const u64 lo = x * q, hi = mulhi64(x, q);
+    x = lo + carry;
+    return hi + (x < lo);
+}
+// significant bits of the lane's coefficient; 0 for a lane past the batch
+template <int LIM> HD u32 noise_bits(const DecryptArgs &a, size_t gid, u64 *col, int cs)
+{
+    const size_t n = (size_t)1 << a.logn;
+    if (gid >= a.B * n) return 0;
+    const size_t b = gid >> a.logn, i = gid & (n - 1);
+    u32 bits = 0;
+    if constexpr (LIM > 0) {
+        u64 x[LIM];
+#pragma unroll
+        for (int j = 0; j < LIM; j++) x[j] = noise_word(a, b, i, j);
+#pragma unroll
+        for (int m = LIM - 1; m >= 1; m--)
+#pragma unroll
+            for (int j = 0; j < m; j++) x[j] = noise_digit_step(x[j], x[m], mod_at(a.mods, j), noise_pair_at(a.pairs, m, j));
+#pragma unroll
+        for (int m = 1; m < LIM; m++) {
+            const u64 qm = mod_at(a.mods, m).q;
+            u64 carry = x[m];
+#pragma unroll
+            for (int w = 0; w < m; w++) carry = noise_horner_word(x[w], qm, carry);
+            x[m] = carry;
+        }
+        bool ge = true, open = true;
+#pragma unroll
+        for (int w = LIM - 1; w >= 0; w--) {
+            const u64 h = a.pt[w];
+            if (open && x[w] != h) { ge = x[w] > h; open = false; }
+        }
+        u64 borrow = 0;
+#pragma unroll
+        for (int w = 0; w < LIM; w++) {
+            const u64 qw = a.cj[w], d = qw - x[w], y = ge ? d - borrow : x[w];
+            borrow = (u64)(qw < x[w]) | (u64)(d < borrow);
+            if (y) bits = 64u * w + 64u - (u32)__builtin_clzll(y);
+        }
+    } else {
+        const int L = a.L;
+        for (int j = 0; j < L; j++) col[j * cs] = noise_word(a, b, i, j);
+        for (int m = L - 1; m >= 1; m--) {
+            const u64 e = col[m * cs];
+            for (int j = 0; j < m; j++) col[j * cs] = noise_digit_step(col[j * cs], e, mod_at(a.mods, j), noise_pair_at(a.pairs, m, j));
+        }
+        for (int m = 1; m < L; m++) {
+            const u64 qm = mod_at(a.mods, m).q;
+            u64 carry = col[m * cs];
+            for (int w = 0; w < m; w++) {
+                u64 x = col[w * cs];
+                carry = noise_horner_word(x, qm, carry);
+                col[w * cs] = x;
+            }
+            col[m * cs] = carry;
+        }
+        bool ge = true;
+        for (int w = L - 1; w >= 0; w--) {
+            const u64 h = a.pt[w], x = col[w * cs];
+            if (x != h) { ge = x > h; break; }
+        }
+        u64 borrow = 0;
+        for (int w = 0; w < L; w++) {
+            const u64 qw = a.cj[w], x = col[w * cs], d = qw - x, y = ge ? d - borrow : x;
+            borrow = (u64)(qw < x) | (u64)(d < borrow);
+            if (y) bits = 64u * w + 64u - (u32)__builtin_clzll(y);
+        }
+    }
+    return bits;
+}
+// bits[b] = max(bits[b], the lane's count).  On the device the 64 lanes of a wave share an item from N = 64 on (a launch covers B * N lanes
+// and a workgroup is a multiple of 64): a wave max, then one 32-bit atomic max per wave.  The tests-only emulator loops the lanes
+// under OpenMP: a compare-exchange max on the same word.
+HD void noise_commit(const DecryptArgs &a, size_t gid, u32 bits)
+{
+    const bool live = gid < (a.B << a.logn);
+    const size_t b = gid >> a.logn;
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (a.logn >= 6) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const u32 o = (u32)__shfl_xor((int)bits, off, 64);
+            bits = o > bits ? o : bits;
+        }
+        if (live && (threadIdx.x & 63) == 0 && bits) atomicMax(a.bits + b, bits);
+    } else if (live && bits) atomicMax(a.bits + b, bits);
+#else
+    if (!live) return;
+    u32 cur = __atomic_load_n(a.bits + b, __ATOMIC_RELAXED);
+    while (cur < bits && !__atomic_compare_exchange_n(a.bits + b, &cur, bits, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+#endif
+}
+constexpr int NOISE_REGS = 8;  // = MOD_DOWN_REGS: the limb counts with a register form
+// the form a launch of L limbs takes, as k_decrypt_round picks the kernel on the device
+HD void noise_any(const DecryptArgs &a, size_t gid)
+{
+    u64 col[HHE_MAXL];
+    u32 bits;
+    switch (a.L <= NOISE_REGS ? a.L : 0) {
+    case 1: bits = noise_bits<1>(a, gid, nullptr, 0); break;
+    case 2: bits = noise_bits<2>(a, gid, nullptr, 0); break;
+    case 3: bits = noise_bits<3>(a, gid, nullptr, 0); break;
+    case 4: bits = noise_bits<4>(a, gid, nullptr, 0); break;
+    case 5: bits = noise_bits<5>(a, gid, nullptr, 0); break;
+    case 6: bits = noise_bits<6>(a, gid, nullptr, 0); break;
+    case 7: bits = noise_bits<7>(a, gid, nullptr, 0); break;
+    case 8: bits = noise_bits<8>(a, gid, nullptr, 0); break;
+    default: bits = noise_bits<0>(a, gid, col, 1); break;
+    }
+    noise_commit(a, gid, bits);
+}
+// the launch as the tests-only emulator loops it; on the device every form of either mode is a kernel of its own
+HD void decrypt_round_body(const DecryptArgs &a, size_t gid)
+{
+    if (a.mode == DEC_NOISE) noise_any(a, gid);
+    else decrypt_scale_body(a, gid);
 }
 // BatchEncoder::decode (seal/batchencoder.h:282): after the forward NTT mod t, slot i = ntt[index_map[i]]
 struct DecodeArgs {

@@ -214,6 +214,7 @@ struct hhe_ctx {
     KsConsts ksc{};
     u64 *d_moddown = nullptr;      // modulus switching: per pair j < m < L three words at mod_down_pair(m, j) (hhe_common.h), written once
     u64 mod_switch_launches = 0;   // kernel launches of hhe_mod_switch (hhe_ctx_query("mod_switch_launches"))
+    int noise_form = 0;            // the form the last hhe_noise_budget launch took: its limb count (register form) or 0 (LDS form) (hhe_ctx_query("noise_form"))
 
     // device tables
     ModDev *d_mods = nullptr;

@@ -759,7 +759,37 @@ void k_pasta_plain(const PastaPlainArgs &a, rt_stream s)
     if (a.nblocks > 0) hipLaunchKernelGGL(pasta_plain_kernel, dim3(a.nblocks), dim3(PASTA_PLAIN_THREADS), 0, (hipStream_t)s, a);
 }
 void k_pasta_crypt(const PastaCryptArgs &a, rt_stream s) { LAUNCH1D(pasta_crypt_kernel, a.S * a.nwords, s, a); }
-__global__ void __launch_bounds__(ELT_THREADS) decrypt_round_kernel(DecryptArgs a) { decrypt_round_body(a, GID); }
+__global__ void __launch_bounds__(ELT_THREADS) decrypt_round_kernel(DecryptArgs a) { decrypt_scale_body(a, GID); }
+// DEC_NOISE: one kernel per register form (L <= NOISE_REGS), and the LDS form for longer chains -- L * ELT_THREADS words of dynamic LDS
+// (HHE_MAXL limbs: 64 KiB; the multi-word integer grows in the column's own words), lane t's column at words t, t + ELT_THREADS, ...
+template <int LIM> __global__ void __launch_bounds__(ELT_THREADS) noise_kernel(DecryptArgs a) { noise_commit(a, GID, noise_bits<LIM>(a, GID, nullptr, 0)); }
+__global__ void __launch_bounds__(ELT_THREADS) noise_lds_kernel(DecryptArgs a)
+{
+    extern __shared__ u64 noise_cols[];
+    noise_commit(a, GID, noise_bits<0>(a, GID, noise_cols + threadIdx.x, ELT_THREADS));
+}
+static void launch_noise(const DecryptArgs &a, rt_stream s)
+{
+    const size_t total = a.B << a.logn;
+    switch (a.L <= NOISE_REGS ? a.L : 0) {
+    case 1: LAUNCH1D(noise_kernel<1>, total, s, a); break;
+    case 2: LAUNCH1D(noise_kernel<2>, total, s, a); break;
+    case 3: LAUNCH1D(noise_kernel<3>, total, s, a); break;
+    case 4: LAUNCH1D(noise_kernel<4>, total, s, a); break;
+    case 5: LAUNCH1D(noise_kernel<5>, total, s, a); break;
+    case 6: LAUNCH1D(noise_kernel<6>, total, s, a); break;
+    case 7: LAUNCH1D(noise_kernel<7>, total, s, a); break;
+    case 8: LAUNCH1D(noise_kernel<8>, total, s, a); break;
+    default:
+        if (total && a.L <= HHE_MAXL)
+            hipLaunchKernelGGL(noise_lds_kernel, dim3(nblocks(total)), dim3(ELT_THREADS), (size_t)a.L * ELT_THREADS * sizeof(u64), (hipStream_t)s, a);
+        break;
+    }
+}
 __global__ void __launch_bounds__(ELT_THREADS) decode_gather_kernel(DecodeArgs a) { decode_gather_body(a, GID); }
-void k_decrypt_round(const DecryptArgs &a, rt_stream s) { LAUNCH1D(decrypt_round_kernel, a.B << a.logn, s, a); }
+void k_decrypt_round(const DecryptArgs &a, rt_stream s)
+{
+    if (a.mode == DEC_NOISE) launch_noise(a, s);
+    else LAUNCH1D(decrypt_round_kernel, a.B << a.logn, s, a);
+}
 void k_decode_gather(const DecodeArgs &a, rt_stream s) { LAUNCH1D(decode_gather_kernel, a.B << a.logn, s, a); }
