@@ -6,12 +6,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
-#include "hhe_internal.h"
+#include "hhe_args.h"
 
 namespace {
-
-int fail(int code, const std::string &msg) { hhe_set_error(msg); return code; }
-int dev_fail(const char *where) { return fail(HHE_ERR_DEVICE, std::string(where) + ": " + rt_last_error()); }
 
 int need(hhe_ctx *c, size_t B)
 {
@@ -33,17 +30,6 @@ void stage_end(Lane &ln)
     else rt_sync(ln.stream);
 }
 
-NttArgs ntt_args(const hhe_ctx *c, const u64 *src, u64 *dst, size_t count, int mod_base, int mod_cycle)
-{
-    NttArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = src; a.dst = dst; a.mods = c->d_mods; a.logn = c->logn; a.count = (int)count;
-    a.mod_base = mod_base; a.mod_cycle = mod_cycle; a.src_div = 1; a.t = c->t;
-    a.load_op = LOAD_PLAIN; a.store_op = STORE_PLAIN; a.mul_cycle = 1; a.mul_item_polys = 1;
-    a.L = c->L; a.K = c->K; a.ks = c->ksc;
-    a.lazy8 = ntt_lazy8(c, mod_base, mod_cycle);
-    return a;
-}
 void op_ntt(hhe_ctx *c, u64 *polys, size_t count, int mod_base, int mod_cycle, bool inverse, int store_op = STORE_PLAIN)
 {
     NttArgs a = ntt_args(c, polys, polys, count, mod_base, mod_cycle);
@@ -52,11 +38,7 @@ void op_ntt(hhe_ctx *c, u64 *polys, size_t count, int mod_base, int mod_cycle, b
 }
 void op_elt(hhe_ctx *c, int op, const u64 *x, const u64 *y, u64 *out, size_t count, int mod_base, int mod_cycle, int b_cycle = 0)
 {
-    EltArgs a;
-    memset(&a, 0, sizeof(a));
-    a.a = x; a.b = y; a.out = out; a.mods = c->d_mods; a.logn = c->logn; a.count = (int)count;
-    a.mod_base = mod_base; a.mod_cycle = mod_cycle; a.b_cycle = b_cycle;
-    k_elt(a, op, c->w->stream);
+    k_elt(elt_args(c, x, y, out, count, mod_base, mod_cycle, b_cycle), op, c->w->stream);
 }
 // ct (+) ct over [B][size][L][N]
 void op_add(hhe_ctx *c, const u64 *x, const u64 *y, u64 *out, size_t B, int size) { op_elt(c, ELT_ADD, x, y, out, B * size * c->L, 0, c->L); }
@@ -74,8 +56,7 @@ void op_add_plain(hhe_ctx *c, const u64 *ct, const u64 *plain, const u64 *const 
 void op_encode(hhe_ctx *c, const u64 *vals, size_t B, int stride, int count, int second_off, u64 *plain)
 {
     rt_memset(plain, 0, B * c->n * 8, c->w->stream);
-    EncodeArgs e;
-    memset(&e, 0, sizeof(e));
+    EncodeArgs e = zeroed<EncodeArgs>();
     e.vals = vals; e.out = plain; e.slot_map = c->d_slot_map; e.logn = c->logn; e.B = (int)B;
     e.stride = stride; e.count = count; e.second_off = second_off; e.t = c->t;
     k_encode_scatter(e, c->w->stream);
@@ -147,6 +128,17 @@ int ensure_key_shoup(hhe_ctx *c, const u64 *key, const u64 **out)
     return HHE_OK;
 }
 
+// The two inverse launches that finish a key switch whose sums sit in a split ws_S: the special limbs (STORE_RSP), then the data limbs
+// with the mod-down in their store (`ksf`, from ks_ksf_args).  one_grid: the row passes of both share a grid (k_ntt2_inv); else each
+// is the second pass of a transform whose row pass a row kernel has already run
+void ks_finish_split(hhe_ctx *c, const KsSplit &sp, const NttArgs &ksf, size_t B, bool one_grid)
+{
+    const NttArgs rsp = ks_rsp_args(c, sp.Usp, sp.Usp, B * 2);
+    if (one_grid) { k_ntt2_inv(rsp, ksf, c->w->stream); return; }
+    k_ntt_pass(rsp, true, true, c->w->stream);
+    k_ntt_pass(ksf, true, true, c->w->stream);
+}
+
 // Evaluator::switch_key_inplace core.  d: item b at d + b*d_stride, [L][N] coefficient form.
 // out[b] = (base ? base polys selected by mask : 0) + key-switched pair.
 // galois_einv > 0 (N >= 4096 only): d and base are the UN-rotated polynomials of a rotation; the digit loads and the base
@@ -154,11 +146,7 @@ int ensure_key_shoup(hhe_ctx *c, const u64 *key, const u64 **out)
 int op_switch_key(hhe_ctx *c, const u64 *d, size_t d_stride, const u64 *key, const u64 *base, size_t base_stride,
                   int base_mask, u64 *out, size_t B, u32 galois_einv = 0)
 {
-    const int L = c->L, K = c->K;
-    NttArgs a = ntt_args(c, d, c->w->ws_T, B * L * K, 0, K);
-    a.src_div = K; a.src_item_polys = L * K; a.src_item_stride = d_stride; a.load_op = LOAD_DIGIT; a.digit_reduce = c->digit_reduce;
-    a.store_op = STORE_LAZY;  // ks_mac reduces: digits may stay in [0,4q)
-    a.load_einv = galois_einv;
+    const NttArgs a = ks_digit_args(c, d, d_stride, c->w->ws_T, B, galois_einv);
     const u64 *key_s = nullptr;
     const bool rowk = use_row_kernel(c) && ensure_key_shoup(c, key, &key_s) == HHE_OK;
     if (galois_einv && !rowk) return fail(HHE_ERR_DEVICE, "switch_key: Shoup table of the key could not be built");
@@ -166,29 +154,15 @@ int op_switch_key(hhe_ctx *c, const u64 *d, size_t d_stride, const u64 *key, con
         // N >= 4096: strided pass of the digit transforms, then ONE kernel for their row pass, the key inner product and
         // the inverse row pass of all 2K sums (ks_row_kernel, as in the matmul loop), then the strided inverse passes with
         // the mod-down fused into the store of the data limbs -- T and S never make a round trip
-        const size_t n = c->n;
-        u64 *W = c->w->ws_S, *Usp = c->w->ws_S + B * 2 * L * n;  // [B][2][L][N] | [B][2][N] inside [B][2][K][N]
+        const KsSplit sp = ks_split(c, c->w->ws_S, B);
         k_ntt_pass(a, false, false, c->w->stream);
-        KsRowArgs x;
-        memset(&x, 0, sizeof(x));
-        x.key = key; x.key_s = key_s; x.U0 = W; x.U1 = W + (size_t)L * n; x.u_stride = (size_t)2 * L * n; x.Usp = Usp;
-        x.B = (int)B; x.L = L; x.K = K;
-        if (k_ks_row(a, x, nullptr, c->w->stream)) return dev_fail("switch_key");
-        NttArgs as = ntt_args(c, Usp, Usp, B * 2, K - 1, 1);
-        as.store_op = STORE_RSP;
-        k_ntt_pass(as, true, true, c->w->stream);
-        NttArgs ad = ntt_args(c, W, W, B * 2 * L, 0, L);
-        ad.store_op = STORE_KSF; ad.aux_r = Usp; ad.aux_in = base; ad.base_stride = base_stride; ad.base_mask = base ? base_mask : 0;
-        ad.aux_out = out; ad.gal_einv = galois_einv;
-        k_ntt_pass(ad, true, true, c->w->stream);
+        if (k_ks_row(a, ks_row_args(c, key, key_s, B, &sp), nullptr, c->w->stream)) return dev_fail("switch_key");
+        ks_finish_split(c, sp, ks_ksf_args(c, sp, B, base, base_stride, base_mask, galois_einv, out), B, false);
         return HHE_OK;
     }
     k_ntt(a, false, c->w->stream);
-    KsMacArgs m;
-    memset(&m, 0, sizeof(m));
-    m.T = c->w->ws_T; m.key = key; m.S = c->w->ws_S; m.mods = c->d_mods; m.logn = c->logn; m.B = (int)B; m.L = L; m.K = K;
-    k_ks_mac(m, c->w->stream);
-    op_ntt(c, c->w->ws_S, B * 2 * K, 0, K, true);
+    k_ks_mac(ks_mac_args(c, c->w->ws_T, key, c->w->ws_S, B), c->w->stream);
+    op_ntt(c, c->w->ws_S, B * 2 * c->K, 0, c->K, true);
     KsFinishArgs f = c->ksf;
     f.S = c->w->ws_S; f.base = base; f.base_item_stride = base_stride; f.base_mask = base ? base_mask : 0; f.out = out; f.B = (int)B;
     k_ks_finish(f, c->w->stream);
@@ -197,11 +171,10 @@ int op_switch_key(hhe_ctx *c, const u64 *d, size_t d_stride, const u64 *key, con
 
 int op_apply_galois(hhe_ctx *c, const u64 *ct, u32 elt, u64 *out, size_t B)
 {
-    auto it = c->gks->gk.find(elt);
-    if (it == c->gks->gk.end()) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
-    const int L = c->L;
-    const size_t n = c->n;
-    const u32 einv = (u32)nt_invmod(elt, 2 * n);
+    const u64 *key = galois_key(c, elt);
+    if (!key) return HHE_ERR_NO_GALOIS_KEY;
+    const size_t ln = (size_t)c->L * c->n;
+    const u32 einv = galois_einv(c, elt);
     const u64 *src = ct;
     if (ct == out) {  // gathers cannot run in place
         rt_d2d(c->w->ws_ct[3], ct, B * c->ct_words() * 8, c->w->stream);
@@ -210,20 +183,14 @@ int op_apply_galois(hhe_ctx *c, const u64 *ct, u32 elt, u64 *out, size_t B)
     if (use_row_kernel(c)) {
         // N >= 4096: no rotated copies -- the digit loads read c1 and the fused mod-down reads c0 through the Galois map
         const u64 *key_s = nullptr;
-        int rc = ensure_key_shoup(c, it->second, &key_s);
+        int rc = ensure_key_shoup(c, key, &key_s);
         if (rc) return rc;
-        return op_switch_key(c, src + L * n, 2 * L * n, it->second, src, 2 * L * n, 1, out, B, einv);
+        return op_switch_key(c, src + ln, 2 * ln, key, src, 2 * ln, 1, out, B, einv);
     }
-    GaloisArgs g;
-    memset(&g, 0, sizeof(g));
-    g.mods = c->d_mods; g.logn = c->logn; g.count = (int)(B * L); g.L = L;
-    g.einv = einv;
     // c0' = galois(c0) -> out poly 0 ; d = galois(c1) -> ws_d
-    g.in = src; g.in_item_stride = 2 * L * n; g.out = out; g.out_item_stride = 2 * L * n;
-    k_galois(g, c->w->stream);
-    g.in = src + L * n; g.out = c->w->ws_d; g.out_item_stride = L * n;
-    k_galois(g, c->w->stream);
-    return op_switch_key(c, c->w->ws_d, L * n, it->second, out, 2 * L * n, 1, out, B);
+    k_galois(galois_args(c, B, einv, src, 2 * ln, out, 2 * ln), c->w->stream);
+    k_galois(galois_args(c, B, einv, src + ln, 2 * ln, c->w->ws_d, ln), c->w->stream);
+    return op_switch_key(c, c->w->ws_d, ln, key, out, 2 * ln, 1, out, B);
 }
 
 // Evaluator::rotate_internal (seal/evaluator.h:1234)
@@ -262,19 +229,16 @@ void op_multiply(hhe_ctx *c, const u64 *x, const u64 *y, u64 *out3, size_t B)
 {
     const int L = c->L, K = c->K;
     auto extend = [&](const u64 *in, u64 *oq, u64 *ob) {
-        BehzExtendArgs e;
-        memset(&e, 0, sizeof(e));
+        BehzExtendArgs e = zeroed<BehzExtendArgs>();
         e.x = in; e.xb = ob; e.mods = c->d_mods; e.bz = c->d_behz; e.logn = c->logn; e.P = (int)(B * 2); e.L = L; e.K = K;
         k_behz_extend(e, c->w->stream);
         op_ntt(c, ob, B * 2 * (L + 1), K, L + 1, false);
-        NttArgs a = ntt_args(c, in, oq, B * 2 * L, 0, L);
-        k_ntt(a, false, c->w->stream);
+        k_ntt(ntt_args(c, in, oq, B * 2 * L, 0, L), false, c->w->stream);
     };
     extend(x, c->w->bz_aq, c->w->bz_ab);
     const u64 *bq = c->w->bz_aq, *bb = c->w->bz_ab;
     if (y != x) { extend(y, c->w->bz_bq, c->w->bz_bb); bq = c->w->bz_bq; bb = c->w->bz_bb; }
-    TensorArgs t;
-    memset(&t, 0, sizeof(t));
+    TensorArgs t = zeroed<TensorArgs>();
     t.mods = c->d_mods; t.logn = c->logn; t.B = (int)B;
     t.a = c->w->bz_aq; t.b = bq; t.d = c->w->bz_dq; t.limbs = L; t.mod_base = 0;
     k_tensor(t, c->w->stream);
@@ -282,8 +246,7 @@ void op_multiply(hhe_ctx *c, const u64 *x, const u64 *y, u64 *out3, size_t B)
     k_tensor(t, c->w->stream);
     op_ntt(c, c->w->bz_dq, B * 3 * L, 0, L, true, STORE_SCALE_T);
     op_ntt(c, c->w->bz_db, B * 3 * (L + 1), K, L + 1, true, STORE_SCALE_T);
-    BehzFloorArgs f;
-    memset(&f, 0, sizeof(f));
+    BehzFloorArgs f = zeroed<BehzFloorArgs>();
     f.dq = c->w->bz_dq; f.db = c->w->bz_db; f.out = out3; f.mods = c->d_mods; f.bz = c->d_behz; f.logn = c->logn;
     f.P = (int)(B * 3); f.L = L; f.K = K;
     k_behz_floor(f, c->w->stream);
@@ -354,8 +317,7 @@ int ensure_block(hhe_ctx *c, u64 block, BlockTables **out)
     rt_h2d(d_rcs.p, rcs.data(), rcs.size() * 8, c->w->stream);
     // 128 diagonals per affine layer -> slot image -> INTT mod t (= batch encode) -> lift + NTT per limb
     rt_memset(slots.p, 0, ndiag * n * 8, c->w->stream);
-    DiagArgs d;
-    memset(&d, 0, sizeof(d));
+    DiagArgs d = zeroed<DiagArgs>();
     d.mats = d_mats.w(); d.out = slots.w(); d.slot_map = c->d_slot_map; d.logn = c->logn;
     k_diag(d, c->w->stream);
     op_ntt(c, slots.w(), ndiag, c->mod_t, 1, true);
@@ -364,10 +326,8 @@ int ensure_block(hhe_ctx *c, u64 block, BlockTables **out)
     op_encode(c, d_rcs.w(), PASTA_R + 1, 2 * PASTA_T, PASTA_T, (int)half, rc.w());
     if (fused) {
         // pdiag = diag o pi_g for g = elt(rotate_rows -1): multiplier tables in the rotated NTT frame
-        PermArgs p;
-        memset(&p, 0, sizeof(p));
-        p.in = diag.w(); p.out = pdiag.w(); p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(ndiag * L); p.L = L;
-        p.out_item_stride = (size_t)L * n; p.elt = galois_elt_from_step(c, -1);
+        PermArgs p = perm_args(c, ndiag * L, diag.w(), pdiag.w(), (size_t)L * n);
+        p.elt = galois_elt_from_step(c, -1);
         k_perm(p, c->w->stream);
         op_elt(c, ELT_SHOUP, pdiag.w(), nullptr, pdiag.w() + ndiag * L * n, ndiag * L, 0, L);
     }
@@ -398,8 +358,7 @@ int ensure_bsgs_tables(hhe_ctx *c, u64 block, BlockTables *bt)
     if (!d_mats.p || !slots.p || !bsgs.p) return dev_fail("bsgs table alloc");
     rt_h2d(d_mats.p, mats.data(), mats.size() * 8, c->w->stream);
     rt_memset(slots.p, 0, ndiag * n * 8, c->w->stream);
-    BsgsDiagArgs d;
-    memset(&d, 0, sizeof(d));
+    BsgsDiagArgs d = zeroed<BsgsDiagArgs>();
     d.mats = d_mats.w(); d.out = slots.w(); d.slot_map = c->d_slot_map; d.logn = c->logn; d.n1 = 16;
     k_bsgs_diag(d, c->w->stream);
     op_ntt(c, slots.w(), ndiag, c->mod_t, 1, true);
@@ -513,16 +472,12 @@ struct L0Capture {
 void l0_flush(hhe_ctx *c, const L0Capture &cap, int first, int steps)
 {
     const size_t ln = (size_t)c->L * c->n;
-    PermArgs p;
-    memset(&p, 0, sizeof(p));
-    p.in = cap.c0; p.out = cap.r0; p.mods = c->d_mods; p.logn = c->logn; p.count = steps * c->L; p.L = c->L;
-    p.out_item_stride = ln; p.elt = galois_elt_from_step(c, -1);
+    PermArgs p = perm_args(c, (size_t)steps * c->L, cap.c0, cap.r0, ln);
+    p.elt = galois_elt_from_step(c, -1);
     k_perm(p, c->w->stream);
     op_ntt(c, cap.d, (size_t)steps * c->L, 0, c->L, false);
-    memset(&p, 0, sizeof(p));
-    p.steps = steps; p.carry = first > 0; p.in = cap.r0; p.in2 = cap.d; p.in_step_stride = ln;
-    p.out = cap.out; p.out2 = cap.out + ln; p.out_item_stride = 2 * ln;
-    p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(cap.B * c->L); p.L = c->L;
+    p = perm_args(c, cap.B * c->L, cap.r0, cap.out, 2 * ln);
+    p.steps = steps; p.carry = first > 0; p.in2 = cap.d; p.in_step_stride = ln; p.out2 = cap.out + ln;
     p.mul_ptrs = c->l0_ptrs.p; p.mul_shift = (size_t)first * ln; p.mul_step_stride = ln;
     k_perm(p, c->w->stream);
 }
@@ -551,10 +506,9 @@ int matmul_diagonal_fused(hhe_ctx *c, const DiagSched &sch, const u64 *const *d_
         if (rc) return rc;
     }
     const u32 g = galois_elt_from_step(c, sch.rot_step);
-    auto it = c->gks->gk.find(g);
-    if (it == c->gks->gk.end()) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
-    const u64 *key = it->second;
-    const u32 ginv = (u32)nt_invmod(g, 2 * n);
+    const u64 *key = galois_key(c, g);
+    if (!key) return HHE_ERR_NO_GALOIS_KEY;
+    const u32 ginv = galois_einv(c, g);
     u64 *accp0 = c->w->ws_ct[1], *accp1 = c->w->ws_ct[1] + bln;
     u64 *c0n[2] = {c->w->ws_ct[2], c->w->ws_ct[2] + bln};
     u64 *scr = c->w->ws_ct[3], *r = c->w->ws_ct[3] + bln, *scr2 = c->w->ws_ct3;
@@ -567,11 +521,7 @@ int matmul_diagonal_fused(hhe_ctx *c, const DiagSched &sch, const u64 *const *d_
         NttArgs a = ntt_args(c, state, c0_of(0), B * L, 0, L);
         a.src_item_polys = L; a.src_item_stride = 2 * ln;
         k_ntt(a, false, c->w->stream);
-        GaloisArgs ga;
-        memset(&ga, 0, sizeof(ga));
-        ga.mods = c->d_mods; ga.logn = c->logn; ga.count = (int)(B * L); ga.L = L; ga.einv = ginv;
-        ga.in = state + ln; ga.in_item_stride = 2 * ln; ga.out = d_src; ga.out_item_stride = ln;
-        k_galois(ga, c->w->stream);
+        k_galois(galois_args(c, B, ginv, state + ln, 2 * ln, d_src, ln), c->w->stream);
     }
     // The c0 branch of step i only feeds the c0 branch of step i+1, and like the digit transforms of step i+1 it depends on
     // nothing later than the inverse transforms of step i: it is held back (k5) and launched in the grids of step i+1.
@@ -587,12 +537,7 @@ int matmul_diagonal_fused(hhe_ctx *c, const DiagSched &sch, const u64 *const *d_
     NttArgs k5;
     bool k5_pending = false;
     // digit transforms of the current d: T[I][J] = NTT_J(d[I] mod q_J)
-    auto digit_args = [&]() {
-        NttArgs a = ntt_args(c, d_src, c->w->ws_T, B * L * K, 0, K);
-        a.src_div = K; a.src_item_polys = L * K; a.src_item_stride = ln; a.load_op = LOAD_DIGIT; a.digit_reduce = c->digit_reduce;
-        a.store_op = STORE_LAZY;
-        return a;
-    };
+    auto digit_args = [&]() { return ks_digit_args(c, d_src, ln, c->w->ws_T, B); };
     // N >= 4096 -- four launches per step: strided pass of the digit transforms (+ the held-back c0 branch's strided pass in
     // the same grid); ks_row_kernel = row pass + key inner product + inverse row pass (+ the c0 branch's row pass as extra
     // tiles; S_0 alternates between the two halves of ws_S, so that branch reads the previous step's while this step's is
@@ -603,19 +548,15 @@ int matmul_diagonal_fused(hhe_ctx *c, const DiagSched &sch, const u64 *const *d_
         const NttArgs a = digit_args();
         if (k5_pending) k_ntt2_fwd_first(k5, a, c->w->stream);
         else k_ntt_pass(a, false, false, c->w->stream);
-        KsRowArgs x;
-        memset(&x, 0, sizeof(x));
-        x.key = key; x.key_s = key_s; x.S = c->w->ws_S + (size_t)(i & 1) * K * n; x.U1 = scr; x.u_stride = ln; x.Usp = r;
-        x.B = (int)B; x.L = L; x.K = K;
+        KsRowArgs x = ks_row_args(c, key, key_s, B);
+        x.S = c->w->ws_S + (size_t)(i & 1) * K * n; x.U1 = scr; x.u_stride = ln; x.Usp = r;
         x.acc = accp1; x.mul_ptrs = d_pdiag_ptrs; x.mul_shift = shift; x.mul_s_off = pdiag_words;
         {
             ProfScope prof(c, *c->w, B);
             krc |= k_ks_row(a, x, k5_pending ? &k5 : nullptr, c->w->stream);
         }
         k5_pending = false;
-        NttArgs as = ntt_args(c, r, r, B * 2, K - 1, 1);
-        as.store_op = STORE_RSP;
-        k_ntt_pass(as, true, true, c->w->stream);
+        k_ntt_pass(ks_rsp_args(c, r, r, B * 2), true, true, c->w->stream);
         NttArgs a1 = ntt_args(c, scr, scr, B * L, 0, L);
         a1.store_op = STORE_KS1; a1.aux_r = r; a1.aux_out = d_dst; a1.gal_elt = g;
         k_ntt_pass(a1, true, true, c->w->stream);
@@ -624,15 +565,12 @@ int matmul_diagonal_fused(hhe_ctx *c, const DiagSched &sch, const u64 *const *d_
     // the pseudo-Mersenne form, e.g. BFVDefault(4096)) -- the same step with the inner product as its own kernel: T and S are materialised
     auto step_separate = [&](size_t shift) {
         const NttArgs a = digit_args();
-        KsMacArgs m;
-        memset(&m, 0, sizeof(m));
-        m.T = c->w->ws_T; m.key = key; m.S = c->w->ws_S; m.mods = c->d_mods; m.logn = c->logn; m.B = (int)B; m.L = L; m.K = K;
+        KsMacArgs m = ks_mac_args(c, c->w->ws_T, key, c->w->ws_S, B);
         if (!cap) { m.acc = accp1; m.mul_ptrs = d_pdiag_ptrs; m.mul_shift = shift; }  // the I = J digit also feeds the plain product
         if (k5_pending) { k_ntt2_fwd(k5, a, c->w->stream); k5_pending = false; }
         else k_ntt(a, false, c->w->stream);
         k_ks_mac(m, c->w->stream);
-        NttArgs as = ntt_args(c, c->w->ws_S + (size_t)(K - 1) * n, r, B * 2, K - 1, 1);
-        as.src_item_polys = 1; as.src_item_stride = (size_t)K * n; as.store_op = STORE_RSP;
+        const NttArgs as = ks_rsp_args(c, c->w->ws_S, r, B * 2, true);
         NttArgs a1 = ntt_args(c, c->w->ws_S + (size_t)K * n, scr, B * L, 0, L);
         a1.src_item_polys = L; a1.src_item_stride = (size_t)2 * K * n; a1.store_op = STORE_KS1;
         a1.aux_r = r; a1.aux_out = d_dst; a1.gal_elt = g;
@@ -672,10 +610,8 @@ int matmul_diagonal_fused(hhe_ctx *c, const DiagSched &sch, const u64 *const *d_
         NttArgs a = ntt_args(c, d_of(nsteps - 1), scr, B * L, 0, L);
         a.store_op = STORE_MAC; a.mul_ptrs = d_pdiag_ptrs; a.mul_shift = shift; a.mul_cycle = L; a.mul_item_polys = L; a.acc = accp1;
         k_ntt(a, false, c->w->stream);
-        PermArgs p;
-        memset(&p, 0, sizeof(p));
-        p.in = c0_of(nsteps - 1); p.out = accp0; p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(B * L); p.L = L;
-        p.out_item_stride = ln; p.elt = g; p.mac = 1; p.mul_ptrs = d_pdiag_ptrs; p.mul_shift = shift;
+        PermArgs p = perm_args(c, B * L, c0_of(nsteps - 1), accp0, ln);
+        p.elt = g; p.mac = 1; p.mul_ptrs = d_pdiag_ptrs; p.mul_shift = shift;
         k_perm(p, c->w->stream);
         // back to the unrotated frame, then to coefficient form
         p.mac = 0; p.mul_ptrs = nullptr; p.elt = ginv; p.out_item_stride = 2 * ln;
@@ -714,12 +650,8 @@ void shared_l0_tail(hhe_ctx *c, const u64 *sums, size_t B)
     const int L = c->L;
     const size_t ln = (size_t)L * c->n;
     u64 *state = c->w->ws_ct[0];
-    PermArgs p;
-    memset(&p, 0, sizeof(p));
-    p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(B * L); p.L = L;
-    p.in_item_stride = 2 * ln; p.out_item_stride = 2 * ln;
-    p.elt = (u32)nt_invmod(galois_elt_from_step(c, -1), 2 * c->n);
-    p.in = sums; p.out = state;
+    PermArgs p = perm_args(c, B * L, sums, state, 2 * ln);
+    p.in_item_stride = 2 * ln; p.elt = galois_einv(c, galois_elt_from_step(c, -1));
     k_perm(p, c->w->stream);
     p.in = sums + ln; p.out = state + ln;
     k_perm(p, c->w->stream);
@@ -815,11 +747,7 @@ extern "C" int hhe_mod_switch(hhe_ctx *c, const uint64_t *ct, int size, size_t B
     const size_t per = std::max<size_t>(1, (((size_t)1 << 30) >> c->logn) / size);
     for (size_t b0 = 0; b0 < B; b0 += per) {
         const size_t bc = std::min(per, B - b0);
-        EltArgs a;
-        memset(&a, 0, sizeof(a));
-        a.a = ct + b0 * in_item; a.b = c->d_moddown; a.out = out + b0 * out_item; a.mods = c->d_mods; a.logn = c->logn;
-        a.count = (int)(bc * size); a.mod_base = 0; a.mod_cycle = limbs_in; a.b_cycle = limbs_out;
-        k_elt(a, ELT_MODDOWN, c->w->stream);
+        k_elt(elt_args(c, ct + b0 * in_item, c->d_moddown, out + b0 * out_item, bc * size, 0, limbs_in, limbs_out), ELT_MODDOWN, c->w->stream);
         ++c->mod_switch_launches;
     }
     if (rt_sync(c->w->stream)) return dev_fail("hhe_mod_switch");
@@ -864,34 +792,30 @@ static int check_sets(const hhe_ctx *c, const hhe_keyset *a, const hhe_keyset *b
         if (ks && ks->ctx != c) return fail(HHE_ERR_INVALID, "key set belongs to another context");
     return HHE_OK;
 }
-extern "C" int hhe_apply_galois_ks(hhe_ctx *c, const hhe_keyset *gk, const uint64_t *ct, uint32_t elt, uint64_t *out, size_t B)
+// the prologue the _ks entry points of the key-switching ops share -- lock, workspace, ownership of the named set, null check, key
+// scope -- then the op
+template <class Op> static int ks_entry(hhe_ctx *c, size_t B, const hhe_keyset *gk, const hhe_keyset *rk, bool args_ok, const char *null_msg, Op op)
 {
     HHE_LOCK(c);
     int rc = need(c, B);
-    if (rc || (rc = check_sets(c, gk))) return rc;
-    if (!ct || !out) return fail(HHE_ERR_INVALID, "hhe_apply_galois: null argument");
-    KeyScope keys(c, gk, nullptr);
-    return op_apply_galois(c, ct, elt, out, B);
+    if (rc || (rc = check_sets(c, gk, rk))) return rc;
+    if (!args_ok) return fail(HHE_ERR_INVALID, null_msg);
+    KeyScope keys(c, gk, rk);
+    return op();
+}
+extern "C" int hhe_apply_galois_ks(hhe_ctx *c, const hhe_keyset *gk, const uint64_t *ct, uint32_t elt, uint64_t *out, size_t B)
+{
+    return ks_entry(c, B, gk, nullptr, ct && out, "hhe_apply_galois: null argument", [&] { return op_apply_galois(c, ct, elt, out, B); });
 }
 extern "C" int hhe_apply_galois(hhe_ctx *c, const uint64_t *ct, uint32_t elt, uint64_t *out, size_t B) { return hhe_apply_galois_ks(c, nullptr, ct, elt, out, B); }
 extern "C" int hhe_rotate_rows_ks(hhe_ctx *c, const hhe_keyset *gk, const uint64_t *ct, int step, uint64_t *out, size_t B)
 {
-    HHE_LOCK(c);
-    int rc = need(c, B);
-    if (rc || (rc = check_sets(c, gk))) return rc;
-    if (!ct || !out) return fail(HHE_ERR_INVALID, "hhe_rotate_rows: null argument");
-    KeyScope keys(c, gk, nullptr);
-    return op_rotate_rows(c, ct, step, out, B);
+    return ks_entry(c, B, gk, nullptr, ct && out, "hhe_rotate_rows: null argument", [&] { return op_rotate_rows(c, ct, step, out, B); });
 }
 extern "C" int hhe_rotate_rows(hhe_ctx *c, const uint64_t *ct, int step, uint64_t *out, size_t B) { return hhe_rotate_rows_ks(c, nullptr, ct, step, out, B); }
 extern "C" int hhe_rotate_columns_ks(hhe_ctx *c, const hhe_keyset *gk, const uint64_t *ct, uint64_t *out, size_t B)
 {
-    HHE_LOCK(c);
-    int rc = need(c, B);
-    if (rc || (rc = check_sets(c, gk))) return rc;
-    if (!ct || !out) return fail(HHE_ERR_INVALID, "hhe_rotate_columns: null argument");
-    KeyScope keys(c, gk, nullptr);
-    return op_apply_galois(c, ct, (u32)(2 * c->n - 1), out, B);
+    return ks_entry(c, B, gk, nullptr, ct && out, "hhe_rotate_columns: null argument", [&] { return op_apply_galois(c, ct, (u32)(2 * c->n - 1), out, B); });
 }
 extern "C" int hhe_rotate_columns(hhe_ctx *c, const uint64_t *ct, uint64_t *out, size_t B) { return hhe_rotate_columns_ks(c, nullptr, ct, out, B); }
 extern "C" int hhe_multiply(hhe_ctx *c, const uint64_t *a, const uint64_t *b, uint64_t *out3, size_t B)
@@ -904,12 +828,7 @@ extern "C" int hhe_multiply(hhe_ctx *c, const uint64_t *a, const uint64_t *b, ui
 }
 extern "C" int hhe_relinearize_ks(hhe_ctx *c, const hhe_keyset *rk, const uint64_t *a3, uint64_t *out, size_t B)
 {
-    HHE_LOCK(c);
-    int rc = need(c, B);
-    if (rc || (rc = check_sets(c, rk))) return rc;
-    if (!a3 || !out) return fail(HHE_ERR_INVALID, "hhe_relinearize: null argument");
-    KeyScope keys(c, nullptr, rk);
-    return op_relinearize(c, a3, out, B);
+    return ks_entry(c, B, nullptr, rk, a3 && out, "hhe_relinearize: null argument", [&] { return op_relinearize(c, a3, out, B); });
 }
 extern "C" int hhe_relinearize(hhe_ctx *c, const uint64_t *a3, uint64_t *out, size_t B) { return hhe_relinearize_ks(c, nullptr, a3, out, B); }
 extern "C" int hhe_relinearize_slot(hhe_ctx *c, int slot, const uint64_t *a3, uint64_t *out, size_t B)
@@ -1275,8 +1194,7 @@ static int flatten_impl(hhe_ctx *c, const uint64_t *blocks, size_t nblocks, uint
     if (rc) return rc;
     const size_t ctw = c->ct_words();
     // gather block i of every sample into a contiguous batch (one strided copy kernel), rotate by -128*i, accumulate
-    CopyItemsArgs g;
-    memset(&g, 0, sizeof(g));
+    CopyItemsArgs g = zeroed<CopyItemsArgs>();
     g.src = blocks; g.words = ctw; g.count = S; g.src_stride = nblocks; g.dst_stride = 1;
     g.dst = out;
     k_copy_items(g, c->w->stream);
@@ -1330,8 +1248,7 @@ extern "C" int hhe_decompose_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keys
         if (!(rc = need(c, S))) {
             u64 *last = c->lanes[0].ws_ct[2];
             rt_stream st = c->lanes[0].stream;
-            CopyItemsArgs g;
-            memset(&g, 0, sizeof(g));
+            CopyItemsArgs g = zeroed<CopyItemsArgs>();
             g.src = blocks; g.dst = last; g.words = ctw; g.count = S; g.src_stride = nb; g.src_off = nb - 1; g.dst_stride = 1;
             k_copy_items(g, st);
             std::vector<u64> ones(rem, 1);
@@ -1372,16 +1289,10 @@ struct FcLeafAcc {  // sums over the leaves of the trie (DESIGN.md "FC rotation 
 // half_j - (r mod q_j) (+ q_sp * galois_l(c0 of leaf l's parent) for k = 0) into acc.accH
 static void fc_leaf_round(hhe_ctx *c, const u64 *S, bool dense, const u64 *const *parents, const u32 *einv, int m, const FcLeafAcc &acc, size_t B)
 {
-    const int L = c->L, K = c->K;
-    const size_t n = c->n, ln = (size_t)L * n;
-    NttArgs r = ntt_args(c, dense ? S : S + (size_t)(K - 1) * n, acc.rscr, B * 2 * m, K - 1, 1);
-    if (!dense) { r.src_item_polys = 1; r.src_item_stride = (size_t)K * n; }
-    r.store_op = STORE_RSP;
-    k_ntt(r, true, c->w->stream);
-    LeafRoundArgs lr;
-    memset(&lr, 0, sizeof(lr));
-    lr.r = acc.rscr; lr.accH = acc.accH; lr.base_stride = 2 * ln; lr.mods = c->d_mods; lr.logn = c->logn;
-    lr.B = (int)B; lr.L = L; lr.m = m; lr.ks = c->ksc;
+    k_ntt(ks_rsp_args(c, S, acc.rscr, B * 2 * m, !dense), true, c->w->stream);
+    LeafRoundArgs lr = zeroed<LeafRoundArgs>();
+    lr.r = acc.rscr; lr.accH = acc.accH; lr.base_stride = c->ct_words(); lr.mods = c->d_mods; lr.logn = c->logn;
+    lr.B = (int)B; lr.L = c->L; lr.m = m; lr.ks = c->ksc;
     for (int l = 0; l < m; l++) { lr.base[l] = parents[l]; lr.gal_einv[l] = einv[l]; }
     k_leaf_round(lr, c->w->stream);
 }
@@ -1391,26 +1302,16 @@ static void fc_leaf_round(hhe_ctx *c, const u64 *S, bool dense, const u64 *const
 // transforms per leaf; identical words because every step is exact modular arithmetic).
 int fc_leaf(hhe_ctx *c, const u64 *parent, u32 elt, const FcLeafAcc &acc, size_t B)
 {
-    auto it = c->gks->gk.find(elt);
-    if (it == c->gks->gk.end()) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
-    const int L = c->L, K = c->K;
-    const size_t n = c->n, ln = (size_t)L * n;
-    GaloisArgs g;
-    memset(&g, 0, sizeof(g));
-    g.mods = c->d_mods; g.logn = c->logn; g.count = (int)(B * L); g.L = L; g.einv = (u32)nt_invmod(elt, 2 * n);
-    g.in_item_stride = 2 * ln; g.out_item_stride = ln;
-    g.in = parent + ln; g.out = c->w->ws_d; g.accumulate = 0;  // galois(c0) joins the sums inside leaf_round_kernel below
-    k_galois(g, c->w->stream);
-    NttArgs a = ntt_args(c, c->w->ws_d, c->w->ws_T, B * L * K, 0, K);
-    a.src_div = K; a.src_item_polys = L * K; a.src_item_stride = ln; a.load_op = LOAD_DIGIT; a.digit_reduce = c->digit_reduce;
-    a.store_op = STORE_LAZY;
-    k_ntt(a, false, c->w->stream);
-    KsMacArgs m;
-    memset(&m, 0, sizeof(m));
-    m.T = c->w->ws_T; m.key = it->second; m.S = c->w->ws_S; m.s_acc = acc.accS; m.mods = c->d_mods; m.logn = c->logn;
-    m.B = (int)B; m.L = L; m.K = K;
+    const u64 *key = galois_key(c, elt);
+    if (!key) return HHE_ERR_NO_GALOIS_KEY;
+    const size_t ln = (size_t)c->L * c->n;
+    const u32 einv = galois_einv(c, elt);
+    // d = galois(c1); galois(c0) joins the sums inside leaf_round_kernel below
+    k_galois(galois_args(c, B, einv, parent + ln, 2 * ln, c->w->ws_d, ln), c->w->stream);
+    k_ntt(ks_digit_args(c, c->w->ws_d, ln, c->w->ws_T, B), false, c->w->stream);
+    KsMacArgs m = ks_mac_args(c, c->w->ws_T, key, c->w->ws_S, B);
+    m.s_acc = acc.accS;
     k_ks_mac(m, c->w->stream);
-    const u32 einv = (u32)nt_invmod(elt, 2 * n);
     fc_leaf_round(c, c->w->ws_S, false, &parent, &einv, 1, acc, B);
     return HHE_OK;
 }
@@ -1456,66 +1357,48 @@ int fc_corr(hhe_ctx *c, u32 elt, const u64 *key, const u64 **out)
 // sp_only: the transforms modulo the special prime alone, tp [B][L][N] (a node whose children are all leaves of the c1-sum scheme)
 void fc_parent_digits(hhe_ctx *c, const u64 *parent, u64 *tp, size_t B, bool sp_only = false)
 {
-    const int L = c->L, K = c->K;
-    const size_t ln = (size_t)L * c->n;
-    NttArgs a = sp_only ? ntt_args(c, parent + ln, tp, B * L, K - 1, 1) : ntt_args(c, parent + ln, tp, B * L * K, 0, K);
-    a.src_div = sp_only ? 1 : K; a.src_item_polys = sp_only ? L : L * K; a.src_item_stride = 2 * ln; a.load_op = LOAD_DIGIT;
-    a.digit_reduce = c->digit_reduce;
-    a.store_op = STORE_LAZY; a.zero_flag = c->w->zero_flag;
-    k_ntt(a, false, c->w->stream);
+    const size_t ln = (size_t)c->L * c->n;
+    k_ntt(ks_digit_args(c, parent + ln, 2 * ln, tp, B, 0, c->w->zero_flag, sp_only), false, c->w->stream);
 }
 // one child of a node from the node's shared digit transforms: leaf (sums only) or full ciphertext into `cur`
 int fc_child_shared(hhe_ctx *c, const u64 *parent, const u64 *tp, u32 elt, const FcLeafAcc *leaf, u64 *cur, size_t B, u64 *add_to = nullptr,
                     const u64 *c0hat = nullptr)
 {
-    auto it = c->gks->gk.find(elt);
-    if (it == c->gks->gk.end()) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+    const u64 *key = galois_key(c, elt);
+    if (!key) return HHE_ERR_NO_GALOIS_KEY;
     const u64 *corr = nullptr;
-    int rc = fc_corr(c, elt, it->second, &corr);
+    int rc = fc_corr(c, elt, key, &corr);
     if (rc) return rc;
-    const int L = c->L, K = c->K;
-    const size_t n = c->n, ln = (size_t)L * n;
-    const u32 einv = (u32)nt_invmod(elt, 2 * n);  // galois(c0) is gathered on the fly (leaf_round_kernel for leaves, the KSF epilogue otherwise)
-    u64 *Usp = c->w->ws_S + B * 2 * L * n;  // split output [B][2][L][N] | [B][2][N] (non-leaf children)
+    const u32 einv = galois_einv(c, elt);  // galois(c0) is gathered on the fly (leaf_round_kernel for leaves, the KSF epilogue otherwise)
+    const KsSplit sp = ks_split(c, c->w->ws_S, B);  // the output of non-leaf children
+    // ... whose mod-down also adds a child that is itself a term of the sum (add_to).  c0_inside: galois(c0) is already in S_0 (KsRowArgs::c0hat)
+    auto ksf = [&](bool c0_inside) {
+        NttArgs a = ks_ksf_args(c, sp, B, c0_inside ? nullptr : parent, c->ct_words(), 1, einv, cur);
+        a.acc = add_to;
+        return a;
+    };
     const u64 *key_s = nullptr;
-    if (!leaf && c->fc_row_fused && use_row_kernel(c) && ensure_key_shoup(c, it->second, &key_s) == HHE_OK) {
+    if (!leaf && c->fc_row_fused && use_row_kernel(c) && ensure_key_shoup(c, key, &key_s) == HHE_OK) {
         // N >= 4096: inner product over the shared digits and the inverse row pass of all 2K sums in one kernel (the sums never make a
         // round trip), then the strided inverse passes with the mod-down, the Galois-gathered c0 and the running sum in the data limbs' store
-        KsRowArgs x;
-        memset(&x, 0, sizeof(x));
-        x.key = it->second; x.key_s = key_s; x.U0 = c->w->ws_S; x.U1 = c->w->ws_S + (size_t)L * n; x.u_stride = (size_t)2 * L * n; x.Usp = Usp;
-        x.B = (int)B; x.L = L; x.K = K; x.T = tp; x.corr = corr; x.perm_elt = elt; x.c0hat = c0hat;
-        NttArgs g = ntt_args(c, nullptr, nullptr, 0, 0, K);
-        if (k_ks_perm_row(g, x, c->w->stream)) return dev_fail("fc: key-switch row kernel");
-        NttArgs as = ntt_args(c, Usp, Usp, B * 2, K - 1, 1);
-        as.store_op = STORE_RSP;
-        k_ntt_pass(as, true, true, c->w->stream);
-        NttArgs ad = ntt_args(c, c->w->ws_S, c->w->ws_S, B * 2 * L, 0, L);
-        ad.store_op = STORE_KSF; ad.aux_r = Usp; ad.aux_in = parent; ad.base_stride = 2 * ln; ad.base_mask = 1; ad.gal_einv = einv; ad.aux_out = cur;
-        if (c0hat) { ad.aux_in = nullptr; ad.base_mask = 0; ad.gal_einv = 0; }   // galois(c0) is already inside S_0 (KsRowArgs::c0hat)
-        ad.acc = add_to;
-        k_ntt_pass(ad, true, true, c->w->stream);
+        KsRowArgs x = ks_row_args(c, key, key_s, B, &sp);
+        x.T = tp; x.corr = corr; x.perm_elt = elt; x.c0hat = c0hat;
+        if (k_ks_perm_row(ntt_args(c, nullptr, nullptr, 0, 0, c->K), x, c->w->stream)) return dev_fail("fc: key-switch row kernel");
+        ks_finish_split(c, sp, ksf(c0hat != nullptr), B, false);
         return HHE_OK;
     }
-    KsMacArgs m;
-    memset(&m, 0, sizeof(m));
-    m.T = tp; m.key = it->second; m.S = c->w->ws_S; m.mods = c->d_mods; m.logn = c->logn; m.B = (int)B; m.L = L; m.K = K;
+    KsMacArgs m = ks_mac_args(c, tp, key, c->w->ws_S, B);
     m.perm_elt = elt; m.corr = corr;
     if (leaf) m.s_acc = leaf->accS;
-    else m.S_sp = Usp;
+    else m.S_sp = sp.Usp;
     k_ks_mac(m, c->w->stream);
     if (leaf) {
         fc_leaf_round(c, c->w->ws_S, false, &parent, &einv, 1, *leaf, B);
         return HHE_OK;
     }
     // all 2K sums are inverse-transformed (the row passes of the special and the data limbs in one grid); the mod-down rides in the
-    // store of the data limbs' last pass (STORE_KSF), and so does the addition of a child that is itself a term of the sum (add_to)
-    NttArgs as = ntt_args(c, Usp, Usp, B * 2, K - 1, 1);
-    as.store_op = STORE_RSP;
-    NttArgs ad = ntt_args(c, c->w->ws_S, c->w->ws_S, B * 2 * L, 0, L);
-    ad.store_op = STORE_KSF; ad.aux_r = Usp; ad.aux_in = parent; ad.base_stride = 2 * ln; ad.base_mask = 1; ad.gal_einv = einv; ad.aux_out = cur;
-    ad.acc = add_to;
-    k_ntt2_inv(as, ad, c->w->stream);
+    // store of the data limbs' last pass (STORE_KSF)
+    ks_finish_split(c, sp, ksf(false), B, true);
     return HHE_OK;
 }
 // The walk over the trie with shared digits.  A node's digit transforms and ciphertext live in a slot of the lane's pool (Lane::FcSlot)
@@ -1546,13 +1429,18 @@ struct FcWalk {
     std::vector<ElemSum> esums;
     static constexpr int CSUM_MAX = 2000;   // terms below 2^61: fewer than 255 wraps of the 64-bit word (CsumArgs::carry is a byte)
 
+    CsumArgs csum_args(const ElemSum &e) const
+    {
+        CsumArgs a = zeroed<CsumArgs>();
+        a.sums = e.sums; a.carry = e.carry; a.mods = c->d_mods; a.logn = c->logn; a.B = (int)B; a.L = c->L; a.K = c->K;
+        return a;
+    }
     int csum_add_pending(ElemSum &e)
     {
         if (!e.npend) return HHE_OK;
         Lane &ln = *c->w;
-        CsumArgs a;
-        memset(&a, 0, sizeof(a));
-        a.sums = e.sums; a.carry = e.carry; a.sums0 = e.sums0; a.src_stride = 2 * (size_t)c->L * c->n; a.m = e.npend; a.mods = c->d_mods; a.logn = c->logn; a.B = (int)B; a.L = c->L; a.K = c->K;
+        CsumArgs a = csum_args(e);
+        a.sums0 = e.sums0; a.src_stride = c->ct_words(); a.m = e.npend;
         for (int l = 0; l < e.npend; l++) a.src[l] = e.pend_c1[l];
         k_csum_add(a, ln.stream);
         for (int l = 0; l < e.npend; l++) ln.fc_slots[e.pend_slot[l]].refs--;
@@ -1566,13 +1454,11 @@ struct FcWalk {
         int rc = csum_add_pending(e);
         if (rc || !e.count) return rc;
         Lane &ln = *c->w;
-        auto it = c->gks->gk.find(e.elt);
-        if (it == c->gks->gk.end()) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+        const u64 *key = galois_key(c, e.elt);
+        if (!key) return HHE_ERR_NO_GALOIS_KEY;
         const int L = c->L, K = c->K;
-        CsumArgs a;
-        memset(&a, 0, sizeof(a));
-        a.sums = e.sums; a.carry = e.carry; a.out = ln.ws_T; a.mods = c->d_mods; a.logn = c->logn; a.B = (int)B; a.L = L; a.K = K;
-        a.einv = (u32)nt_invmod(e.elt, 2 * c->n); a.count = (u32)e.count;
+        CsumArgs a = csum_args(e);
+        a.out = ln.ws_T; a.einv = galois_einv(c, e.elt); a.count = (u32)e.count;
         k_csum_digits(a, ln.stream);
         a.sums0 = e.sums0; a.accH = acc->accH;
         for (int j = 0; j < L; j++) { a.qsp_mod[j] = c->ksc.qsp_mod[j]; a.qsp_mod_s[j] = c->ksc.qsp_mod_s[j]; }
@@ -1580,9 +1466,7 @@ struct FcWalk {
         NttArgs t = ntt_args(c, ln.ws_T, ln.ws_T, B * L * K, 0, K);
         t.store_op = STORE_LAZY;
         k_ntt(t, false, ln.stream);
-        KsMacArgs mm;
-        memset(&mm, 0, sizeof(mm));
-        mm.T = ln.ws_T; mm.key = it->second; mm.S = ln.ws_S; mm.mods = c->d_mods; mm.logn = c->logn; mm.B = (int)B; mm.L = L; mm.K = K;
+        KsMacArgs mm = ks_mac_args(c, ln.ws_T, key, ln.ws_S, B);
         mm.s_acc = acc->accS; mm.perm_elt = 1; mm.corr = c->d_zero_corr;  // the digits are those of the ROTATED sum: identity map, no correction
         k_ks_mac(mm, ln.stream);
         rt_memset(e.sums, 0, B * (size_t)L * c->n * 17, ln.stream);   // sums | sums0 | carry
@@ -1624,20 +1508,17 @@ struct FcWalk {
         if (m > 0 && !csum && (group == 1 || m == 1)) {
             for (int l = 0; l < m && !rc; l++) rc = fc_child_shared(c, q[l].parent, ln.fc_slots[q[l].slot].tp, q[l].elt, acc, nullptr, B);
         } else if (m > 0) {
-            const int L = c->L, K = c->K;
-            KsMacLeavesArgs a;
-            memset(&a, 0, sizeof(a));
+            KsMacLeavesArgs a = zeroed<KsMacLeavesArgs>();
             u32 einv[HHE_LEAF_GROUP];
             const u64 *parents[HHE_LEAF_GROUP];
             for (int l = 0; l < m; l++) {
-                auto it = c->gks->gk.find(q[l].elt);
-                if (it == c->gks->gk.end()) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
-                if ((rc = fc_corr(c, q[l].elt, it->second, &a.corr[l]))) return rc;
-                a.T[l] = ln.fc_slots[q[l].slot].tp; a.t_polys[l] = ln.fc_slots[q[l].slot].tp_polys; a.key[l] = it->second; a.perm_elt[l] = q[l].elt;
-                einv[l] = (u32)nt_invmod(q[l].elt, 2 * c->n);
+                if (!(a.key[l] = galois_key(c, q[l].elt))) return HHE_ERR_NO_GALOIS_KEY;
+                if ((rc = fc_corr(c, q[l].elt, a.key[l], &a.corr[l]))) return rc;
+                a.T[l] = ln.fc_slots[q[l].slot].tp; a.t_polys[l] = ln.fc_slots[q[l].slot].tp_polys; a.perm_elt[l] = q[l].elt;
+                einv[l] = galois_einv(c, q[l].elt);
                 parents[l] = csum ? nullptr : q[l].parent;   // the c0 terms of the leaves come from the per-element sums
             }
-            a.S_sp = ln.ws_leaf.p; a.s_acc = acc->accS; a.mods = c->d_mods; a.logn = c->logn; a.B = (int)B; a.L = L; a.K = K; a.m = m;
+            a.S_sp = ln.ws_leaf.p; a.s_acc = acc->accS; a.mods = c->d_mods; a.logn = c->logn; a.B = (int)B; a.L = c->L; a.K = c->K; a.m = m;
             a.sp_only = csum ? 1 : 0;
             if (k_ks_mac_leaves(a, ln.stream)) return fail(HHE_ERR_INVALID, "fc: leaf group");
             fc_leaf_round(c, ln.ws_leaf.p, true, parents, einv, m, *acc, B);
@@ -1837,8 +1718,7 @@ static int fc_row_chunk(hhe_ctx *c, bool shared, const std::vector<NafNode> &tri
     rt_memset(acc.accH, 0, 2 * bln * 8, ln.stream);
     if ((rc = dfs(&acc))) return rc;
     op_ntt(c, acc.accS, B * 2 * L, 0, L, true);
-    LeafSumArgs ls;
-    memset(&ls, 0, sizeof(ls));
+    LeafSumArgs ls = zeroed<LeafSumArgs>();
     ls.accS = acc.accS; ls.accH = acc.accH; ls.out = out; ls.mods = c->d_mods; ls.logn = c->logn;
     ls.B = (int)B; ls.L = L; ls.ks = c->ksc;
     k_leaf_sum(ls, ln.stream);
@@ -1973,13 +1853,10 @@ int affine_chunk(hhe_ctx *c, const hhe_matrix *m, const u64 *in, u64 *out, size_
         for (size_t j = 1; j < n1; ++j)
             if ((rc = op_rotate_rows(c, rot + (j - 1) * B * ctw, 1, rot + j * B * ctw, B))) return rc;
         op_ntt(c, rot, n1 * B * 2 * L, 0, L, false);
-        PermArgs p;
-        memset(&p, 0, sizeof(p));
+        PermArgs p = perm_args(c, B * 2 * L, rot, inner, ctw);
         p.bsgs_n1 = (int)n1; p.bsgs_n2 = (int)n2;
-        p.in = rot; p.in_step_stride = B * ctw; p.in_item_stride = ctw;
-        p.out = inner; p.out_step_stride = B * ctw; p.out_item_stride = ctw;
+        p.in_step_stride = B * ctw; p.in_item_stride = ctw; p.out_step_stride = B * ctw;
         p.mul_ptrs = m->self.p; p.mul_step_stride = ln;
-        p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(B * 2 * L); p.L = L;
         k_perm(p, w.stream);
         op_ntt(c, inner, n2 * B * 2 * L, 0, L, true);
         // the generic key switch adds its base polynomials of the ROTATED ciphertext only (STORE_KSF), so the outer sum is an op_add
@@ -2071,10 +1948,8 @@ extern "C" int hhe_matrix_create(hhe_ctx *c, const uint64_t *M, size_t dim, cons
     op_lift_ntt(c, plain.w(), dim, diag.w());
     if (!n1) {
         // multipliers in the frame of rotate_rows(+1) and their Shoup quotients: the `pdiag` form of ensure_block
-        PermArgs p;
-        memset(&p, 0, sizeof(p));
-        p.in = diag.w(); p.out = m->tab; p.mods = c->d_mods; p.logn = c->logn; p.count = (int)(dim * c->L); p.L = c->L;
-        p.out_item_stride = ln; p.elt = galois_elt_from_step(c, 1);
+        PermArgs p = perm_args(c, dim * c->L, diag.w(), m->tab, ln);
+        p.elt = galois_elt_from_step(c, 1);
         k_perm(p, st);
         op_elt(c, ELT_SHOUP, m->tab, nullptr, m->tab + dim * ln, dim * c->L, 0, c->L);
     }

@@ -5,13 +5,10 @@
 #include <algorithm>
 #include <cstring>
 #include <vector>
-#include "hhe_internal.h"
-#include "../../include/hhe_gfx950.h"
+#include "hhe_args.h"
 
 namespace {
 typedef unsigned __int128 u128;
-int fail(int code, const std::string &msg) { hhe_set_error(msg); return code; }
-int dev_fail(const char *where) { return fail(HHE_ERR_DEVICE, std::string(where) + ": " + rt_last_error()); }
 void barrett_ratio(u64 q, u64 &lo, u64 &hi)
 {
     const u128 two64 = (u128)1 << 64;
@@ -79,18 +76,12 @@ extern "C" int hhe_pasta3_plain_crypt(hhe_ctx *c, const uint64_t *key, const uin
 static void phase_c1s(hhe_ctx *c, const u64 *dsk, u64 *s2, const uint64_t *ct, int size, const int L, size_t B, u64 *c1s, rt_stream st)
 {
     const size_t ln = (size_t)L * c->n;
-    NttArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = ct + ln; a.dst = c1s; a.mods = c->d_mods; a.logn = c->logn; a.count = (int)(B * L);
-    a.mod_base = 0; a.mod_cycle = L; a.src_div = 1; a.src_item_polys = L; a.src_item_stride = (size_t)size * ln; a.t = c->t;
-    a.load_op = LOAD_PLAIN; a.store_op = STORE_MUL; a.mul = dsk; a.mul_cycle = L; a.mul_item_polys = 1;
-    a.L = L; a.K = c->K; a.ks = c->ksc; a.lazy8 = ntt_lazy8(c, 0, L);
+    NttArgs a = ntt_args(c, ct + ln, c1s, B * L, 0, L);
+    a.L = L;  // the limb count of the call's level, not the context's
+    a.src_item_polys = L; a.src_item_stride = (size_t)size * ln; a.store_op = STORE_MUL; a.mul = dsk; a.mul_cycle = L;
     k_ntt(a, false, st);
     if (size == 3) {
-        EltArgs e;
-        memset(&e, 0, sizeof(e));
-        e.a = dsk; e.b = dsk; e.out = s2; e.mods = c->d_mods; e.logn = c->logn; e.count = L; e.mod_base = 0; e.mod_cycle = L;
-        k_elt(e, ELT_MUL, st);  // s^2, a dyadic product of the uploaded key (NTT form)
+        k_elt(elt_args(c, dsk, dsk, s2, L, 0, L), ELT_MUL, st);  // s^2, a dyadic product of the uploaded key (NTT form)
         NttArgs m = a;
         m.src = ct + 2 * ln; m.dst = s2 + ln; m.store_op = STORE_MAC; m.mul = s2; m.acc = c1s;
         k_ntt(m, false, st);
@@ -111,8 +102,7 @@ static int decrypt_level(hhe_ctx *c, const uint64_t *sk, const uint64_t *ct, con
     if (rt_h2d(dsk.p, sk, ln * 8, st)) return dev_fail("hhe_decrypt");  // the level's limbs of the key-level secret key
     phase_c1s(c, dsk.w(), nullptr, ct, 2, L, B, c1s.w(), st);
 
-    DecryptArgs d;
-    memset(&d, 0, sizeof(d));
+    DecryptArgs d = zeroed<DecryptArgs>();
     d.mods = c->d_mods; d.ct = ct; d.c1s = c1s.w(); d.plain = plain.w(); d.logn = c->logn; d.L = L; d.B = B;
     d.t = c->t; d.gamma = c->gamma;
     barrett_ratio(c->t, d.t_rlo, d.t_rhi);
@@ -141,11 +131,8 @@ static int decrypt_level(hhe_ctx *c, const uint64_t *sk, const uint64_t *ct, con
     k_decrypt_round(d, st);
 
     // BatchEncoder::decode: forward NTT mod t, then the slot index map
-    NttArgs p;
-    memset(&p, 0, sizeof(p));
-    p.src = plain.w(); p.dst = plain.w(); p.mods = c->d_mods; p.logn = c->logn; p.count = (int)B;
-    p.mod_base = c->mod_t; p.mod_cycle = 1; p.src_div = 1; p.t = c->t; p.mul_cycle = 1; p.mul_item_polys = 1;
-    p.L = L; p.K = c->K; p.ks = c->ksc; p.lazy8 = ntt_lazy8(c, c->mod_t, 1);
+    NttArgs p = ntt_args(c, plain.w(), plain.w(), B, c->mod_t, 1);
+    p.L = L;  // as in phase_c1s
     k_ntt(p, false, st);
     DecodeArgs g2;
     g2.in = plain.w(); g2.vals = vals; g2.slot_map = c->d_slot_map; g2.logn = c->logn; g2.B = B;
@@ -185,8 +172,7 @@ extern "C" int hhe_noise_budget(hhe_ctx *c, const uint64_t *sk, const uint64_t *
     if (rt_h2d(dsk.p, sk, ln * 8, st) || rt_memset(dbits.p, 0, B * 4, st)) return dev_fail("hhe_noise_budget");
     phase_c1s(c, dsk.w(), dsk.w() + ln, ct, size, L, B, c1s.w(), st);
 
-    DecryptArgs d;
-    memset(&d, 0, sizeof(d));
+    DecryptArgs d = zeroed<DecryptArgs>();
     d.mode = DEC_NOISE; d.size = size; d.mods = c->d_mods; d.ct = ct; d.c1s = c1s.w(); d.logn = c->logn; d.L = L; d.B = B;
     d.t = c->t; d.pairs = c->d_moddown; d.bits = (u32 *)dbits.p;
     d.cj[0] = 1;  // Q = q_0 ... q_{L-1} < 2^(64 L): L words
@@ -230,8 +216,7 @@ enum { PUR_SECRET = 1, PUR_PUBLIC = 2, PUR_RELIN = 3, PUR_GALOIS = 4, PUR_ENCRYP
 
 PastaXofArgs sample_args(const hhe_ctx *c, const uint8_t *seed, u32 purpose, u32 elt, u32 first_index)
 {
-    PastaXofArgs x;
-    memset(&x, 0, sizeof(x));
+    PastaXofArgs x = zeroed<PastaXofArgs>();
     x.mode = XOF_SAMPLE;
     for (int w = 0; w < 4; ++w)
         for (int b = 0; b < 8; ++b) x.seed[w] |= (u64)seed[8 * w + b] << (8 * b);
@@ -254,24 +239,8 @@ void sample_launch(const hhe_ctx *c, PastaXofArgs &x, rt_stream st)
     x.nblocks = (int)(polys << (c->logn - 6));  // one lane per 64-coefficient chunk
     k_pasta_xof(x, st);
 }
-NttArgs plain_ntt(const hhe_ctx *c, u64 *polys, size_t count, int mod_cycle)
-{
-    NttArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = polys; a.dst = polys; a.mods = c->d_mods; a.logn = c->logn; a.count = (int)count;
-    a.mod_base = 0; a.mod_cycle = mod_cycle; a.src_div = 1; a.t = c->t;
-    a.load_op = LOAD_PLAIN; a.store_op = STORE_PLAIN; a.mul_cycle = 1; a.mul_item_polys = 1;
-    a.L = c->L; a.K = c->K; a.ks = c->ksc; a.lazy8 = ntt_lazy8(c, 0, mod_cycle);
-    return a;
-}
-EltArgs elt_args(const hhe_ctx *c, const u64 *x, const u64 *y, u64 *out, size_t count, int mod_cycle, int b_cycle)
-{
-    EltArgs a;
-    memset(&a, 0, sizeof(a));
-    a.a = x; a.b = y; a.out = out; a.mods = c->d_mods; a.logn = c->logn; a.count = (int)count;
-    a.mod_base = 0; a.mod_cycle = mod_cycle; a.b_cycle = b_cycle;
-    return a;
-}
+// in-place transform of `count` polynomials under q_0 .. q_{mod_cycle-1}
+NttArgs plain_ntt(const hhe_ctx *c, u64 *polys, size_t count, int mod_cycle) { return ntt_args(c, polys, polys, count, 0, mod_cycle); }
 // D encryptions of zero under the secret key at the key level, NTT form, into key [D][2][K][N] (generate_one_kswitch_key; D = 1 without
 // new_key: a public key): one sampler launch (a into the c1 slots, e into noise [D][K][N]), one forward transform, one fused launch.
 // with_key: new_key [K][N] (NTT form) sits behind the noise, at noise + D * K * N (new_key_of)
@@ -285,7 +254,7 @@ void gen_enc_zero(hhe_ctx *c, const u64 *sk, bool with_key, const uint8_t *seed,
     seg_small(x.seg[1], SMP_NOISE, D, 1, K, K, noise, (size_t)K * n, 0);
     sample_launch(c, x, st);
     k_ntt(plain_ntt(c, noise, (size_t)D * K, K), false, st);
-    EltArgs e = elt_args(c, noise, sk, key, (size_t)D * K, K, K);
+    EltArgs e = elt_args(c, noise, sk, key, (size_t)D * K, 0, K, K);
     e.with_key = with_key ? 1 : 0;
     k_elt(e, ELT_ENCZ, st);
 }
@@ -353,7 +322,7 @@ extern "C" int hhe_keyset_generate_relin(hhe_keyset *ks, const uint64_t *sk, con
     const size_t kn = (size_t)c->K * c->n;
     DevBuf key(c->ksk_words() * 8), noise((size_t)(c->L + 1) * kn * 8);
     if (!key.p || !noise.p) return dev_fail("hhe_keyset_generate_relin");
-    k_elt(elt_args(c, sk, sk, new_key_of(c, noise.w(), c->L), c->K, c->K, 0), ELT_MUL, st);  // new_key = s^2 (NTT form)
+    k_elt(elt_args(c, sk, sk, new_key_of(c, noise.w(), c->L), c->K, 0, c->K), ELT_MUL, st);  // new_key = s^2 (NTT form)
     gen_enc_zero(c, sk, true, seed, PUR_RELIN, 0, c->L, key.w(), noise.w(), st);
     if (rt_sync(st)) return dev_fail("hhe_keyset_generate_relin");
     keyset_adopt_relin(ks, key.release());
@@ -393,10 +362,8 @@ extern "C" int hhe_keyset_generate_galois(hhe_keyset *ks, const uint64_t *sk, co
         u64 *key = (u64 *)rt_malloc(c->ksk_words() * 8);
         if (!key) { rt_sync(st); drop(); return dev_fail("hhe_keyset_generate_galois"); }
         keys.push_back(key);
-        GaloisArgs g;  // new_key = sigma_e(s): GaloisTool::apply_galois between the transforms
-        memset(&g, 0, sizeof(g));
-        g.mods = c->d_mods; g.logn = c->logn; g.count = c->K; g.L = c->K; g.einv = (u32)nt_invmod(e, 2 * n);
-        g.in = scoef.w(); g.out = sg; g.in_item_stride = kn; g.out_item_stride = kn;
+        GaloisArgs g = galois_args(c, 1, galois_einv(c, e), scoef.w(), kn, sg, kn);  // new_key = sigma_e(s): GaloisTool::apply_galois between the transforms
+        g.count = g.L = c->K;  // one item of K limbs: the key level
         k_galois(g, st);
         k_ntt(plain_ntt(c, sg, c->K, c->K), false, st);
         gen_enc_zero(c, sk, true, seed, PUR_GALOIS, e, c->L, key, noise.w(), st);
@@ -452,7 +419,7 @@ extern "C" int hhe_encrypt(hhe_ctx *c, const uint64_t *pk, const uint64_t *plain
     a.store_op = STORE_MUL; a.mul = pkd.w(); a.mul_cycle = 2 * L; a.mul_item_polys = 1;
     k_ntt(a, false, st);
     k_ntt(plain_ntt(c, out, B * 2 * L, L), true, st);
-    k_elt(elt_args(c, out, e.w(), out, B * 2 * L, L, 0), ELT_ADD, st);
+    k_elt(elt_args(c, out, e.w(), out, B * 2 * L, 0, L), ELT_ADD, st);
     // + the scaled plaintext (multiply_add_plain_with_scaling_variant), as hhe_add_plain does
     AddPlainArgs p = c->apl;
     p.ct = out; p.ct_map = nullptr; p.plain = plain; p.plain_ptrs = nullptr; p.plain_shift = 0; p.out = out; p.B = (int)B;
