@@ -332,9 +332,13 @@ public:
 
     // PASTA_SEAL::decomposition (pasta_3_seal.cpp:106-172): every 128-word block of the record, one batched call; item b of the
     // sink is block b of blocks_of(record.size()).  enc_key: enc_ssk[0], ct_words() words.
+    // nonce: the one the record was encrypted under (a (nonce, counter) pair encrypts one block, ever: hhe_gfx950.h "PASTA under a
+    // caller's nonce"); the default is the reference's fixed one (:115)
+    static constexpr uint64_t fixed_nonce = 123456789;
     static size_t blocks_of(size_t words) { return (words + 127) / 128; }
     template <class Sink>
-    void transcipher(const std::vector<uint64_t> &record, const uint64_t *enc_key, const KeySet &rk, const KeySet &gk, bool bsgs, Sink dst)
+    void transcipher(const std::vector<uint64_t> &record, const uint64_t *enc_key, const KeySet &rk, const KeySet &gk, bool bsgs, Sink dst,
+                     uint64_t nonce = fixed_nonce)
     {
         const size_t nb = blocks_of(record.size());
         if (nb == 0) return;
@@ -347,16 +351,24 @@ public:
         }
         std::lock_guard<std::mutex> lk(arena_.mutex());
         uint64_t *key = encrypted_key(enc_key), *out = arena_.get(3, nb * ct_words() * 8);
-        check(hhe_pasta3_transcipher_ks(h(), or_empty(rk).get(), or_empty(gk).get(), key, cw.data(), ncw.data(), bidx.data(), nb, bsgs ? 1 : 0, out));
+        if (nonce == fixed_nonce)
+            check(hhe_pasta3_transcipher_ks(h(), or_empty(rk).get(), or_empty(gk).get(), key, cw.data(), ncw.data(), bidx.data(), nb, bsgs ? 1 : 0, out));
+        else {
+            const std::vector<uint64_t> nonces(nb, nonce);
+            check(hhe_pasta3_transcipher_nonce_ks(h(), or_empty(rk).get(), or_empty(gk).get(), key, cw.data(), ncw.data(), nonces.data(), bidx.data(), nb,
+                                                  bsgs ? 1 : 0, out));
+        }
         download(out, nb, 2, dst);
     }
     // BaseCSP::decompose's per-record loop (CSP.cpp:247-278) as ONE device call: decomposition of every record, the mask of the
-    // ragged last block (mask_last) and flatten with `flatten_gk`; item s of the sink is record s
+    // ragged last block (mask_last) and flatten with `flatten_gk`; item s of the sink is record s.  nonces: empty = the reference's
+    // fixed nonce for every record, else one per record
     template <class Sink>
     void decompose(const std::vector<std::vector<uint64_t>> &records, const uint64_t *enc_key, const KeySet &rk, const KeySet &gk,
-                   const GaloisWords &flatten_gk, bool mask_last, Sink dst)
+                   const GaloisWords &flatten_gk, bool mask_last, Sink dst, const std::vector<uint64_t> &nonces = {})
     {
         if (records.empty()) return;
+        if (!nonces.empty() && nonces.size() != records.size()) throw std::invalid_argument("decompose: one nonce per record");
         const size_t nwords = records[0].size();
         std::vector<uint64_t> flat(records.size() * nwords);
         for (size_t s = 0; s < records.size(); s++) {
@@ -366,7 +378,11 @@ public:
         std::lock_guard<std::mutex> lk(arena_.mutex());
         const KeySet fgk = or_empty(keys_.galois(flatten_gk));
         uint64_t *key = encrypted_key(enc_key), *out = arena_.get(3, records.size() * ct_words() * 8);
-        check(hhe_decompose_ks(h(), or_empty(rk).get(), or_empty(gk).get(), fgk.get(), key, flat.data(), records.size(), nwords, mask_last ? 1 : 0, out));
+        if (nonces.empty())
+            check(hhe_decompose_ks(h(), or_empty(rk).get(), or_empty(gk).get(), fgk.get(), key, flat.data(), records.size(), nwords, mask_last ? 1 : 0, out));
+        else
+            check(hhe_decompose_nonce_ks(h(), or_empty(rk).get(), or_empty(gk).get(), fgk.get(), key, flat.data(), nonces.data(), records.size(), nwords,
+                                         mask_last ? 1 : 0, out));
         download(out, records.size(), 2, dst);
     }
 
@@ -401,12 +417,13 @@ public:
     }
 
     // client end: pasta::PASTA::encrypt / decrypt (pasta_3_plain.cpp:9-46) of `count` words in place, key: 256 words
-    void pasta_crypt(const uint64_t *key, uint64_t *v, size_t count, bool dec)
+    void pasta_crypt(const uint64_t *key, uint64_t *v, size_t count, bool dec, uint64_t nonce = fixed_nonce)
     {
         if (!count) return;
         DevBuf d(count * 8);
         check(hhe_copy_h2d(h(), d.p, v, count * 8));
-        check(hhe_pasta3_plain_crypt(h(), key, d.u64(), 1, count, dec ? 1 : 0, d.u64()));
+        if (nonce == fixed_nonce) check(hhe_pasta3_plain_crypt(h(), key, d.u64(), 1, count, dec ? 1 : 0, d.u64()));
+        else check(hhe_pasta3_plain_crypt_nonce(h(), key, &nonce, d.u64(), 1, count, dec ? 1 : 0, d.u64()));
         check(hhe_copy_d2h(h(), v, d.p, count * 8));
     }
     // ---- keys and ciphertexts from a seed, on the device (hhe_gfx950.h "key generation and encryption").  seed: 32 bytes, THE ONLY

@@ -278,6 +278,55 @@ int hhe_pasta3_plain_keystream(hhe_ctx *c, const uint64_t *key_hptr, uint64_t fi
  * [S][nwords]); every record starts at block counter 0, as each PASTA::encrypt call does.  in == out is allowed. */
 int hhe_pasta3_plain_crypt(hhe_ctx *c, const uint64_t *key_hptr, const uint64_t *in_dptr, size_t S, size_t nwords,
                            int decrypt, uint64_t *out_dptr);
+
+/* ---- PASTA under a caller's nonce ----
+ * THE CONTRACT.  PASTA's definition draws a block's keystream from a nonce and a block counter (Pasta::init_shake(nonce,
+ * block_counter), src/pasta/pasta_3_plain.cpp:56).  Under one PASTA key a (nonce, counter) pair encrypts one block, ever: two blocks
+ * under one pair are a two-time pad, and whoever sees both symmetric ciphertexts learns the difference of the plaintexts mod t.  The
+ * library does not and cannot check this -- it never sees the secret key on the server's end, and keeps no record of pairs on the
+ * client's.  Choosing pairs that never repeat (a fresh nonce per record with counters from 0, or one nonce with a running counter)
+ * is the caller's duty.  The entry points above that take no nonce repeat the reference, which fixes the nonce at 123456789 and
+ * restarts at counter 0 for every record (pasta_3_seal.cpp:47,115; PASTA::encrypt, pasta_3_plain.cpp:9-27): they exist for parity
+ * with it.  They name the same objects: a pair with nonce 123456789 reached through an entry below is the cache entry (public tables,
+ * kept keystream) of that counter reached through an entry above. */
+/* hhe_pasta3_block_randomness with the nonce of Pasta::init_shake (pasta_3_plain.cpp:56) as an argument (host) */
+int hhe_pasta3_block_randomness_nonce(uint64_t t, uint64_t nonce, uint64_t block_index, uint64_t *mats_hptr, uint64_t *rcs_hptr);
+/* hhe_pasta3_plain_keystream under `nonce` (Pasta::keystream(nonce, block_counter), pasta_3_plain.cpp:156-178) */
+int hhe_pasta3_plain_keystream_nonce(hhe_ctx *c, const uint64_t *key_hptr, uint64_t nonce, uint64_t first_block, size_t nblocks,
+                                     uint64_t *ks_dptr);
+/* hhe_pasta3_plain_crypt with one nonce per record (PASTA::encrypt, pasta_3_plain.cpp:9-27, with its `nonce` a parameter): record s
+ * runs under nonces_hptr[s], block counters from 0.  The other parameters are those of hhe_pasta3_plain_crypt. */
+int hhe_pasta3_plain_crypt_nonce(hhe_ctx *c, const uint64_t *key_hptr, const uint64_t *nonces_hptr, const uint64_t *in_dptr, size_t S,
+                                 size_t nwords, int decrypt, uint64_t *out_dptr);
+/* hhe_pasta3_transcipher_ks with item i under the pair (nonce_hptr[i], block_index_hptr[i]) (PASTA_SEAL::decomposition,
+ * pasta_3_seal.cpp:106-172, with the nonce of :115 a parameter).  rk / gk NULL: the context's default set.
+ * A call through this entry runs its items in contiguous groups whose distinct pairs fit the block-cache limit (at least one pair per
+ * group; 42 pairs at N = 2^15, L = 3 and the 32 GiB default), one group after the other, so that the tables of an earlier group can
+ * make room for a later one: a stream of fresh pairs never needs all its tables at once.  The output words are those of one call.
+ * hhe_ctx_query("transcipher_groups") reports the groups of the last call; "transcipher_unique" / "transcipher_evaluated" /
+ * "ks_cache_hits" count pairs, summed over the groups. */
+int hhe_pasta3_transcipher_nonce_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const uint64_t *enc_key_dptr,
+                                    const uint64_t *cw_hptr, const uint32_t *ncw_hptr, const uint64_t *nonce_hptr,
+                                    const uint64_t *block_index_hptr, size_t B, int use_bsgs, uint64_t *out_dptr);
+/* hhe_decompose_ks with one nonce per record (BaseCSP::decompose, CSP.cpp:235-283): the blocks of record s run under
+ * (nonces_hptr[s], 0), (nonces_hptr[s], 1), ...; grouped like hhe_pasta3_transcipher_nonce_ks */
+int hhe_decompose_nonce_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_keyset *flatten_gk, const uint64_t *enc_key_dptr,
+                           const uint64_t *records_hptr, const uint64_t *nonces_hptr, size_t S, size_t nwords, int mask_last,
+                           uint64_t *out_dptr);
+/* The public randomness of `count` pairs drawn on the device (Pasta::init_shake, get_random_matrix, get_rc_vec;
+ * pasta_3_plain.cpp:56-119): one XOF launch with a pair per lane, one expansion launch with a workgroup per pair and affine layer.
+ * mats_dptr [count][4][2][128][128], rcs_dptr [count][4][2][128] device: pair after pair what hhe_pasta3_block_randomness writes.
+ * These are the launches a transciphering call uses for the pairs it has no tables for when the randomness is drawn on the device:
+ * HHE_PUBLIC_DEVICE, read at context creation (0: on the host, pair by pair; 1: on the device, all missing pairs of a call at once;
+ * unset: on the device when a call misses 8 pairs or more, where it measured faster, else on the host).  hhe_ctx_query("public_device")
+ * reports the knob ((uint64_t)-1 when unset), "public_device_built" the pairs whose randomness the last call drew on the device. */
+int hhe_pasta3_block_randomness_dev(hhe_ctx *c, const uint64_t *nonces_hptr, const uint64_t *blocks_hptr, size_t count,
+                                    uint64_t *mats_dptr, uint64_t *rcs_dptr);
+/* Builds the public tables the cache lacks for these pairs, exactly as a call of hhe_pasta3_transcipher_nonce_ks on them would
+ * (groups included), without evaluating anything: a service warms a counter range with it.  *built_out (optional): the pairs
+ * anything was built for. */
+int hhe_pasta3_prepare_tables(hhe_ctx *c, const uint64_t *nonces_hptr, const uint64_t *blocks_hptr, size_t count, int use_bsgs,
+                              size_t *built_out);
 /* Decryptor::decrypt + BatchEncoder::decode (seal/decryptor.h:70, seal/batchencoder.h:282) as used by
  * sealhelper::decrypting / Analyst::decrypt_result (src/util/sealhelper.cpp:252-266): B size-2 data-level
  * ciphertexts [B][2][L][N] -> slot values [B][N] (unsigned, < t; the signed view of decode_int64 is v > t/2 ? v - t : v).

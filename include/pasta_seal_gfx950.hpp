@@ -309,6 +309,22 @@ public:
         context->transcipher(ciphertexts, enc_ssk[0].words.data(), rk_set, gk_set, use_bsgs, detail::into(*context, res));
         return res;
     }
+    // ... of a record that was encrypted under `nonce` (PASTA::encrypt with a nonce below): block b runs under the pair (nonce, b).
+    // Under one PASTA key a pair encrypts one block, ever (hhe_gfx950.h "PASTA under a caller's nonce"); nobody checks it
+    std::vector<Ciphertext> HE_decrypt(std::vector<uint64_t> &ciphertexts, bool batch_encoder, uint64_t nonce)
+    {
+        if (secret_key_encrypted.empty()) throw std::logic_error("HE_decrypt: encrypted key not set");
+        return decomposition(ciphertexts, secret_key_encrypted, batch_encoder, nonce);
+    }
+    std::vector<Ciphertext> decomposition(std::vector<uint64_t> &ciphertexts, std::vector<Ciphertext> enc_ssk, bool batch_encoder, uint64_t nonce)
+    {
+        (void)batch_encoder;
+        if (enc_ssk.empty()) throw std::invalid_argument("decomposition: enc_ssk is empty");
+        if (enc_ssk[0].words.size() != context->ct_words()) throw std::invalid_argument("decomposition: enc_ssk is not valid for encryption parameters");
+        std::vector<Ciphertext> res(context->blocks_of(ciphertexts.size()));
+        context->transcipher(ciphertexts, enc_ssk[0].words.data(), rk_set, gk_set, use_bsgs, detail::into(*context, res), nonce);
+        return res;
+    }
 
     // BaseCSP::decompose's per-record loop (CSP.cpp:247-278) as ONE device call: decomposition of every record, the mask of the
     // ragged last block (mask_last: as hhe_pktnn_examples.cpp:620-626; the CSP's own loop masks a copy, i.e. pass false to reproduce
@@ -321,6 +337,18 @@ public:
         if (enc_ssk.empty()) throw std::invalid_argument("decompose: enc_ssk is empty");
         if (enc_ssk[0].words.size() != context->ct_words()) throw std::invalid_argument("decompose: enc_ssk is not valid for encryption parameters");
         context->decompose(records, enc_ssk[0].words.data(), rk_set, gk_set, detail::words(flatten_gk), mask_last, detail::into(*context, res));
+        return res;
+    }
+    // ... with one nonce per record
+    std::vector<Ciphertext> decompose(const std::vector<std::vector<uint64_t>> &records, std::vector<Ciphertext> enc_ssk,
+                                      const GaloisKeys &flatten_gk, bool mask_last, const std::vector<uint64_t> &nonces)
+    {
+        std::vector<Ciphertext> res(records.size());
+        if (records.empty()) return res;
+        if (enc_ssk.empty()) throw std::invalid_argument("decompose: enc_ssk is empty");
+        if (enc_ssk[0].words.size() != context->ct_words()) throw std::invalid_argument("decompose: enc_ssk is not valid for encryption parameters");
+        if (nonces.size() != records.size()) throw std::invalid_argument("decompose: one nonce per record");
+        context->decompose(records, enc_ssk[0].words.data(), rk_set, gk_set, detail::words(flatten_gk), mask_last, detail::into(*context, res), nonces);
         return res;
     }
 
@@ -346,11 +374,15 @@ public:
     size_t get_cipher_size() const { return params.cipher_size; }
     virtual std::vector<uint64_t> encrypt(std::vector<uint64_t> plaintext) const { return crypt(std::move(plaintext), 0); }
     virtual std::vector<uint64_t> decrypt(std::vector<uint64_t> ciphertext) const { return crypt(std::move(ciphertext), 1); }
+    // the record under a caller's nonce, block counters from 0 (Pasta::keystream(nonce, block_counter), pasta_3_plain.cpp:156-178, with
+    // the nonce of PASTA::encrypt :9-27 a parameter).  Under one key a nonce encrypts one record, ever; nobody checks it
+    std::vector<uint64_t> encrypt(std::vector<uint64_t> plaintext, uint64_t nonce) const { return crypt(std::move(plaintext), 0, nonce); }
+    std::vector<uint64_t> decrypt(std::vector<uint64_t> ciphertext, uint64_t nonce) const { return crypt(std::move(ciphertext), 1, nonce); }
 
 private:
-    std::vector<uint64_t> crypt(std::vector<uint64_t> v, int dec) const
+    std::vector<uint64_t> crypt(std::vector<uint64_t> v, int dec, uint64_t nonce = HheContext::fixed_nonce) const
     {
-        context->pasta_crypt(secret_key.data(), v.data(), v.size(), dec != 0);
+        context->pasta_crypt(secret_key.data(), v.data(), v.size(), dec != 0, nonce);
         return v;
     }
     std::shared_ptr<HheContext> context;

@@ -411,6 +411,21 @@ public:
         device->transcipher(ciphertext, device->words(enc_ssk[0]), rk_set, gk_set, use_bsgs, device->into(*context, res));
         return res;
     }
+    // ... of a record that was encrypted under `nonce`: block b runs under the pair (nonce, b).  Under one PASTA key a pair encrypts
+    // one block, ever (hhe_gfx950.h "PASTA under a caller's nonce"); nobody checks it
+    std::vector<seal::Ciphertext> HE_decrypt(std::vector<uint64_t> &ciphertext, bool batch_encoder, uint64_t nonce)
+    {
+        return decomposition(ciphertext, secret_key_encrypted, batch_encoder, nonce);
+    }
+    std::vector<seal::Ciphertext> decomposition(std::vector<uint64_t> &ciphertext, std::vector<seal::Ciphertext> enc_ssk, bool batch_encoder,
+                                                uint64_t nonce)
+    {
+        (void)batch_encoder;
+        if (enc_ssk.empty()) throw std::invalid_argument("decomposition: enc_ssk is empty");
+        std::vector<seal::Ciphertext> res(device->blocks_of(ciphertext.size()));
+        device->transcipher(ciphertext, device->words(enc_ssk[0]), rk_set, gk_set, use_bsgs, device->into(*context, res), nonce);
+        return res;
+    }
 
     // BaseCSP::decompose's per-record loop (CSP.cpp:247-278) as ONE device call: decomposition of every record, the mask of the
     // ragged last block (mask_last: as hhe_pktnn_examples.cpp:620-626; the CSP's own loop masks a copy, i.e. pass false to reproduce
@@ -423,6 +438,18 @@ public:
         if (enc_ssk.empty()) throw std::invalid_argument("decompose: enc_ssk is empty");
         device->decompose(records, device->words(enc_ssk[0]), rk_set, gk_set, gfx950::DeviceContext::words(flatten_gk), mask_last,
                           device->into(*context, res));
+        return res;
+    }
+    // ... with one nonce per record
+    std::vector<seal::Ciphertext> decompose(const std::vector<std::vector<uint64_t>> &records, std::vector<seal::Ciphertext> enc_ssk,
+                                            const seal::GaloisKeys &flatten_gk, bool mask_last, const std::vector<uint64_t> &nonces)
+    {
+        std::vector<seal::Ciphertext> res(records.size());
+        if (records.empty()) return res;
+        if (enc_ssk.empty()) throw std::invalid_argument("decompose: enc_ssk is empty");
+        if (nonces.size() != records.size()) throw std::invalid_argument("decompose: one nonce per record");
+        device->decompose(records, device->words(enc_ssk[0]), rk_set, gk_set, gfx950::DeviceContext::words(flatten_gk), mask_last,
+                          device->into(*context, res), nonces);
         return res;
     }
 

@@ -44,7 +44,13 @@ _SYMBOLS = [
     "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
     "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level",
     "hhe_noise_budget",
+    "hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystream_nonce", "hhe_pasta3_plain_crypt_nonce",
+    "hhe_pasta3_transcipher_nonce_ks", "hhe_decompose_nonce_ks", "hhe_pasta3_block_randomness_dev", "hhe_pasta3_prepare_tables",
 ]
+
+_NONCE_SYMBOLS = {"hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystream_nonce", "hhe_pasta3_plain_crypt_nonce",
+                  "hhe_pasta3_transcipher_nonce_ks", "hhe_decompose_nonce_ks", "hhe_pasta3_block_randomness_dev",
+                  "hhe_pasta3_prepare_tables"}
 
 
 # exports a library built from an earlier commit may lack (HHE_LIB selects such a build for A/B runs): bound when present, and the method
@@ -52,7 +58,7 @@ _SYMBOLS = [
 _OPTIONAL = {"hhe_pasta3_clear_keystream_cache", "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin",
              "hhe_keyset_generate_galois", "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
              "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level",
-             "hhe_noise_budget"}
+             "hhe_noise_budget"} | _NONCE_SYMBOLS
 
 
 def exported_symbols():
@@ -346,14 +352,26 @@ class Context:
             self._chk(self.lib.hhe_relinearize_slot(self.h, C.c_int(slot), _ptr(a3), _ptr(out), C.c_size_t(B)))
 
     # ---- hot path ----
-    def transcipher(self, enc_key, cw, ncw, block_index, out, use_bsgs=False, rk=None, gk=None):
-        """cw: host uint64 [B][128]; ncw [B]; block_index [B]; enc_key/out device."""
+    def _need(self, name):
+        if not hasattr(self.lib, name):
+            raise RuntimeError(f"this library has no {name} (built before nonces reached the boundary)")
+        return getattr(self.lib, name)
+
+    def transcipher(self, enc_key, cw, ncw, block_index, out, use_bsgs=False, rk=None, gk=None, nonces=None):
+        """cw: host uint64 [B][128]; ncw [B]; block_index [B]; enc_key/out device.  nonces [B]: item i runs under the pair
+        (nonces[i], block_index[i]) -- a pair encrypts one block, ever; None: the reference's fixed nonce"""
         cw = np.ascontiguousarray(cw, dtype=np.uint64)
         B = cw.shape[0]
         assert cw.shape == (B, PASTA_T)
         ncw = np.ascontiguousarray(ncw, dtype=np.uint32)
         bi = np.ascontiguousarray(block_index, dtype=np.uint64)
         assert ncw.shape == (B,) and bi.shape == (B,)
+        if nonces is not None:
+            nn = np.ascontiguousarray(nonces, dtype=np.uint64)
+            assert nn.shape == (B,)
+            self._chk(self._need("hhe_pasta3_transcipher_nonce_ks")(self.h, _ks(rk), _ks(gk), _ptr(enc_key), _ptr(cw), _ptr(ncw), _ptr(nn),
+                                                                    _ptr(bi), C.c_size_t(B), C.c_int(int(use_bsgs)), _ptr(out)))
+            return
         self._chk(self.lib.hhe_pasta3_transcipher_ks(self.h, _ks(rk), _ks(gk), _ptr(enc_key), _ptr(cw), _ptr(ncw), _ptr(bi), C.c_size_t(B),
                                                      C.c_int(int(use_bsgs)), _ptr(out)))
 
@@ -376,10 +394,33 @@ class Context:
     def flatten(self, blocks, nblocks, out, S, gk=None):
         self._chk(self.lib.hhe_flatten_ks(self.h, _ks(gk), _ptr(blocks), C.c_size_t(nblocks), _ptr(out), C.c_size_t(S)))
 
-    def decompose(self, enc_key, records, out, mask_last=True, rk=None, gk=None, flatten_gk=None):
-        """records: host uint64 [S][nwords]; out device [S][2][L][N]; rk / gk: the PASTA_SEAL's keys, flatten_gk: the GaloisKeys of flatten"""
+    def block_randomness_dev(self, nonces, blocks, mats_out, rcs_out):
+        """the public randomness of len(nonces) pairs drawn on the device: mats_out device [count][4][2][128][128], rcs_out [count][4][2][128]"""
+        nn = np.ascontiguousarray(nonces, dtype=np.uint64)
+        bb = np.ascontiguousarray(blocks, dtype=np.uint64)
+        assert nn.shape == bb.shape and nn.ndim == 1
+        self._chk(self._need("hhe_pasta3_block_randomness_dev")(self.h, _ptr(nn), _ptr(bb), C.c_size_t(len(nn)), _ptr(mats_out), _ptr(rcs_out)))
+
+    def prepare_tables(self, nonces, blocks, use_bsgs=False):
+        """build the public tables the cache lacks for these pairs; returns how many pairs anything was built for"""
+        nn = np.ascontiguousarray(nonces, dtype=np.uint64)
+        bb = np.ascontiguousarray(blocks, dtype=np.uint64)
+        assert nn.shape == bb.shape and nn.ndim == 1
+        built = C.c_size_t(0)
+        self._chk(self._need("hhe_pasta3_prepare_tables")(self.h, _ptr(nn), _ptr(bb), C.c_size_t(len(nn)), C.c_int(int(use_bsgs)), C.byref(built)))
+        return int(built.value)
+
+    def decompose(self, enc_key, records, out, mask_last=True, rk=None, gk=None, flatten_gk=None, nonces=None):
+        """records: host uint64 [S][nwords]; out device [S][2][L][N]; rk / gk: the PASTA_SEAL's keys, flatten_gk: the GaloisKeys of flatten;
+        nonces [S]: one per record (None: the reference's fixed nonce)"""
         rec = np.ascontiguousarray(records, dtype=np.uint64)
         S, nwords = rec.shape
+        if nonces is not None:
+            nn = np.ascontiguousarray(nonces, dtype=np.uint64)
+            assert nn.shape == (S,)
+            self._chk(self._need("hhe_decompose_nonce_ks")(self.h, _ks(rk), _ks(gk), _ks(flatten_gk), _ptr(enc_key), _ptr(rec), _ptr(nn),
+                                                           C.c_size_t(S), C.c_size_t(nwords), C.c_int(int(mask_last)), _ptr(out)))
+            return
         self._chk(self.lib.hhe_decompose_ks(self.h, _ks(rk), _ks(gk), _ks(flatten_gk), _ptr(enc_key), _ptr(rec), C.c_size_t(S), C.c_size_t(nwords),
                                             C.c_int(int(mask_last)), _ptr(out)))
 
@@ -428,16 +469,26 @@ class Context:
         return int(used.value), int(cnt.value)
 
     # ---- client / analyst ends ----
-    def plain_keystream(self, key, first_block, nblocks, ks_out):
-        """key: host uint64 [256]; ks_out device [nblocks][128]"""
+    def plain_keystream(self, key, first_block, nblocks, ks_out, nonce=None):
+        """key: host uint64 [256]; ks_out device [nblocks][128]; nonce: None = the reference's fixed one"""
         key = np.ascontiguousarray(key, dtype=np.uint64)
         assert key.shape == (2 * PASTA_T,)
+        if nonce is not None:
+            self._chk(self._need("hhe_pasta3_plain_keystream_nonce")(self.h, _ptr(key), C.c_uint64(nonce), C.c_uint64(first_block),
+                                                                     C.c_size_t(nblocks), _ptr(ks_out)))
+            return
         self._chk(self.lib.hhe_pasta3_plain_keystream(self.h, _ptr(key), C.c_uint64(first_block), C.c_size_t(nblocks), _ptr(ks_out)))
 
-    def plain_crypt(self, key, records, S, nwords, out, decrypt=False):
-        """records/out: device uint64 [S][nwords]"""
+    def plain_crypt(self, key, records, S, nwords, out, decrypt=False, nonces=None):
+        """records/out: device uint64 [S][nwords]; nonces [S]: one per record, counters from 0 (None: the reference's fixed nonce)"""
         key = np.ascontiguousarray(key, dtype=np.uint64)
         assert key.shape == (2 * PASTA_T,)
+        if nonces is not None:
+            nn = np.ascontiguousarray(nonces, dtype=np.uint64)
+            assert nn.shape == (S,)
+            self._chk(self._need("hhe_pasta3_plain_crypt_nonce")(self.h, _ptr(key), _ptr(nn), _ptr(records), C.c_size_t(S), C.c_size_t(nwords),
+                                                                 C.c_int(int(decrypt)), _ptr(out)))
+            return
         self._chk(self.lib.hhe_pasta3_plain_crypt(self.h, _ptr(key), _ptr(records), C.c_size_t(S), C.c_size_t(nwords),
                                                   C.c_int(int(decrypt)), _ptr(out)))
 
@@ -529,11 +580,14 @@ def affine_galois_steps(n, dim, n1=0, n2=0, lib=None):
     return [int(v) for v in out[:cnt.value]]
 
 
-def block_randomness(t, block_index, lib=None):
+def block_randomness(t, block_index, lib=None, nonce=None):
     lib = lib or load_library()
     mats = np.zeros((4, 2, PASTA_T, PASTA_T), np.uint64)
     rcs = np.zeros((4, 2, PASTA_T), np.uint64)
-    rc = lib.hhe_pasta3_block_randomness(C.c_uint64(t), C.c_uint64(block_index), _ptr(mats), _ptr(rcs))
+    if nonce is None:
+        rc = lib.hhe_pasta3_block_randomness(C.c_uint64(t), C.c_uint64(block_index), _ptr(mats), _ptr(rcs))
+    else:
+        rc = lib.hhe_pasta3_block_randomness_nonce(C.c_uint64(t), C.c_uint64(nonce), C.c_uint64(block_index), _ptr(mats), _ptr(rcs))
     if rc:
         raise HheError(rc, lib.hhe_last_error().decode())
     return mats, rcs

@@ -294,36 +294,46 @@ void evict_blocks(hhe_ctx *c, size_t need)
         c->blocks.erase(victim);
     }
 }
-// Public tables of one block counter, built on the device on first use.  Footprint per counter: (4 x 128 x L) x N words of
+// Public tables of one (nonce, counter) pair, built on the device on first use.  Footprint per pair: (4 x 128 x L) x N words of
 // multipliers -- twice that for `pdiag` with its Shoup quotients (fused pipeline; 768 MiB at N = 2^15, L = 3), once for `diag`
 // (op-by-op schedule, HHE_MATMUL=0) -- plus 4 N words of round constants; the babystep-giantstep variant adds (4 x 128 x L) x N on
 // its first use.  The cache is bounded (hhe_pasta3_set_block_cache_limit); hhe_pasta3_clear_block_cache() releases everything.
-int ensure_block(hhe_ctx *c, u64 block, BlockTables **out)
+constexpr size_t PASTA_MATS_WORDS = (size_t)(PASTA_R + 1) * 2 * PASTA_T * PASTA_T, PASTA_RCS_WORDS = (size_t)(PASTA_R + 1) * 2 * PASTA_T;
+size_t block_entry_bytes(const hhe_ctx *c)
 {
-    auto it = c->blocks.find(block);
-    if (it != c->blocks.end()) { it->second.last_call = c->block_call; *out = &it->second; return HHE_OK; }
+    const size_t ndiag = (size_t)(PASTA_R + 1) * PASTA_T;
+    return (c->matmul_mode == 1 ? 2 : 1) * ndiag * c->L * c->n * 8 + (size_t)(PASTA_R + 1) * c->n * 8;
+}
+size_t block_bsgs_bytes(const hhe_ctx *c) { return (size_t)(PASTA_R + 1) * PASTA_T * c->L * c->n * 8; }
+// the randomness of a pair as the table pipeline takes it: on the host (uploaded here, behind the eviction) or already on the device
+struct PairRandomness {
+    const u64 *h_mats = nullptr, *h_rcs = nullptr;
+    const u64 *d_mats = nullptr, *d_rcs = nullptr;
+};
+int build_block(hhe_ctx *c, const PastaPair &id, const PairRandomness &r, BlockTables **out)
+{
     const size_t n = c->n, half = n / 2;
     const int L = c->L;
     const size_t ndiag = (size_t)(PASTA_R + 1) * PASTA_T;
-    std::vector<u64> mats((size_t)(PASTA_R + 1) * 2 * PASTA_T * PASTA_T), rcs((size_t)(PASTA_R + 1) * 2 * PASTA_T);
-    pasta3_block_randomness(c->t, PASTA_NONCE, block, mats.data(), rcs.data());
     const bool fused = c->matmul_mode == 1;
-    const size_t entry_bytes = (fused ? 2 : 1) * ndiag * L * n * 8 + (size_t)(PASTA_R + 1) * n * 8;
+    const size_t entry_bytes = block_entry_bytes(c);
     evict_blocks(c, entry_bytes);
-    DevBuf d_mats(mats.size() * 8), d_rcs(rcs.size() * 8), slots(ndiag * n * 8), diag(ndiag * L * n * 8),
+    DevBuf d_mats(r.d_mats ? 8 : PASTA_MATS_WORDS * 8), d_rcs(r.d_rcs ? 8 : PASTA_RCS_WORDS * 8), slots(ndiag * n * 8), diag(ndiag * L * n * 8),
         rc((size_t)(PASTA_R + 1) * n * 8), pdiag(fused ? 2 * ndiag * L * n * 8 : 8);  // pdiag | its Shoup quotients
     if (!d_mats.p || !d_rcs.p || !slots.p || !diag.p || !rc.p || !pdiag.p) return dev_fail("block table alloc");
-    rt_h2d(d_mats.p, mats.data(), mats.size() * 8, c->w->stream);
-    rt_h2d(d_rcs.p, rcs.data(), rcs.size() * 8, c->w->stream);
+    if (!r.d_mats) {
+        rt_h2d(d_mats.p, r.h_mats, PASTA_MATS_WORDS * 8, c->w->stream);
+        rt_h2d(d_rcs.p, r.h_rcs, PASTA_RCS_WORDS * 8, c->w->stream);
+    }
     // 128 diagonals per affine layer -> slot image -> INTT mod t (= batch encode) -> lift + NTT per limb
     rt_memset(slots.p, 0, ndiag * n * 8, c->w->stream);
     DiagArgs d = zeroed<DiagArgs>();
-    d.mats = d_mats.w(); d.out = slots.w(); d.slot_map = c->d_slot_map; d.logn = c->logn;
+    d.mats = r.d_mats ? r.d_mats : d_mats.w(); d.out = slots.w(); d.slot_map = c->d_slot_map; d.logn = c->logn;
     k_diag(d, c->w->stream);
     op_ntt(c, slots.w(), ndiag, c->mod_t, 1, true);
     op_lift_ntt(c, slots.w(), ndiag, diag.w());
     // round constants: rc1 -> slots [0,128), rc2 -> slots [N/2, N/2+128) (pasta_3_plain.cpp:286-295)
-    op_encode(c, d_rcs.w(), PASTA_R + 1, 2 * PASTA_T, PASTA_T, (int)half, rc.w());
+    op_encode(c, r.d_rcs ? r.d_rcs : d_rcs.w(), PASTA_R + 1, 2 * PASTA_T, PASTA_T, (int)half, rc.w());
     if (fused) {
         // pdiag = diag o pi_g for g = elt(rotate_rows -1): multiplier tables in the rotated NTT frame
         PermArgs p = perm_args(c, ndiag * L, diag.w(), pdiag.w(), (size_t)L * n);
@@ -339,27 +349,24 @@ int ensure_block(hhe_ctx *c, u64 block, BlockTables **out)
     bt.bytes = entry_bytes;
     bt.last_call = c->block_call;
     c->block_bytes += entry_bytes;
-    auto ins = c->blocks.emplace(block, bt);
+    auto ins = c->blocks.emplace(id, bt);
     *out = &ins.first->second;
     return HHE_OK;
 }
 
-// babystep-giantstep multiplier tables of one block (lazy): same pipeline as `diag` with the rearranged diagonals
-int ensure_bsgs_tables(hhe_ctx *c, u64 block, BlockTables *bt)
+// babystep-giantstep multiplier tables of one pair (lazy): same pipeline as `diag` with the rearranged diagonals
+int build_bsgs(hhe_ctx *c, BlockTables *bt, const PairRandomness &r)
 {
-    if (bt->bsgs) return HHE_OK;
     const size_t n = c->n;
     const int L = c->L;
     const size_t ndiag = (size_t)(PASTA_R + 1) * PASTA_T;
-    std::vector<u64> mats((size_t)(PASTA_R + 1) * 2 * PASTA_T * PASTA_T), rcs((size_t)(PASTA_R + 1) * 2 * PASTA_T);
-    pasta3_block_randomness(c->t, PASTA_NONCE, block, mats.data(), rcs.data());
     evict_blocks(c, ndiag * L * n * 8);
-    DevBuf d_mats(mats.size() * 8), slots(ndiag * n * 8), bsgs(ndiag * L * n * 8);
+    DevBuf d_mats(r.d_mats ? 8 : PASTA_MATS_WORDS * 8), slots(ndiag * n * 8), bsgs(ndiag * L * n * 8);
     if (!d_mats.p || !slots.p || !bsgs.p) return dev_fail("bsgs table alloc");
-    rt_h2d(d_mats.p, mats.data(), mats.size() * 8, c->w->stream);
+    if (!r.d_mats) rt_h2d(d_mats.p, r.h_mats, PASTA_MATS_WORDS * 8, c->w->stream);
     rt_memset(slots.p, 0, ndiag * n * 8, c->w->stream);
     BsgsDiagArgs d = zeroed<BsgsDiagArgs>();
-    d.mats = d_mats.w(); d.out = slots.w(); d.slot_map = c->d_slot_map; d.logn = c->logn; d.n1 = 16;
+    d.mats = r.d_mats ? r.d_mats : d_mats.w(); d.out = slots.w(); d.slot_map = c->d_slot_map; d.logn = c->logn; d.n1 = 16;
     k_bsgs_diag(d, c->w->stream);
     op_ntt(c, slots.w(), ndiag, c->mod_t, 1, true);
     op_lift_ntt(c, slots.w(), ndiag, bsgs.w());
@@ -367,6 +374,91 @@ int ensure_bsgs_tables(hhe_ctx *c, u64 block, BlockTables *bt)
     bt->bsgs = bsgs.release();
     bt->bytes += ndiag * L * n * 8;
     c->block_bytes += ndiag * L * n * 8;
+    return HHE_OK;
+}
+
+// Pasta::init_shake + get_random_matrix + get_rc_vec (pasta_3_plain.cpp:56-119) for `count` pairs on the device: one XOF launch with a
+// pair per lane, one expansion launch (a workgroup per pair and layer), nothing in between -- the stream orders them.  d_pairs
+// [count], d_rand [count][2048], mats [count][4][2][128][128], rcs [count][4][2][128] are the caller's; enqueued on st
+void public_randomness_enqueue(hhe_ctx *c, const PastaPair *pairs, size_t count, PastaPair *d_pairs, u64 *d_rand, u64 *mats, u64 *rcs, rt_stream st)
+{
+    rt_h2d(d_pairs, pairs, count * sizeof(PastaPair), st);
+    PastaXofArgs x = zeroed<PastaXofArgs>();
+    x.mode = XOF_PASTA;
+    x.t = c->t; x.nblocks = (int)count; x.rand = d_rand; x.pairs = d_pairs;
+    int bits = 0;
+    for (u64 v = c->t; v; v >>= 1) ++bits;
+    x.mask = bits >= 64 ? ~(u64)0 : (((u64)1 << bits) - 1);  // Pasta::Pasta(): max_prime_size (pasta_3_plain.cpp:150-153)
+    k_pasta_xof(x, st);
+    PastaPlainArgs p = zeroed<PastaPlainArgs>();
+    p.mode = PP_MODE_EXPAND;
+    p.t = c->t;
+    p.r_hi = (u64)(((unsigned __int128)1 << 64) / c->t);
+    p.r_lo = (u64)(((((unsigned __int128)1 << 64) % c->t) << 64) / c->t);
+    p.rand = d_rand; p.nblocks = (int)count; p.mats = mats; p.rcs = rcs;
+    k_pasta_plain(p, st);
+}
+
+// From this many missing pairs on, a call with HHE_PUBLIC_DEVICE unset draws their randomness on the device: a single lane's sponge
+// is slower than a host core, many lanes at once are not.  profiles/block_tables_time.json (tools/block_tables_time.py, one MI355X):
+// the host draws a pair in 0.53 ms, the two device launches take 3.0 ms for 1 to 40 pairs alike; builds of 1 and 4 missing pairs
+// measured faster with the host's randomness (2.1 / 4.7 ms, 8.4 / 9.4 ms), builds of 16 and 40 with the device's.
+constexpr size_t PUBLIC_DEVICE_MIN = 8;
+constexpr size_t PUBLIC_DEVICE_BATCH = 256;  // pairs per XOF / expansion launch (1 MiB of matrices each); a call with more misses runs in rounds
+
+// The public tables of the U pairs of a call (pinned for its duration; duplicates allowed): tabs[u], with the babystep-giantstep
+// variant where use_bsgs.  The pairs the cache lacks get their randomness first -- on the host, pair by pair, or on the device for
+// all of them at once (public_randomness_enqueue) -- and then go through the per-pair table pipeline.  *built: pairs anything was built for
+int ensure_blocks(hhe_ctx *c, const PastaPair *pairs, size_t U, int use_bsgs, BlockTables **tabs, size_t *built = nullptr)
+{
+    std::vector<PastaPair> miss;  // distinct, in order of first appearance
+    {
+        std::map<PastaPair, bool> seen;
+        for (size_t u = 0; u < U; ++u) {
+            auto it = c->blocks.find(pairs[u]);
+            if (it != c->blocks.end()) it->second.last_call = c->block_call;
+            if ((it == c->blocks.end() || (use_bsgs && !it->second.bsgs)) && seen.emplace(pairs[u], true).second) miss.push_back(pairs[u]);
+        }
+    }
+    if (built) *built = miss.size();
+    if (miss.empty()) {  // the steady state of a service: nothing below is allocated
+        for (size_t u = 0; u < U; ++u) tabs[u] = &c->blocks.find(pairs[u])->second;
+        return HHE_OK;
+    }
+    const bool on_device = c->public_device >= 0 ? c->public_device != 0 : miss.size() >= PUBLIC_DEVICE_MIN;
+    int rc = HHE_OK;
+    auto build = [&](const PastaPair &id, const PairRandomness &r) {
+        BlockTables *bt = nullptr;
+        auto it = c->blocks.find(id);
+        if (it != c->blocks.end()) bt = &it->second;
+        else if (int e = build_block(c, id, r, &bt)) return e;
+        return use_bsgs && !bt->bsgs ? build_bsgs(c, bt, r) : (int)HHE_OK;
+    };
+    if (on_device) {
+        for (size_t m0 = 0; m0 < miss.size() && !rc; m0 += PUBLIC_DEVICE_BATCH) {
+            const size_t cnt = std::min(PUBLIC_DEVICE_BATCH, miss.size() - m0);
+            DevBuf d_pairs(cnt * sizeof(PastaPair)), d_rand(cnt * PASTA_RAND_PER_BLOCK * 8), d_mats(cnt * PASTA_MATS_WORDS * 8), d_rcs(cnt * PASTA_RCS_WORDS * 8);
+            if (!d_pairs.p || !d_rand.p || !d_mats.p || !d_rcs.p) return dev_fail("public randomness alloc");
+            public_randomness_enqueue(c, miss.data() + m0, cnt, (PastaPair *)d_pairs.p, d_rand.w(), d_mats.w(), d_rcs.w(), c->w->stream);
+            c->last_public_built += cnt;
+            for (size_t m = 0; m < cnt && !rc; ++m) {
+                PairRandomness r;
+                r.d_mats = d_mats.w() + m * PASTA_MATS_WORDS; r.d_rcs = d_rcs.w() + m * PASTA_RCS_WORDS;
+                rc = build(miss[m0 + m], r);
+            }
+            if (rc) rt_sync(c->w->stream);  // the buffers above go with this scope
+        }
+    } else {
+        std::vector<u64> mats(PASTA_MATS_WORDS), rcs(PASTA_RCS_WORDS);
+        for (size_t m = 0; m < miss.size() && !rc; ++m) {
+            pasta3_block_randomness(c->t, miss[m].nonce, miss[m].counter, mats.data(), rcs.data());
+            PairRandomness r;
+            r.h_mats = mats.data(); r.h_rcs = rcs.data();
+            rc = build(miss[m], r);
+        }
+    }
+    if (rc) return rc;
+    for (size_t u = 0; u < U; ++u) tabs[u] = &c->blocks.find(pairs[u])->second;
     return HHE_OK;
 }
 
@@ -481,7 +573,7 @@ void l0_flush(hhe_ctx *c, const L0Capture &cap, int first, int steps)
     p.mul_ptrs = c->l0_ptrs.p; p.mul_shift = (size_t)first * ln; p.mul_step_stride = ln;
     k_perm(p, c->w->stream);
 }
-// What the loop is run for: PASTA's affine layer `layer` (128 steps of rotate_rows(-1), the tables of ensure_block) or a plain-matrix
+// What the loop is run for: PASTA's affine layer `layer` (128 steps of rotate_rows(-1), the tables of build_block) or a plain-matrix
 // handle (hhe_matrix: dim steps of rotate_rows(+1), one table for every item)
 struct DiagSched {
     int steps;      // diagonals = states of the chain
@@ -528,7 +620,7 @@ int matmul_diagonal_fused(hhe_ctx *c, const DiagSched &sch, const u64 *const *d_
     // the shared chain takes the separate-kernel step for every N: one ciphertext is latency-bound either way, and the row kernel's
     // profile counters (hhe_ctx_profile) keep counting batch launches only
     const bool rowk = use_row_kernel(c) && !cap;
-    const size_t pdiag_words = sch.s_off;  // the Shoup quotients of pdiag follow the table (ensure_block, hhe_matrix_create)
+    const size_t pdiag_words = sch.s_off;  // the Shoup quotients of pdiag follow the table (build_block, hhe_matrix_create)
     const u64 *key_s = nullptr;
     if (rowk) {
         int rc = ensure_key_shoup(c, key, &key_s);
@@ -926,7 +1018,7 @@ static int ks_match_resolve(hhe_ctx *c, u64 *snap)
 // final wait has succeeded (commit); on every other path they are freed when the call returns, which is after that wait as well
 struct KsPending {
     u64 *snap = nullptr;                       // copy of enc_key (no resident snapshot equals it)
-    std::vector<std::pair<u64, u64 *>> cts;    // (counter, copy of its new keystream)
+    std::vector<std::pair<PastaPair, u64 *>> cts;    // (pair, copy of its new keystream)
     ~KsPending()
     {
         rt_free(snap);
@@ -959,7 +1051,7 @@ struct KsPending {
 // Without the cache (HHE_KS_CACHE=0, or a profiled call) a call of distinct counters (U == B) runs as one phase, with no table and no map.
 // transcipher_enqueue returns after enqueueing; whatever it returns, its caller waits for the main stream before anything it staged goes.
 static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64_t *cw, const uint32_t *ncw,
-                               const uint64_t *block_index, size_t B, int use_bsgs, uint64_t *out, KsPending &pend, KsCache::Entry &kkey)
+                               const PastaPair *block_index, size_t B, int use_bsgs, uint64_t *out, KsPending &pend, KsCache::Entry &kkey)
 {
     const size_t n = c->n, ctw = c->ct_words();
     Lane &main = c->lanes[0];
@@ -971,12 +1063,13 @@ static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64
     const bool may_predict = cache && item && !c->ks_cache.snaps.empty();
     if (cache && !may_predict && (rc = ks_match_enqueue(c, enc_key))) return rc;
     // 2. host preparation.  The distinct counters in order of first appearance; umap[b]: where item b's counter stands among them
-    std::vector<u64> uniq;
+    std::vector<PastaPair> uniq;
     std::vector<u32> umap;
     if (c->dedup) {
-        std::map<u64, u32> seen;
+        std::map<PastaPair, u32> seen;
         umap.resize(B);
         for (size_t b = 0; b < B; ++b) {
+            if (b && block_index[b] == block_index[b - 1]) { umap[b] = umap[b - 1]; continue; }  // a run of one pair: no lookup
             auto ins = seen.emplace(block_index[b], (u32)uniq.size());
             if (ins.second) uniq.push_back(block_index[b]);
             umap[b] = ins.first->second;
@@ -984,7 +1077,7 @@ static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64
     }
     const bool dedup = c->dedup && (cache || uniq.size() < B);
     const size_t U = dedup ? uniq.size() : B;  // keystreams the call needs
-    const uint64_t *counters = dedup ? uniq.data() : block_index;
+    const PastaPair *counters = dedup ? uniq.data() : block_index;
     c->last_unique = c->last_evaluated = U;
     // staging: [MAX_SNAPSHOTS] flags | [B] pointers or map | [B][128] words.  Every word of the last part is written: nothing of an earlier call stays
     u64 *const h_tab = c->fin_host.p + KsCache::MAX_SNAPSHOTS, *const h_words = h_tab + fin_tab_words(B);
@@ -995,10 +1088,7 @@ static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64
     }
     // public tables of every counter of the call (pinned for its duration), kept keystreams or not
     std::vector<BlockTables *> tabs(U);
-    for (size_t u = 0; u < U; ++u) {
-        if ((rc = ensure_block(c, counters[u], &tabs[u]))) return rc;
-        if (use_bsgs && (rc = ensure_bsgs_tables(c, counters[u], tabs[u]))) return rc;
-    }
+    if ((rc = ensure_blocks(c, counters, U, use_bsgs, tabs.data()))) return rc;
     // 2b. The item kernel has no half that runs ahead of the keystreams, so nothing would hide the wait for the comparison: predict
     // its answer -- the snapshot used last -- and, if every counter of the call has a kept keystream under it, enqueue the whole
     // finishing pass behind the comparison before waiting.  The probe touches no stamp.  A call the flags do not confirm goes on as
@@ -1114,10 +1204,26 @@ static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64
     if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_pasta3_transcipher");  // `keep` and the host vectors above go with this frame
     return rc;
 }
-static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t *cw, const uint32_t *ncw,
-                            const uint64_t *block_index, size_t B, int use_bsgs, uint64_t *out)
+// Groups of a call through an entry point that takes nonces: contiguous runs of items whose distinct pairs fit block_cache_limit (at
+// least one pair per group), so that an earlier group's tables are evictable when a later one needs room -- an honest stream has a
+// fresh pair per block, and the tables of all of them need not fit at once.  ends[g] = one past the last item of group g
+static std::vector<size_t> pair_groups(const hhe_ctx *c, const PastaPair *ids, size_t B, int use_bsgs)
 {
-    if (!c || !enc_key || !cw || !ncw || !block_index || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_pasta3_transcipher: null argument or empty batch");
+    const size_t per = block_entry_bytes(c) + (use_bsgs ? block_bsgs_bytes(c) : 0), cap = std::max<size_t>(1, c->block_cache_limit / per);
+    std::vector<size_t> ends;
+    std::map<PastaPair, bool> in;
+    for (size_t b = 0; b < B; ++b) {
+        if (!in.count(ids[b]) && in.size() == cap) { ends.push_back(b); in.clear(); }
+        in.emplace(ids[b], true);
+    }
+    ends.push_back(B);
+    return ends;
+}
+// grouped: the call came through an entry point with nonces (pair_groups); else it is one group whatever it needs
+static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t *cw, const uint32_t *ncw,
+                            const PastaPair *ids, size_t B, int use_bsgs, uint64_t *out, bool grouped)
+{
+    if (!c || !enc_key || !cw || !ncw || !ids || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_pasta3_transcipher: null argument or empty batch");
     const size_t n = c->n, half = n / 2;
     // pasta_3_seal.cpp:376-377
     if ((size_t)PASTA_T * 2 != n && (size_t)PASTA_T * 4 > n) return fail(HHE_ERR_TOO_FEW_SLOTS, "too little slots for matmul implementation!");
@@ -1133,15 +1239,31 @@ static int transcipher_impl(hhe_ctx *c, const uint64_t *enc_key, const uint64_t 
     c->w = &main;
     int rc;
     if ((rc = ensure_feistel_mask(c))) return rc;
-    ++c->block_call;
-    c->last_hits = 0;
-    // from here on work is enqueued that reads host staging and the pending copies: every path ends in the final wait
-    KsPending pend;
-    KsCache::Entry kkey{nullptr, 0, c->gks->serial, c->rks->serial, use_bsgs != 0, c->block_call};
-    rc = transcipher_enqueue(c, enc_key, cw, ncw, block_index, B, use_bsgs, out, pend, kkey);
-    if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_pasta3_transcipher");
-    if (!rc) pend.commit(c, kkey);  // a failed call leaves nothing behind
+    const std::vector<size_t> ends = grouped ? pair_groups(c, ids, B, use_bsgs) : std::vector<size_t>{B};
+    size_t unique = 0, evaluated = 0, hits = 0;
+    c->last_public_built = 0;
+    for (size_t g = 0, b0 = 0; g < ends.size() && !rc; b0 = ends[g++]) {
+        const size_t bc = ends[g] - b0;
+        ++c->block_call;
+        c->last_hits = 0;
+        // from here on work is enqueued that reads host staging and the pending copies: every path ends in the final wait
+        KsPending pend;
+        KsCache::Entry kkey{nullptr, 0, c->gks->serial, c->rks->serial, use_bsgs != 0, c->block_call};
+        rc = transcipher_enqueue(c, enc_key, cw + b0 * PASTA_T, ncw + b0, ids + b0, bc, use_bsgs, out + b0 * c->ct_words(), pend, kkey);
+        if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_pasta3_transcipher");
+        if (!rc) pend.commit(c, kkey);  // a failed call leaves nothing behind
+        unique += c->last_unique; evaluated += c->last_evaluated; hits += c->last_hits;
+    }
+    c->last_unique = unique; c->last_evaluated = evaluated; c->last_hits = hits;
+    c->last_groups = ends.size();
     return rc;
+}
+// the items' pairs: (nonce[b], block_index[b]), or the counters under the reference's fixed nonce
+static std::vector<PastaPair> pairs_of(const uint64_t *nonce, const uint64_t *block_index, size_t B)
+{
+    std::vector<PastaPair> ids(block_index ? B : 0);
+    for (size_t b = 0; b < ids.size(); ++b) ids[b] = nonce ? PastaPair(nonce[b], block_index[b]) : PastaPair(block_index[b]);
+    return ids;
 }
 extern "C" int hhe_pasta3_transcipher_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const uint64_t *enc_key, const uint64_t *cw,
                                          const uint32_t *ncw, const uint64_t *block_index, size_t B, int use_bsgs, uint64_t *out)
@@ -1151,12 +1273,65 @@ extern "C" int hhe_pasta3_transcipher_ks(hhe_ctx *c, const hhe_keyset *rk, const
     int rc = check_sets(c, rk, gk);
     if (rc) return rc;
     KeyScope keys(c, gk, rk);
-    return transcipher_impl(c, enc_key, cw, ncw, block_index, B, use_bsgs, out);
+    const std::vector<PastaPair> ids = pairs_of(nullptr, block_index, B);
+    return transcipher_impl(c, enc_key, cw, ncw, block_index ? ids.data() : nullptr, B, use_bsgs, out, false);
 }
 extern "C" int hhe_pasta3_transcipher(hhe_ctx *c, const uint64_t *enc_key, const uint64_t *cw, const uint32_t *ncw,
                                       const uint64_t *block_index, size_t B, int use_bsgs, uint64_t *out)
 {
     return hhe_pasta3_transcipher_ks(c, nullptr, nullptr, enc_key, cw, ncw, block_index, B, use_bsgs, out);
+}
+extern "C" int hhe_pasta3_transcipher_nonce_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const uint64_t *enc_key, const uint64_t *cw,
+                                               const uint32_t *ncw, const uint64_t *nonce, const uint64_t *block_index, size_t B, int use_bsgs,
+                                               uint64_t *out)
+{
+    HHE_LOCK(c);
+    if (!c) return fail(HHE_ERR_INVALID, "hhe_pasta3_transcipher: null context");
+    int rc = check_sets(c, rk, gk);
+    if (rc) return rc;
+    KeyScope keys(c, gk, rk);
+    const bool have = nonce && block_index;
+    const std::vector<PastaPair> ids = pairs_of(nonce, have ? block_index : nullptr, B);
+    return transcipher_impl(c, enc_key, cw, ncw, have ? ids.data() : nullptr, B, use_bsgs, out, true);
+}
+
+// Pasta::init_shake + get_random_matrix + get_rc_vec (pasta_3_plain.cpp:56-119) on the device, for callers that want the matrices there
+// (and for the tests of the kernels behind ensure_blocks)
+extern "C" int hhe_pasta3_block_randomness_dev(hhe_ctx *c, const uint64_t *nonces, const uint64_t *blocks, size_t count, uint64_t *mats, uint64_t *rcs)
+{
+    HHE_LOCK(c);
+    if (!c || !nonces || !blocks || !mats || !rcs || count == 0 || count > ((size_t)1 << 16))
+        return fail(HHE_ERR_INVALID, "hhe_pasta3_block_randomness_dev: bad arguments");
+    const std::vector<PastaPair> ids = pairs_of(nonces, blocks, count);
+    rt_stream st = c->lanes[0].stream;
+    DevBuf d_pairs(count * sizeof(PastaPair)), d_rand(count * PASTA_RAND_PER_BLOCK * 8);
+    if (!d_pairs.p || !d_rand.p) return dev_fail("hhe_pasta3_block_randomness_dev");
+    public_randomness_enqueue(c, ids.data(), count, (PastaPair *)d_pairs.p, d_rand.w(), mats, rcs, st);
+    if (rt_sync(st)) return dev_fail("hhe_pasta3_block_randomness_dev");  // temporaries are released on return
+    return HHE_OK;
+}
+
+// The table half of a transciphering call through hhe_pasta3_transcipher_nonce_ks on these pairs, in its groups: a service warms a
+// counter range with it
+extern "C" int hhe_pasta3_prepare_tables(hhe_ctx *c, const uint64_t *nonces, const uint64_t *blocks, size_t count, int use_bsgs, size_t *built_out)
+{
+    HHE_LOCK(c);
+    if (!c || !nonces || !blocks || count == 0) return fail(HHE_ERR_INVALID, "hhe_pasta3_prepare_tables: bad arguments");
+    const std::vector<PastaPair> ids = pairs_of(nonces, blocks, count);
+    const std::vector<size_t> ends = pair_groups(c, ids.data(), count, use_bsgs);
+    c->w = &c->lanes[0];
+    c->last_public_built = 0;
+    size_t total = 0;
+    int rc = HHE_OK;
+    for (size_t g = 0, b0 = 0; g < ends.size() && !rc; b0 = ends[g++]) {
+        ++c->block_call;
+        std::vector<BlockTables *> tabs(ends[g] - b0);
+        size_t built = 0;
+        rc = ensure_blocks(c, ids.data() + b0, tabs.size(), use_bsgs, tabs.data(), &built);
+        if (!rc) total += built;
+    }
+    if (built_out) *built_out = total;
+    return rc;
 }
 
 extern "C" int hhe_pasta3_set_block_cache_limit(hhe_ctx *c, size_t bytes)
@@ -1219,29 +1394,31 @@ extern "C" int hhe_flatten(hhe_ctx *c, const uint64_t *blocks, size_t nblocks, u
 
 // BaseCSP::decompose (src/examples/CSP/CSP.cpp:235-283) / hhe_pktnn_1fc_inference (hhe_pktnn_examples.cpp:578-630) on device:
 // per record: decomposition of every 128-word block, mask of the ragged last block, flatten -- without leaving HBM.
-extern "C" int hhe_decompose_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_keyset *flatten_gk, const uint64_t *enc_key,
-                                const uint64_t *records, size_t S, size_t nwords, int mask_last, uint64_t *out)
+// nonces: one per record (its blocks run under (nonces[s], 0), (nonces[s], 1), ...), or null = the reference's fixed nonce
+static int decompose_impl(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_keyset *flatten_gk, const uint64_t *enc_key,
+                          const uint64_t *records, const uint64_t *nonces, size_t S, size_t nwords, int mask_last, uint64_t *out)
 {
     HHE_LOCK(c);
     if (c) { int rcs = check_sets(c, rk, gk, flatten_gk); if (rcs) return rcs; }
     if (!c || !enc_key || !records || !out || S == 0 || nwords == 0) return fail(HHE_ERR_INVALID, "hhe_decompose: bad arguments");
     const size_t nb = (nwords + PASTA_T - 1) / PASTA_T, rem = nwords % PASTA_T, ctw = c->ct_words();
     if (nb * PASTA_T > c->n / 2) return fail(HHE_ERR_INVALID, "hhe_decompose: record does not fit one batching row");
-    std::vector<u64> cw(S * nb * PASTA_T, 0), bidx(S * nb);
+    std::vector<u64> cw(S * nb * PASTA_T, 0);
+    std::vector<PastaPair> bidx(S * nb);
     std::vector<uint32_t> ncw(S * nb);
     for (size_t s = 0; s < S; ++s)
         for (size_t b = 0; b < nb; ++b) {
             const size_t lo = b * PASTA_T, hi = std::min(lo + PASTA_T, nwords);
             memcpy(&cw[(s * nb + b) * PASTA_T], records + s * nwords + lo, (hi - lo) * 8);
             ncw[s * nb + b] = (uint32_t)(hi - lo);
-            bidx[s * nb + b] = b;
+            bidx[s * nb + b] = nonces ? PastaPair(nonces[s], b) : PastaPair(b);
         }
     int rc = c->d_blocks.reserve(c, S * nb * ctw, "hhe_decompose");  // the decompositions of all blocks
     if (rc) return rc;
     u64 *blocks = c->d_blocks.p;
     {   // PASTA_SEAL HHE(context, pk, sk, analyst rk, analyst gk).decomposition(...) (CSP.cpp:238-252)
         KeyScope keys(c, gk, rk);
-        rc = transcipher_impl(c, enc_key, cw.data(), ncw.data(), bidx.data(), S * nb, 0, blocks);
+        rc = transcipher_impl(c, enc_key, cw.data(), ncw.data(), bidx.data(), S * nb, 0, blocks, nonces != nullptr);
     }
     if (!rc && mask_last && rem) {
         // hhe_pktnn_examples.cpp:620-625: ones on the first `rem` slots (CSP.cpp:264-269 intends the same)
@@ -1263,6 +1440,17 @@ extern "C" int hhe_decompose_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keys
     }
     if (!rc && rt_sync(c->lanes[0].stream)) rc = dev_fail("hhe_decompose");
     return rc;
+}
+extern "C" int hhe_decompose_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_keyset *flatten_gk, const uint64_t *enc_key,
+                                const uint64_t *records, size_t S, size_t nwords, int mask_last, uint64_t *out)
+{
+    return decompose_impl(c, rk, gk, flatten_gk, enc_key, records, nullptr, S, nwords, mask_last, out);
+}
+extern "C" int hhe_decompose_nonce_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_keyset *flatten_gk, const uint64_t *enc_key,
+                                      const uint64_t *records, const uint64_t *nonces, size_t S, size_t nwords, int mask_last, uint64_t *out)
+{
+    if (!nonces) return fail(HHE_ERR_INVALID, "hhe_decompose: bad arguments");
+    return decompose_impl(c, rk, gk, flatten_gk, enc_key, records, nonces, S, nwords, mask_last, out);
 }
 extern "C" int hhe_decompose(hhe_ctx *c, const uint64_t *enc_key, const uint64_t *records, size_t S, size_t nwords,
                              int mask_last, uint64_t *out)
@@ -1947,7 +2135,7 @@ extern "C" int hhe_matrix_create(hhe_ctx *c, const uint64_t *M, size_t dim, cons
     op_encode(c, dv.w(), dim, (int)stride, (int)stride, -1, plain.w());
     op_lift_ntt(c, plain.w(), dim, diag.w());
     if (!n1) {
-        // multipliers in the frame of rotate_rows(+1) and their Shoup quotients: the `pdiag` form of ensure_block
+        // multipliers in the frame of rotate_rows(+1) and their Shoup quotients: the `pdiag` form of build_block
         PermArgs p = perm_args(c, dim * c->L, diag.w(), m->tab, ln);
         p.elt = galois_elt_from_step(c, 1);
         k_perm(p, st);

@@ -16,21 +16,24 @@ void barrett_ratio(u64 q, u64 &lo, u64 &hi)
     lo = (u64)(((two64 % q) << 64) / q);
 }
 
-int keystream_into(hhe_ctx *c, const uint64_t *key, uint64_t first_block, size_t nblocks, u64 *ks, rt_stream st)
+// nblocks keystream blocks under (nonce, first_block + i), or -- pairs set -- under pairs[i]
+int keystream_into(hhe_ctx *c, const uint64_t *key, uint64_t nonce, uint64_t first_block, const PastaPair *pairs, size_t nblocks, u64 *ks, rt_stream st)
 {
     for (int i = 0; i < 2 * PASTA_T; ++i)
         if (key[i] >= c->t) return fail(HHE_ERR_INVALID, "PASTA secret key word is not below the plain modulus");
-    DevBuf rnd(nblocks * PASTA_RAND_PER_BLOCK * 8), dkey(2 * PASTA_T * 8);
-    if (!rnd.p || !dkey.p) return dev_fail("hhe_pasta3_plain_keystream");
+    DevBuf rnd(nblocks * PASTA_RAND_PER_BLOCK * 8), dkey(2 * PASTA_T * 8), dpairs(pairs ? nblocks * sizeof(PastaPair) : 8);
+    if (!rnd.p || !dkey.p || !dpairs.p) return dev_fail("hhe_pasta3_plain_keystream");
     if (rt_h2d(dkey.p, key, 2 * PASTA_T * 8, st)) return dev_fail("hhe_pasta3_plain_keystream");
-    PastaXofArgs x;
+    if (pairs && rt_h2d(dpairs.p, pairs, nblocks * sizeof(PastaPair), st)) return dev_fail("hhe_pasta3_plain_keystream");
+    PastaXofArgs x = zeroed<PastaXofArgs>();
     x.mode = XOF_PASTA;
-    x.t = c->t; x.nonce = PASTA_NONCE; x.first_block = first_block; x.nblocks = (int)nblocks; x.rand = rnd.w();
+    x.t = c->t; x.nonce = nonce; x.first_block = first_block; x.nblocks = (int)nblocks; x.rand = rnd.w();
+    x.pairs = pairs ? (const PastaPair *)dpairs.p : nullptr;
     int bits = 0;
     for (u64 v = c->t; v; v >>= 1) ++bits;
     x.mask = bits >= 64 ? ~(u64)0 : (((u64)1 << bits) - 1);  // Pasta::Pasta(): max_prime_size (pasta_3_plain.cpp:150-153)
     k_pasta_xof(x, st);
-    PastaPlainArgs p;
+    PastaPlainArgs p = zeroed<PastaPlainArgs>();
     p.t = c->t; barrett_ratio(c->t, p.r_lo, p.r_hi);
     p.rand = rnd.w(); p.key = dkey.w(); p.ks = ks; p.nblocks = (int)nblocks;
     k_pasta_plain(p, st);
@@ -44,28 +47,52 @@ extern "C" int hhe_pasta3_plain_keystream(hhe_ctx *c, const uint64_t *key, uint6
     HHE_LOCK(c);
     if (!c || !key || !ks || nblocks == 0 || nblocks > ((size_t)1 << 24))
         return fail(HHE_ERR_INVALID, "hhe_pasta3_plain_keystream: bad arguments");
-    return keystream_into(c, key, first_block, nblocks, ks, c->lanes[0].stream);
+    return keystream_into(c, key, PASTA_NONCE, first_block, nullptr, nblocks, ks, c->lanes[0].stream);
 }
-
-extern "C" int hhe_pasta3_plain_crypt(hhe_ctx *c, const uint64_t *key, const uint64_t *in, size_t S, size_t nwords, int decrypt,
-                                      uint64_t *out)
+extern "C" int hhe_pasta3_plain_keystream_nonce(hhe_ctx *c, const uint64_t *key, uint64_t nonce, uint64_t first_block, size_t nblocks, uint64_t *ks)
 {
     HHE_LOCK(c);
-    if (!c || !key || !in || !out || S == 0 || nwords == 0) return fail(HHE_ERR_INVALID, "hhe_pasta3_plain_crypt: bad arguments");
+    if (!c || !key || !ks || nblocks == 0 || nblocks > ((size_t)1 << 24))
+        return fail(HHE_ERR_INVALID, "hhe_pasta3_plain_keystream: bad arguments");
+    return keystream_into(c, key, nonce, first_block, nullptr, nblocks, ks, c->lanes[0].stream);
+}
+
+// nonces: one per record (each record restarts at block counter 0 under its own nonce), or null: every PASTA::encrypt call of the
+// reference restarts at block counter 0 with the fixed nonce, so all records share one keystream
+static int plain_crypt(hhe_ctx *c, const uint64_t *key, const uint64_t *nonces, const uint64_t *in, size_t S, size_t nwords, int decrypt, uint64_t *out)
+{
     const size_t nb = (nwords + PASTA_T - 1) / PASTA_T;  // ceil(size / plain_size) (pasta_3_plain.cpp:13)
+    const size_t nks = nonces ? S * nb : nb;
+    if (nks > ((size_t)1 << 24)) return fail(HHE_ERR_INVALID, "hhe_pasta3_plain_crypt: bad arguments");
     rt_stream st = c->lanes[0].stream;
-    DevBuf ks(nb * PASTA_T * 8);
+    DevBuf ks(nks * PASTA_T * 8);
     if (!ks.p) return dev_fail("hhe_pasta3_plain_crypt");
-    // every PASTA::encrypt call restarts at block counter 0 with the fixed nonce, so all records share one keystream
-    int rc = keystream_into(c, key, 0, nb, ks.w(), st);
+    std::vector<PastaPair> pairs(nonces ? nks : 0);
+    for (size_t i = 0; i < pairs.size(); ++i) pairs[i] = PastaPair(nonces[i / nb], i % nb);
+    int rc = keystream_into(c, key, PASTA_NONCE, 0, nonces ? pairs.data() : nullptr, nks, ks.w(), st);
     if (rc) return rc;
     PastaCryptArgs a;
     u64 lo;
     a.t = c->t; barrett_ratio(c->t, lo, a.r_hi);
     a.in = in; a.ks = ks.w(); a.out = out; a.S = S; a.nwords = nwords; a.decrypt = decrypt != 0;
+    a.ks_stride = nonces ? nb * PASTA_T : 0;
     k_pasta_crypt(a, st);
     if (rt_sync(st)) return dev_fail("hhe_pasta3_plain_crypt");
     return HHE_OK;
+}
+extern "C" int hhe_pasta3_plain_crypt(hhe_ctx *c, const uint64_t *key, const uint64_t *in, size_t S, size_t nwords, int decrypt,
+                                      uint64_t *out)
+{
+    HHE_LOCK(c);
+    if (!c || !key || !in || !out || S == 0 || nwords == 0) return fail(HHE_ERR_INVALID, "hhe_pasta3_plain_crypt: bad arguments");
+    return plain_crypt(c, key, nullptr, in, S, nwords, decrypt, out);
+}
+extern "C" int hhe_pasta3_plain_crypt_nonce(hhe_ctx *c, const uint64_t *key, const uint64_t *nonces, const uint64_t *in, size_t S, size_t nwords,
+                                            int decrypt, uint64_t *out)
+{
+    HHE_LOCK(c);
+    if (!c || !key || !nonces || !in || !out || S == 0 || nwords == 0) return fail(HHE_ERR_INVALID, "hhe_pasta3_plain_crypt: bad arguments");
+    return plain_crypt(c, key, nonces, in, S, nwords, decrypt, out);
 }
 
 // The phase of B ciphertexts [B][size][L][N] (coefficient form) under q_0 .. q_{L-1} without its c0: c1s [B][L][N] = c1 s (+ c2 s^2 for

@@ -8,6 +8,9 @@
 //                     linear_layer, :205-211)
 //   pasta_plain_phase one workgroup (256 lanes = 2 state halves x 128 columns) per block counter; the sequential
 //                     matrix rows (calculate_row, :86-100) are rebuilt on the fly in LDS (two rows live), never stored.
+// The server's end draws the same randomness for its public tables (PastaPlainArgs::mode = PP_MODE_EXPAND): the XOF launch then
+// reads a (nonce, counter) pair per lane, and the row phases write every row of the eight matrices and the round constants to
+// global memory in the layout of hhe_pasta3_block_randomness, where diag_kernel / bsgs_diag_kernel and the encoder read them.
 // Bodies are functions of (block, lane, phase) with a workgroup barrier between phases, so the tests-only CPU emulator
 // runs the same code.
 #pragma once
@@ -35,6 +38,7 @@ struct PastaXofArgs {
     int nblocks;  // lanes: block counters (XOF_PASTA) or 64-coefficient chunks (XOF_SAMPLE)
     u64 *rand;  // [nblocks][4][4][128]
     int mode;     // XofMode
+    const PastaPair *pairs;  // XOF_PASTA, optional (device) [nblocks]: lane gid absorbs pairs[gid] instead of (nonce, first_block + gid)
     // XOF_SAMPLE
     u64 seed[4];  // the 32 seed bytes as little-endian words
     u32 purpose, elt, first_index;
@@ -48,13 +52,19 @@ struct PastaPlainArgs {
     const u64 *key;   // [256] secret key words (device)
     u64 *ks;          // [nblocks][128] keystream blocks
     int nblocks;
+    int mode;         // PlainMode
+    // PP_MODE_EXPAND: block = one (nonce, counter) pair of the XOF launch; key and ks are unused
+    u64 *mats;        // [nblocks][4][2][128][128] rows of get_random_matrix, as DiagArgs::mats / BsgsDiagArgs::mats are read
+    u64 *rcs;         // [nblocks][4][2][128] round constants, as op_encode reads them for BlockTables::rc
 };
+enum PlainMode { PP_MODE_KEYSTREAM = 0, PP_MODE_EXPAND = 1 };
 struct PastaCryptArgs {  // records [S][nwords]; word i of a record uses keystream block i / 128, element i % 128
     u64 t, r_hi;  // r_hi = floor(2^64 / t)
     const u64 *in, *ks;
     u64 *out;
     size_t S, nwords;
     int decrypt;
+    size_t ks_stride;  // words between the keystreams of two records; 0: one keystream for all (the reference's fixed nonce)
 };
 
 // ------------------------------------------------------------------ SHAKE128 (FIPS 202), one sponge per lane
@@ -110,8 +120,8 @@ HD void pasta_xof_fields_body(const PastaXofArgs &a, size_t gid)
 #pragma unroll
     for (int i = 0; i < 25; i++) A[i] = 0;
     // message = BE64(nonce) || BE64(counter); lanes are little-endian, so each lane is the byte swap of its word
-    A[0] = pasta_bswap(a.nonce);
-    A[1] = pasta_bswap(a.first_block + gid);
+    A[0] = pasta_bswap(a.pairs ? a.pairs[gid].nonce : a.nonce);
+    A[1] = pasta_bswap(a.pairs ? a.pairs[gid].counter : a.first_block + gid);
     A[2] = 0x1f;                    // SHAKE domain suffix right after the 16 message bytes
     A[20] = 0x8000000000000000ULL;  // final pad bit of the 168-byte rate
     keccak_f1600(A);
@@ -139,8 +149,35 @@ constexpr int PP_STEPS_PER_LAYER = PASTA_T + 2 * (PASTA_T / 8) + 3;  // rows + r
 // One phase of layer `layer` for lane tau of the block's workgroup.  step: 0..127 row i; 128+2g / 129+2g reduction of
 // row group g (rows 8g..8g+7) -- issued by the driver loop right after row 8g+7; PP_* finish phases at the end.
 enum { PP_ROWSTEP = 0, PP_RED1 = 1, PP_RED2 = 2, PP_AFFINE = 3, PP_SBOX_A = 4, PP_SBOX_B = 5, PP_INIT = 6, PP_OUT = 7 };
+// PP_MODE_EXPAND: the phases of the keystream schedule that touch the matrices, with the state left out.  PP_ROWSTEP i rebuilds row i
+// of the layer's two matrices exactly as below (two rows live in LDS) and stores it; PP_AFFINE stores the layer's round constants;
+// every other phase is empty.  Rows of one matrix depend on each other only through LDS of the same layer, so a layer of a pair is
+// a unit of work of its own (the device launches one workgroup per (pair, layer); the emulator walks the layers of a pair in turn).
+HD void pasta_expand_phase(const PastaPlainArgs &a, int block, int tau, int layer, int kind, int i, u64 *lds)
+{
+    const int h = tau >> 7, j = tau & (PASTA_T - 1);
+    const u64 *rnd = a.rand + ((size_t)block * (PASTA_R + 1) + layer) * 4 * PASTA_T;
+    if (kind == PP_ROWSTEP) {
+        ModDev m;
+        m.q = a.t; m.r_lo = a.r_lo; m.r_hi = a.r_hi;
+        u64 v;
+        if (i == 0) {
+            v = rnd[h * PASTA_T + j];
+            lds[PP_ROW0 + tau] = v;
+        } else {  // calculate_row (:86-100)
+            const u64 *prev = lds + PP_ROW + ((i - 1) & 1) * 256 + h * PASTA_T;
+            v = mulmod(lds[PP_ROW0 + tau], prev[PASTA_T - 1], m);
+            if (j) v = addmod(v, prev[j - 1], a.t);
+        }
+        lds[PP_ROW + (i & 1) * 256 + tau] = v;
+        a.mats[((((size_t)block * (PASTA_R + 1) + layer) * 2 + h) * PASTA_T + i) * PASTA_T + j] = v;
+    } else if (kind == PP_AFFINE) {
+        a.rcs[((size_t)block * (PASTA_R + 1) + layer) * 2 * PASTA_T + tau] = rnd[2 * PASTA_T + tau];
+    }
+}
 HD void pasta_plain_phase(const PastaPlainArgs &a, int block, int tau, int layer, int kind, int i, u64 *lds)
 {
+    if (a.mode == PP_MODE_EXPAND) { pasta_expand_phase(a, block, tau, layer, kind, i, lds); return; }
     ModDev m;
     m.q = a.t; m.r_lo = a.r_lo; m.r_hi = a.r_hi;
     const u64 t = a.t;
@@ -214,6 +251,12 @@ template <class F> HD void pasta_plain_schedule(F &&f)
     }
     f(PP_OUT, PASTA_R, 0);
 }
+// the phases of one layer that PP_MODE_EXPAND does anything in: what a device workgroup of that mode walks
+template <class F> HD void pasta_expand_schedule(int layer, F &&f)
+{
+    for (int i = 0; i < PASTA_T; i++) f(PP_ROWSTEP, layer, i);
+    f(PP_AFFINE, layer, 0);
+}
 
 // PASTA::encrypt / decrypt (pasta_3_plain.cpp:9-46), element-wise over [S][nwords], literally: encrypt
 // (v + ks) % t on 64-bit words, decrypt v - ks with one conditional + t (no reduction of an input that is not below t)
@@ -221,7 +264,7 @@ HD void pasta_crypt_body(const PastaCryptArgs &a, size_t gid)
 {
     if (gid >= a.S * a.nwords) return;
     const size_t i = gid % a.nwords;
-    const u64 k = a.ks[i];
+    const u64 k = a.ks[(gid / a.nwords) * a.ks_stride + i];
     u64 v = a.in[gid];
     if (a.decrypt) {
         if (k > v) v += a.t;

@@ -18,6 +18,17 @@ constexpr int HHE_MAXK = HHE_MAXL + 1;
 constexpr int PASTA_T = 128;          // pasta_3_plain.h:18,32
 constexpr int PASTA_R = 3;            // pasta_3_plain.h:33
 constexpr u64 PASTA_NONCE = 123456789ULL;  // pasta_3_seal.cpp:47,115
+// What one PASTA block is drawn from: Pasta::init_shake(nonce, block_counter) (pasta_3_plain.cpp:56).  A bare counter is the pair under
+// the reference's fixed nonce, so the entry points that take counters and the ones that take pairs name the same cache entries.
+// Also the element of the device array a per-pair XOF launch reads (PastaXofArgs::pairs): two words, nonce first.
+struct PastaPair {
+    u64 nonce, counter;
+    PastaPair() = default;
+    constexpr PastaPair(u64 counter_) : nonce(PASTA_NONCE), counter(counter_) {}
+    constexpr PastaPair(u64 nonce_, u64 counter_) : nonce(nonce_), counter(counter_) {}
+    bool operator<(const PastaPair &o) const { return nonce != o.nonce ? nonce < o.nonce : counter < o.counter; }
+    bool operator==(const PastaPair &o) const { return nonce == o.nonce && counter == o.counter; }
+};
 
 // One RNS modulus as the kernels see it.  Tables live in device memory.
 struct ModDev {

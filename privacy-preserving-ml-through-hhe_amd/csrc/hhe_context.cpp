@@ -372,6 +372,7 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
     if (const char *mm = getenv("HHE_MATMUL")) c->matmul_mode = atoi(mm);
     if (const char *e = getenv("HHE_SHARED_L0")) c->shared_l0 = std::max(0, atoi(e));
     if (const char *e = getenv("HHE_DEDUP")) c->dedup = atoi(e) != 0;
+    if (const char *e = getenv("HHE_PUBLIC_DEVICE")) c->public_device = atoi(e) != 0;
     if (const char *e = getenv("HHE_KS_CACHE")) c->ks_cache.enabled = atoi(e) != 0;
     if (const char *e = getenv("HHE_FIN_FUSED")) c->fin_fused = atoi(e) != 0;
     if (const char *e = getenv("HHE_FIN_ITEM")) c->fin_item = atoi(e) != 0;
@@ -614,6 +615,9 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "fin_scale32") return fin_item_on(c) && c->fin_scale32 ? 1 : 0;  // ... with the plaintext scaled by 32-bit products and -c1 written early (HHE_FIN_SCALE32; t < 2^30 below every data prime)
     if (w == "mod_switch_launches") return c->mod_switch_launches;  // kernel launches of hhe_mod_switch: one per call of up to one chunk
     if (w == "noise_form") return (u64)c->noise_form;  // the last hhe_noise_budget launch: limb count of its register form, 0 = the LDS form
+    if (w == "public_device") return (u64)(int64_t)c->public_device;  // HHE_PUBLIC_DEVICE: 0 host, 1 device; unset: (uint64_t)-1, the path is chosen per call
+    if (w == "public_device_built") return c->last_public_built;     // pairs whose randomness the last call drew on the device
+    if (w == "transcipher_groups") return c->last_groups;            // groups the last transciphering call ran in (1 through the entries without nonces)
     if (w == "ks_cache") return c->ks_cache.enabled ? 1 : 0;      // keystreams are kept across calls (HHE_KS_CACHE)
     if (w == "ks_cache_hits") return c->last_hits;                // counters of the last call served from a kept keystream
     if (w == "ks_cache_entries") return c->ks_cache.entries();

@@ -205,7 +205,7 @@ struct hhe_ctx {
                                    // zero padded | [B][N] the intermediate of the transform mod t (unfused: the plaintexts)
     HostStage fin_host;            // [KsCache::MAX_SNAPSHOTS] flags of the key comparison, read back | the first two parts of fin_dev as they are uploaded
     void *ev_cmp = nullptr;        // recorded behind the read-back of the flags
-    size_t last_unique = 0;        // distinct counters of the last transciphering call: U, or B when it ran per item
+    size_t last_unique = 0;        // distinct (nonce, counter) pairs of the last transciphering call: U, or B when it ran per item (a call in groups: summed over its groups)
     size_t last_evaluated = 0;     // keystream chains the last call ran (= last_unique unless kept keystreams were found), and
     size_t last_hits = 0;          // the counters it found a kept keystream for
     KsCache ks_cache;              // keystream ciphertexts kept across calls, per counter (hhe_kscache.h; HHE_KS_CACHE, HHE_KS_CACHE_MB); it stands aside
@@ -243,7 +243,11 @@ struct hhe_ctx {
     GrowBuf<u32> d_flags;
 
     // PASTA public tables
-    std::map<u64, BlockTables> blocks;
+    std::map<PastaPair, BlockTables> blocks;     // by (nonce, counter); the entry points without a nonce name the pairs under PASTA_NONCE
+    int public_device = -1;                      // where the randomness of missing pairs is drawn (HHE_PUBLIC_DEVICE): 0 host (pasta3_block_randomness + upload),
+                                                 // 1 device (per-pair XOF + matrix expansion, ensure_blocks), -1 (unset): by the number of missing pairs, public_device_min
+    size_t last_public_built = 0;                // pairs whose randomness the last call drew on the device (hhe_ctx_query("public_device_built"))
+    size_t last_groups = 0;                      // groups the last transciphering call ran its items in (hhe_ctx_query("transcipher_groups"))
     size_t block_bytes = 0;                      // footprint of all cached block tables
     size_t block_cache_limit = (size_t)32 << 30; // bytes (hhe_pasta3_set_block_cache_limit, HHE_BLOCK_CACHE_MB): beyond it the least recently used counters go
     u64 block_call = 0;                          // running number of the transciphering calls

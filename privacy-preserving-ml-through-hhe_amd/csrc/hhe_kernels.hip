@@ -747,6 +747,17 @@ __global__ void __launch_bounds__(PASTA_PLAIN_THREADS) pasta_plain_kernel(PastaP
         __syncthreads();
     });
 }
+// PP_MODE_EXPAND: one workgroup per (pair, layer) -- the 127 dependent row steps of a layer are the critical path, and the four
+// layers of a pair share nothing but the XOF output; 3 x 256 words of LDS (first rows, two live rows)
+__global__ void __launch_bounds__(PASTA_PLAIN_THREADS) pasta_expand_kernel(PastaPlainArgs a)
+{
+    __shared__ u64 lds[PP_PROD];
+    const int block = (int)(blockIdx.x / (PASTA_R + 1));
+    pasta_expand_schedule((int)(blockIdx.x % (PASTA_R + 1)), [&](int kind, int layer, int i) {
+        pasta_expand_phase(a, block, (int)threadIdx.x, layer, kind, i, lds);
+        __syncthreads();
+    });
+}
 __global__ void __launch_bounds__(ELT_THREADS) pasta_crypt_kernel(PastaCryptArgs a) { pasta_crypt_body(a, GID); }
 void k_pasta_xof(const PastaXofArgs &a, rt_stream s)
 {
@@ -756,7 +767,9 @@ void k_pasta_xof(const PastaXofArgs &a, rt_stream s)
 }
 void k_pasta_plain(const PastaPlainArgs &a, rt_stream s)
 {
-    if (a.nblocks > 0) hipLaunchKernelGGL(pasta_plain_kernel, dim3(a.nblocks), dim3(PASTA_PLAIN_THREADS), 0, (hipStream_t)s, a);
+    if (a.nblocks <= 0) return;
+    if (a.mode == PP_MODE_EXPAND) hipLaunchKernelGGL(pasta_expand_kernel, dim3(a.nblocks * (PASTA_R + 1)), dim3(PASTA_PLAIN_THREADS), 0, (hipStream_t)s, a);
+    else hipLaunchKernelGGL(pasta_plain_kernel, dim3(a.nblocks), dim3(PASTA_PLAIN_THREADS), 0, (hipStream_t)s, a);
 }
 void k_pasta_crypt(const PastaCryptArgs &a, rt_stream s) { LAUNCH1D(pasta_crypt_kernel, a.S * a.nwords, s, a); }
 __global__ void __launch_bounds__(ELT_THREADS) decrypt_round_kernel(DecryptArgs a) { decrypt_scale_body(a, GID); }

@@ -2,8 +2,8 @@
 // (DESIGN.md "one keystream per key").  Host code only, no device runtime beyond rt_malloc / rt_free: tests/cpp/kscache_main.cpp
 // compiles it against logging stubs.
 //
-// The keystream ciphertext of a block counter is a function of the words of enc_key, the Galois and relinearization keys the call
-// names, the counter and use_bsgs.  What identifies them here:
+// The keystream ciphertext of a block is a function of the words of enc_key, the Galois and relinearization keys the call
+// names, the (nonce, counter) pair (PastaPair; "counter" below) and use_bsgs.  What identifies them here:
 //  - enc_key is the caller's device buffer, so only its words do: the cache keeps device copies (snapshots) of the key ciphertexts it
 //    holds keystreams for, at most MAX_SNAPSHOTS of them, and the call compares enc_key against them word for word on the device
 //    (ELT_DIFF; no hash).  An entry names its snapshot by a number that is never reused.
@@ -38,7 +38,7 @@ struct KsCache {
     size_t bytes = 0;
     u64 next_snap = 0;
     std::vector<Snapshot> snaps;
-    std::map<u64, std::vector<Entry>> by_counter;
+    std::map<PastaPair, std::vector<Entry>> by_counter;  // by (nonce, counter); a bare counter names the pair under PASTA_NONCE
 
     size_t entries() const
     {
@@ -47,7 +47,7 @@ struct KsCache {
         return k;
     }
     // the keystream of `counter` under the identity in `key` (ct and last_use ignored), or null; a hit is touched
-    const u64 *find(u64 counter, const Entry &key, u64 now)
+    const u64 *find(const PastaPair &counter, const Entry &key, u64 now)
     {
         auto it = by_counter.find(counter);
         if (it == by_counter.end()) return nullptr;
@@ -56,7 +56,7 @@ struct KsCache {
         return nullptr;
     }
     // the same without touching the hit: a call that predicts its key looks before it knows (hhe_api.cpp, transcipher_enqueue)
-    const u64 *peek(u64 counter, const Entry &key) const
+    const u64 *peek(const PastaPair &counter, const Entry &key) const
     {
         auto it = by_counter.find(counter);
         if (it == by_counter.end()) return nullptr;
@@ -77,45 +77,45 @@ struct KsCache {
             wait(c, synced);
             rt_free(snaps[v].words);
             snaps.erase(snaps.begin() + v);
-            drop_if(c, synced, [&](u64, const Entry &e) { return e.snap == id; });
+            drop_if(c, synced, [&](const PastaPair &, const Entry &e) { return e.snap == id; });
         }
         snaps.push_back({words, ++next_snap, now});
         return next_snap;
     }
     // takes e.ct.  Entries that the running call (`now`) neither made nor used go, least recently used first, while the budget is
     // passed; when that does not make room the new ciphertext is freed instead.  Returns whether it was kept
-    bool insert(hhe_ctx *c, u64 counter, const Entry &e)
+    bool insert(hhe_ctx *c, const PastaPair &counter, const Entry &e)
     {
         bool synced = false;
-        drop_if(c, synced, [&](u64 ctr, const Entry &o) { return ctr == counter && o.same_key(e); });  // never two of one identity
+        drop_if(c, synced, [&](const PastaPair &ctr, const Entry &o) { return ctr == counter && o.same_key(e); });  // never two of one identity
         while (bytes + entry_bytes > budget) {
-            u64 vc = 0;
+            PastaPair vc(0);
             const Entry *v = nullptr;
             for (auto &kv : by_counter)
                 for (const Entry &o : kv.second)
                     if (o.last_use != e.last_use && (!v || o.last_use < v->last_use)) { v = &o; vc = kv.first; }
             if (!v) { wait(c, synced); rt_free(e.ct); return false; }
             const u64 *ct = v->ct;
-            drop_if(c, synced, [&](u64 ctr, const Entry &o) { return ctr == vc && o.ct == ct; });
+            drop_if(c, synced, [&](const PastaPair &ctr, const Entry &o) { return ctr == vc && o.ct == ct; });
         }
         by_counter[counter].push_back(e);
         bytes += entry_bytes;
         return true;
     }
-    void drop_counter(hhe_ctx *c, u64 counter)
+    void drop_counter(hhe_ctx *c, const PastaPair &counter)
     {
         bool synced = false;
-        drop_if(c, synced, [&](u64 ctr, const Entry &) { return ctr == counter; });
+        drop_if(c, synced, [&](const PastaPair &ctr, const Entry &) { return ctr == counter; });
     }
     void drop_serial(hhe_ctx *c, u64 serial)
     {
         bool synced = false;
-        drop_if(c, synced, [&](u64, const Entry &e) { return e.gks == serial || e.rks == serial; });
+        drop_if(c, synced, [&](const PastaPair &, const Entry &e) { return e.gks == serial || e.rks == serial; });
     }
     void clear(hhe_ctx *c)  // entries and snapshots
     {
         bool synced = false;
-        drop_if(c, synced, [](u64, const Entry &) { return true; });
+        drop_if(c, synced, [](const PastaPair &, const Entry &) { return true; });
         for (Snapshot &s : snaps) { wait(c, synced); rt_free(s.words); }
         snaps.clear();
     }

@@ -140,9 +140,13 @@ void pasta3_block_randomness(u64 t, u64 nonce, u64 block, u64 *mats, u64 *rcs)
     }
 }
 
-extern "C" int hhe_pasta3_block_randomness(uint64_t t, uint64_t block_index, uint64_t *mats, uint64_t *rcs)
+extern "C" int hhe_pasta3_block_randomness_nonce(uint64_t t, uint64_t nonce, uint64_t block_index, uint64_t *mats, uint64_t *rcs)
 {
     if (!mats || !rcs || t < 2) { hhe_set_error("hhe_pasta3_block_randomness: invalid arguments"); return HHE_ERR_INVALID; }
-    pasta3_block_randomness(t, PASTA_NONCE, block_index, mats, rcs);
+    pasta3_block_randomness(t, nonce, block_index, mats, rcs);
     return HHE_OK;
+}
+extern "C" int hhe_pasta3_block_randomness(uint64_t t, uint64_t block_index, uint64_t *mats, uint64_t *rcs)
+{
+    return hhe_pasta3_block_randomness_nonce(t, PASTA_NONCE, block_index, mats, rcs);
 }
