@@ -1035,6 +1035,20 @@ struct KsPending {
         cts.clear();
     }
 };
+// Every upload into the table part of fin_dev (the pointer tables of the fused finishing pass, the u32 map of the unfused one), on
+// the main stream.  The context keeps the bytes of the last one (fin_tab_shadow); a table of the same length and bytes is what the
+// device holds -- or will hold when anything enqueued after this call runs -- and is not sent again.  A table equal to the
+// device's is right whatever lives at its addresses: the kernels would read the same pointers either way.
+static int fin_tab_upload(hhe_ctx *c, const u64 *h_tab, size_t bytes)
+{
+    std::vector<unsigned char> &sh = c->fin_tab_shadow;
+    if (sh.size() == bytes && !memcmp(sh.data(), h_tab, bytes)) return HHE_OK;
+    sh.clear();
+    if (rt_h2d(c->fin_dev.p, h_tab, bytes, c->lanes[0].stream)) return dev_fail("hhe_pasta3_transcipher: table upload");
+    sh.assign((const unsigned char *)h_tab, (const unsigned char *)h_tab + bytes);
+    ++c->fin_tab_uploads;
+    return HHE_OK;
+}
 
 // hhe_pasta3_transcipher with the key objects already named (c->rks / c->gks)
 // Everything before res = Enc(c_b) - KS is a function of the key ciphertext, the named key sets and the item's block counter only, so
@@ -1047,7 +1061,12 @@ struct KsPending {
 // an evaluated one in ks_tab.  The unfused one reads ks_tab through a map: the M evaluated counters first, in order of first
 // appearance, then copies of the kept ones.
 // Order of a call: the key comparison is enqueued first and the host does not wait for it until it has prepared the call and
-// enqueued the half of the finishing pass that does not depend on the keystreams (upload of the words, first pass).
+// enqueued the half of the finishing pass that does not depend on the keystreams (upload of the words, first pass).  A call that
+// may take the item kernel on a prediction (2b) prepares first and enqueues that kernel IN FRONT of the comparison: the kernel
+// reads no word of enc_key, so it starts while the runtime calls of the comparison are still being issued, and the comparison,
+// its event and ks_match_resolve mean what they mean elsewhere.  Such a call learns that it was refuted one kernel later.
+// What a steady call sends to the device: the item kernel reads the words where they are staged (page-locked staging), and a
+// table the device already holds is not uploaded again (fin_tab_upload) -- nothing, when the same counters come back.
 // Without the cache (HHE_KS_CACHE=0, or a profiled call) a call of distinct counters (U == B) runs as one phase, with no table and no map.
 // transcipher_enqueue returns after enqueueing; whatever it returns, its caller waits for the main stream before anything it staged goes.
 static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64_t *cw, const uint32_t *ncw,
@@ -1057,10 +1076,16 @@ static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64
     Lane &main = c->lanes[0];
     int rc;
     if ((rc = fin_reserve(c, B))) return rc;  // before anything reads the staging: growth replaces it
+    if (c->fin_tab_items != B) {  // the words and the intermediate of this call lie where the table of another item count was
+        c->fin_tab_shadow.clear();
+        c->fin_tab_items = B;
+    }
     const bool cache = c->dedup && c->ks_cache.enabled && !c->profile;
     const bool item = c->dedup && fin_item_for(c, B);  // the finishing pass of a two-phase call is one launch, one workgroup per item
-    // 1. the key comparison.  Where the item kernel may be enqueued on a prediction (2b) the comparison goes right in front of it
-    const bool may_predict = cache && item && !c->ks_cache.snaps.empty();
+    // 1. the key comparison.  Where the item kernel may be enqueued on a prediction (2b) the comparison goes right behind it.  Not
+    // where `out` overlaps the key ciphertext: every other path has read the key before it writes a result
+    const bool apart = (uintptr_t)(enc_key + ctw) <= (uintptr_t)out || (uintptr_t)(out + B * ctw) <= (uintptr_t)enc_key;
+    const bool may_predict = cache && item && apart && !c->ks_cache.snaps.empty();
     if (cache && !may_predict && (rc = ks_match_enqueue(c, enc_key))) return rc;
     // 2. host preparation.  The distinct counters in order of first appearance; umap[b]: where item b's counter stands among them
     std::vector<PastaPair> uniq;
@@ -1082,6 +1107,15 @@ static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64
     // staging: [MAX_SNAPSHOTS] flags | [B] pointers or map | [B][128] words.  Every word of the last part is written: nothing of an earlier call stays
     u64 *const h_tab = c->fin_host.p + KsCache::MAX_SNAPSHOTS, *const h_words = h_tab + fin_tab_words(B);
     u64 *const d_tab = c->fin_dev.p, *const d_words = d_tab + fin_tab_words(B), *const d_tmp = d_words + B * PASTA_T;
+    // The item kernel reads an item's 128 words once (fin_item_encode): out of page-locked staging it reads them where they are, and
+    // they are not uploaded.  The staging is not rewritten before the final wait of the call, which every path ends in.  The table is
+    // reloaded in every phase of the kernel and stays in device memory
+    const bool words_in_place = item && c->fin_host.pinned;
+    const u64 *const item_words = words_in_place ? h_words : d_words;
+    auto upload_words = [&] {
+        rt_h2d(d_words, h_words, B * PASTA_T * 8, main.stream);
+        ++c->fin_word_uploads;
+    };
     for (size_t b = 0; b < B; ++b) {
         memcpy(h_words + b * PASTA_T, cw + b * PASTA_T, ncw[b] * 8);
         memset(h_words + b * PASTA_T + ncw[b], 0, (PASTA_T - ncw[b]) * 8);
@@ -1091,9 +1125,9 @@ static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64
     if ((rc = ensure_blocks(c, counters, U, use_bsgs, tabs.data()))) return rc;
     // 2b. The item kernel has no half that runs ahead of the keystreams, so nothing would hide the wait for the comparison: predict
     // its answer -- the snapshot used last -- and, if every counter of the call has a kept keystream under it, enqueue the whole
-    // finishing pass behind the comparison before waiting.  The probe touches no stamp.  A call the flags do not confirm goes on as
-    // it would have without the prediction and finishes over `out` again, behind the stale launch on the same stream; what that
-    // launch read are cache entries, which go only behind a wait for the context's streams.
+    // finishing pass, then the comparison behind it, before waiting.  The probe touches no stamp.  A call the flags do not confirm
+    // goes on as it would have without the prediction and finishes over `out` again, behind the stale launch on the same stream; what
+    // that launch read are cache entries, which go only behind a wait for the context's streams.
     u64 predicted = 0;
     if (may_predict) {
         const KsCache &kc = c->ks_cache;
@@ -1107,16 +1141,18 @@ static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64
         for (size_t u = 0; u < U && all; ++u) all = (kept[u] = kc.peek(counters[u], probe)) != nullptr;
         if (all) {
             for (size_t b = 0; b < B; ++b) h_tab[b] = (u64)kept[umap[b]];
-            rt_h2d(d_tab, h_tab, (fin_tab_words(B) + B * PASTA_T) * 8, main.stream);  // table and words: one block
+            if ((rc = fin_tab_upload(c, h_tab, B * sizeof(u64)))) return rc;
+            if (!words_in_place) upload_words();
+            c->w = &main;
+            op_finish_item(c, item_words, d_tmp, nullptr, (const u64 *const *)d_tab, out, B);
             predicted = probe.snap;
         }
         if ((rc = ks_match_enqueue(c, enc_key))) return rc;
-        if (predicted) op_finish_item(c, d_words, d_tmp, nullptr, (const u64 *const *)d_tab, out, B);
     }
     // 3. the half of the finishing pass that does not depend on the keystreams
     const ChunkPlan fin = item ? ChunkPlan(B, B, 0) : plan_balanced(c, B);  // the item kernel takes the batch whole
     if (dedup && !predicted) {
-        rt_h2d(d_words, h_words, B * PASTA_T * 8, main.stream);
+        if (!words_in_place) upload_words();
         if (!item) rc = run_chunks(c, fin, [&](Lane &, size_t, size_t b0, size_t bc) {
             op_finish_front(c, d_words + b0 * PASTA_T, d_tmp + b0 * n, bc);
             return (int)HHE_OK;
@@ -1193,9 +1229,12 @@ static int transcipher_enqueue(hhe_ctx *c, const uint64_t *enc_key, const uint64
             }
         else
             for (size_t b = 0; b < B; ++b) ((u32 *)h_tab)[b] = (u32)slot[umap[b]];
-        rt_h2d(d_tab, h_tab, B * (by_ptr ? sizeof(u64) : sizeof(u32)), main.stream);
+        if ((rc = fin_tab_upload(c, h_tab, B * (by_ptr ? sizeof(u64) : sizeof(u32))))) {
+            rt_sync(main.stream);  // as above
+            return rc;
+        }
         c->w = &main;
-        if (item) op_finish_item(c, d_words, d_tmp, ks, (const u64 *const *)d_tab, out, B);
+        if (item) op_finish_item(c, item_words, d_tmp, ks, (const u64 *const *)d_tab, out, B);
         else rc = run_chunks(c, fin, [&](Lane &, size_t, size_t b0, size_t bc) {
             op_finish_back(c, d_tmp + b0 * n, ks, by_ptr ? (const u64 *const *)d_tab + b0 : nullptr, by_ptr ? nullptr : (const u32 *)d_tab + b0, out + b0 * ctw, bc);
             return (int)HHE_OK;

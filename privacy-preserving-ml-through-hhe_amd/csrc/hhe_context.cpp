@@ -436,7 +436,9 @@ void sync_ctx(hhe_ctx *c)
 // device block and host staging of the finishing pass of a transciphering call of B items
 int fin_reserve(hhe_ctx *c, size_t B)
 {
-    int rc = c->fin_dev.reserve(c, fin_tab_words(B) + B * (PASTA_T + c->n), "transciphering: finishing pass");
+    bool grew;
+    int rc = c->fin_dev.reserve(c, fin_tab_words(B) + B * (PASTA_T + c->n), "transciphering: finishing pass", &grew);
+    if (grew || rc) c->fin_tab_shadow.clear();  // a new block holds no table
     if (!rc) rc = c->fin_host.reserve(c, KsCache::MAX_SNAPSHOTS + fin_tab_words(B) + B * PASTA_T, "transciphering: finishing pass");
     return rc;
 }
@@ -612,6 +614,8 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "fin_item") return fin_item_on(c) ? 1 : 0;          // ... or as one kernel with one workgroup per item, from query("fin_item_min") items on (HHE_FIN_ITEM)
     if (w == "fin_item_min") return fin_item_on(c) ? (c->fin_item > 0 ? 1 : (u64)c->fin_item_min) : 0;
     if (w == "fin_item_launches") return c->fin_item_launches;
+    if (w == "fin_tab_uploads") return c->fin_tab_uploads;       // uploads of a finishing pass's pointer table or map that were enqueued: one the device already holds is skipped
+    if (w == "fin_word_uploads") return c->fin_word_uploads;     // uploads of the items' words: none where the item kernel reads them in the page-locked staging
     if (w == "fin_scale32") return fin_item_on(c) && c->fin_scale32 ? 1 : 0;  // ... with the plaintext scaled by 32-bit products and -c1 written early (HHE_FIN_SCALE32; t < 2^30 below every data prime)
     if (w == "mod_switch_launches") return c->mod_switch_launches;  // kernel launches of hhe_mod_switch: one per call of up to one chunk
     if (w == "noise_form") return (u64)c->noise_form;  // the last hhe_noise_budget launch: limb count of its register form, 0 = the LDS form

@@ -203,7 +203,14 @@ struct hhe_ctx {
     u32 *d_slot_inv = nullptr;     // [N] inverse of slot_map (FinArgs::slot_inv)
     GrowBuf<u64> fin_dev;          // [B] per item: pointer to its keystream (fused) or its slot of ks_tab as u32 (unfused) | [B][128] the items' words,
                                    // zero padded | [B][N] the intermediate of the transform mod t (unfused: the plaintexts)
-    HostStage fin_host;            // [KsCache::MAX_SNAPSHOTS] flags of the key comparison, read back | the first two parts of fin_dev as they are uploaded
+    HostStage fin_host;            // [KsCache::MAX_SNAPSHOTS] flags of the key comparison, read back | the first two parts of fin_dev as they are uploaded;
+                                   // where it is page-locked the item kernel reads the words here and they are not uploaded
+    std::vector<unsigned char> fin_tab_shadow;  // what the table part of fin_dev holds: the bytes of the last upload into it (fin_tab_upload, hhe_api.cpp), which
+                                   // skips an upload of the same bytes; empty = unknown: fin_dev grew (fin_reserve) or a call of another item count, whose
+                                   // words and intermediate lie where this table was, has begun (fin_tab_items)
+    size_t fin_tab_items = 0;      // the item count of the call the shadow belongs to: the parts of fin_dev behind the table start at fin_tab_words(B)
+    u64 fin_tab_uploads = 0;       // uploads into the table part that were enqueued (hhe_ctx_query("fin_tab_uploads")), and
+    u64 fin_word_uploads = 0;      // uploads of the words into fin_dev (hhe_ctx_query("fin_word_uploads")): none where the item kernel reads the staging
     void *ev_cmp = nullptr;        // recorded behind the read-back of the flags
     size_t last_unique = 0;        // distinct (nonce, counter) pairs of the last transciphering call: U, or B when it ran per item (a call in groups: summed over its groups)
     size_t last_evaluated = 0;     // keystream chains the last call ran (= last_unique unless kept keystreams were found), and
