@@ -10,7 +10,8 @@
 //   MatrixCache  maps every public matrix (+ bias, + method) a packed affine layer is called with to one device handle (hhe_matrix), by
 //                the same kind of content hash: a CSP that applies the same layer per request uploads it once.
 //   DeviceArena  grow-only device buffers reused across calls instead of a hipMalloc / hipFree pair per call.
-//   AdapterCore  the hhe_ctx, its cache, its arena, the resident encrypted PASTA key and the call bodies.
+//   AdapterCore  the hhe_ctx, its cache, its arena, the resident encrypted PASTA key and the call bodies; and, per level of its
+//                chain that is evaluated at, one further core (level()) whose key sets are derived on the device from this one's.
 //
 // Ownership and threading, stated once:
 //   * A key set is a std::shared_ptr (KeySet).  The cache holds one reference, every cipher object holds one for each key member
@@ -29,6 +30,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <iterator>
 #include <list>
 #include <map>
 #include <memory>
@@ -238,8 +240,8 @@ class AdapterCore {
 public:
     // q: coeff_modulus incl. the special prime; max_sets / max_matrices: capacities of the key-set and the matrix cache
     AdapterCore(int logn, const std::vector<uint64_t> &q, uint64_t t, int device = 0, size_t max_sets = 16, size_t max_matrices = 8)
-        : n_((size_t)1 << logn), L_(q.size() - 1), t_(t), h_(create(logn, q, t, device), hhe_ctx_destroy), keys_(h_.get(), max_sets),
-          empty_(keys_.new_set()), mats_(h_.get(), max_matrices) {}
+        : n_((size_t)1 << logn), L_(q.size() - 1), t_(t), max_sets_(max_sets), max_matrices_(max_matrices),
+          h_(create(logn, q, t, device), hhe_ctx_destroy), keys_(h_.get(), max_sets), empty_(keys_.new_set()), mats_(h_.get(), max_matrices) {}
 
     size_t poly_modulus_degree() const { return n_; }
     size_t data_limbs() const { return L_; }
@@ -321,9 +323,10 @@ public:
         check(hhe_relinearize_ks(h(), or_empty(rk).get(), o3.u64(), a.u64(), 1));
         download(a.u64(), 1, 2, dst);
     }
-    template <class Sink> void relinearize(const uint64_t *e3, const RelinWords &rk, Sink dst)  // CSP.cpp:306
+    // RK: the RelinWords of the object the call names, or a held KeySet
+    template <class RK, class Sink> void relinearize(const uint64_t *e3, const RK &rk, Sink dst)  // CSP.cpp:306
     {
-        const KeySet r = named(keys_.relin(rk), "relin_keys is not valid for encryption parameters");
+        const KeySet r = named(set(rk), "relin_keys is not valid for encryption parameters");
         DevBuf a3(ct_words(3) * 8), o(ct_words() * 8);
         upload(a3.u64(), e3, 3);
         check(hhe_relinearize_ks(h(), r.get(), a3.u64(), o.u64(), 1));
@@ -388,9 +391,9 @@ public:
 
     // sealhelper::encrypted_vec_sum (sealhelper.cpp:385-391), literally:
     // destination = in; for i = -1 .. -(vec_size-1): destination += rotate_rows(in, i, gk)
-    template <class Sink> void vec_sum(const uint64_t *in_words, const GaloisWords &gk, size_t vec_size, Sink dst)
+    template <class GK, class Sink> void vec_sum(const uint64_t *in_words, const GK &gk, size_t vec_size, Sink dst)
     {
-        const KeySet g = named(keys_.galois(gk), "Galois key not present");
+        const KeySet g = named(set(gk), "Galois key not present");
         const size_t w = ct_words();
         DevBuf in(w * 8), acc(w * 8), rot(w * 8);
         upload(in.u64(), in_words);
@@ -532,8 +535,9 @@ public:
         return out;
     }
 
-    // ---- levels (SEALZpCipher::get_cipher_size(ct, mod_switch, levels_from_last), SEAL_Cipher.cpp:363-378).  A ciphertext below the
-    // data level is a finished result: it can be switched further, measured and decrypted; every evaluation call refuses it.
+    // ---- levels (SEALZpCipher::get_cipher_size(ct, mod_switch, levels_from_last), SEAL_Cipher.cpp:363-378).  On THIS core a ciphertext
+    // below the data level can be switched further, measured and decrypted, and every evaluation call refuses it; it is evaluated on the
+    // core of its level (level() below), whose data level it is.
     size_t limbs_or_data(size_t limbs) const
     {
         if (limbs > L_) throw std::invalid_argument("encrypted is not valid for encryption parameters");
@@ -569,7 +573,61 @@ public:
         return need;
     }
 
+    // ---- evaluation at a level.  The core of the level with `limbs` data primes of this chain (hhe_ctx_create_level): made on first
+    // use and kept, one per (this core, limbs), with its own context, arena and caches; every call body above runs on it unchanged, on
+    // [.][limbs][N].  It holds no keys of its own: the sets its calls name are derived() from this core's.
+    std::shared_ptr<AdapterCore> level(size_t limbs)
+    {
+        if (limbs < 1 || limbs > L_) throw std::invalid_argument("level: the chain has no level with that many data primes");
+        std::lock_guard<std::mutex> lk(levels_mu_);
+        std::shared_ptr<AdapterCore> &slot = levels_[limbs];
+        if (!slot) slot.reset(new AdapterCore(*this, limbs));
+        return slot;
+    }
+    // On a level core: its set that is the projection of `parent_set`, a set of the core higher up the chain -- derived on the device on
+    // first use (hhe_keyset_derive_level: nothing is uploaded twice), kept per (parent set, this level), dropped once the parent set is
+    // gone (its last holder let go: the parent's cache evicted it and no cipher object holds it).  A null set stays null.
+    KeySet derived(const KeySet &parent_set)
+    {
+        if (!parent_set) return nullptr;
+        std::lock_guard<std::mutex> lk(derived_mu_);
+        for (auto it = derived_.begin(); it != derived_.end();) it = it->second.first.expired() ? derived_.erase(it) : std::next(it);
+        auto it = derived_.find(parent_set.get());
+        if (it != derived_.end()) return it->second.second;
+        KeySet ks = keys_.new_set();
+        check(hhe_keyset_derive_level(ks.get(), parent_set.get()));
+        ++derivations;
+        derived_[parent_set.get()] = std::make_pair(std::weak_ptr<hhe_keyset>(parent_set), ks);
+        return ks;
+    }
+    uint64_t derivations = 0;  // instrumentation: how many sets were derived (a repeated parent set is not)
+    size_t derived_resident()
+    {
+        std::lock_guard<std::mutex> lk(derived_mu_);
+        return derived_.size();
+    }
+    // rows {0..limbs-1, K-1} of a key-level object [polys][K][N] of this core: the object of that level (sk: polys 1, pk: polys 2)
+    std::vector<uint64_t> level_rows(const uint64_t *words, size_t polys, size_t limbs) const
+    {
+        const size_t K = key_limbs();
+        std::vector<uint64_t> out(polys * (limbs + 1) * n_);
+        for (size_t p = 0; p < polys; p++)
+            for (size_t j = 0; j <= limbs; j++)
+                std::copy(words + (p * K + (j == limbs ? K - 1 : j)) * n_, words + (p * K + (j == limbs ? K - 1 : j) + 1) * n_,
+                          out.begin() + (p * (limbs + 1) + j) * n_);
+        return out;
+    }
+
 private:
+    AdapterCore(const AdapterCore &parent, size_t limbs)
+        : n_(parent.n_), L_(limbs), t_(parent.t_), max_sets_(parent.max_sets_), max_matrices_(parent.max_matrices_),
+          h_(create_level(parent.h(), limbs), hhe_ctx_destroy), keys_(h_.get(), max_sets_), empty_(keys_.new_set()), mats_(h_.get(), max_matrices_) {}
+    static hhe_ctx *create_level(const hhe_ctx *parent, size_t limbs)
+    {
+        hhe_ctx *h = nullptr;
+        check(hhe_ctx_create_level(parent, (int)limbs, &h));
+        return h;
+    }
     static hhe_ctx *create(int logn, const std::vector<uint64_t> &q, uint64_t t, int device)
     {
         hhe_ctx *h = nullptr;
@@ -584,6 +642,7 @@ private:
     }
     const KeySet &set(const KeySet &held) { return held; }
     KeySet set(const GaloisWords &g) { return keys_.galois(g); }
+    KeySet set(const RelinWords &r) { return keys_.relin(r); }
     const KeySet &or_empty(const KeySet &ks) const { return ks ? ks : empty_; }
     static const KeySet &named(const KeySet &ks, const char *what_if_empty)
     {
@@ -607,6 +666,7 @@ private:
     }
     size_t n_, L_;
     uint64_t t_;
+    size_t max_sets_, max_matrices_;
     std::unique_ptr<hhe_ctx, void (*)(hhe_ctx *)> h_;  // declared before the key sets: destroyed after every set the core holds
     KeySetCache keys_;
     KeySet empty_;   // what a cipher object built without some key runs with; nothing can put a key into it
@@ -614,6 +674,12 @@ private:
     DeviceArena arena_;
     ContentHash key_hash_;
     bool key_resident_ = false;
+    // on a level core: parent set -> (the parent set, watched; its projection on this level).  Declared after the context: every set dies before it
+    std::mutex derived_mu_;
+    std::map<const hhe_keyset *, std::pair<std::weak_ptr<hhe_keyset>, KeySet>> derived_;
+    // the cores of this chain's levels, by data primes; independent contexts, released with this core unless a level object still holds one
+    std::mutex levels_mu_;
+    std::map<size_t, std::shared_ptr<AdapterCore>> levels_;
 };
 
 }  // namespace hhe

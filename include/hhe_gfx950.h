@@ -330,7 +330,9 @@ int hhe_pasta3_prepare_tables(hhe_ctx *c, const uint64_t *nonces_hptr, const uin
 /* Decryptor::decrypt + BatchEncoder::decode (seal/decryptor.h:70, seal/batchencoder.h:282) as used by
  * sealhelper::decrypting / Analyst::decrypt_result (src/util/sealhelper.cpp:252-266): B size-2 data-level
  * ciphertexts [B][2][L][N] -> slot values [B][N] (unsigned, < t; the signed view of decode_int64 is v > t/2 ? v - t : v).
- * sk_hptr: the secret key polynomial at the key level, NTT form [K][N] (SecretKey::data().data()). */
+ * sk_hptr: the secret key polynomial at the key level, NTT form [K][N] (SecretKey::data().data()).
+ * On a level context (hhe_ctx_create_level, l data primes) the key is [l+1][N]: rows {0..l-1, K-1} of the parent's
+ * (api.py: level_rows(sk, l)). */
 int hhe_decrypt(hhe_ctx *c, const uint64_t *sk_hptr, const uint64_t *ct_dptr, size_t B, uint64_t *vals_dptr);
 /* hhe_decrypt for ciphertexts [B][2][limbs][N]; sk_hptr stays [K][N], its first `limbs` rows are used
  * (Decryptor::decrypt on a ciphertext whose parms_id names a lower level of the modulus switching chain, seal/decryptor.h:70;
@@ -350,8 +352,9 @@ int hhe_decrypt_level(hhe_ctx *c, const uint64_t *sk_hptr, const uint64_t *ct_dp
 int hhe_noise_budget(hhe_ctx *c, const uint64_t *sk_hptr, const uint64_t *ct_dptr, int size, int limbs, size_t B, int32_t *budget_hptr,
                      uint32_t *norm_bits_hptr);
 
-/* ---- levels: modulus switching of finished results.  Evaluation (add, multiply, rotate, key switch, transciphering, affine
- *      layers, FC rows) stays at the data level; a lower-level ciphertext can be switched further, saved, loaded and decrypted. ---- */
+/* ---- levels: modulus switching.  On ONE context evaluation (add, multiply, rotate, key switch, transciphering, affine layers, FC
+ *      rows) is at its data level; a lower-level ciphertext can be switched further, saved, loaded and decrypted there, and is
+ *      evaluated on the context of its level (hhe_ctx_create_level below). ---- */
 /* Evaluator::mod_switch_to_inplace (seal/evaluator.h:426) on B coefficient-form ciphertexts:
  * ct [B][size][limbs_in][N] under q_0..q_{limbs_in-1} -> out [B][size][limbs_out][N], dense.
  * Every dropped prime q_m rounds on its own, floor((x + floor(q_m/2)) / q_m), as the chain of mod_switch_to_next does.  size is 2 or
@@ -359,6 +362,27 @@ int hhe_noise_budget(hhe_ctx *c, const uint64_t *sk_hptr, const uint64_t *ct_dpt
  * with out untouched (SEAL throws std::invalid_argument on a switch to a higher level).  One kernel launch per chunk of 2^30
  * coefficients, i.e. one per call for any batch a service sends (hhe_ctx_query("mod_switch_launches") counts them).  Synchronous. */
 int hhe_mod_switch(hhe_ctx *c, const uint64_t *ct_dptr, int size, size_t B, int limbs_in, int limbs_out, uint64_t *out_dptr);
+
+/* ---- evaluation below the data level.  SEAL's level with l data primes is a BFV context over {q_0 .. q_{l-1}, q_sp}: a level is
+ *      a context, and every entry point of this header works at it, unchanged, on [.][l][N]. ---- */
+/* the context of the level with `limbs` data primes of c's chain: q_0..q_{limbs-1} and c's special prime, same N, t, device;
+ * 1 <= limbs <= L (limbs == L: a second context of the same chain).  An independent context: own lock, workspaces, stream
+ * (the default stream until hhe_ctx_set_stream), caches, knobs read from the environment as hhe_ctx_create reads them.
+ * Ciphertexts [B][size][limbs][N] written by hhe_mod_switch on c are its data-level ciphertexts, word for word.  Its BEHZ base is a
+ * prefix of c's with the same m_sk and gamma.  Destroyed on its own with hhe_ctx_destroy, before or after c. */
+int hhe_ctx_create_level(const hhe_ctx *c, int limbs, hhe_ctx **out);
+/* dst (a set of a level context) becomes the image of src (a set of a context higher up the same chain): every key src holds,
+ * RelinKeys::key(2) and each Galois element, projected to digits I < l and limbs {0..l-1, special}; keys dst held before are gone.
+ * Allowed when dst's and src's contexts have the same logn, t and device, equal special primes, and dst's data primes are a prefix of
+ * src's (l_dst <= l_src: a level derives from a higher level, equal chains copy); otherwise, and for dst == src, HHE_ERR_INVALID with
+ * dst exactly as it was.  All-or-nothing: the new buffers are complete before anything in dst is replaced.  A derived key enters the
+ * set as an uploaded one does (a new serial, tables derived from replaced keys dropped, keystreams kept under the old content gone);
+ * Shoup quotients and FC correction tables of the level's keys are built on first use.  One kernel launch per key
+ * (hhe_ctx_query(dst's context, "key_proj_launches") counts them); runs on the stream dst's context has at the call and waits; src's
+ * keys are complete by the contract of hhe_ctx_set_stream.  Locks BOTH contexts, the one with more data limbs first (equal: the lower
+ * address first): concurrent derivations in any direction do not deadlock.  hhe_keyset_get_relin / _get_galois on dst return the
+ * projected words [l][2][l+1][N]. */
+int hhe_keyset_derive_level(hhe_keyset *dst, const hhe_keyset *src);
 
 /* ---- key generation and encryption on the device, from a seed.
  *      THE SEED IS THE ONLY ENTROPY.  seed_hptr is 32 bytes on the host; every random word is SHAKE128 of the seed and a position
@@ -398,7 +422,8 @@ int hhe_keyset_get_galois(const hhe_keyset *ks, uint32_t galois_elt, uint64_t *k
  * src/util/sealhelper.cpp:123-142) for B plaintexts plain_dptr [B][N] (or [1][N] if plain_bcast; coefficients mod t, from hhe_encode):
  * item b draws u (ternary), e_0, e_1 (noise) at index b; c_k = INTT(NTT(u) pk_k) + e_k on the data-level primes, then the scaled
  * plaintext is added as hhe_add_plain adds it.  out_dptr [B][2][L][N].  (SEAL encrypts at the key level and drops the special
- * prime; the noise is the same to a fraction of a bit.) */
+ * prime; the noise is the same to a fraction of a bit.)  On a level context (hhe_ctx_create_level, l data primes) pk is
+ * [2][l+1][N]: rows {0..l-1, K-1} of both polynomials of the parent's (api.py: level_rows(pk, l)). */
 int hhe_encrypt(hhe_ctx *c, const uint64_t *pk_dptr, const uint64_t *plain_dptr, int plain_bcast, const uint8_t *seed_hptr, size_t B,
                 uint64_t *out_dptr);
 

@@ -34,7 +34,8 @@ struct ZpCipherParams {  // src/pasta/Cipher.h:14-18
 constexpr ZpCipherParams PASTA_PARAMS = {256, 128, 128};  // src/pasta/pasta_3_plain.h:15
 
 // seal::Ciphertext stand-in: data() words, [size][L][N], data level, non-NTT form.  limbs: coeff_modulus_size() of a ciphertext that
-// get_cipher_size switched down ([size][limbs][N]); 0 = the data level, which is all that evaluation accepts
+// get_cipher_size switched down ([size][limbs][N]); 0 = the data level, which is all that a cipher object's evaluation accepts -- a
+// switched ciphertext is evaluated by the object of its level (SEALZpCipher::level)
 struct Ciphertext {
     std::vector<uint64_t> words;
     size_t size = 0;
@@ -93,7 +94,106 @@ inline std::vector<int> noise_budgets(HheContext &ctx, const std::vector<const C
     }
     return ctx.noise_budget(items, he_sk.words.data());
 }
+// ... and at a level: `core` is the core of that level (hhe::AdapterCore::level), whose data level the ciphertext must be at
+inline const uint64_t *level_words(const hhe::AdapterCore &core, size_t chain_limbs, const Ciphertext &ct, size_t size = 2)
+{
+    const size_t l = core.data_limbs();
+    if (ct.words.size() != core.ct_words(size) || !(ct.limbs == l || (ct.limbs == 0 && l == chain_limbs)))
+        throw std::invalid_argument("encrypted is not at the level of this object");
+    return ct.words.data();
+}
+inline auto into_level(const hhe::AdapterCore &core, Ciphertext &ct, size_t size = 2)
+{
+    return [&core, &ct, size](size_t) { ct.words.resize(core.ct_words(size)); ct.size = size; ct.limbs = core.data_limbs(); return ct.words.data(); };
+}
 }  // namespace detail
+
+// What SEALZpCipher::level(levels_from_last) returns: the evaluation members of a cipher object, bound to one level of the modulus
+// switching chain.  Every member takes and produces ciphertexts of exactly that level (Ciphertext::limbs == limbs()) and refuses any
+// other with std::invalid_argument.  The object keeps no keys of its own: it names the key sets of the cipher object it came from,
+// and the core derives their projections on the device on first use (hhe::AdapterCore::derived).  Key objects a call names
+// (flatten, relinearize_inplace, encrypted_vec_sum) are the parties' ordinary, top-level objects.
+class SEALZpLevel {
+    // boundary conversions at this level (before their users: `out` has a deduced return type)
+    const uint64_t *in(const Ciphertext &ct, size_t size = 2) const { return detail::level_words(*core, context->data_limbs(), ct, size); }
+    auto out(Ciphertext &ct, size_t size = 2) const { return detail::into_level(*core, ct, size); }
+    std::vector<const uint64_t *> pointers(const std::vector<Ciphertext> &cts) const
+    {
+        std::vector<const uint64_t *> p;
+        for (auto &ct : cts) p.push_back(in(ct));
+        return p;
+    }
+
+public:
+    typedef std::vector<uint64_t> vector;
+    typedef std::vector<std::vector<uint64_t>> matrix;
+    SEALZpLevel(std::shared_ptr<HheContext> con, size_t limbs, const SecretKey &sk, hhe::KeySet rk, hhe::KeySet gk, bool use_bsgs, size_t n1, size_t n2)
+        : context(std::move(con)), core(context->level(limbs)), use_bsgs(use_bsgs), bsgs_n1(n1), bsgs_n2(n2), rk_top(std::move(rk)), gk_top(std::move(gk))
+    {
+        if (sk.words.size() == context->key_limbs() * context->poly_modulus_degree()) sk_level = context->level_rows(sk.words.data(), 1, limbs);
+    }
+    size_t limbs() const { return core->data_limbs(); }
+
+    void mask(Ciphertext &cipher, std::vector<uint64_t> &mask_vec) { core->mask(in(cipher), mask_vec.data(), mask_vec.size(), out(cipher)); }
+    void flatten(std::vector<Ciphertext> &in_cts, Ciphertext &o, const GaloisKeys &galois_keys)
+    {
+        core->flatten(pointers(in_cts), core->derived(context->keys().galois(detail::words(galois_keys))), out(o));
+    }
+    void flatten(std::vector<Ciphertext> &in_cts, Ciphertext &o) { core->flatten(pointers(in_cts), core->derived(gk_top), out(o)); }
+    void packed_enc_mul(const Ciphertext &e1, const Ciphertext &e2, Ciphertext &destination) { core->multiply(in(e1), in(e2), out(destination, 3)); }
+    void packed_enc_add(const Ciphertext &e1, const Ciphertext &e2, Ciphertext &destination)
+    {
+        if (e1.size != e2.size) throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
+        core->add(in(e1, e1.size), in(e2, e1.size), e1.size, out(destination, e1.size));
+    }
+    void packed_square(Ciphertext &vo, const Ciphertext &vi) { core->square_relinearize(in(vi), core->derived(rk_top), out(vo)); }
+    void packed_matMul(Ciphertext &vo, const matrix &M, const Ciphertext &vi)
+    {
+        core->packed_affine(M, nullptr, use_bsgs, bsgs_n1, bsgs_n2, in(vi), core->derived(gk_top), out(vo));
+    }
+    void packed_affine(Ciphertext &vo, const matrix &M, const Ciphertext &vi, const vector &b)
+    {
+        core->packed_affine(M, &b, use_bsgs, bsgs_n1, bsgs_n2, in(vi), core->derived(gk_top), out(vo));
+    }
+    // Evaluator::relinearize_inplace(encrypted, relin_keys) and sealhelper::encrypted_vec_sum with the key object the call names
+    void relinearize_inplace(Ciphertext &encrypted, const RelinKeys &relin_keys)
+    {
+        core->relinearize(in(encrypted, 3), core->derived(context->keys().relin(detail::words(relin_keys))), out(encrypted));
+    }
+    void encrypted_vec_sum(const Ciphertext &encrypted_inp, Ciphertext &destination, const GaloisKeys &gal_keys, size_t vec_size)
+    {
+        core->vec_sum(in(encrypted_inp), core->derived(context->keys().galois(detail::words(gal_keys))), vec_size, out(destination));
+    }
+    // SEALZpCipher::print_noise / sealhelper::decrypting on the level's context, with the rows of the secret key that level has
+    int print_noise(Ciphertext &ciph)
+    {
+        if (sk_level.empty()) throw std::invalid_argument("invariant_noise_budget: no secret key");
+        if (ciph.size < 2) throw std::invalid_argument("encrypted is not at the level of this object");
+        const int noise = core->noise_budget({in(ciph, ciph.size)}, ciph.size, 0, sk_level.data())[0];
+        std::cout << "noise budget: " << noise << std::endl;
+        return noise;
+    }
+    std::vector<int64_t> decrypting(const Ciphertext &enc_input, size_t size)
+    {
+        const size_t n = context->poly_modulus_degree();
+        if (sk_level.empty() || size > n) throw std::invalid_argument("decrypting: ciphertext / secret key do not match the context");
+        std::vector<uint64_t> u(n);
+        core->decrypt(sk_level.data(), in(enc_input), u.data());
+        const uint64_t t = context->plain_modulus(), half = (t + 1) >> 1;
+        std::vector<int64_t> o(size);
+        for (size_t i = 0; i < size; i++) o[i] = u[i] > half ? (int64_t)u[i] - (int64_t)t : (int64_t)u[i];
+        return o;
+    }
+    hhe::AdapterCore &level_core() { return *core; }  // instrumentation (derivations, matrices().uploads())
+
+private:
+    std::shared_ptr<HheContext> context;        // the chain's core: its key-set cache holds the sets the level's are derived from
+    std::shared_ptr<hhe::AdapterCore> core;     // the level's
+    bool use_bsgs;
+    size_t bsgs_n1, bsgs_n2;
+    std::vector<uint64_t> sk_level;             // [limbs + 1][N]
+    hhe::KeySet rk_top, gk_top;                 // the cipher object's sets, kept alive; declared after the contexts
+};
 
 class SEALZpCipher {
 public:
@@ -134,6 +234,14 @@ public:
             });
         }
         return context->saved_size(ct.size, ct.limbs);
+    }
+    // Evaluation at a level (no reference counterpart: the reference only measures and ships switched ciphertexts).  The object bound to
+    // the level `levels_from_last` steps above last_context_data(), the numbering of get_cipher_size: limbs = 1 + levels_from_last.  It
+    // evaluates what get_cipher_size(ct, true, levels_from_last) produced, with this object's keys (their projections, derived on the
+    // device) and its BSGS settings as they are now.  This object itself keeps refusing lower-level ciphertexts.
+    SEALZpLevel level(size_t levels_from_last)
+    {
+        return SEALZpLevel(context, context->level_limbs(levels_from_last), he_sk, rk_set, gk_set, use_bsgs, bsgs_n1, bsgs_n2);
     }
     // SEALZpCipher::print_noise (SEAL_Cipher.cpp:71-99): Decryptor::invariant_noise_budget with this object's secret key, on the device
     // (one batched call for the vector), the reference's lines on std::cout and its return values.  An empty vector, where the

@@ -173,6 +173,104 @@ private:
 }  // namespace gfx950
 
 // ---------------------------------------------------------------------------------------------------------------------
+// What SEALZpCipher::level(levels_from_last) returns: the evaluation members of a cipher object bound to one level of the modulus
+// switching chain, named by its parms_id.  Every member takes and produces coefficient-form ciphertexts whose parms_id is that
+// level's and refuses any other with std::invalid_argument.  The object keeps no keys of its own: the device core of the level
+// (hhe::AdapterCore::level) derives, on the device and on first use, the projections of the key sets of the cipher object it came
+// from and of the top-level key objects a call names.
+class SEALZpLevel {
+    const std::uint64_t *in(const seal::Ciphertext &ct, std::size_t size = 2) const
+    {
+        if (ct.is_ntt_form() || ct.parms_id() != id || ct.poly_modulus_degree() != core->poly_modulus_degree() ||
+            ct.coeff_modulus_size() != core->data_limbs() || ct.size() != size)
+            throw std::invalid_argument("encrypted is not at the level of this object");
+        return ct.data();
+    }
+    auto out(seal::Ciphertext &ct, std::size_t size = 2) const { return gfx950::DeviceContext::into_level(*context, ct, id, size); }
+    std::vector<const std::uint64_t *> pointers(const std::vector<seal::Ciphertext> &cts) const
+    {
+        std::vector<const std::uint64_t *> p;
+        for (const auto &ct : cts) p.push_back(in(ct));
+        return p;
+    }
+
+public:
+    typedef std::vector<uint64_t> vector;
+    typedef std::vector<std::vector<uint64_t>> matrix;
+    SEALZpLevel(std::shared_ptr<seal::SEALContext> con, std::shared_ptr<gfx950::DeviceContext> dev, seal::parms_id_type level_id, std::size_t limbs,
+                const seal::SecretKey &sk, hhe::KeySet rk, hhe::KeySet gk, bool use_bsgs, size_t n1, size_t n2)
+        : context(std::move(con)), device(std::move(dev)), core(device->level(limbs)), id(level_id), use_bsgs(use_bsgs), bsgs_n1(n1), bsgs_n2(n2),
+          rk_top(std::move(rk)), gk_top(std::move(gk))
+    {
+        if (sk.data().coeff_count() == device->key_limbs() * device->poly_modulus_degree()) sk_level = device->level_rows(sk.data().data(), 1, limbs);
+    }
+    const seal::parms_id_type &parms_id() const { return id; }
+
+    void mask(seal::Ciphertext &cipher, std::vector<uint64_t> &mask_vec) { core->mask(in(cipher), mask_vec.data(), mask_vec.size(), out(cipher)); }
+    void flatten(std::vector<seal::Ciphertext> &in_cts, seal::Ciphertext &o, const seal::GaloisKeys &galois_keys)
+    {
+        core->flatten(pointers(in_cts), core->derived(device->galois_set(galois_keys)), out(o));
+    }
+    void packed_matMul(seal::Ciphertext &vo, const matrix &M, const seal::Ciphertext &vi)
+    {
+        core->packed_affine(M, nullptr, use_bsgs, bsgs_n1, bsgs_n2, in(vi), core->derived(gk_top), out(vo));
+    }
+    void packed_affine(seal::Ciphertext &vo, const matrix &M, const seal::Ciphertext &vi, const vector &b)
+    {
+        core->packed_affine(M, &b, use_bsgs, bsgs_n1, bsgs_n2, in(vi), core->derived(gk_top), out(vo));
+    }
+    void packed_square(seal::Ciphertext &vo, const seal::Ciphertext &vi) { core->square_relinearize(in(vi), core->derived(rk_top), out(vo)); }
+    void packed_enc_mul(const seal::Ciphertext &e1, const seal::Ciphertext &e2, seal::Ciphertext &destination)
+    {
+        core->multiply(in(e1), in(e2), out(destination, 3));
+    }
+    void packed_enc_add(const seal::Ciphertext &e1, const seal::Ciphertext &e2, seal::Ciphertext &destination)
+    {
+        if (e1.size() != e2.size()) throw std::invalid_argument("encrypted1 and encrypted2 parameter mismatch");
+        core->add(in(e1, e1.size()), in(e2, e1.size()), e1.size(), out(destination, e1.size()));
+    }
+    // Evaluator::relinearize_inplace(encrypted, relin_keys) and sealhelper::encrypted_vec_sum with the key object the call names
+    void relinearize_inplace(seal::Ciphertext &encrypted, const seal::RelinKeys &relin_keys)
+    {
+        core->relinearize(in(encrypted, 3), core->derived(device->relin_set(relin_keys)), out(encrypted));
+    }
+    void encrypted_vec_sum(const seal::Ciphertext &encrypted_inp, seal::Ciphertext &destination, const seal::GaloisKeys &gal_keys, size_t vec_size)
+    {
+        core->vec_sum(in(encrypted_inp), core->derived(device->galois_set(gal_keys)), vec_size, out(destination));
+    }
+    // SEALZpCipher::print_noise / sealhelper::decrypting on the level's device context, with the rows of the secret key that level has
+    int print_noise(seal::Ciphertext &ciph)
+    {
+        if (sk_level.empty()) throw std::invalid_argument("invariant_noise_budget: no secret key");
+        if (ciph.size() < 2) throw std::invalid_argument("encrypted is not at the level of this object");
+        const int noise = core->noise_budget({in(ciph, ciph.size())}, ciph.size(), 0, sk_level.data())[0];
+        std::cout << "noise budget: " << noise << std::endl;
+        return noise;
+    }
+    std::vector<int64_t> decrypting(const seal::Ciphertext &enc_input, size_t size)
+    {
+        const std::size_t n = core->poly_modulus_degree();
+        if (sk_level.empty() || size > n) throw std::invalid_argument("decrypting: ciphertext / secret key do not match the context");
+        std::vector<std::uint64_t> u(n);
+        core->decrypt(sk_level.data(), in(enc_input), u.data());
+        const std::uint64_t t = core->plain_modulus(), half = (t + 1) >> 1;
+        std::vector<int64_t> o(size);
+        for (size_t i = 0; i < size; i++) o[i] = u[i] > half ? (int64_t)u[i] - (int64_t)t : (int64_t)u[i];
+        return o;
+    }
+
+private:
+    std::shared_ptr<seal::SEALContext> context;
+    std::shared_ptr<gfx950::DeviceContext> device;  // the chain's core: its key-set cache holds the sets the level's are derived from
+    std::shared_ptr<hhe::AdapterCore> core;         // the level's
+    seal::parms_id_type id;
+    bool use_bsgs;
+    size_t bsgs_n1, bsgs_n2;
+    std::vector<std::uint64_t> sk_level;            // [limbs + 1][N]
+    hhe::KeySet rk_top, gk_top;                     // the cipher object's sets, kept alive; declared after the contexts
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
 // pasta::SEALZpCipher (src/pasta/SEAL_Cipher.h:11-129).  The members the CSP path uses run on the device; the SEAL objects
 // the reference keeps as members are kept too (encrypt_key, decrypt_result and the analyst/user sides use them unchanged).
 class SEALZpCipher {
@@ -256,6 +354,17 @@ public:
         return device->saved_size(ct.size(), ct.coeff_modulus_size());
     }
 
+    // Evaluation at a level (no reference counterpart): the object bound to the level `levels_from_last` steps above
+    // last_context_data(), the numbering of get_cipher_size, found by the same walk.  It evaluates what
+    // get_cipher_size(ct, true, levels_from_last) produced, with this object's keys (their projections, derived on the device) and its
+    // BSGS settings as they are now.  This object itself keeps refusing lower-level ciphertexts.
+    SEALZpLevel level(size_t levels_from_last)
+    {
+        const std::size_t limbs = device->level_limbs(levels_from_last);
+        auto c = context->last_context_data();
+        for (uint64_t _ = 0; _ < levels_from_last; _++) c = c->prev_context_data();
+        return SEALZpLevel(context, device, c->parms_id(), limbs, he_sk, rk_set, gk_set, use_bsgs, bsgs_n1, bsgs_n2);
+    }
     // SEALZpCipher::print_noise (SEAL_Cipher.cpp:71-99): Decryptor::invariant_noise_budget with he_sk, on the device (one batched call for
     // the vector; a ciphertext below the data level at its coeff_modulus_size), the reference's lines on std::cout and its return
     // values.  An empty vector, where the reference reads ciphs[0], and an object without a secret key throw std::invalid_argument

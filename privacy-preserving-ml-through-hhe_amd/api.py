@@ -43,7 +43,7 @@ _SYMBOLS = [
     "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin", "hhe_keyset_generate_galois",
     "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
     "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level",
-    "hhe_noise_budget",
+    "hhe_noise_budget", "hhe_ctx_create_level", "hhe_keyset_derive_level",
     "hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystream_nonce", "hhe_pasta3_plain_crypt_nonce",
     "hhe_pasta3_transcipher_nonce_ks", "hhe_decompose_nonce_ks", "hhe_pasta3_block_randomness_dev", "hhe_pasta3_prepare_tables",
 ]
@@ -58,7 +58,7 @@ _NONCE_SYMBOLS = {"hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystre
 _OPTIONAL = {"hhe_pasta3_clear_keystream_cache", "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin",
              "hhe_keyset_generate_galois", "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
              "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level",
-             "hhe_noise_budget"} | _NONCE_SYMBOLS
+             "hhe_noise_budget", "hhe_ctx_create_level", "hhe_keyset_derive_level"} | _NONCE_SYMBOLS
 
 
 def exported_symbols():
@@ -189,6 +189,14 @@ class KeySet:
         self.ctx._chk(self.ctx.lib.hhe_keyset_get_galois(self.h, C.c_uint32(elt), _ptr(ksk)))
         return ksk
 
+    def derive_from(self, src):
+        """this set (of a level context, Context.at_level) becomes the projection of `src`, a set higher up the same chain: every key
+        src holds, digits I < l and limbs {0..l-1, special}, made on the device; what this set held before is gone"""
+        if not hasattr(self.ctx.lib, "hhe_keyset_derive_level"):
+            raise RuntimeError("this library build does not export hhe_keyset_derive_level")
+        self.ctx._chk(self.ctx.lib.hhe_keyset_derive_level(self.h, src.h))
+        return self
+
     def seal_load_relin_keys(self, blob):
         buf = (C.c_uint8 * len(blob)).from_buffer_copy(bytes(blob))
         used = C.c_size_t(0)
@@ -243,7 +251,23 @@ class Context:
         h = C.c_void_p()
         self._chk(self.lib.hhe_ctx_create(C.c_int(logn), C.c_int(self.K), _ptr(qa), C.c_uint64(t), C.c_int(device), C.byref(h)))
         self.h = h
+        self.device = device
         self.ct_shape = (2, self.L, self.n)
+
+    def at_level(self, limbs):
+        """the context of the level with `limbs` data primes of this chain (hhe_ctx_create_level): q_0..q_{limbs-1} and the special
+        prime.  Independent of this one; what hhe_mod_switch writes at `limbs` are its data-level ciphertexts."""
+        if not hasattr(self.lib, "hhe_ctx_create_level"):
+            raise RuntimeError("this library build does not export hhe_ctx_create_level")
+        h = C.c_void_p()
+        self._chk(self.lib.hhe_ctx_create_level(self.h, C.c_int(limbs), C.byref(h)))
+        X = Context.__new__(Context)
+        X.lib, X.logn, X.n, X.t, X.device = self.lib, self.logn, self.n, self.t, self.device
+        X.q = self.q[:limbs] + [self.q[-1]]
+        X.K, X.L = limbs + 1, limbs
+        X.h = h
+        X.ct_shape = (2, X.L, X.n)
+        return X
 
     def _chk(self, rc):
         if rc != 0:
@@ -557,6 +581,16 @@ class Context:
     def encrypt(self, pk, plain, seed, B, out, bcast=False):
         """pk device [2][K][N]; plain device [B][N] ([1][N] if bcast); out device [B][2][L][N]"""
         self._chk(self.lib.hhe_encrypt(self.h, _ptr(pk), _ptr(plain), C.c_int(int(bcast)), _seed(seed), C.c_size_t(B), _ptr(out)))
+
+
+def level_rows(words, limbs):
+    """rows {0..limbs-1, K-1} of the limb axis of a key-level object [..][K][N] (sk [K][N], pk [2][K][N], a digit of a key-switch
+    key): the object of the level with `limbs` data primes (Context.at_level)"""
+    K = words.shape[-2]
+    assert 1 <= limbs < K
+    if isinstance(words, np.ndarray):
+        return np.ascontiguousarray(words[..., list(range(limbs)) + [K - 1], :])
+    return words[..., list(range(limbs)) + [K - 1], :].contiguous()
 
 
 def bfv_default_coeff_modulus(n, lib=None):

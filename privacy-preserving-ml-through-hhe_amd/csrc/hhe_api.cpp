@@ -845,6 +845,46 @@ extern "C" int hhe_mod_switch(hhe_ctx *c, const uint64_t *ct, int size, size_t B
     if (rt_sync(c->w->stream)) return dev_fail("hhe_mod_switch");
     return HHE_OK;
 }
+// The key sets of a level (hhe_ctx_create_level) from resident sets higher up the chain: the key-switch key of the level with l data
+// primes is digits I < l and limbs {0 .. l-1, special} of the parent's -- digit I carries q_sp s' in limb I only, whatever L is -- so
+// one gather launch per key makes it, on the device.  Every new buffer is complete before anything of dst is replaced.
+extern "C" int hhe_keyset_derive_level(hhe_keyset *dst, const hhe_keyset *src)
+{
+    if (!dst || !src) return fail(HHE_ERR_INVALID, "hhe_keyset_derive_level: null argument");
+    hhe_ctx *cd = dst->ctx, *cs = src->ctx;
+    // both contexts, the one with more data limbs first (equal: by address); L never changes after creation
+    hhe_ctx *first = cs, *second = cd;
+    if (cd->L > cs->L || (cd->L == cs->L && std::less<hhe_ctx *>()(cd, cs))) std::swap(first, second);
+    CtxLock lock1(first), lock2(second == first ? nullptr : second);
+    const int l = cd->L;
+    bool ok = dst != src && cd->logn == cs->logn && cd->t == cs->t && cd->device == cs->device && l <= cs->L && cd->q[l] == cs->q[cs->L];
+    for (int j = 0; ok && j < l; ++j) ok = cd->q[j] == cs->q[j];
+    if (!ok)
+        return fail(HHE_ERR_INVALID, "hhe_keyset_derive_level: dst is not a level of src's chain (same N, t, device and special prime, data primes a prefix)");
+    rt_stream st = cd->lanes[0].stream;
+    u64 *rk = nullptr;
+    std::vector<std::pair<u32, u64 *>> gk;
+    auto drop = [&]() { rt_free(rk); for (auto &kv : gk) rt_free(kv.second); };
+    auto project = [&](const u64 *key) -> u64 * {
+        u64 *out = (u64 *)rt_malloc(cd->ksk_words() * 8);
+        if (!out) return nullptr;
+        k_elt(elt_args(cd, key, nullptr, out, (size_t)l * 2 * cd->K, 0, cd->K, cs->K), ELT_KEYPROJ, st);
+        ++cd->key_proj_launches;
+        return out;
+    };
+    if (src->rk && !(rk = project(src->rk))) { rt_sync(st); drop(); return dev_fail("hhe_keyset_derive_level"); }
+    for (auto &kv : src->gk) {
+        u64 *key = project(kv.second);
+        if (!key) { rt_sync(st); drop(); return dev_fail("hhe_keyset_derive_level"); }
+        gk.emplace_back(kv.first, key);
+    }
+    if (rt_sync(st)) { drop(); return dev_fail("hhe_keyset_derive_level"); }
+    sync_ctx(cd);  // a key of dst may still be read by work in flight on any lane
+    keyset_clear(dst);  // a new serial; the tables derived from the replaced keys go with them
+    dst->rk = rk;
+    for (auto &kv : gk) dst->gk[kv.first] = kv.second;
+    return HHE_OK;
+}
 extern "C" int hhe_add_plain(hhe_ctx *c, const uint64_t *ct, const uint64_t *plain, int bcast, int subtract, uint64_t *out, size_t B)
 {
     HHE_LOCK(c);

@@ -198,7 +198,8 @@ struct NttArgs {
 enum EltOp { ELT_ADD = 0, ELT_SUB = 1, ELT_NEG = 2, ELT_MUL = 3, ELT_MAC = 4, ELT_COPY = 5, ELT_BCAST = 6, ELT_SHOUP = 7,
              ELT_DIFF = 8,    // ELT_DIFF writes no polynomial: out[0] = 1 when a word of a differs from its word of b (out[0] cleared by the caller)
              ELT_ENCZ = 9,    // key generation: c0 = -(a s + e) (+ f new_key) of an encryption of zero under the secret key (elt_encz_body; a kernel of its own)
-             ELT_MODDOWN = 10 };  // modulus switching: a [count][mod_cycle][N] -> out [count][b_cycle][N], b = the context's pair table (mod_down_body; kernels of its own)
+             ELT_MODDOWN = 10,  // modulus switching: a [count][mod_cycle][N] -> out [count][b_cycle][N], b = the context's pair table (mod_down_body; kernels of its own)
+             ELT_KEYPROJ = 11 };  // a key-switch key of a level from one higher up its chain (key_proj_body; a kernel of its own)
 
 struct EltArgs {  // element-wise kernels over [count][N] polys, modulus = mod_base + p % mod_cycle
     const u64 *a, *b;
@@ -218,6 +219,12 @@ struct EltArgs {  // element-wise kernels over [count][N] polys, modulus = mod_b
 constexpr int MOD_DOWN_REGS = 8;
 HD size_t mod_down_pair(int m, int j) { return (size_t)3 * ((size_t)m * (m - 1) / 2 + j); }
 inline size_t mod_down_table_words(int L) { return mod_down_pair(L, 0) + 3; }  // never empty (L = 1 has no pair)
+
+// ELT_KEYPROJ (hhe_keyset_derive_level): the key-switch key of the level with l data primes is digits I < l and limbs
+// {0 .. l-1, special} of a key higher up the chain.  a = the source key [L_src][2][K_src][N], b_cycle = K_src; out = [l][2][l+1][N],
+// mod_cycle = l + 1, count = l * 2 * (l + 1) output polynomials.  Output polynomial p = (I * 2 + k) * (l + 1) + J is source polynomial
+// (I * 2 + k) * K_src + (J == l ? K_src - 1 : J).  One lane moves 16 bytes: count << (logn - 1) lanes do the work; the launch
+// entry's count << logn covers them, the rest return at the bound.
 
 struct CopyItemsArgs {  // dst item (s * dst_stride + dst_off) <- src item (s * src_stride + src_off), `words` words each, s < count
     const u64 *src;

@@ -409,6 +409,27 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
     return HHE_OK;
 }
 
+// SEAL's level with `limbs` data primes is the BFV context over {q_0 .. q_{limbs-1}, q_sp}: the same derivation on the shorter list.
+// get_primes(2N, 61, limbs + 2) is a prefix of the parent's draw, so the level's BEHZ base is a prefix of the parent's with the same
+// m_sk and gamma.  Nothing is shared with the parent: the level has its own tables, lock, workspaces, stream and caches.
+extern "C" int hhe_ctx_create_level(const hhe_ctx *c, int limbs, hhe_ctx **out)
+{
+    std::vector<u64> q;
+    int logn, device;
+    u64 t;
+    {
+        HHE_LOCK(c);
+        if (!c || !out || limbs < 1 || limbs > c->L) {
+            hhe_set_error("hhe_ctx_create_level: need a context, 1 <= limbs <= L and an output pointer");
+            return HHE_ERR_INVALID;
+        }
+        q.assign(c->q.begin(), c->q.begin() + limbs);
+        q.push_back(c->q[c->K - 1]);
+        logn = c->logn; device = c->device; t = c->t;
+    }
+    return hhe_ctx_create(logn, limbs + 1, q.data(), t, device, out);
+}
+
 static void free_lane(Lane &ln)
 {
     rt_free(ln.ws_T); rt_free(ln.ws_S); rt_free(ln.ws_d); rt_free(ln.ws_ct3); rt_free(ln.ws_plain); rt_free(ln.ws_vals);
@@ -455,7 +476,9 @@ int lane_reserve(hhe_ctx *c, Lane &ln, size_t B)
     ok &= !!(ln.ws_T = alloc(B * L * K * n));
     ok &= !!(ln.ws_S = alloc(B * 2 * K * n));
     ok &= !!(ln.ws_d = alloc(B * L * n));
-    for (auto &p : ln.ws_ct) ok &= !!(p = alloc(B * 2 * L * n));
+    // the fused matmul loop carves ws_ct[3] into scr [B][L][N] | r [B][2][N] (matmul_diagonal_fused): L + 2 polynomials per item, which
+    // is more than a ciphertext's 2 L at L = 1 (a context of two primes, e.g. the last level of a chain)
+    for (auto &p : ln.ws_ct) ok &= !!(p = alloc(B * std::max<size_t>(2 * L, L + 2) * n));
     ok &= !!(ln.ws_ct3 = alloc(B * 3 * L * n));
     ok &= !!(ln.ws_plain = alloc(B * n));
     ok &= !!(ln.ws_vals = alloc(B * PASTA_T));
@@ -618,6 +641,7 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "fin_word_uploads") return c->fin_word_uploads;     // uploads of the items' words: none where the item kernel reads them in the page-locked staging
     if (w == "fin_scale32") return fin_item_on(c) && c->fin_scale32 ? 1 : 0;  // ... with the plaintext scaled by 32-bit products and -c1 written early (HHE_FIN_SCALE32; t < 2^30 below every data prime)
     if (w == "mod_switch_launches") return c->mod_switch_launches;  // kernel launches of hhe_mod_switch: one per call of up to one chunk
+    if (w == "key_proj_launches") return c->key_proj_launches;      // kernel launches of hhe_keyset_derive_level into this context's sets: one per key
     if (w == "noise_form") return (u64)c->noise_form;  // the last hhe_noise_budget launch: limb count of its register form, 0 = the LDS form
     if (w == "public_device") return (u64)(int64_t)c->public_device;  // HHE_PUBLIC_DEVICE: 0 host, 1 device; unset: (uint64_t)-1, the path is chosen per call
     if (w == "public_device_built") return c->last_public_built;     // pairs whose randomness the last call drew on the device

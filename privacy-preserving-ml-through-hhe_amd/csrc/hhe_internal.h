@@ -116,7 +116,7 @@ struct Lane {
     u64 *ws_T = nullptr;     // [B][L][K][N]
     u64 *ws_S = nullptr;     // [B][2][K][N]
     u64 *ws_d = nullptr;     // [B][L][N]
-    u64 *ws_ct[4] = {nullptr, nullptr, nullptr, nullptr};  // [B][2][L][N] each
+    u64 *ws_ct[4] = {nullptr, nullptr, nullptr, nullptr};  // [B][2][L][N] each ([B][3][N] at L = 1: lane_reserve)
     u64 *ws_ct3 = nullptr;   // [B][3][L][N]
     u64 *ws_plain = nullptr; // [B][N]
     u64 *ws_vals = nullptr;  // [B][128]
@@ -221,7 +221,8 @@ struct hhe_ctx {
     KsConsts ksc{};
     u64 *d_moddown = nullptr;      // modulus switching: per pair j < m < L three words at mod_down_pair(m, j) (hhe_common.h), written once
     u64 mod_switch_launches = 0;   // kernel launches of hhe_mod_switch (hhe_ctx_query("mod_switch_launches"))
-    int noise_form = 0;            // the form the last hhe_noise_budget launch took: its limb count (register form) or 0 (LDS form) (hhe_ctx_query("noise_form"))
+    u64 key_proj_launches = 0;     // kernel launches of hhe_keyset_derive_level into sets of this context: one per key (hhe_ctx_query("key_proj_launches"))
+    int noise_form = 0;           // the form the last hhe_noise_budget launch took: its limb count (register form) or 0 (LDS form) (hhe_ctx_query("noise_form"))
 
     // device tables
     ModDev *d_mods = nullptr;

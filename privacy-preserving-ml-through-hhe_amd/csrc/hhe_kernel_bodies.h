@@ -739,12 +739,26 @@ HD void mod_down_any(const EltArgs &a, size_t gid)
     default: mod_down_body<0>(a, gid, col, 1); break;
     }
 }
+// ------------------------------------------------------------------ key projection to a level (ELT_KEYPROJ)
+// gid over [count][N / 2], 16 bytes per lane: output polynomial (I, k, J) of the level's key [l][2][l+1][N] is polynomial
+// (I, k, J == l ? K_src - 1 : J) of the source key [..][2][K_src][N] (hhe_common.h).  Adjacent lanes move adjacent words.
+HD void key_proj_body(const EltArgs &a, size_t gid)
+{
+    const size_t p = gid >> (a.logn - 1);
+    if (p >= (size_t)a.count) return;
+    const size_t w = (gid & (((size_t)1 << (a.logn - 1)) - 1)) << 1;
+    const size_t kd = (size_t)a.mod_cycle, ks = (size_t)a.b_cycle;
+    const size_t ik = p / kd, j = p % kd;
+    const size_t sp = ik * ks + (j == kd - 1 ? ks - 1 : j);
+    st2(a.out + (p << a.logn) + w, ld2(a.a + (sp << a.logn) + w));
+}
 // the element-wise launch as the tests-only emulator loops it; on the device the fused key-generation epilogue is a kernel of its own
-// and so is every form of the modulus switch
+// and so are every form of the modulus switch and the key projection
 HD void elt_body(const EltArgs &a, int op, size_t gid)
 {
     if (op == ELT_ENCZ) elt_encz_body(a, gid);
     else if (op == ELT_MODDOWN) mod_down_any(a, gid);
+    else if (op == ELT_KEYPROJ) key_proj_body(a, gid);
     else elt_base_body(a, op, gid);
 }
 

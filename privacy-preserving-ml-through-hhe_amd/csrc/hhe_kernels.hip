@@ -593,6 +593,7 @@ __global__ void __launch_bounds__(ELT_THREADS) mod_down_lds_kernel(EltArgs a)
     extern __shared__ u64 mod_down_cols[];
     mod_down_body<0>(a, GID, mod_down_cols + threadIdx.x, ELT_THREADS);
 }
+__global__ void __launch_bounds__(ELT_THREADS) key_proj_kernel(EltArgs a) { key_proj_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) copy_items_kernel(CopyItemsArgs a) { copy_items_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) galois_kernel(GaloisArgs a) { galois_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) perm_kernel(PermArgs a) { perm_body(a, GID); }
@@ -665,6 +666,7 @@ void k_elt(const EltArgs &a, int op, rt_stream s)
 {
     if (op == ELT_ENCZ) LAUNCH1D(elt_encz_kernel, (size_t)a.count << a.logn, s, a);
     else if (op == ELT_MODDOWN) launch_mod_down(a, s);
+    else if (op == ELT_KEYPROJ) LAUNCH1D(key_proj_kernel, (size_t)a.count << (a.logn - 1), s, a);
     else LAUNCH1D(elt_kernel, (size_t)a.count << a.logn, s, a, op);
 }
 void k_copy_items(const CopyItemsArgs &a, rt_stream s) { LAUNCH1D(copy_items_kernel, a.count * (a.words >> 1), s, a); }
