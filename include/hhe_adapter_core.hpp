@@ -213,6 +213,10 @@ private:
     uint64_t uploads_ = 0;
 };
 
+// The encrypted weight matrix of a packed encrypted FC layer as a resident handle (hhe_enc_matrix): shared ownership with
+// hhe_enc_matrix_destroy as deleter, as for key sets.  Whoever holds one also holds the core it was made on (the handle names its context).
+typedef std::shared_ptr<hhe_enc_matrix> EncMatrix;
+
 // A few grow-only device buffers ("slots"); a call takes the arena's lock for its duration (the library serialises calls on one
 // context anyway) and gets buffers that survive the call.
 class DeviceArena {
@@ -417,6 +421,37 @@ public:
         upload(b, w_row);
         check(hhe_fc_row_ks(h(), r.get(), g.get(), a, b, 1, vec_size, o, 1));
         download(o, 1, 2, dst);
+    }
+
+    // ---- packed encrypted FC (hhe_gfx950.h "packed encrypted FC"): all rows of the layer in one ciphertext, in place of one fc_row per
+    // neuron.  diagonals: the r = fc_packed_shape().first encryptions of the generalized diagonals, ct_words() words each; they are
+    // extended and transformed once, here, and are not needed afterwards.
+    std::pair<size_t, size_t> fc_packed_shape(size_t rows, size_t cols) const
+    {
+        size_t r = 0, c = 0;
+        check(hhe_fc_packed_shape(n_, rows, cols, &r, &c));
+        return {r, c};
+    }
+    EncMatrix enc_matrix(const std::vector<const uint64_t *> &diagonals, size_t rows, size_t cols)
+    {
+        if (diagonals.size() != fc_packed_shape(rows, cols).first) throw std::invalid_argument("enc_matrix: one ciphertext per generalized diagonal");
+        DevBuf d(diagonals.size() * ct_words() * 8);
+        for (size_t i = 0; i < diagonals.size(); i++) upload(d.u64() + i * ct_words(), diagonals[i]);
+        hhe_enc_matrix *raw = nullptr;
+        check(hhe_enc_matrix_create(h(), d.u64(), rows, cols, &raw));
+        return EncMatrix(raw, hhe_enc_matrix_destroy);
+    }
+    // the layer on one ciphertext: slots [0, rows) of the result are (M x) mod t.  RK / GK: the key objects the call names (their
+    // words, or a held KeySet)
+    template <class RK, class GK, class Sink> void fc_packed(const uint64_t *vi, const EncMatrix &m, const RK &rk, const GK &gk, Sink dst)
+    {
+        if (!m) throw std::invalid_argument("fc_packed: no encrypted matrix");
+        std::lock_guard<std::mutex> lk(arena_.mutex());
+        const KeySet r = named(set(rk), "fc_packed: empty key object"), g = named(set(gk), "fc_packed: empty key object");
+        uint64_t *d = arena_.get(0, ct_words() * 8);
+        upload(d, vi);
+        check(hhe_fc_packed_ks(h(), r.get(), g.get(), m.get(), d, d, 1));
+        download(d, 1, 2, dst);
     }
 
     // client end: pasta::PASTA::encrypt / decrypt (pasta_3_plain.cpp:9-46) of `count` words in place, key: 256 words

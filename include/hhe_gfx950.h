@@ -66,13 +66,13 @@ void hhe_ctx_destroy(hhe_ctx *c);
  *    there too: enc_key is taken as what the buffer holds in stream order.  Work the caller has on OTHER streams is not waited for.
  *    Host inputs (cw, ncw, block_index, records, keys, matrices, mask values) are read before the call returns.
  *  - The batched calls return after their work has finished (hhe_pasta3_transcipher[_ks], hhe_decompose[_ks], hhe_fc_row[_ks],
- *    hhe_packed_affine[_ks], hhe_mod_switch, every upload, read-back, key generation and matrix creation): they fork onto the
+ *    hhe_packed_affine[_ks], hhe_fc_packed_ks, hhe_mod_switch, every upload, read-back, key generation and matrix creation): they fork onto the
  *    context's internal non-blocking streams (HHE_STREAMS), join the context's stream again and wait for it, so `out` may be read
- *    from any stream when they return.  The generic evaluator ops (hhe_ntt, hhe_encode, hhe_add, hhe_negate, hhe_add_plain,
+ *    from any stream when they return.  The generic evaluator ops (hhe_ntt, hhe_encode, hhe_add, hhe_add_many, hhe_negate, hhe_add_plain,
  *    hhe_multiply_plain, hhe_multiply, hhe_relinearize, hhe_apply_galois, hhe_rotate_*, hhe_mask, hhe_flatten) only ENQUEUE on the
  *    context's stream: their result is ordered for later work on that stream, and for the host after hhe_ctx_sync (or a wait for
  *    the stream).  A non-blocking stream is not ordered with the default stream.
- *  - hhe_ctx_create uploads its tables on the default stream and waits.  Key uploads, key generation and hhe_matrix_create use the
+ *  - hhe_ctx_create uploads its tables on the default stream and waits.  Key uploads, key generation, hhe_matrix_create and hhe_enc_matrix_create use the
  *    stream the context has at that call and wait: what they leave resident is complete, whichever stream later calls run on.
  *  - Changing the stream waits for nothing.  Resident objects (keys, block tables, kept keystreams, matrices) stay valid, as they
  *    were finished under a host wait.  Generic ops still in flight on the old stream are NOT ordered with calls on the new one,
@@ -92,7 +92,8 @@ int hhe_ctx_sync(hhe_ctx *c);
 int hhe_ctx_profile(hhe_ctx *c, int enable);
 int hhe_ctx_profile_read(hhe_ctx *c, char *kernel_name, size_t name_cap, uint64_t *launches, double *total_ms, uint64_t *items);
 /* derived parameters, for cross-checking against SEAL's context: what in
- * {"root" i<K, "bsk" i<=L (B_0.., m_sk), "gamma", "galois_elt" i=step, "fc_fallbacks", "fc_csum_closes"};
+ * {"root" i<K, "bsk" i<=L (B_0.., m_sk), "gamma", "galois_elt" i=step, "fc_fallbacks", "fc_csum_closes", "fc_packed_key_switches",
+ * "add_many_launches"};
  * which kernels the context dispatches to (read-only diagnostics): "row_kernel" (1 = the fused key-switch row kernels run,
  * 0 = the separate-kernel path), "pm_ok" i<K (coefficient prime i has the pseudo-Mersenne form the lazy kernels need),
  * "digit_reduce" (key-switch digits are reduced before their transforms: some q_I >= 4 q_J) */
@@ -265,6 +266,60 @@ int hhe_packed_affine_ks(hhe_ctx *c, const hhe_keyset *gk, const hhe_matrix *mat
 /* add_diagonal_indices / add_bsgs_indices (:337-355), host only: the rotate_rows steps a layer needs keys for, in the reference's
  * order.  *count: in = capacity of steps_out, out = number of steps (HHE_ERR_CAPACITY when too small). */
 int hhe_affine_galois_steps(size_t N, size_t dim, size_t n1, size_t n2, int *steps_out, size_t *count);
+
+/* ---- packed encrypted FC: a rows x cols matrix of ENCRYPTED weights times an encrypted packed vector, all outputs in one ciphertext,
+ *      by the Halevi-Shoup hybrid diagonal method.  It replaces `rows` calls of the FC row above (src/examples/CSP/CSP.cpp:296-316):
+ *      the analyst encrypts r generalized diagonals instead of `rows` weight rows and decrypts one ciphertext.
+ *      Shape: r = the smallest power of two >= rows; c = the smallest power of two >= cols, raised to r if smaller.  Admitted when
+ *      2c == N or 4c <= N, else HHE_ERR_TOO_FEW_SLOTS (the rule of src/pasta/SEAL_Cipher.cpp:192-193 with c for the dimension).
+ *      Diagonals (host): with M zero-padded to r x c, d_i[j] = M[j mod r][(j + i) mod c], j in [0, c), i in [0, r); the analyst encodes
+ *      d_i into slots [0, c) of row 0 and encrypts it: W_0 .. W_{r-1}.
+ *      The layer on an input ciphertext x, in SEAL's operations:
+ *        1. if 2c != N:  x = add(x, rotate_rows(x, -c, gk))
+ *        2. rot_0 = x;  rot_i = rotate_rows(rot_{i-1}, 1, gk), i = 1 .. r-1
+ *        3. acc = multiply(rot_0, W_0);  acc = add(acc, multiply(rot_i, W_i)), i = 1 .. r-1, at size 3
+ *        4. y = relinearize(acc, rk)
+ *        5. for s = r, 2r, .., c/2:  y = add(y, rotate_rows(y, s, gk))
+ *      The words of `out` are the words of that composition.  Slots [0, rows) of the decryption are (M x) mod t; the other slots hold
+ *      partial sums (hhe_mask removes them if they must not be returned).
+ *      PRECONDITION, which cannot be checked: slots [c, N/2) of the input's row 0 are zero.  Slots [cols, c) may hold anything (the
+ *      padded columns of the diagonals are zero).  Row 1 of the batching is carried along independently: a caller who also encodes the
+ *      diagonals into row 1 gets a second input vector served per ciphertext.
+ *      Galois keys: every step is +- a power of two -- -c (when 2c != N), +1 (when r > 1), r 2^k below c -- whose NAF has one term, so
+ *      each needs a key of its own in `gk` (create_galois_keys() without arguments makes all of them).
+ *      Key switches per item: (2c != N) + (r - 1) + log2(c / r) rotations and one relinearization, against `rows` relinearizations and
+ *      the rotation tries of `rows` FC rows. ---- */
+/* host only: r and c of a rows x cols layer at degree N; rows or cols == 0 or N not a power of two: HHE_ERR_INVALID */
+int hhe_fc_packed_shape(size_t N, size_t rows, size_t cols, size_t *r_out, size_t *c_out);
+/* host only: the generalized diagonals of M_hptr (row-major rows x cols, entries < t, else HHE_ERR_INVALID) as slot vectors
+ * vals_hptr [r][c], r and c as above (no degree enters) */
+int hhe_fc_packed_diagonals(uint64_t t, const uint64_t *M_hptr, size_t rows, size_t cols, uint64_t *vals_hptr);
+/* host only: the rotate_rows steps of the layer in the order it takes them.  *count: in = capacity, out = number of steps
+ * (HHE_ERR_CAPACITY when too small), as hhe_affine_galois_steps */
+int hhe_fc_packed_galois_steps(size_t N, size_t rows, size_t cols, int *steps_out, size_t *count);
+/* The encrypted matrix as a resident handle, created once per model like hhe_matrix: it names its context and is destroyed explicitly
+ * (hhe_ctx_destroy releases forgotten ones).  wdiag_dptr: the r diagonal ciphertexts [r][2][L][N] at the data level of c, coefficient
+ * form.  The handle holds what a BEHZ product needs from its second operand -- every diagonal extended to q u B_sk and in NTT form,
+ * 2 (2L + 1) N words per diagonal (hhe_enc_matrix_bytes) -- computed once, here; the extension is deterministic, so the products of
+ * the layer are the words of multiply(rot_i, W_i).  wdiag is not needed after the call.  Runs on the stream c has and waits. */
+typedef struct hhe_enc_matrix hhe_enc_matrix;
+int hhe_enc_matrix_create(hhe_ctx *c, const uint64_t *wdiag_dptr, size_t rows, size_t cols, hhe_enc_matrix **out);
+void hhe_enc_matrix_destroy(hhe_enc_matrix *m);
+size_t hhe_enc_matrix_bytes(const hhe_enc_matrix *m);
+/* The layer: vi and out [B][2][L][N], out_dptr == vi_dptr is allowed; rk / gk NULL: the context's default set.  Refused before anything
+ * is written: a null argument or B == 0 or a handle or key set of another context (HHE_ERR_INVALID), no relinearization key
+ * (HHE_ERR_NO_RELIN_KEY), a step without its key (HHE_ERR_NO_GALOIS_KEY).  The batch is chunked over the internal streams
+ * (HHE_STREAMS); a chunk keeps its r rotations and r size-3 products per item, 5 r L N words, reserved per lane, and runs the BEHZ
+ * passes of all its r x items products at once, so a chunk holds max(1, HHE_CHUNK / r) items: r x items never exceeds what the other
+ * batched calls reserve a lane for.  hhe_ctx_query("fc_packed_key_switches"): Galois key switches per item of the last call.
+ * Synchronous. */
+int hhe_fc_packed_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *mat, const uint64_t *vi_dptr,
+                     uint64_t *out_dptr, size_t B);
+/* Evaluator::add_many (seal/evaluator.h:150) for K stacked batches in_dptr [K][B][size][L][N], size 2 or 3: out [B][size][L][N] = their
+ * sum, in ONE kernel launch whatever K is (hhe_ctx_query("add_many_launches") counts them); the sum of a coefficient is kept in two
+ * words and reduced once.  out may be one of the K operands.  K == 0, B == 0, a null pointer or another size: HHE_ERR_INVALID.
+ * Enqueues on the context's stream like hhe_add. */
+int hhe_add_many(hhe_ctx *c, const uint64_t *in_dptr, size_t K, uint64_t *out_dptr, size_t B, int size);
 
 /* PASTA-3 public randomness for one block as the kernels consume it (host; src/pasta/pasta_3_plain.cpp:56-119,286-295):
  * mats [4][2][128][128], rcs [4][2][128] */

@@ -108,6 +108,37 @@ inline auto into_level(const hhe::AdapterCore &core, Ciphertext &ct, size_t size
 }
 }  // namespace detail
 
+// The analyst's encrypted weight matrix of a packed encrypted FC layer, resident on the device (hhe_gfx950.h "packed encrypted FC";
+// no reference counterpart: the reference evaluates one encrypted row per neuron, CSP.cpp:296-316).  diagonals: the r encryptions of the
+// generalized diagonals hhe_fc_packed_diagonals lays out, at the data level -- or, made by SEALZpLevel::enc_matrix, at that level.  The
+// object holds the cores it needs, so it may outlive the cipher objects; a conversion into hhe::AdapterCore and nothing else.
+struct EncMatrix {
+    EncMatrix() = default;
+    EncMatrix(std::shared_ptr<HheContext> con, const std::vector<Ciphertext> &diagonals, size_t rows, size_t cols)
+        : EncMatrix(con, con, diagonals, rows, cols) {}
+    EncMatrix(std::shared_ptr<HheContext> con, std::shared_ptr<hhe::AdapterCore> at, const std::vector<Ciphertext> &diagonals, size_t rows, size_t cols)
+        : context(std::move(con)), core(std::move(at)), rows(rows), cols(cols)
+    {
+        std::vector<const uint64_t *> p;
+        for (auto &ct : diagonals) p.push_back(detail::level_words(*core, context->data_limbs(), ct));
+        handle = core->enc_matrix(p, rows, cols);
+    }
+    // slots [0, rows) of the decryption of `out` are (M x) mod t; rk / gal_keys: the parties' ordinary, top-level key objects
+    void apply(const Ciphertext &vi, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out) const
+    {
+        if (!core) throw std::invalid_argument("fc_packed: no encrypted matrix");
+        const bool top = core.get() == context.get();
+        hhe::KeySet r = context->keys().relin(detail::words(rk)), g = context->keys().galois(detail::words(gal_keys));
+        if (!top) { r = core->derived(r); g = core->derived(g); }
+        core->fc_packed(detail::level_words(*core, context->data_limbs(), vi), handle, r, g, detail::into_level(*core, out));
+        if (top) out.limbs = 0;  // the data level, as every cipher object's results
+    }
+    std::shared_ptr<HheContext> context;      // the chain's core: its key-set cache holds the sets the calls name
+    std::shared_ptr<hhe::AdapterCore> core;   // where the handle lives: the chain's core, or a level's
+    hhe::EncMatrix handle;                    // declared after the cores: released before them
+    size_t rows = 0, cols = 0;
+};
+
 // What SEALZpCipher::level(levels_from_last) returns: the evaluation members of a cipher object, bound to one level of the modulus
 // switching chain.  Every member takes and produces ciphertexts of exactly that level (Ciphertext::limbs == limbs()) and refuses any
 // other with std::invalid_argument.  The object keeps no keys of its own: it names the key sets of the cipher object it came from,
@@ -163,6 +194,13 @@ public:
     void encrypted_vec_sum(const Ciphertext &encrypted_inp, Ciphertext &destination, const GaloisKeys &gal_keys, size_t vec_size)
     {
         core->vec_sum(in(encrypted_inp), core->derived(context->keys().galois(detail::words(gal_keys))), vec_size, out(destination));
+    }
+    // packed encrypted FC at this level: the handle is made on the level's context from diagonals of this level
+    EncMatrix enc_matrix(const std::vector<Ciphertext> &diagonals, size_t rows, size_t cols) { return EncMatrix(context, core, diagonals, rows, cols); }
+    void fc_packed(const Ciphertext &vi, const EncMatrix &mat, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out)
+    {
+        if (mat.core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
+        mat.apply(vi, rk, gal_keys, out);
     }
     // SEALZpCipher::print_noise / sealhelper::decrypting on the level's context, with the rows of the secret key that level has
     int print_noise(Ciphertext &ciph)
@@ -557,5 +595,14 @@ inline void fc_row(pasta::HheContext &ctx, const pasta::Ciphertext &vi, const pa
 {
     ctx.fc_row(pasta::detail::words(ctx, vi), pasta::detail::words(ctx, w_row), pasta::detail::words(csp_rk), pasta::detail::words(gal_keys), vec_size,
                pasta::detail::into(ctx, destination));
+}
+// The whole FC layer under the analyst's encrypted weights as ONE device call and one result ciphertext (the hybrid diagonal method,
+// hhe_gfx950.h "packed encrypted FC"), in place of fc_row per neuron: mat holds the r encrypted generalized diagonals, rk / gal_keys are
+// the key objects CSP.cpp:306 and :312-316 name.  Slots [0, rows) of the decryption are the neurons.
+typedef pasta::EncMatrix EncMatrix;
+inline void fc_packed(const pasta::Ciphertext &vi, const EncMatrix &mat, const pasta::RelinKeys &rk, const pasta::GaloisKeys &gal_keys,
+                      pasta::Ciphertext &out)
+{
+    mat.apply(vi, rk, gal_keys, out);
 }
 }  // namespace sealhelper

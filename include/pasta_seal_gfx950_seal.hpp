@@ -173,6 +173,49 @@ private:
 }  // namespace gfx950
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The analyst's encrypted weight matrix of a packed encrypted FC layer, resident on the device (hhe_gfx950.h "packed encrypted FC"; no
+// reference counterpart: the reference evaluates one encrypted row per neuron, CSP.cpp:296-316).  diagonals: the r encryptions of the
+// generalized diagonals at the data level -- or, made by SEALZpLevel::enc_matrix, at that level's parms_id.  A conversion into
+// hhe::AdapterCore and nothing else; the object holds the cores it needs.
+struct EncMatrix {
+    EncMatrix() = default;
+    EncMatrix(std::shared_ptr<seal::SEALContext> con, const std::vector<seal::Ciphertext> &diagonals, std::size_t rows, std::size_t cols)
+        : EncMatrix(con, gfx950::DeviceContext::get(*con), nullptr, con->first_parms_id(), diagonals, rows, cols) {}
+    // at: the core of a level (null: the chain's own), level_id: that level's parms_id
+    EncMatrix(std::shared_ptr<seal::SEALContext> con, std::shared_ptr<gfx950::DeviceContext> dev, std::shared_ptr<hhe::AdapterCore> at,
+              seal::parms_id_type level_id, const std::vector<seal::Ciphertext> &diagonals, std::size_t rows, std::size_t cols)
+        : context(std::move(con)), device(std::move(dev)), core(at ? std::move(at) : std::shared_ptr<hhe::AdapterCore>(device)), id(level_id), rows(rows), cols(cols)
+    {
+        std::vector<const std::uint64_t *> p;
+        for (const auto &ct : diagonals) p.push_back(in(ct));
+        handle = core->enc_matrix(p, rows, cols);
+    }
+    // slots [0, rows) of the decryption of `out` are (M x) mod t; rk / gal_keys: the parties' ordinary, top-level key objects
+    void apply(const seal::Ciphertext &vi, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out) const
+    {
+        if (!core) throw std::invalid_argument("fc_packed: no encrypted matrix");
+        hhe::KeySet r = device->relin_set(rk), g = device->galois_set(gal_keys);
+        if (core.get() != device.get()) { r = core->derived(r); g = core->derived(g); }
+        core->fc_packed(in(vi), handle, r, g, gfx950::DeviceContext::into_level(*context, out, id, 2));
+    }
+    std::shared_ptr<seal::SEALContext> context;
+    std::shared_ptr<gfx950::DeviceContext> device;  // the chain's core: its key-set cache holds the sets the calls name
+    std::shared_ptr<hhe::AdapterCore> core;         // where the handle lives: the chain's core, or a level's
+    seal::parms_id_type id{};                       // the level of the diagonals, the inputs and the results
+    hhe::EncMatrix handle;                          // declared after the cores: released before them
+    std::size_t rows = 0, cols = 0;
+
+private:
+    const std::uint64_t *in(const seal::Ciphertext &ct) const
+    {
+        if (ct.is_ntt_form() || ct.parms_id() != id || ct.poly_modulus_degree() != core->poly_modulus_degree() ||
+            ct.coeff_modulus_size() != core->data_limbs() || ct.size() != 2)
+            throw std::invalid_argument("encrypted is not at the level of this object");
+        return ct.data();
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
 // What SEALZpCipher::level(levels_from_last) returns: the evaluation members of a cipher object bound to one level of the modulus
 // switching chain, named by its parms_id.  Every member takes and produces coefficient-form ciphertexts whose parms_id is that
 // level's and refuses any other with std::invalid_argument.  The object keeps no keys of its own: the device core of the level
@@ -237,6 +280,16 @@ public:
     void encrypted_vec_sum(const seal::Ciphertext &encrypted_inp, seal::Ciphertext &destination, const seal::GaloisKeys &gal_keys, size_t vec_size)
     {
         core->vec_sum(in(encrypted_inp), core->derived(device->galois_set(gal_keys)), vec_size, out(destination));
+    }
+    // packed encrypted FC at this level: the handle is made on the level's context from diagonals of this level
+    EncMatrix enc_matrix(const std::vector<seal::Ciphertext> &diagonals, std::size_t rows, std::size_t cols)
+    {
+        return EncMatrix(context, device, core, id, diagonals, rows, cols);
+    }
+    void fc_packed(const seal::Ciphertext &vi, const EncMatrix &mat, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out)
+    {
+        if (mat.core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
+        mat.apply(vi, rk, gal_keys, out);
     }
     // SEALZpCipher::print_noise / sealhelper::decrypting on the level's device context, with the rows of the secret key that level has
     int print_noise(seal::Ciphertext &ciph)
@@ -630,6 +683,15 @@ inline void fc_row(const seal::Ciphertext &vi, const seal::Ciphertext &w_row, co
 {
     auto dev = DeviceContext::find(vi.parms_id());
     dev->fc_row(dev->words(vi), dev->words(w_row), DeviceContext::words(csp_rk), DeviceContext::words(gal_keys), vec_size, DeviceContext::into(destination, vi));
+}
+
+// The whole FC layer under the analyst's encrypted weights as ONE device call and one result ciphertext (the hybrid diagonal method,
+// hhe_gfx950.h "packed encrypted FC"), in place of fc_row per neuron: mat holds the r encrypted generalized diagonals, rk / gal_keys are
+// the key objects CSP.cpp:306 and :312-316 name.  Slots [0, rows) of the decryption are the neurons.
+typedef pasta::EncMatrix EncMatrix;
+inline void fc_packed(const seal::Ciphertext &vi, const EncMatrix &mat, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out)
+{
+    mat.apply(vi, rk, gal_keys, out);
 }
 
 }  // namespace sealhelper

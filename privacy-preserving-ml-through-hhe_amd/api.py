@@ -24,6 +24,7 @@ class HheError(RuntimeError):
 
 # error codes of include/hhe_gfx950.h
 ERR_INVALID, ERR_NO_GALOIS_KEY, ERR_TOO_FEW_SLOTS, ERR_DEVICE, ERR_NO_RELIN_KEY = 1, 2, 3, 4, 5
+ERR_CAPACITY = 6
 
 _SYMBOLS = [
     "hhe_last_error", "hhe_backend", "hhe_ctx_create", "hhe_bfv_default_coeff_modulus", "hhe_ctx_destroy", "hhe_ctx_set_stream",
@@ -46,8 +47,12 @@ _SYMBOLS = [
     "hhe_noise_budget", "hhe_ctx_create_level", "hhe_keyset_derive_level",
     "hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystream_nonce", "hhe_pasta3_plain_crypt_nonce",
     "hhe_pasta3_transcipher_nonce_ks", "hhe_decompose_nonce_ks", "hhe_pasta3_block_randomness_dev", "hhe_pasta3_prepare_tables",
+    "hhe_fc_packed_shape", "hhe_fc_packed_diagonals", "hhe_fc_packed_galois_steps", "hhe_enc_matrix_create", "hhe_enc_matrix_destroy",
+    "hhe_enc_matrix_bytes", "hhe_fc_packed_ks", "hhe_add_many",
 ]
 
+_FC_PACKED_SYMBOLS = {"hhe_fc_packed_shape", "hhe_fc_packed_diagonals", "hhe_fc_packed_galois_steps", "hhe_enc_matrix_create",
+                      "hhe_enc_matrix_destroy", "hhe_enc_matrix_bytes", "hhe_fc_packed_ks", "hhe_add_many"}
 _NONCE_SYMBOLS = {"hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystream_nonce", "hhe_pasta3_plain_crypt_nonce",
                   "hhe_pasta3_transcipher_nonce_ks", "hhe_decompose_nonce_ks", "hhe_pasta3_block_randomness_dev",
                   "hhe_pasta3_prepare_tables"}
@@ -58,7 +63,7 @@ _NONCE_SYMBOLS = {"hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystre
 _OPTIONAL = {"hhe_pasta3_clear_keystream_cache", "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin",
              "hhe_keyset_generate_galois", "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
              "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level",
-             "hhe_noise_budget", "hhe_ctx_create_level", "hhe_keyset_derive_level"} | _NONCE_SYMBOLS
+             "hhe_noise_budget", "hhe_ctx_create_level", "hhe_keyset_derive_level"} | _NONCE_SYMBOLS | _FC_PACKED_SYMBOLS
 
 
 def exported_symbols():
@@ -99,6 +104,11 @@ def load_library(path=None):
     lib.hhe_matrix_destroy.restype = None
     lib.hhe_matrix_bytes.argtypes = [C.c_void_p]
     lib.hhe_matrix_bytes.restype = C.c_size_t
+    if hasattr(lib, "hhe_enc_matrix_create"):
+        lib.hhe_enc_matrix_destroy.argtypes = [C.c_void_p]
+        lib.hhe_enc_matrix_destroy.restype = None
+        lib.hhe_enc_matrix_bytes.argtypes = [C.c_void_p]
+        lib.hhe_enc_matrix_bytes.restype = C.c_size_t
     return lib
 
 
@@ -240,6 +250,39 @@ class Matrix:
         return int(self.ctx.lib.hhe_matrix_bytes(self.h))
 
 
+class EncMatrix:
+    """The encrypted weight matrix of a packed encrypted FC layer on the device (hhe_enc_matrix): its r generalized diagonals,
+    extended and transformed once.  diag_cts: device uint64 [r][2][L][N], the encryptions of fc_packed_diagonals' slot vectors."""
+
+    def __init__(self, ctx, diag_cts, rows, cols):
+        self.ctx, self.rows, self.cols = ctx, int(rows), int(cols)
+        h = C.c_void_p()
+        ctx._chk(ctx._need("hhe_enc_matrix_create")(ctx.h, _ptr(diag_cts), C.c_size_t(rows), C.c_size_t(cols), C.byref(h)))
+        self.h = h
+
+    def apply(self, ct, B, rk=None, gk=None, out=None):
+        """out[b] = the layer on ct[b] (device [B][2][L][N]; out None: in place); slots [0, rows) of the decryption are (M x) mod t.
+        rk / gk: the KeySet the call names (None = the context's default set).  Returns out."""
+        out = ct if out is None else out
+        self.ctx._chk(self.ctx.lib.hhe_fc_packed_ks(self.ctx.h, _ks(rk), _ks(gk), self.h, _ptr(ct), _ptr(out), C.c_size_t(B)))
+        return out
+
+    def destroy(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.hhe_enc_matrix_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    @property
+    def bytes(self):
+        return int(self.ctx.lib.hhe_enc_matrix_bytes(self.h))
+
+
 class Context:
     """One BFV context on one GPU (hhe_ctx)."""
 
@@ -364,6 +407,14 @@ class Context:
         """out[b] = M * ct[b] (+ bias) on packed ciphertexts (SEALZpCipher::packed_matMul / packed_affine)"""
         self._chk(self.lib.hhe_packed_affine_ks(self.h, _ks(gk), mat.h, _ptr(ct), _ptr(out), C.c_size_t(B)))
 
+    def enc_matrix(self, diag_cts, rows, cols):
+        """resident encrypted matrix of a packed encrypted FC layer from its r diagonal ciphertexts (device [r][2][L][N])"""
+        return EncMatrix(self, diag_cts, rows, cols)
+
+    def add_many(self, stacked, K, out, B, size=2):
+        """out [B][size][L][N] = the sum of the K batches stacked [K][B][size][L][N] (Evaluator::add_many), one launch"""
+        self._chk(self._need("hhe_add_many")(self.h, _ptr(stacked), C.c_size_t(K), _ptr(out), C.c_size_t(B), C.c_int(size)))
+
     def multiply(self, a, b, out3, B):
         self._chk(self.lib.hhe_multiply(self.h, _ptr(a), _ptr(b), _ptr(out3), C.c_size_t(B)))
 
@@ -378,7 +429,7 @@ class Context:
     # ---- hot path ----
     def _need(self, name):
         if not hasattr(self.lib, name):
-            raise RuntimeError(f"this library has no {name} (built before nonces reached the boundary)")
+            raise RuntimeError(f"this library has no {name} (built from an earlier commit)")
         return getattr(self.lib, name)
 
     def transcipher(self, enc_key, cw, ncw, block_index, out, use_bsgs=False, rk=None, gk=None, nonces=None):
@@ -609,6 +660,48 @@ def affine_galois_steps(n, dim, n1=0, n2=0, lib=None):
     out = (C.c_int * 64)()
     cnt = C.c_size_t(64)
     rc = lib.hhe_affine_galois_steps(C.c_size_t(n), C.c_size_t(dim), C.c_size_t(n1), C.c_size_t(n2), out, C.byref(cnt))
+    if rc:
+        raise HheError(rc, lib.hhe_last_error().decode())
+    return [int(v) for v in out[:cnt.value]]
+
+
+def _lib_fn(lib, name):
+    if not hasattr(lib, name):
+        raise RuntimeError(f"this library has no {name} (built from an earlier commit)")
+    return getattr(lib, name)
+
+
+def fc_packed_shape(n, rows, cols, lib=None):
+    """(r, c) of a rows x cols packed encrypted FC layer at degree n: powers of two, c >= r; HheError when the slots do not suffice"""
+    lib = lib or load_library()
+    r, c = C.c_size_t(0), C.c_size_t(0)
+    rc = _lib_fn(lib, "hhe_fc_packed_shape")(C.c_size_t(n), C.c_size_t(rows), C.c_size_t(cols), C.byref(r), C.byref(c))
+    if rc:
+        raise HheError(rc, lib.hhe_last_error().decode())
+    return int(r.value), int(c.value)
+
+
+def fc_packed_diagonals(t, M, lib=None):
+    """the generalized diagonals of M (rows x cols, entries < t) as slot vectors [r][c]: d_i[j] = M[j mod r][(j + i) mod c], zero padded"""
+    lib = lib or load_library()
+    M = np.ascontiguousarray(M, dtype=np.uint64)
+    assert M.ndim == 2
+    rows, cols = M.shape
+    r = 1 << max(rows - 1, 0).bit_length()
+    c = max(1 << max(cols - 1, 0).bit_length(), r)
+    vals = np.zeros((r, c), np.uint64)
+    rc = _lib_fn(lib, "hhe_fc_packed_diagonals")(C.c_uint64(t), _ptr(M), C.c_size_t(rows), C.c_size_t(cols), _ptr(vals))
+    if rc:
+        raise HheError(rc, lib.hhe_last_error().decode())
+    return vals
+
+
+def fc_packed_galois_steps(n, rows, cols, lib=None):
+    """the rotate_rows steps a packed encrypted FC layer needs Galois keys for, in the order it takes them"""
+    lib = lib or load_library()
+    out = (C.c_int * 64)()
+    cnt = C.c_size_t(64)
+    rc = _lib_fn(lib, "hhe_fc_packed_galois_steps")(C.c_size_t(n), C.c_size_t(rows), C.c_size_t(cols), out, C.byref(cnt))
     if rc:
         raise HheError(rc, lib.hhe_last_error().decode())
     return [int(v) for v in out[:cnt.value]]

@@ -224,22 +224,24 @@ int op_prep_rows(hhe_ctx *c, u64 *state, int step, u64 *scratch, size_t B)
     return rc;
 }
 
-// Evaluator::bfv_multiply (BEHZ; SURVEY A.7): a, b [B][2][L][N] -> out3 [B][3][L][N]
-void op_multiply(hhe_ctx *c, const u64 *x, const u64 *y, u64 *out3, size_t B)
+// One operand of a BEHZ product: in [B][2][L][N] coefficient form -> oq [B][2][L][N] NTT form under the data primes, ob [B][2][L+1][N]
+// NTT form of its extension to B_sk (fastbconv_m_tilde + sm_mrq).  Deterministic in the words of `in`.
+void op_behz_operand(hhe_ctx *c, const u64 *in, u64 *oq, u64 *ob, size_t B)
 {
     const int L = c->L, K = c->K;
-    auto extend = [&](const u64 *in, u64 *oq, u64 *ob) {
-        BehzExtendArgs e = zeroed<BehzExtendArgs>();
-        e.x = in; e.xb = ob; e.mods = c->d_mods; e.bz = c->d_behz; e.logn = c->logn; e.P = (int)(B * 2); e.L = L; e.K = K;
-        k_behz_extend(e, c->w->stream);
-        op_ntt(c, ob, B * 2 * (L + 1), K, L + 1, false);
-        k_ntt(ntt_args(c, in, oq, B * 2 * L, 0, L), false, c->w->stream);
-    };
-    extend(x, c->w->bz_aq, c->w->bz_ab);
-    const u64 *bq = c->w->bz_aq, *bb = c->w->bz_ab;
-    if (y != x) { extend(y, c->w->bz_bq, c->w->bz_bb); bq = c->w->bz_bq; bb = c->w->bz_bb; }
+    BehzExtendArgs e = zeroed<BehzExtendArgs>();
+    e.x = in; e.xb = ob; e.mods = c->d_mods; e.bz = c->d_behz; e.logn = c->logn; e.P = (int)(B * 2); e.L = L; e.K = K;
+    k_behz_extend(e, c->w->stream);
+    op_ntt(c, ob, B * 2 * (L + 1), K, L + 1, false);
+    k_ntt(ntt_args(c, in, oq, B * 2 * L, 0, L), false, c->w->stream);
+}
+// The passes of a BEHZ product behind its operands: the first operand of B items in the lane's bz_aq / bz_ab, the second at bq / bb in
+// the same form; b_div > 0: item b multiplies ciphertext b / b_div of the second operand (TensorArgs::b_div)
+void behz_product(hhe_ctx *c, const u64 *bq, const u64 *bb, size_t b_div, u64 *out3, size_t B)
+{
+    const int L = c->L, K = c->K;
     TensorArgs t = zeroed<TensorArgs>();
-    t.mods = c->d_mods; t.logn = c->logn; t.B = (int)B;
+    t.mods = c->d_mods; t.logn = c->logn; t.B = (int)B; t.b_div = (int)b_div;
     t.a = c->w->bz_aq; t.b = bq; t.d = c->w->bz_dq; t.limbs = L; t.mod_base = 0;
     k_tensor(t, c->w->stream);
     t.a = c->w->bz_ab; t.b = bb; t.d = c->w->bz_db; t.limbs = L + 1; t.mod_base = K;
@@ -250,6 +252,22 @@ void op_multiply(hhe_ctx *c, const u64 *x, const u64 *y, u64 *out3, size_t B)
     f.dq = c->w->bz_dq; f.db = c->w->bz_db; f.out = out3; f.mods = c->d_mods; f.bz = c->d_behz; f.logn = c->logn;
     f.P = (int)(B * 3); f.L = L; f.K = K;
     k_behz_floor(f, c->w->stream);
+}
+// Evaluator::bfv_multiply (BEHZ; SURVEY A.7): a, b [B][2][L][N] -> out3 [B][3][L][N]
+void op_multiply(hhe_ctx *c, const u64 *x, const u64 *y, u64 *out3, size_t B)
+{
+    op_behz_operand(c, x, c->w->bz_aq, c->w->bz_ab, B);
+    const u64 *bq = c->w->bz_aq, *bb = c->w->bz_ab;
+    if (y != x) { op_behz_operand(c, y, c->w->bz_bq, c->w->bz_bb, B); bq = c->w->bz_bq; bb = c->w->bz_bb; }
+    behz_product(c, bq, bb, 0, out3, B);
+}
+// ... against a resident encrypted matrix: x [r][per][2][L][N], the r rotations of `per` items, rotation-major; product (i, b) is
+// multiply(x[i][b], W_i) with W_i in the form the handle keeps -> out3 [r][per][3][L][N].  One extension, one transform and one floor
+// over all r * per products; the lane is reserved for that many items.
+void op_multiply_enc(hhe_ctx *c, const u64 *x, const hhe_enc_matrix *m, u64 *out3, size_t per)
+{
+    op_behz_operand(c, x, c->w->bz_aq, c->w->bz_ab, m->r * per);
+    behz_product(c, m->wq, m->wb, per, out3, m->r * per);
 }
 
 int op_relinearize(hhe_ctx *c, const u64 *a3, u64 *out, size_t B)
@@ -2269,4 +2287,179 @@ extern "C" int hhe_packed_affine_ks(hhe_ctx *c, const hhe_keyset *gk, const hhe_
     rc = run_chunks(c, plan, [&](Lane &, size_t, size_t b0, size_t bc) { return affine_chunk(c, m, ct + b0 * ctw, out + b0 * ctw, bc); });
     if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_packed_affine");
     return rc;
+}
+
+// ====================================================================== packed encrypted FC (hybrid diagonal method)
+// The definition is in include/hhe_gfx950.h; DESIGN.md section 4 "Packed encrypted FC" has the schedule and the workspace.
+namespace {
+size_t pow2_ceil(size_t v)
+{
+    size_t p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+// r and c of a rows x cols layer; n = 0: no degree, no slot rule (the diagonals' layout does not depend on it)
+int fc_packed_dims(size_t n, size_t rows, size_t cols, size_t &r, size_t &cc)
+{
+    if (rows == 0 || cols == 0 || rows > ((size_t)1 << 30) || cols > ((size_t)1 << 30)) return fail(HHE_ERR_INVALID, "packed FC: rows and cols must be positive (and at most 2^30)");
+    if (n && (n < 4 || (n & (n - 1)))) return fail(HHE_ERR_INVALID, "packed FC: the degree must be a power of two");
+    r = pow2_ceil(rows);
+    cc = std::max(pow2_ceil(cols), r);
+    if (n && cc * 2 != n && cc * 4 > n) return fail(HHE_ERR_TOO_FEW_SLOTS, "too little slots for matmul implementation!");
+    return HHE_OK;
+}
+// the rotate_rows steps in the order the layer takes them: -c unless the row is full, +1 when there is a chain, the tail r 2^k < c
+void fc_packed_steps(size_t n, size_t r, size_t cc, std::vector<int> &steps)
+{
+    steps.clear();
+    if (cc * 2 != n) steps.push_back(-(int)cc);
+    if (r > 1) steps.push_back(1);
+    for (size_t s = r; s < cc; s <<= 1) steps.push_back((int)s);
+}
+// one chunk on the current lane: in / out [per][2][L][N] (may be the same buffer); the lane is reserved for r * per items
+int fc_packed_chunk(hhe_ctx *c, const hhe_enc_matrix *m, const u64 *in, u64 *out, size_t per)
+{
+    const size_t ctw = c->ct_words(), r = m->r;
+    Lane &w = *c->w;
+    u64 *rot = w.ws_fcp.p, *prod = rot + r * per * ctw;  // [r][per][2][L][N] | [r][per][3][L][N]
+    int rc;
+    rt_d2d(rot, in, per * ctw * 8, w.stream);
+    if (m->c * 2 != c->n && (rc = op_prep_rows(c, rot, -(int)m->c, w.ws_ct[2], per))) return rc;
+    for (size_t i = 1; i < r; ++i)
+        if ((rc = op_rotate_rows(c, rot + (i - 1) * per * ctw, 1, rot + i * per * ctw, per))) return rc;
+    op_multiply_enc(c, rot, m, prod, per);
+    if (r > 1) {  // acc = the sum of the r products of every item, into the first one
+        k_elt(elt_args(c, prod, nullptr, prod, per * 3 * c->L, 0, c->L, (int)r), ELT_ADDMANY, w.stream);
+        ++c->add_many_launches;
+    }
+    u64 *y = w.ws_ct[0];
+    if ((rc = op_relinearize(c, prod, y, per))) return rc;
+    for (size_t s = r; s < m->c; s <<= 1)
+        if ((rc = op_prep_rows(c, y, (int)s, w.ws_ct[2], per))) return rc;
+    rt_d2d(out, y, per * ctw * 8, w.stream);
+    return HHE_OK;
+}
+}  // namespace
+
+void enc_matrix_free(hhe_enc_matrix *m)
+{
+    if (!m) return;
+    rt_free(m->wq); rt_free(m->wb);
+    delete m;
+}
+
+extern "C" int hhe_fc_packed_shape(size_t N, size_t rows, size_t cols, size_t *r_out, size_t *c_out)
+{
+    if (!r_out || !c_out || N == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed_shape: null argument or no degree");
+    size_t r, cc;
+    int rc = fc_packed_dims(N, rows, cols, r, cc);
+    if (rc) return rc;
+    *r_out = r; *c_out = cc;
+    return HHE_OK;
+}
+extern "C" int hhe_fc_packed_diagonals(uint64_t t, const uint64_t *M, size_t rows, size_t cols, uint64_t *vals)
+{
+    if (!M || !vals) return fail(HHE_ERR_INVALID, "hhe_fc_packed_diagonals: null argument");
+    size_t r, cc;
+    int rc = fc_packed_dims(0, rows, cols, r, cc);
+    if (rc) return rc;
+    for (size_t i = 0; i < rows * cols; ++i)
+        if (M[i] >= t) return fail(HHE_ERR_INVALID, "hhe_fc_packed_diagonals: matrix entry not below the plain modulus");
+    // d_i[j] = M[j mod r][(j + i) mod c] of the zero-padded matrix
+    for (size_t i = 0; i < r; ++i)
+        for (size_t j = 0; j < cc; ++j) {
+            const size_t row = j % r, col = (j + i) % cc;
+            vals[i * cc + j] = row < rows && col < cols ? M[row * cols + col] : 0;
+        }
+    return HHE_OK;
+}
+extern "C" int hhe_fc_packed_galois_steps(size_t N, size_t rows, size_t cols, int *steps_out, size_t *count)
+{
+    if (!count || N == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed_galois_steps: null argument or no degree");
+    size_t r, cc;
+    int rc = fc_packed_dims(N, rows, cols, r, cc);
+    if (rc) return rc;
+    std::vector<int> steps;
+    fc_packed_steps(N, r, cc, steps);
+    const size_t cap = *count;
+    *count = steps.size();
+    if (!steps_out || cap < steps.size()) return fail(HHE_ERR_CAPACITY, "hhe_fc_packed_galois_steps: output too small");
+    std::copy(steps.begin(), steps.end(), steps_out);
+    return HHE_OK;
+}
+
+extern "C" int hhe_enc_matrix_create(hhe_ctx *c, const uint64_t *wdiag, size_t rows, size_t cols, hhe_enc_matrix **out)
+{
+    HHE_LOCK(c);
+    if (!c || !wdiag || !out) return fail(HHE_ERR_INVALID, "hhe_enc_matrix_create: null argument");
+    size_t r, cc;
+    int rc = fc_packed_dims(c->n, rows, cols, r, cc);
+    if (rc) return rc;
+    const size_t n = c->n, L = c->L;
+    hhe_enc_matrix *m = new hhe_enc_matrix();
+    m->ctx = c; m->rows = rows; m->cols = cols; m->r = r; m->c = cc;
+    m->wq = (u64 *)rt_malloc(r * 2 * L * n * 8);
+    m->wb = (u64 *)rt_malloc(r * 2 * (L + 1) * n * 8);
+    if (!m->wq || !m->wb) { enc_matrix_free(m); return dev_fail("hhe_enc_matrix_create: table alloc"); }
+    c->w = &c->lanes[0];
+    op_behz_operand(c, wdiag, m->wq, m->wb, r);
+    if (rt_sync(c->w->stream)) { enc_matrix_free(m); return dev_fail("hhe_enc_matrix_create"); }
+    m->bytes = r * 2 * (2 * L + 1) * n * 8;
+    c->enc_mats.push_back(m);
+    *out = m;
+    return HHE_OK;
+}
+extern "C" void hhe_enc_matrix_destroy(hhe_enc_matrix *m)
+{
+    if (!m) return;
+    hhe_ctx *c = m->ctx;
+    HHE_LOCK(c);
+    sync_ctx(c);
+    c->enc_mats.erase(std::remove(c->enc_mats.begin(), c->enc_mats.end(), m), c->enc_mats.end());
+    enc_matrix_free(m);
+}
+extern "C" size_t hhe_enc_matrix_bytes(const hhe_enc_matrix *m) { return m ? m->bytes : 0; }
+
+extern "C" int hhe_fc_packed_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi,
+                                uint64_t *out, size_t B)
+{
+    HHE_LOCK(c);
+    if (!c || !m || !vi || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed: null argument or empty batch");
+    if (m->ctx != c) return fail(HHE_ERR_INVALID, "encrypted matrix belongs to another context");
+    int rc = check_sets(c, rk, gk);
+    if (rc) return rc;
+    KeyScope keys(c, gk, rk);
+    // everything the layer needs, before anything is written: the relinearization key, and every step's own key -- the NAF of +- a
+    // power of two has one term, so Evaluator::rotate_rows throws without it
+    if (!c->rks->rk) return fail(HHE_ERR_NO_RELIN_KEY, "relinearization key not set");
+    std::vector<int> steps;
+    fc_packed_steps(c->n, m->r, m->c, steps);
+    for (int s : steps)
+        if (!c->gks->gk.count(galois_elt_from_step(c, s))) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+    Lane &main = c->lanes[0];
+    c->w = &main;
+    // a chunk runs the BEHZ passes of its r * per products at once: r * per stays within the HHE_CHUNK items a lane is reserved for elsewhere
+    const size_t per = std::min(B, std::max<size_t>(1, c->chunk / m->r));
+    const ChunkPlan plan(B, per, c->nstreams);
+    const size_t ctw = c->ct_words();
+    for (int s = plan.first_lane(); s <= plan.last_lane(); ++s) {
+        if ((rc = lane_reserve(c, c->lanes[s], m->r * per))) return rc;
+        if ((rc = c->lanes[s].ws_fcp.reserve(c, m->r * per * (size_t)5 * c->L * c->n, "hhe_fc_packed: rotations and products"))) return rc;
+    }
+    rc = run_chunks(c, plan, [&](Lane &, size_t, size_t b0, size_t bc) { return fc_packed_chunk(c, m, vi + b0 * ctw, out + b0 * ctw, bc); });
+    if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_fc_packed");
+    if (!rc) c->fc_packed_key_switches = steps.size() - (m->r > 1 ? 1 : 0) + (m->r - 1);
+    return rc;
+}
+
+extern "C" int hhe_add_many(hhe_ctx *c, const uint64_t *in, size_t K, uint64_t *out, size_t B, int size)
+{
+    HHE_LOCK(c);
+    if (!c || !in || !out || K == 0 || B == 0 || size < 2 || size > 3) return fail(HHE_ERR_INVALID, "hhe_add_many: bad arguments");
+    const size_t polys = B * size * c->L;
+    if (K > 0x7fffffff || polys > ((size_t)0x7fffffff >> (c->logn - 1))) return fail(HHE_ERR_INVALID, "hhe_add_many: batch too large");
+    c->w = &c->lanes[0];
+    k_elt(elt_args(c, in, nullptr, out, polys, 0, c->L, (int)K), ELT_ADDMANY, c->w->stream);
+    ++c->add_many_launches;
+    return HHE_OK;
 }

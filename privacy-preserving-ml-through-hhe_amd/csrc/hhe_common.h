@@ -199,7 +199,8 @@ enum EltOp { ELT_ADD = 0, ELT_SUB = 1, ELT_NEG = 2, ELT_MUL = 3, ELT_MAC = 4, EL
              ELT_DIFF = 8,    // ELT_DIFF writes no polynomial: out[0] = 1 when a word of a differs from its word of b (out[0] cleared by the caller)
              ELT_ENCZ = 9,    // key generation: c0 = -(a s + e) (+ f new_key) of an encryption of zero under the secret key (elt_encz_body; a kernel of its own)
              ELT_MODDOWN = 10,  // modulus switching: a [count][mod_cycle][N] -> out [count][b_cycle][N], b = the context's pair table (mod_down_body; kernels of its own)
-             ELT_KEYPROJ = 11 };  // a key-switch key of a level from one higher up its chain (key_proj_body; a kernel of its own)
+             ELT_KEYPROJ = 11,  // a key-switch key of a level from one higher up its chain (key_proj_body; a kernel of its own)
+             ELT_ADDMANY = 12 };  // out = the sum of b_cycle stacked operands (add_many_body; a kernel of its own)
 
 struct EltArgs {  // element-wise kernels over [count][N] polys, modulus = mod_base + p % mod_cycle
     const u64 *a, *b;
@@ -225,6 +226,12 @@ inline size_t mod_down_table_words(int L) { return mod_down_pair(L, 0) + 3; }  /
 // mod_cycle = l + 1, count = l * 2 * (l + 1) output polynomials.  Output polynomial p = (I * 2 + k) * (l + 1) + J is source polynomial
 // (I * 2 + k) * K_src + (J == l ? K_src - 1 : J).  One lane moves 16 bytes: count << (logn - 1) lanes do the work; the launch
 // entry's count << logn covers them, the rest return at the bound.
+
+// ELT_ADDMANY (Evaluator::add_many, seal/evaluator.h:150): a = b_cycle operands stacked [b_cycle][count][N], out [count][N], polynomial p
+// under modulus mod_base + p % mod_cycle:  out[p][i] = sum_k a[k][p][i] mod q.  One lane owns two adjacent coefficients (16-byte
+// accesses): count << (logn - 1) lanes do the work, the launch entry's count << logn covers them and the rest return at the bound.
+// The sum rides in a 128-bit accumulator and is reduced once: any 64-bit input words, any b_cycle an int holds.  A lane reads all
+// its operands before it writes, and no other lane touches its words, so out may be one of the operands.
 
 struct CopyItemsArgs {  // dst item (s * dst_stride + dst_off) <- src item (s * src_stride + src_off), `words` words each, s < count
     const u64 *src;
@@ -480,6 +487,8 @@ struct TensorArgs {  // d[b][0..2][j] from a[b][0..1][j], b[b][0..1][j]; NTT dom
     u64 *d;
     const ModDev *mods;
     int logn, B, limbs, mod_base;
+    int b_div;  // > 0: the second operand of item b is ciphertext b / b_div of `b` (the resident diagonals of a packed encrypted FC layer,
+                // each shared by the b_div items of a chunk; a kernel of its own); 0: item b of `b`
 };
 
 struct BehzFloorArgs {  // (dq [P][L][N], db [P][L+1][N]) coeff, already *t -> out [P][L][N]

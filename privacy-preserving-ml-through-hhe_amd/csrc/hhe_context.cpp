@@ -434,7 +434,7 @@ static void free_lane(Lane &ln)
 {
     rt_free(ln.ws_T); rt_free(ln.ws_S); rt_free(ln.ws_d); rt_free(ln.ws_ct3); rt_free(ln.ws_plain); rt_free(ln.ws_vals);
     for (auto &p : ln.ws_ct) { rt_free(p); p = nullptr; }
-    ln.ws_rot.release(); ln.ws_aff.release(); ln.ws_leaf.release();
+    ln.ws_rot.release(); ln.ws_aff.release(); ln.ws_fcp.release(); ln.ws_leaf.release();
     for (auto &sl : ln.fc_slots) { rt_free(sl.tp); rt_free(sl.ct); rt_free(sl.c0hat); }
     ln.fc_slots.clear(); ln.fc_slot_cap = 0;
     for (u64 *p : ln.csum_bufs) rt_free(p);
@@ -530,6 +530,7 @@ extern "C" void hhe_ctx_destroy(hhe_ctx *c)
     for (auto &ks : c->rk_slots) keyset_clear(&ks);
     for (hhe_keyset *ks : c->sets) { keyset_clear(ks); delete ks; }  // sets the caller did not destroy
     for (hhe_matrix *m : c->mats) matrix_free(m);  // handles the caller did not destroy
+    for (hhe_enc_matrix *m : c->enc_mats) enc_matrix_free(m);
     for (auto &kv : c->d_key_shoup) rt_free(kv.second);
     rt_free(c->d_feistel_mask);
     rt_free(c->d_zero_corr);
@@ -642,6 +643,8 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "fin_scale32") return fin_item_on(c) && c->fin_scale32 ? 1 : 0;  // ... with the plaintext scaled by 32-bit products and -c1 written early (HHE_FIN_SCALE32; t < 2^30 below every data prime)
     if (w == "mod_switch_launches") return c->mod_switch_launches;  // kernel launches of hhe_mod_switch: one per call of up to one chunk
     if (w == "key_proj_launches") return c->key_proj_launches;      // kernel launches of hhe_keyset_derive_level into this context's sets: one per key
+    if (w == "fc_packed_key_switches") return c->fc_packed_key_switches;  // Galois key switches per item of the last hhe_fc_packed_ks call
+    if (w == "add_many_launches") return c->add_many_launches;            // launches of the sum kernel (hhe_add_many: one per call)
     if (w == "noise_form") return (u64)c->noise_form;  // the last hhe_noise_budget launch: limb count of its register form, 0 = the LDS form
     if (w == "public_device") return (u64)(int64_t)c->public_device;  // HHE_PUBLIC_DEVICE: 0 host, 1 device; unset: (uint64_t)-1, the path is chosen per call
     if (w == "public_device_built") return c->last_public_built;     // pairs whose randomness the last call drew on the device

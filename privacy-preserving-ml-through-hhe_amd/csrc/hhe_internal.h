@@ -106,6 +106,15 @@ struct hhe_matrix {
     GrowBuf<const u64 *> self;   // device pointers, all = tab: the per-item pointer array the kernels take (refilled when it grows)
     size_t bytes = 0;            // device footprint of tab + bias
 };
+// The encrypted weight matrix of a packed encrypted FC layer, resident (hhe_enc_matrix_create): its r generalized diagonals as the second
+// operand of a BEHZ product, i.e. extended to q u B_sk and transformed, once.  Lives until hhe_enc_matrix_destroy (or its context goes).
+struct hhe_enc_matrix {
+    hhe_ctx *ctx = nullptr;
+    size_t rows = 0, cols = 0, r = 0, c = 0;
+    u64 *wq = nullptr;           // [r][2][L][N]: NTT form under the data primes
+    u64 *wb = nullptr;           // [r][2][L+1][N]: NTT form of the extension to B_sk
+    size_t bytes = 0;            // device footprint of wq + wb
+};
 // one stream + the per-batch workspaces of the ops: lane_reserve allocates the fixed set for `cap` ciphertexts under that one
 // capacity; the GrowBuf members belong to single schedules, grow on their own and go with the lane's workspaces (free_lane)
 struct Lane {
@@ -128,6 +137,7 @@ struct Lane {
     size_t ptr_cap = 0;
     GrowBuf<u64> ws_rot;     // [16][B][2][L][N]: PASTA's babystep rotations, and the FC's product + per-depth buffers of the unshared walk
     GrowBuf<u64> ws_aff;     // [n1 + n2][B][2][L][N] baby-step ciphertexts | inner sums of hhe_packed_affine (BSGS)
+    GrowBuf<u64> ws_fcp;     // [r][B][2][L][N] rotations | [r][B][3][L][N] products of a chunk of hhe_fc_packed_ks
     // FC shared digits: one slot per trie node that is still needed -- the digit transforms of its un-rotated c1 (tp [B][L][K][N]) and its
     // ciphertext (ct [B][2][L][N]); refs = 1 while the depth-first walk is below the node + 1 per queued leaf key switch that reads it
     struct FcSlot { u64 *tp = nullptr, *ct = nullptr, *c0hat = nullptr; int refs = 0; int tp_polys = 0; };  // c0hat [B][L][N]: NTT form of the node's c0 (nodes with a non-leaf child)  // tp_polys: K, or 1 when tp holds the special-prime transforms only
@@ -241,6 +251,9 @@ struct hhe_ctx {
     hhe_keyset rk_slots[HHE_RELIN_SLOTS];      // [0] unused (slot 0 is keys0.rk)
     std::vector<hhe_keyset *> sets;
     std::vector<hhe_matrix *> mats;            // plain-matrix handles created on this context
+    std::vector<hhe_enc_matrix *> enc_mats;    // encrypted-matrix handles created on this context
+    u64 fc_packed_key_switches = 0;            // Galois key switches per item of the last hhe_fc_packed_ks call (hhe_ctx_query("fc_packed_key_switches"))
+    u64 add_many_launches = 0;                 // launches of the sum kernel, by hhe_add_many and by the packed FC (hhe_ctx_query("add_many_launches"))
     hhe_keyset *gks = &keys0, *rks = &keys0;
     u64 next_serial = 0;                       // the last hhe_keyset::serial handed out
     std::map<const u64 *, u64 *> d_key_shoup;  // per key-switch key (by device address): Shoup quotients of its words (fused row kernel), built on first use
@@ -340,3 +353,4 @@ inline bool fin_fused_on(const hhe_ctx *c) { return c->fin_fused && c->logn <= 1
 inline bool fin_item_on(const hhe_ctx *c) { return c->fin_item != 0 && fin_fused_on(c) && c->d_fin_itw != nullptr; }
 inline bool fin_item_for(const hhe_ctx *c, size_t B) { return fin_item_on(c) && (c->fin_item > 0 || B >= c->fin_item_min); }
 void matrix_free(hhe_matrix *m);  // hhe_api.cpp: device memory of a handle and the handle
+void enc_matrix_free(hhe_enc_matrix *m);

@@ -752,13 +752,37 @@ HD void key_proj_body(const EltArgs &a, size_t gid)
     const size_t sp = ik * ks + (j == kd - 1 ? ks - 1 : j);
     st2(a.out + (p << a.logn) + w, ld2(a.a + (sp << a.logn) + w));
 }
+// ------------------------------------------------------------------ sum of many ciphertexts (ELT_ADDMANY)
+// gid over [count][N / 2], 16 bytes per lane: every input word is read once and every output word written once, adjacent lanes own
+// adjacent coefficients.  The b_cycle addends of a coefficient are below 2^64 each: the sum is kept in two words and reduced once
+// (b_cycle < 2^31 terms stay below 2^95, far inside barrett128's range).
+HD void add_many_body(const EltArgs &a, size_t gid)
+{
+    const size_t p = gid >> (a.logn - 1);
+    if (p >= (size_t)a.count) return;
+    const size_t w = (gid & (((size_t)1 << (a.logn - 1)) - 1)) << 1;
+    const ModDev m = mod_at(a.mods, a.mod_base + (int)(p % a.mod_cycle));
+    const size_t off = (p << a.logn) + w, term = (size_t)a.count << a.logn;
+    Acc128 s0 = {0, 0}, s1 = {0, 0};
+#pragma unroll 4
+    for (int k = 0; k < a.b_cycle; k++) {
+        const U2 v = ld2(a.a + (size_t)k * term + off);
+        acc_add(s0, v.a);
+        acc_add(s1, v.b);
+    }
+    U2 r;
+    r.a = barrett128(s0.lo, s0.hi, m);
+    r.b = barrett128(s1.lo, s1.hi, m);
+    st2(a.out + off, r);
+}
 // the element-wise launch as the tests-only emulator loops it; on the device the fused key-generation epilogue is a kernel of its own
-// and so are every form of the modulus switch and the key projection
+// and so are every form of the modulus switch, the key projection and the sum of many
 HD void elt_body(const EltArgs &a, int op, size_t gid)
 {
     if (op == ELT_ENCZ) elt_encz_body(a, gid);
     else if (op == ELT_MODDOWN) mod_down_any(a, gid);
     else if (op == ELT_KEYPROJ) key_proj_body(a, gid);
+    else if (op == ELT_ADDMANY) add_many_body(a, gid);
     else elt_base_body(a, op, gid);
 }
 
@@ -1633,8 +1657,9 @@ HD void behz_extend_body(const BehzExtendArgs &a, size_t gid)
     }
 }
 
-// ciphertext tensor product in the NTT domain: gid over [B][limbs][N]
-HD void tensor_body(const TensorArgs &a, size_t gid)
+// ciphertext tensor product in the NTT domain: gid over [B][limbs][N].  BCAST: item b multiplies ciphertext b / b_div of `b`
+// (TensorArgs::b_div), so the r B products of a packed encrypted FC chunk against its r resident diagonals are one launch
+template <bool BCAST> HD void tensor_body_t(const TensorArgs &a, size_t gid)
 {
     const size_t n = (size_t)1 << a.logn;
     const size_t i = gid & (n - 1);
@@ -1645,13 +1670,20 @@ HD void tensor_body(const TensorArgs &a, size_t gid)
     const ModDev m = mod_at(a.mods, a.mod_base + j);
     const size_t lim = a.limbs;
     const u64 a0 = a.a[((b * 2 + 0) * lim + j) * n + i], a1 = a.a[((b * 2 + 1) * lim + j) * n + i];
-    const u64 b0 = a.b[((b * 2 + 0) * lim + j) * n + i], b1 = a.b[((b * 2 + 1) * lim + j) * n + i];
+    const size_t bb = BCAST ? (size_t)((u32)b / (u32)a.b_div) : b;
+    const u64 b0 = a.b[((bb * 2 + 0) * lim + j) * n + i], b1 = a.b[((bb * 2 + 1) * lim + j) * n + i];
     a.d[((b * 3 + 0) * lim + j) * n + i] = mulmod(a0, b0, m);
     Acc128 s = {0, 0};
     acc_mac(s, a0, b1);
     acc_mac(s, a1, b0);
     a.d[((b * 3 + 1) * lim + j) * n + i] = barrett128(s.lo, s.hi, m);
     a.d[((b * 3 + 2) * lim + j) * n + i] = mulmod(a1, b1, m);
+}
+// the launch as the tests-only emulator loops it; on the device each form is a kernel of its own
+HD void tensor_body(const TensorArgs &a, size_t gid)
+{
+    if (a.b_div) tensor_body_t<true>(a, gid);
+    else tensor_body_t<false>(a, gid);
 }
 
 // fast_floor + fastbconv_sk (seal/util/rns.h:221-228): gid over [P][N]

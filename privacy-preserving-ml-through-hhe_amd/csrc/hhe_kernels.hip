@@ -594,6 +594,7 @@ __global__ void __launch_bounds__(ELT_THREADS) mod_down_lds_kernel(EltArgs a)
     mod_down_body<0>(a, GID, mod_down_cols + threadIdx.x, ELT_THREADS);
 }
 __global__ void __launch_bounds__(ELT_THREADS) key_proj_kernel(EltArgs a) { key_proj_body(a, GID); }
+__global__ void __launch_bounds__(ELT_THREADS) add_many_kernel(EltArgs a) { add_many_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) copy_items_kernel(CopyItemsArgs a) { copy_items_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) galois_kernel(GaloisArgs a) { galois_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) perm_kernel(PermArgs a) { perm_body(a, GID); }
@@ -635,7 +636,8 @@ __global__ void __launch_bounds__(ELT_THREADS) encode_scatter_kernel(EncodeArgs 
 __global__ void __launch_bounds__(ELT_THREADS) diag_kernel(DiagArgs a) { diag_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) bsgs_diag_kernel(BsgsDiagArgs a) { bsgs_diag_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) behz_extend_kernel(BehzExtendArgs a) { behz_extend_body(a, GID); }
-__global__ void __launch_bounds__(ELT_THREADS) tensor_kernel(TensorArgs a) { tensor_body(a, GID); }
+__global__ void __launch_bounds__(ELT_THREADS) tensor_kernel(TensorArgs a) { tensor_body_t<false>(a, GID); }
+__global__ void __launch_bounds__(ELT_THREADS) tensor_bcast_kernel(TensorArgs a) { tensor_body_t<true>(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) behz_floor_kernel(BehzFloorArgs a) { behz_floor_body(a, GID); }
 
 #define LAUNCH1D(kern, total, s, ...)                                                                   \
@@ -667,6 +669,7 @@ void k_elt(const EltArgs &a, int op, rt_stream s)
     if (op == ELT_ENCZ) LAUNCH1D(elt_encz_kernel, (size_t)a.count << a.logn, s, a);
     else if (op == ELT_MODDOWN) launch_mod_down(a, s);
     else if (op == ELT_KEYPROJ) LAUNCH1D(key_proj_kernel, (size_t)a.count << (a.logn - 1), s, a);
+    else if (op == ELT_ADDMANY) LAUNCH1D(add_many_kernel, (size_t)a.count << (a.logn - 1), s, a);
     else LAUNCH1D(elt_kernel, (size_t)a.count << a.logn, s, a, op);
 }
 void k_copy_items(const CopyItemsArgs &a, rt_stream s) { LAUNCH1D(copy_items_kernel, a.count * (a.words >> 1), s, a); }
@@ -734,7 +737,11 @@ void k_encode_scatter(const EncodeArgs &a, rt_stream s)
 void k_diag(const DiagArgs &a, rt_stream s) { LAUNCH1D(diag_kernel, (size_t)(PASTA_R + 1) * PASTA_T * 2 * PASTA_T, s, a); }
 void k_bsgs_diag(const BsgsDiagArgs &a, rt_stream s) { LAUNCH1D(bsgs_diag_kernel, (size_t)(PASTA_R + 1) * PASTA_T * 2 * PASTA_T, s, a); }
 void k_behz_extend(const BehzExtendArgs &a, rt_stream s) { LAUNCH1D(behz_extend_kernel, (size_t)a.P << a.logn, s, a); }
-void k_tensor(const TensorArgs &a, rt_stream s) { LAUNCH1D(tensor_kernel, ((size_t)a.B * a.limbs) << a.logn, s, a); }
+void k_tensor(const TensorArgs &a, rt_stream s)
+{
+    if (a.b_div) LAUNCH1D(tensor_bcast_kernel, ((size_t)a.B * a.limbs) << a.logn, s, a);
+    else LAUNCH1D(tensor_kernel, ((size_t)a.B * a.limbs) << a.logn, s, a);
+}
 void k_behz_floor(const BehzFloorArgs &a, rt_stream s) { LAUNCH1D(behz_floor_kernel, (size_t)a.P << a.logn, s, a); }
 
 // ---------------------------------------------------------------- plain PASTA-3 (client / analyst side)
