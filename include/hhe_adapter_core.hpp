@@ -454,6 +454,29 @@ public:
         download(d, 1, 2, dst);
     }
 
+    // ... with its rotation chain hoisted (hhe_fc_packed_hoisted_ks): rot_i = rotate_rows(x, i, gk); same slots, other words
+    template <class RK, class GK, class Sink> void fc_packed_hoisted(const uint64_t *vi, const EncMatrix &m, const RK &rk, const GK &gk, Sink dst)
+    {
+        if (!m) throw std::invalid_argument("fc_packed: no encrypted matrix");
+        std::lock_guard<std::mutex> lk(arena_.mutex());
+        const KeySet r = named(set(rk), "fc_packed: empty key object"), g = named(set(gk), "fc_packed: empty key object");
+        uint64_t *d = arena_.get(0, ct_words() * 8);
+        upload(d, vi);
+        check(hhe_fc_packed_hoisted_ks(h(), r.get(), g.get(), m.get(), d, d, 1));
+        download(d, 1, 2, dst);
+    }
+    // Hoisted rotations (hhe_rotate_rows_many_ks): item k of dst = Evaluator::rotate_rows(in, steps[k], gk), the digit transforms of `in`
+    // (and of every node of the steps' NAF trie) computed once.  An empty step list is refused by the device call.
+    template <class GK, class Sink> void rotate_rows_many(const uint64_t *in_words, const std::vector<int> &steps, const GK &gk, Sink dst)
+    {
+        const KeySet g = named(set(gk), "Galois key not present");
+        const size_t w = ct_words();
+        DevBuf in(w * 8), out((steps.empty() ? 1 : steps.size()) * w * 8);
+        upload(in.u64(), in_words);
+        check(hhe_rotate_rows_many_ks(h(), g.get(), in.u64(), steps.data(), steps.size(), out.u64(), 1));
+        download(out.u64(), steps.size(), 2, dst);
+    }
+
     // client end: pasta::PASTA::encrypt / decrypt (pasta_3_plain.cpp:9-46) of `count` words in place, key: 256 words
     void pasta_crypt(const uint64_t *key, uint64_t *v, size_t count, bool dec, uint64_t nonce = fixed_nonce)
     {

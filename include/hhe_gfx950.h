@@ -66,7 +66,7 @@ void hhe_ctx_destroy(hhe_ctx *c);
  *    there too: enc_key is taken as what the buffer holds in stream order.  Work the caller has on OTHER streams is not waited for.
  *    Host inputs (cw, ncw, block_index, records, keys, matrices, mask values) are read before the call returns.
  *  - The batched calls return after their work has finished (hhe_pasta3_transcipher[_ks], hhe_decompose[_ks], hhe_fc_row[_ks],
- *    hhe_packed_affine[_ks], hhe_fc_packed_ks, hhe_mod_switch, every upload, read-back, key generation and matrix creation): they fork onto the
+ *    hhe_packed_affine[_ks], hhe_fc_packed_ks, hhe_rotate_rows_many_ks, hhe_fc_packed_hoisted_ks, hhe_mod_switch, every upload, read-back, key generation and matrix creation): they fork onto the
  *    context's internal non-blocking streams (HHE_STREAMS), join the context's stream again and wait for it, so `out` may be read
  *    from any stream when they return.  The generic evaluator ops (hhe_ntt, hhe_encode, hhe_add, hhe_add_many, hhe_negate, hhe_add_plain,
  *    hhe_multiply_plain, hhe_multiply, hhe_relinearize, hhe_apply_galois, hhe_rotate_*, hhe_mask, hhe_flatten) only ENQUEUE on the
@@ -93,7 +93,7 @@ int hhe_ctx_profile(hhe_ctx *c, int enable);
 int hhe_ctx_profile_read(hhe_ctx *c, char *kernel_name, size_t name_cap, uint64_t *launches, double *total_ms, uint64_t *items);
 /* derived parameters, for cross-checking against SEAL's context: what in
  * {"root" i<K, "bsk" i<=L (B_0.., m_sk), "gamma", "galois_elt" i=step, "fc_fallbacks", "fc_csum_closes", "fc_packed_key_switches",
- * "add_many_launches"};
+ * "add_many_launches", "rot_hoist", "rot_many_fallbacks", "rot_many_key_switches", "rot_many_launches", "rot_many_group"};
  * which kernels the context dispatches to (read-only diagnostics): "row_kernel" (1 = the fused key-switch row kernels run,
  * 0 = the separate-kernel path), "pm_ok" i<K (coefficient prime i has the pseudo-Mersenne form the lazy kernels need),
  * "digit_reduce" (key-switch digits are reduced before their transforms: some q_I >= 4 q_J) */
@@ -315,6 +315,33 @@ size_t hhe_enc_matrix_bytes(const hhe_enc_matrix *m);
  * Synchronous. */
 int hhe_fc_packed_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *mat, const uint64_t *vi_dptr,
                      uint64_t *out_dptr, size_t B);
+/* ---- Hoisted rotations: many rotate_rows of the same ciphertexts.  ct [B][2][L][N]; out [n_steps][B][2][L][N], step-major: out[k][b] holds
+ *      the words of Evaluator::rotate_rows(ct[b], steps[k], gk), exactly what hhe_rotate_rows_ks writes for that step under that set -- one key
+ *      switch when gk holds the step's element, else the step's NAF terms over gk (terms equal to +-N/2 skipped).  Step 0 copies; repeated
+ *      steps give equal words.  gk NULL: the context's default set.
+ *      Refused before anything is written: a null pointer, B == 0, n_steps == 0, a step with |step| >= N/2, a key set of another context, out
+ *      overlapping ct (HHE_ERR_INVALID); a step rotate_rows could not serve from gk (HHE_ERR_NO_GALOIS_KEY).
+ *      Schedule: the steps' term sequences form a trie.  A node's ciphertext is computed once, and the children of a node share the digit
+ *      transforms of its c1: K L forward transforms per node with children instead of per key switch.  Where the row kernels run
+ *      ("row_kernel" == 1) up to "rot_many_group" children of a node are served by ONE launch of the key-switch row kernel and one mod-down.
+ *      The shared transforms are exact unless a residue of some c1 is zero; a chunk that meets one is recomputed step by step after the wait
+ *      (hhe_ctx_query("rot_many_fallbacks") counts those chunks).  HHE_ROT_HOIST (read at hhe_ctx_create, "rot_hoist"): 1 as described,
+ *      0 every step through the path of hhe_rotate_rows_ks, 2 as 1 with every chunk also recomputed (tests).
+ *      Synchronous and batched like hhe_fc_row_ks: chunked over the internal streams; a chunk keeps the sums of up to "rot_many_group"
+ *      children of its items at once, so it holds max(1, HHE_CHUNK / min(group, most children of a node)) items.  About the last call:
+ *      "rot_many_key_switches" (the trie's nodes = key switches per item), "rot_many_launches" (multi-child launches per chunk). ---- */
+int hhe_rotate_rows_many_ks(hhe_ctx *c, const hhe_keyset *gk, const uint64_t *ct_dptr, const int *steps_hptr, size_t n_steps,
+                            uint64_t *out_dptr, size_t B);
+/* hhe_fc_packed_ks with step 2 hoisted: rot_0 = x; rot_i = rotate_rows(x, i, gk), i = 1 .. r-1 -- every rotation comes from the x of step 1,
+ * served as hhe_rotate_rows_many_ks serves steps 1 .. r-1 (one node with r-1 children when gk holds a key for each; the NAF trie over the
+ * power-of-two keys otherwise).  Handle, diagonals, precondition, steps 1, 3, 4, 5 and the refusals are those of hhe_fc_packed_ks; -c and
+ * the tail r 2^k still need their own keys.  The words of `out` are the words of that composition (they differ from hhe_fc_packed_ks's:
+ * rot_i carries the noise of one key switch instead of i); slots [0, rows) decrypt to the same (M x) mod t.  out == vi is allowed.
+ * "fc_packed_key_switches" after the call: (2c != N) + the trie's nodes + log2(c / r).
+ * hhe_fc_packed_hoisted_galois_steps lists the keys of the one-pass schedule: -c (when 2c != N), 1 .. r-1, then r, 2r, .. below c. */
+int hhe_fc_packed_hoisted_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *mat, const uint64_t *vi_dptr,
+                             uint64_t *out_dptr, size_t B);
+int hhe_fc_packed_hoisted_galois_steps(size_t N, size_t rows, size_t cols, int *steps_out, size_t *count);
 /* Evaluator::add_many (seal/evaluator.h:150) for K stacked batches in_dptr [K][B][size][L][N], size 2 or 3: out [B][size][L][N] = their
  * sum, in ONE kernel launch whatever K is (hhe_ctx_query("add_many_launches") counts them); the sum of a coefficient is kept in two
  * words and reduced once.  out may be one of the K operands.  K == 0, B == 0, a null pointer or another size: HHE_ERR_INVALID.

@@ -124,13 +124,16 @@ struct EncMatrix {
         handle = core->enc_matrix(p, rows, cols);
     }
     // slots [0, rows) of the decryption of `out` are (M x) mod t; rk / gal_keys: the parties' ordinary, top-level key objects
-    void apply(const Ciphertext &vi, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out) const
+    // hoisted: the rotation chain of the layer as rotations of one ciphertext (fc_packed_hoisted)
+    void apply(const Ciphertext &vi, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out, bool hoisted = false) const
     {
         if (!core) throw std::invalid_argument("fc_packed: no encrypted matrix");
         const bool top = core.get() == context.get();
         hhe::KeySet r = context->keys().relin(detail::words(rk)), g = context->keys().galois(detail::words(gal_keys));
         if (!top) { r = core->derived(r); g = core->derived(g); }
-        core->fc_packed(detail::level_words(*core, context->data_limbs(), vi), handle, r, g, detail::into_level(*core, out));
+        const uint64_t *x = detail::level_words(*core, context->data_limbs(), vi);
+        if (hoisted) core->fc_packed_hoisted(x, handle, r, g, detail::into_level(*core, out));
+        else core->fc_packed(x, handle, r, g, detail::into_level(*core, out));
         if (top) out.limbs = 0;  // the data level, as every cipher object's results
     }
     std::shared_ptr<HheContext> context;      // the chain's core: its key-set cache holds the sets the calls name
@@ -201,6 +204,17 @@ public:
     {
         if (mat.core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
         mat.apply(vi, rk, gal_keys, out);
+    }
+    void fc_packed_hoisted(const Ciphertext &vi, const EncMatrix &mat, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out)
+    {
+        if (mat.core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
+        mat.apply(vi, rk, gal_keys, out, true);
+    }
+    // hoisted rotations at this level: out[k] = Evaluator::rotate_rows(ct, steps[k], gal_keys) with the key object the call names
+    void rotate_rows_many(const Ciphertext &ct, const std::vector<int> &steps, const GaloisKeys &gal_keys, std::vector<Ciphertext> &o)
+    {
+        o.resize(steps.size());
+        core->rotate_rows_many(in(ct), steps, core->derived(context->keys().galois(detail::words(gal_keys))), [&](size_t i) { return out(o[i])(0); });
     }
     // SEALZpCipher::print_noise / sealhelper::decrypting on the level's context, with the rows of the secret key that level has
     int print_noise(Ciphertext &ciph)
@@ -365,6 +379,14 @@ public:
     void packed_square(Ciphertext &vo, const Ciphertext &vi)  // evaluator.square + relinearize_inplace(he_rk)
     {
         context->square_relinearize(detail::words(*context, vi), rk_set, detail::into(*context, vo));
+    }
+
+    // Hoisted rotations (no reference counterpart: SEAL rotates one step per call): out[k] = Evaluator::rotate_rows(ct, steps[k], gal_keys)
+    // with the GaloisKeys object the call names, every rotation from the one set of digit transforms of ct
+    void rotate_rows_many(const Ciphertext &ct, const std::vector<int> &steps, const GaloisKeys &gal_keys, std::vector<Ciphertext> &out)
+    {
+        out.resize(steps.size());
+        context->rotate_rows_many(detail::words(*context, ct), steps, detail::words(gal_keys), detail::into(*context, out));
     }
 
     // SEALZpCipher::packed_matMul / packed_affine (SEAL_Cipher.cpp:522-543): vo = M * vi (+ b), M public, with this object's Galois keys
@@ -604,5 +626,19 @@ inline void fc_packed(const pasta::Ciphertext &vi, const EncMatrix &mat, const p
                       pasta::Ciphertext &out)
 {
     mat.apply(vi, rk, gal_keys, out);
+}
+// ... with the layer's rotation chain hoisted: every rot_i = rotate_rows(x, i, gal_keys).  With a key for each of 1 .. r-1 in gal_keys
+// (hhe_fc_packed_hoisted_galois_steps) the chain is one dependent step; the slots are the same, the words are not
+inline void fc_packed_hoisted(const pasta::Ciphertext &vi, const EncMatrix &mat, const pasta::RelinKeys &rk, const pasta::GaloisKeys &gal_keys,
+                              pasta::Ciphertext &out)
+{
+    mat.apply(vi, rk, gal_keys, out, true);
+}
+// out[k] = Evaluator::rotate_rows(ct, steps[k], gal_keys), hoisted (hhe_gfx950.h "Hoisted rotations")
+inline void rotate_rows_many(pasta::HheContext &ctx, const pasta::Ciphertext &ct, const std::vector<int> &steps, const pasta::GaloisKeys &gal_keys,
+                             std::vector<pasta::Ciphertext> &out)
+{
+    out.resize(steps.size());
+    ctx.rotate_rows_many(pasta::detail::words(ctx, ct), steps, pasta::detail::words(gal_keys), pasta::detail::into(ctx, out));
 }
 }  // namespace sealhelper

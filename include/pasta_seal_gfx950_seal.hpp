@@ -191,12 +191,14 @@ struct EncMatrix {
         handle = core->enc_matrix(p, rows, cols);
     }
     // slots [0, rows) of the decryption of `out` are (M x) mod t; rk / gal_keys: the parties' ordinary, top-level key objects
-    void apply(const seal::Ciphertext &vi, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out) const
+    // hoisted: the rotation chain of the layer as rotations of one ciphertext (fc_packed_hoisted)
+    void apply(const seal::Ciphertext &vi, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out, bool hoisted = false) const
     {
         if (!core) throw std::invalid_argument("fc_packed: no encrypted matrix");
         hhe::KeySet r = device->relin_set(rk), g = device->galois_set(gal_keys);
         if (core.get() != device.get()) { r = core->derived(r); g = core->derived(g); }
-        core->fc_packed(in(vi), handle, r, g, gfx950::DeviceContext::into_level(*context, out, id, 2));
+        if (hoisted) core->fc_packed_hoisted(in(vi), handle, r, g, gfx950::DeviceContext::into_level(*context, out, id, 2));
+        else core->fc_packed(in(vi), handle, r, g, gfx950::DeviceContext::into_level(*context, out, id, 2));
     }
     std::shared_ptr<seal::SEALContext> context;
     std::shared_ptr<gfx950::DeviceContext> device;  // the chain's core: its key-set cache holds the sets the calls name
@@ -290,6 +292,17 @@ public:
     {
         if (mat.core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
         mat.apply(vi, rk, gal_keys, out);
+    }
+    void fc_packed_hoisted(const seal::Ciphertext &vi, const EncMatrix &mat, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out)
+    {
+        if (mat.core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
+        mat.apply(vi, rk, gal_keys, out, true);
+    }
+    // hoisted rotations at this level: o[k] = Evaluator::rotate_rows(ct, steps[k], gal_keys) with the key object the call names
+    void rotate_rows_many(const seal::Ciphertext &ct, const std::vector<int> &steps, const seal::GaloisKeys &gal_keys, std::vector<seal::Ciphertext> &o)
+    {
+        o.resize(steps.size());
+        core->rotate_rows_many(in(ct), steps, core->derived(device->galois_set(gal_keys)), [&](std::size_t i) { return out(o[i])(0); });
     }
     // SEALZpCipher::print_noise / sealhelper::decrypting on the level's device context, with the rows of the secret key that level has
     int print_noise(seal::Ciphertext &ciph)
@@ -495,6 +508,14 @@ public:
         device->flatten(device->words(in), gfx950::DeviceContext::words(galois_keys), device->into(*context, out));
     }
 
+    // Hoisted rotations (no reference counterpart: SEAL rotates one step per call): out[k] = Evaluator::rotate_rows(ct, steps[k], gal_keys)
+    // with the GaloisKeys object the call names, every rotation from the one set of digit transforms of ct
+    void rotate_rows_many(const seal::Ciphertext &ct, const std::vector<int> &steps, const seal::GaloisKeys &gal_keys, std::vector<seal::Ciphertext> &out)
+    {
+        out.resize(steps.size());
+        device->rotate_rows_many(device->words(ct), steps, gfx950::DeviceContext::words(gal_keys), device->into(*context, out));
+    }
+
     // SEALZpCipher::packed_matMul / packed_affine (SEAL_Cipher.cpp:522-543): vo = M * vi (+ b), M public, rotations with he_gk
     void packed_matMul(seal::Ciphertext &vo, const matrix &M, const seal::Ciphertext &vi)
     {
@@ -692,6 +713,22 @@ typedef pasta::EncMatrix EncMatrix;
 inline void fc_packed(const seal::Ciphertext &vi, const EncMatrix &mat, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out)
 {
     mat.apply(vi, rk, gal_keys, out);
+}
+// ... with the layer's rotation chain hoisted: every rot_i = rotate_rows(x, i, gal_keys).  With a key for each of 1 .. r-1 in gal_keys
+// (hhe_fc_packed_hoisted_galois_steps) the chain is one dependent step; the slots are the same, the words are not
+inline void fc_packed_hoisted(const seal::Ciphertext &vi, const EncMatrix &mat, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys,
+                              seal::Ciphertext &out)
+{
+    mat.apply(vi, rk, gal_keys, out, true);
+}
+// out[k] = Evaluator::rotate_rows(ct, steps[k], gal_keys), hoisted (hhe_gfx950.h "Hoisted rotations"); the Evaluator argument is unused
+inline void rotate_rows_many(const seal::Ciphertext &ct, const std::vector<int> &steps, const seal::GaloisKeys &gal_keys,
+                             std::vector<seal::Ciphertext> &out, const seal::Evaluator &evaluator)
+{
+    (void)evaluator;
+    auto dev = DeviceContext::find(ct.parms_id());
+    out.resize(steps.size());
+    dev->rotate_rows_many(dev->words(ct), steps, DeviceContext::words(gal_keys), [&](std::size_t i) { return DeviceContext::into(out[i], ct)(0); });
 }
 
 }  // namespace sealhelper

@@ -49,10 +49,12 @@ _SYMBOLS = [
     "hhe_pasta3_transcipher_nonce_ks", "hhe_decompose_nonce_ks", "hhe_pasta3_block_randomness_dev", "hhe_pasta3_prepare_tables",
     "hhe_fc_packed_shape", "hhe_fc_packed_diagonals", "hhe_fc_packed_galois_steps", "hhe_enc_matrix_create", "hhe_enc_matrix_destroy",
     "hhe_enc_matrix_bytes", "hhe_fc_packed_ks", "hhe_add_many",
+    "hhe_rotate_rows_many_ks", "hhe_fc_packed_hoisted_ks", "hhe_fc_packed_hoisted_galois_steps",
 ]
 
 _FC_PACKED_SYMBOLS = {"hhe_fc_packed_shape", "hhe_fc_packed_diagonals", "hhe_fc_packed_galois_steps", "hhe_enc_matrix_create",
                       "hhe_enc_matrix_destroy", "hhe_enc_matrix_bytes", "hhe_fc_packed_ks", "hhe_add_many"}
+_ROT_MANY_SYMBOLS = {"hhe_rotate_rows_many_ks", "hhe_fc_packed_hoisted_ks", "hhe_fc_packed_hoisted_galois_steps"}
 _NONCE_SYMBOLS = {"hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystream_nonce", "hhe_pasta3_plain_crypt_nonce",
                   "hhe_pasta3_transcipher_nonce_ks", "hhe_decompose_nonce_ks", "hhe_pasta3_block_randomness_dev",
                   "hhe_pasta3_prepare_tables"}
@@ -63,7 +65,7 @@ _NONCE_SYMBOLS = {"hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystre
 _OPTIONAL = {"hhe_pasta3_clear_keystream_cache", "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin",
              "hhe_keyset_generate_galois", "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
              "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level",
-             "hhe_noise_budget", "hhe_ctx_create_level", "hhe_keyset_derive_level"} | _NONCE_SYMBOLS | _FC_PACKED_SYMBOLS
+             "hhe_noise_budget", "hhe_ctx_create_level", "hhe_keyset_derive_level"} | _NONCE_SYMBOLS | _FC_PACKED_SYMBOLS | _ROT_MANY_SYMBOLS
 
 
 def exported_symbols():
@@ -267,6 +269,12 @@ class EncMatrix:
         self.ctx._chk(self.ctx.lib.hhe_fc_packed_ks(self.ctx.h, _ks(rk), _ks(gk), self.h, _ptr(ct), _ptr(out), C.c_size_t(B)))
         return out
 
+    def apply_hoisted(self, ct, B, rk=None, gk=None, out=None):
+        """the layer with its rotation chain hoisted (hhe_fc_packed_hoisted_ks): every rot_i = rotate_rows(x, i, gk); same slots, other words"""
+        out = ct if out is None else out
+        self.ctx._chk(self.ctx._need("hhe_fc_packed_hoisted_ks")(self.ctx.h, _ks(rk), _ks(gk), self.h, _ptr(ct), _ptr(out), C.c_size_t(B)))
+        return out
+
     def destroy(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
             self.ctx.lib.hhe_enc_matrix_destroy(self.h)
@@ -395,6 +403,16 @@ class Context:
 
     def rotate_rows(self, ct, step, out, B, gk=None):
         self._chk(self.lib.hhe_rotate_rows_ks(self.h, _ks(gk), _ptr(ct), C.c_int(step), _ptr(out), C.c_size_t(B)))
+
+    def rotate_rows_many(self, ct, steps, out, B, gk=None):
+        """out [len(steps)][B][2][L][N], step-major: out[k][b] = rotate_rows(ct[b], steps[k], gk), the rotations hoisted (one set of
+        digit transforms per trie node).  Synchronous."""
+        arr = (C.c_int * max(len(steps), 1))(*[int(v) for v in steps])
+        self._chk(self._need("hhe_rotate_rows_many_ks")(self.h, _ks(gk), _ptr(ct), arr, C.c_size_t(len(steps)), _ptr(out), C.c_size_t(B)))
+
+    def fc_packed_hoisted(self, ct, mat, out, B, rk=None, gk=None):
+        """out[b] = the packed encrypted FC layer `mat` (an EncMatrix) on ct[b] with the rotation chain hoisted; out may be ct"""
+        return mat.apply_hoisted(ct, B, rk=rk, gk=gk, out=out)
 
     def rotate_columns(self, ct, out, B, gk=None):
         self._chk(self.lib.hhe_rotate_columns_ks(self.h, _ks(gk), _ptr(ct), _ptr(out), C.c_size_t(B)))
@@ -702,6 +720,17 @@ def fc_packed_galois_steps(n, rows, cols, lib=None):
     out = (C.c_int * 64)()
     cnt = C.c_size_t(64)
     rc = _lib_fn(lib, "hhe_fc_packed_galois_steps")(C.c_size_t(n), C.c_size_t(rows), C.c_size_t(cols), out, C.byref(cnt))
+    if rc:
+        raise HheError(rc, lib.hhe_last_error().decode())
+    return [int(v) for v in out[:cnt.value]]
+
+
+def fc_packed_hoisted_galois_steps(n, rows, cols, lib=None):
+    """the Galois keys of the one-pass schedule of the hoisted layer: -c (when 2c != n), 1 .. r-1, then r, 2r, .. below c"""
+    lib = lib or load_library()
+    out = (C.c_int * max(int(n), 64))()
+    cnt = C.c_size_t(len(out))
+    rc = _lib_fn(lib, "hhe_fc_packed_hoisted_galois_steps")(C.c_size_t(n), C.c_size_t(rows), C.c_size_t(cols), out, C.byref(cnt))
     if rc:
         raise HheError(rc, lib.hhe_last_error().decode())
     return [int(v) for v in out[:cnt.value]]

@@ -128,6 +128,24 @@ int ensure_key_shoup(hhe_ctx *c, const u64 *key, const u64 **out)
     return HHE_OK;
 }
 
+// [L][N] with q_sp mod q_j in every slot, once per context: the multiplier that turns the transform of a node's c0 into KsRowArgs::c0hat
+int ensure_qsp_poly(hhe_ctx *c)
+{
+    if (c->d_qsp_poly) return 0;
+    std::vector<u64> h((size_t)c->L * c->n);
+    for (int j = 0; j < c->L; j++) std::fill(h.begin() + (size_t)j * c->n, h.begin() + (size_t)(j + 1) * c->n, c->ksc.qsp_mod[j]);
+    if (!(c->d_qsp_poly = (u64 *)rt_malloc(h.size() * 8))) return -1;
+    return rt_h2d(c->d_qsp_poly, h.data(), h.size() * 8, c->w->stream) || rt_sync(c->w->stream) ? -1 : 0;
+}
+// q_sp * NTT(c0) of B items (item b's c0 at ct + b * ct_words) into c0hat [B][L][N]
+void op_c0hat(hhe_ctx *c, const u64 *ct, u64 *c0hat, size_t B)
+{
+    NttArgs t = ntt_args(c, ct, c0hat, B * c->L, 0, c->L);
+    t.src_item_polys = c->L; t.src_item_stride = c->ct_words();
+    t.store_op = STORE_MUL; t.mul = c->d_qsp_poly; t.mul_cycle = c->L;   // times q_sp: the sum it joins is divided by q_sp in the mod-down
+    k_ntt(t, false, c->w->stream);
+}
+
 // The two inverse launches that finish a key switch whose sums sit in a split ws_S: the special limbs (STORE_RSP), then the data limbs
 // with the mod-down in their store (`ksf`, from ks_ksf_args).  one_grid: the row passes of both share a grid (k_ntt2_inv); else each
 // is the second pass of a transform whose row pass a row kernel has already run
@@ -1852,10 +1870,7 @@ struct FcWalk {
         const u64 *c0hat = nullptr;
         if (has_nonleaf && c->fc_c0hat && c->fc_row_fused && use_row_kernel(c)) {
             // NTT form of the node's c0: its non-leaf children take galois(c0) through the NTT-domain map inside ks_perm_row_kernel
-            NttArgs t = ntt_args(c, parent, ln.fc_slots[slot].c0hat, B * c->L, 0, c->L);
-            t.src_item_polys = c->L; t.src_item_stride = c->ct_words();
-            t.store_op = STORE_MUL; t.mul = c->d_qsp_poly; t.mul_cycle = c->L;   // times q_sp: the sum it joins is divided by q_sp in the mod-down
-            k_ntt(t, false, ln.stream);
+            op_c0hat(c, parent, ln.fc_slots[slot].c0hat, B);
             c0hat = ln.fc_slots[slot].c0hat;
         }
         int rc;
@@ -1896,12 +1911,7 @@ int fc_dfs_shared(hhe_ctx *c, const std::vector<NafNode> &trie, int max_depth, c
     }
     for (auto &sl : ln.fc_slots) sl.refs = 0;
     const int group = c->L <= 4 ? std::min(HHE_LEAF_GROUP, c->fc_leaf_group) : 1;  // k_ks_mac_leaves is instantiated for L <= 4
-    if (c->fc_c0hat && !c->d_qsp_poly) {
-        std::vector<u64> h((size_t)c->L * c->n);
-        for (int j = 0; j < c->L; j++) std::fill(h.begin() + (size_t)j * c->n, h.begin() + (size_t)(j + 1) * c->n, c->ksc.qsp_mod[j]);
-        if (!(c->d_qsp_poly = (u64 *)rt_malloc(h.size() * 8))) return dev_fail("hhe_fc_row workspace");
-        if (rt_h2d(c->d_qsp_poly, h.data(), h.size() * 8, ln.stream) || rt_sync(ln.stream)) return dev_fail("hhe_fc_row workspace");
-    }
+    if (c->fc_c0hat && ensure_qsp_poly(c)) return dev_fail("hhe_fc_row workspace");
     // the c1-sum scheme serves leaf sums (acc) with a group kernel (L <= 4); its zero table stands in for the correction of the closing product
     bool csum = acc && c->fc_csum && c->L <= 4;
     if (csum && !c->d_zero_corr) {
@@ -2289,6 +2299,224 @@ extern "C" int hhe_packed_affine_ks(hhe_ctx *c, const hhe_keyset *gk, const hhe_
     return rc;
 }
 
+// ====================================================================== hoisted rotations
+// hhe_rotate_rows_many_ks and step 2 of hhe_fc_packed_hoisted_ks: many rotate_rows of ONE ciphertext.  The definition is in
+// include/hhe_gfx950.h; DESIGN.md section 4 "Hoisted rotations" has the schedule and the workspace.
+namespace {
+struct RotNode {
+    u32 elt = 0;             // Galois element of the key switch that makes the node from its parent
+    std::vector<int> kids;   // nodes
+    std::vector<int> outs;   // the steps (indices into the call's list) that end here
+    size_t kid_ofs = 0;      // first row of the node's children in the call's table (RotPlan::kids)
+};
+struct RotPlan {
+    std::vector<int> steps;
+    std::vector<RotNode> trie;   // node 0 is the input itself (step 0 ends there)
+    std::vector<KsKid> kids;     // host copy of the per-child table, node after node
+    const KsKid *d_kids = nullptr;
+    bool rowk = false;           // the row kernels run: children of a node in multi-child launches of ks_perm_row_kernel
+    size_t max_kids = 0;
+    u64 launches = 0;            // such launches per chunk
+    size_t group() const { return std::min<size_t>(std::max<size_t>(max_kids, 1), HHE_ROT_GROUP); }
+};
+// The term sequences of the steps as Evaluator::rotate_rows takes them from the named set (a step's own key, else its NAF terms with
+// +-N/2 skipped) form a trie, as in fc_build_trie; here every node that ends a step is an output.  Host only: nothing is enqueued.
+int rot_plan_build(const hhe_ctx *c, const int *steps, size_t n_steps, RotPlan &p)
+{
+    p.steps.assign(steps, steps + n_steps);
+    p.trie.assign(1, RotNode());
+    for (size_t k = 0; k < n_steps; ++k)
+        if ((size_t)std::abs((long long)steps[k]) >= c->n / 2) return fail(HHE_ERR_INVALID, "step count too large");
+    for (size_t k = 0; k < n_steps; ++k) {
+        const int step = steps[k];
+        std::vector<int> terms;
+        if (step != 0) {
+            if (c->gks->gk.count(galois_elt_from_step(c, step))) terms.push_back(step);
+            else
+                for (int t : nt_naf(step))
+                    if ((size_t)std::abs(t) != c->n / 2) terms.push_back(t);
+        }
+        int node = 0;
+        for (int t : terms) {
+            // children are told apart by their element: two terms that name one element (-1 and N/2 - 1) are the same key switch
+            const u32 elt = galois_elt_from_step(c, t);
+            if (!c->gks->gk.count(elt)) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+            int next = -1;
+            for (int kid : p.trie[node].kids)
+                if (p.trie[kid].elt == elt) { next = kid; break; }
+            if (next < 0) {
+                next = (int)p.trie.size();
+                p.trie.push_back(RotNode());
+                p.trie[next].elt = elt;
+                p.trie[node].kids.push_back(next);
+            }
+            node = next;
+        }
+        p.trie[node].outs.push_back((int)k);
+    }
+    p.rowk = use_row_kernel(c);
+    for (const RotNode &nd : p.trie) {
+        p.max_kids = std::max(p.max_kids, nd.kids.size());
+        if (p.rowk) p.launches += (nd.kids.size() + HHE_ROT_GROUP - 1) / HHE_ROT_GROUP;
+    }
+    return HHE_OK;
+}
+// Everything the chunks read that is made once per call, on the main lane before they fork: the correction table of every key of the
+// trie (and its Shoup quotients where the row kernels run), and the per-child table on the device
+int rot_plan_tables(hhe_ctx *c, RotPlan &p)
+{
+    int rc;
+    p.kids.clear();
+    for (RotNode &nd : p.trie) {
+        nd.kid_ofs = p.kids.size();
+        for (int kid : nd.kids) {
+            KsKid kd;
+            memset(&kd, 0, sizeof(kd));
+            kd.elt = p.trie[kid].elt;
+            if (!(kd.key = galois_key(c, kd.elt))) return HHE_ERR_NO_GALOIS_KEY;
+            if ((rc = fc_corr(c, kd.elt, kd.key, &kd.corr))) return rc;
+            if (p.rowk && (rc = ensure_key_shoup(c, kd.key, &kd.key_s))) return rc;
+            p.kids.push_back(kd);
+        }
+    }
+    if (!p.rowk || p.kids.empty()) return HHE_OK;
+    if (ensure_qsp_poly(c)) return dev_fail("hoisted rotations: workspace");
+    if ((rc = c->d_rot_kids.reserve(c, p.kids.size(), "hoisted rotations: child table"))) return rc;
+    // the earlier call's chunks have completed (the calls are synchronous); the host copy must outlive the upload
+    if (rt_h2d(c->d_rot_kids.p, p.kids.data(), p.kids.size() * sizeof(KsKid), c->w->stream) || rt_sync(c->w->stream)) return dev_fail("hoisted rotations: child table");
+    p.d_kids = c->d_rot_kids.p;
+    return HHE_OK;
+}
+// The children of `node` may be written straight into the output when they land there as one block: the chunk covers the whole stride
+// (item b of step k at out + (k * ostride + b) * ct_words with ostride == per) and child i's first step is the first child's first step + i
+bool rot_direct(const RotPlan &p, int node, bool whole)
+{
+    const RotNode &nd = p.trie[node];
+    if (!whole || nd.kids.empty()) return false;
+    for (size_t i = 0; i < nd.kids.size(); ++i) {
+        const RotNode &kd = p.trie[nd.kids[i]];
+        if (kd.outs.empty() || (i && kd.outs[0] != p.trie[nd.kids[0]].outs[0] + (int)i)) return false;
+    }
+    return true;
+}
+// words of the lane's node arena (Lane::ws_rotm) that the walk below `node` needs for chunks of `per` items
+size_t rot_arena_words(const hhe_ctx *c, const RotPlan &p, int node, bool whole, size_t per)
+{
+    const RotNode &nd = p.trie[node];
+    size_t below = 0;
+    for (int kid : nd.kids) below = std::max(below, rot_arena_words(c, p, kid, whole, per));
+    return (rot_direct(p, node, whole) ? 0 : nd.kids.size() * per * c->ct_words()) + below;
+}
+// All children of `node` from ONE set of digit transforms of its ciphertext `parent` ([per][2][L][N]), then the walk below them.  Item b of
+// step k goes to out + (k * ostride + b) * ct_words.  ws_T holds the node's transforms, ws_d its c0hat, ws_S the sums of one launch's
+// children x items: the lane is reserved for group() * per items.
+int rot_many_node(hhe_ctx *c, const RotPlan &p, int node, const u64 *parent, u64 *out, size_t ostride, size_t per, u64 *arena)
+{
+    const RotNode &nd = p.trie[node];
+    const size_t m = nd.kids.size(), ctw = c->ct_words(), blk = per * ctw;
+    if (!m) return HHE_OK;
+    Lane &w = *c->w;
+    u64 *dst = arena;
+    if (rot_direct(p, node, ostride == per)) dst = out + (size_t)p.trie[nd.kids[0]].outs[0] * ostride * ctw;
+    else arena += m * blk;
+    fc_parent_digits(c, parent, w.ws_T, per);
+    int rc;
+    if (p.rowk) {
+        op_c0hat(c, parent, w.ws_d, per);
+        for (size_t g0 = 0; g0 < m; g0 += HHE_ROT_GROUP) {
+            const size_t vb = std::min<size_t>(HHE_ROT_GROUP, m - g0) * per;   // virtual items of this launch: child-major
+            const KsSplit sp = ks_split(c, w.ws_S, vb);
+            KsRowArgs x = ks_row_args(c, nullptr, nullptr, vb, &sp);
+            x.T = w.ws_T; x.c0hat = w.ws_d; x.kids = p.d_kids + nd.kid_ofs + g0; x.kid_B = (int)per;
+            if (k_ks_perm_row(ntt_args(c, nullptr, nullptr, 0, 0, c->K), x, w.stream)) return dev_fail("hoisted rotations: key-switch row kernel");
+            // galois(c0) is inside S_0 already: one mod-down over all child x item pairs writes the finished ciphertexts
+            ks_finish_split(c, sp, ks_ksf_args(c, sp, vb, nullptr, ctw, 1, 0, dst + g0 * blk), vb, false);
+        }
+    } else {
+        for (size_t i = 0; i < m; ++i)
+            if ((rc = fc_child_shared(c, parent, w.ws_T, p.kids[nd.kid_ofs + i].elt, nullptr, dst + i * blk, per))) return rc;
+    }
+    for (size_t i = 0; i < m; ++i)
+        for (int k : p.trie[nd.kids[i]].outs) {
+            u64 *o = out + (size_t)k * ostride * ctw;
+            if (o != dst + i * blk) rt_d2d(o, dst + i * blk, blk * 8, w.stream);
+        }
+    for (size_t i = 0; i < m; ++i)
+        if ((rc = rot_many_node(c, p, nd.kids[i], dst + i * blk, out, ostride, per, arena))) return rc;
+    return HHE_OK;
+}
+// one chunk on the current lane: every step of `per` items of `in`; hoisted, or step by step through op_rotate_rows (HHE_ROT_HOIST=0 and
+// the exactness fallback)
+int rot_many_chunk(hhe_ctx *c, const RotPlan &p, bool hoisted, const u64 *in, u64 *out, size_t ostride, size_t per)
+{
+    const size_t ctw = c->ct_words();
+    int rc;
+    if (!hoisted) {
+        for (size_t k = 0; k < p.steps.size(); ++k)
+            if ((rc = op_rotate_rows(c, in, p.steps[k], out + k * ostride * ctw, per))) return rc;
+        return HHE_OK;
+    }
+    for (int k : p.trie[0].outs) rt_d2d(out + (size_t)k * ostride * ctw, in, per * ctw * 8, c->w->stream);
+    return rot_many_node(c, p, 0, in, out, ostride, per, c->w->ws_rotm.p);
+}
+// lane workspaces of a chunk of `per` items; hoisted chunks keep the sums of group() children at once
+int rot_many_reserve(hhe_ctx *c, Lane &ln, const RotPlan &p, bool hoisted, bool whole, size_t per, size_t lane_items = 0)
+{
+    int rc = lane_reserve(c, ln, std::max(lane_items, hoisted ? p.group() * per : per));
+    if (!rc && hoisted) rc = ln.ws_rotm.reserve(c, rot_arena_words(c, p, 0, whole, per), "hoisted rotations: node ciphertexts");
+    return rc;
+}
+}  // namespace
+
+extern "C" int hhe_rotate_rows_many_ks(hhe_ctx *c, const hhe_keyset *gk, const uint64_t *ct, const int *steps, size_t n_steps, uint64_t *out, size_t B)
+{
+    HHE_LOCK(c);
+    if (!c || !ct || !steps || !out || B == 0 || n_steps == 0) return fail(HHE_ERR_INVALID, "hhe_rotate_rows_many: null argument, empty batch or no step");
+    int rc = check_sets(c, gk);
+    if (rc) return rc;
+    KeyScope keys(c, gk, nullptr);
+    const size_t ctw = c->ct_words();
+    if (ct < out + n_steps * B * ctw && out < ct + B * ctw) return fail(HHE_ERR_INVALID, "hhe_rotate_rows_many: out overlaps ct");
+    RotPlan plan;
+    if ((rc = rot_plan_build(c, steps, n_steps, plan))) return rc;
+    Lane &main = c->lanes[0];
+    c->w = &main;
+    const bool hoisted = c->rot_hoist != 0 && plan.trie.size() > 1;
+    if (hoisted && (rc = rot_plan_tables(c, plan))) return rc;
+    // a chunk keeps the sums of group() children of its items at once: group() * per stays within the HHE_CHUNK items a lane is reserved for elsewhere
+    const size_t per = std::min(B, std::max<size_t>(1, c->chunk / plan.group()));
+    const ChunkPlan cp(B, per, c->nstreams);
+    const bool whole = cp.nch == 1;   // ostride == per
+    for (int s = cp.first_lane(); s <= cp.last_lane(); ++s)
+        if ((rc = rot_many_reserve(c, c->lanes[s], plan, hoisted, whole, per))) return rc;
+    u32 *flags = nullptr;
+    if (hoisted) {
+        if ((rc = c->d_flags.reserve(c, cp.nch, "hhe_rotate_rows_many"))) return rc;  // one flag per chunk
+        flags = c->d_flags.p;
+        rt_memset(flags, 0, cp.nch * 4, main.stream);
+    }
+    rc = run_chunks(c, cp, [&](Lane &ln, size_t idx, size_t b0, size_t bc) {
+        ln.zero_flag = hoisted ? flags + idx : nullptr;
+        // a shorter last chunk of several does not cover the stride: its children go through the arena, which is sized for that
+        return rot_many_chunk(c, plan, hoisted, ct + b0 * ctw, out + b0 * ctw, B, bc);
+    });
+    if (hoisted && !rc) {
+        std::vector<u32> h(cp.nch, 0);
+        if (rt_d2h(h.data(), flags, cp.nch * 4, main.stream) || rt_sync(main.stream)) rc = dev_fail("hhe_rotate_rows_many");
+        // a zero residue in some c1: that chunk is recomputed step by step on the main lane (everything has completed by then)
+        for (size_t idx = 0; idx < cp.nch && !rc; ++idx)
+            if (h[idx] || c->rot_hoist == 2) {
+                c->rot_many_fallbacks++;
+                main.zero_flag = nullptr;
+                if (!(rc = rot_many_reserve(c, main, plan, false, false, per)))
+                    rc = rot_many_chunk(c, plan, false, ct + idx * per * ctw, out + idx * per * ctw, B, cp.count(idx));
+            }
+    }
+    if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_rotate_rows_many");
+    if (!rc) { c->rot_many_key_switches = plan.trie.size() - 1; c->rot_many_launches = hoisted ? plan.launches : 0; }
+    return rc;
+}
+
 // ====================================================================== packed encrypted FC (hybrid diagonal method)
 // The definition is in include/hhe_gfx950.h; DESIGN.md section 4 "Packed encrypted FC" has the schedule and the workspace.
 namespace {
@@ -2317,7 +2545,9 @@ void fc_packed_steps(size_t n, size_t r, size_t cc, std::vector<int> &steps)
     for (size_t s = r; s < cc; s <<= 1) steps.push_back((int)s);
 }
 // one chunk on the current lane: in / out [per][2][L][N] (may be the same buffer); the lane is reserved for r * per items
-int fc_packed_chunk(hhe_ctx *c, const hhe_enc_matrix *m, const u64 *in, u64 *out, size_t per)
+// hoist: step 2 as rotations of the x of step 1 (hhe_fc_packed_hoisted_ks) -- one hoisted rotation of the chunk's items into rot + per * ctw,
+// or with `stepwise` each through op_rotate_rows (HHE_ROT_HOIST=0 and the exactness fallback); null: the chain of hhe_fc_packed_ks
+int fc_packed_chunk(hhe_ctx *c, const hhe_enc_matrix *m, const u64 *in, u64 *out, size_t per, const RotPlan *hoist = nullptr, bool stepwise = false)
 {
     const size_t ctw = c->ct_words(), r = m->r;
     Lane &w = *c->w;
@@ -2325,8 +2555,11 @@ int fc_packed_chunk(hhe_ctx *c, const hhe_enc_matrix *m, const u64 *in, u64 *out
     int rc;
     rt_d2d(rot, in, per * ctw * 8, w.stream);
     if (m->c * 2 != c->n && (rc = op_prep_rows(c, rot, -(int)m->c, w.ws_ct[2], per))) return rc;
-    for (size_t i = 1; i < r; ++i)
-        if ((rc = op_rotate_rows(c, rot + (i - 1) * per * ctw, 1, rot + i * per * ctw, per))) return rc;
+    if (hoist) {
+        if (r > 1 && (rc = rot_many_chunk(c, *hoist, !stepwise, rot, rot + per * ctw, per, per))) return rc;
+    } else
+        for (size_t i = 1; i < r; ++i)
+            if ((rc = op_rotate_rows(c, rot + (i - 1) * per * ctw, 1, rot + i * per * ctw, per))) return rc;
     op_multiply_enc(c, rot, m, prod, per);
     if (r > 1) {  // acc = the sum of the r products of every item, into the first one
         k_elt(elt_args(c, prod, nullptr, prod, per * 3 * c->L, 0, c->L, (int)r), ELT_ADDMANY, w.stream);
@@ -2449,6 +2682,96 @@ extern "C" int hhe_fc_packed_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keys
     rc = run_chunks(c, plan, [&](Lane &, size_t, size_t b0, size_t bc) { return fc_packed_chunk(c, m, vi + b0 * ctw, out + b0 * ctw, bc); });
     if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_fc_packed");
     if (!rc) c->fc_packed_key_switches = steps.size() - (m->r > 1 ? 1 : 0) + (m->r - 1);
+    return rc;
+}
+
+// the steps of the hoisted layer: -c unless the row is full, 1 .. r-1, the tail r 2^k < c
+static void fc_packed_hoisted_steps(size_t n, size_t r, size_t cc, std::vector<int> &steps)
+{
+    steps.clear();
+    if (cc * 2 != n) steps.push_back(-(int)cc);
+    for (size_t i = 1; i < r; ++i) steps.push_back((int)i);
+    for (size_t s = r; s < cc; s <<= 1) steps.push_back((int)s);
+}
+extern "C" int hhe_fc_packed_hoisted_galois_steps(size_t N, size_t rows, size_t cols, int *steps_out, size_t *count)
+{
+    if (!count || N == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed_hoisted_galois_steps: null argument or no degree");
+    size_t r, cc;
+    int rc = fc_packed_dims(N, rows, cols, r, cc);
+    if (rc) return rc;
+    std::vector<int> steps;
+    fc_packed_hoisted_steps(N, r, cc, steps);
+    const size_t cap = *count;
+    *count = steps.size();
+    if (!steps_out || cap < steps.size()) return fail(HHE_ERR_CAPACITY, "hhe_fc_packed_hoisted_galois_steps: output too small");
+    std::copy(steps.begin(), steps.end(), steps_out);
+    return HHE_OK;
+}
+extern "C" int hhe_fc_packed_hoisted_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi,
+                                        uint64_t *out, size_t B)
+{
+    HHE_LOCK(c);
+    if (!c || !m || !vi || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed_hoisted: null argument or empty batch");
+    if (m->ctx != c) return fail(HHE_ERR_INVALID, "encrypted matrix belongs to another context");
+    int rc = check_sets(c, rk, gk);
+    if (rc) return rc;
+    KeyScope keys(c, gk, rk);
+    if (!c->rks->rk) return fail(HHE_ERR_NO_RELIN_KEY, "relinearization key not set");
+    // -c and the tail need their own keys (their NAF has one term); 1 .. r-1 are served as hhe_rotate_rows_many_ks serves them
+    std::vector<int> own, chain;
+    fc_packed_steps(c->n, m->r, m->c, own);
+    for (int s : own)
+        if (s != 1 && !c->gks->gk.count(galois_elt_from_step(c, s))) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+    for (size_t i = 1; i < m->r; ++i) chain.push_back((int)i);
+    RotPlan plan;
+    if (m->r > 1 && (rc = rot_plan_build(c, chain.data(), chain.size(), plan))) return rc;
+    Lane &main = c->lanes[0];
+    c->w = &main;
+    const bool hoisted = c->rot_hoist != 0 && m->r > 1;
+    if (hoisted && (rc = rot_plan_tables(c, plan))) return rc;
+    const size_t per = std::min(B, std::max<size_t>(1, c->chunk / m->r));
+    const ChunkPlan cp(B, per, c->nstreams);
+    const size_t ctw = c->ct_words();
+    auto reserve = [&](Lane &ln, bool h) {
+        int r = rot_many_reserve(c, ln, plan, h, true, per, m->r * per);
+        if (!r) r = ln.ws_fcp.reserve(c, m->r * per * (size_t)5 * c->L * c->n, "hhe_fc_packed: rotations and products");
+        return r;
+    };
+    for (int s = cp.first_lane(); s <= cp.last_lane(); ++s)
+        if ((rc = reserve(c->lanes[s], hoisted))) return rc;
+    // in place, a recomputed chunk would read its own result: the results then wait in a buffer of the context until the flags are known
+    u64 *res = out;
+    if (hoisted && vi == out) {
+        if ((rc = c->d_blocks.reserve(c, B * ctw, "hhe_fc_packed_hoisted: results in place"))) return rc;
+        res = c->d_blocks.p;
+    }
+    u32 *flags = nullptr;
+    if (hoisted) {
+        if ((rc = c->d_flags.reserve(c, cp.nch, "hhe_fc_packed_hoisted"))) return rc;
+        flags = c->d_flags.p;
+        rt_memset(flags, 0, cp.nch * 4, main.stream);
+    }
+    rc = run_chunks(c, cp, [&](Lane &ln, size_t idx, size_t b0, size_t bc) {
+        ln.zero_flag = hoisted ? flags + idx : nullptr;
+        return fc_packed_chunk(c, m, vi + b0 * ctw, res + b0 * ctw, bc, &plan, !hoisted);
+    });
+    if (hoisted && !rc) {
+        std::vector<u32> h(cp.nch, 0);
+        if (rt_d2h(h.data(), flags, cp.nch * 4, main.stream) || rt_sync(main.stream)) rc = dev_fail("hhe_fc_packed_hoisted");
+        for (size_t idx = 0; idx < cp.nch && !rc; ++idx)
+            if (h[idx] || c->rot_hoist == 2) {
+                c->rot_many_fallbacks++;
+                main.zero_flag = nullptr;
+                if (!(rc = reserve(main, false))) rc = fc_packed_chunk(c, m, vi + idx * per * ctw, res + idx * per * ctw, cp.count(idx), &plan, true);
+            }
+        if (!rc && res != out) rt_d2d(out, res, B * ctw * 8, main.stream);
+    }
+    if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_fc_packed_hoisted");
+    if (!rc) {
+        c->rot_many_key_switches = m->r > 1 ? plan.trie.size() - 1 : 0;
+        c->rot_many_launches = hoisted ? plan.launches : 0;
+        c->fc_packed_key_switches = own.size() - (m->r > 1 ? 1 : 0) + c->rot_many_key_switches;
+    }
     return rc;
 }
 

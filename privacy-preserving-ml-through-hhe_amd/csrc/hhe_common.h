@@ -270,6 +270,12 @@ struct KsMacArgs {  // S[b][k][J][n] = sum_I T[b][I][J][n] * key[I][k][J][n]
     // special limb to S_sp [B][2][N] instead of S [B][2][K][N]
     u64 *S_sp;
 };
+// one child of a node in a multi-child launch of the key-switch row kernel (ks_perm_row_many_kernel; KsRowArgs::kids)
+struct KsKid {
+    const u64 *key, *key_s, *corr;   // [L][2][K][N] key and Shoup quotients, [2][K][N] correction table (KsCorrArgs)
+    u32 elt, pad;                    // Galois element of the child's rotation
+};
+constexpr int HHE_ROT_GROUP = 16;    // children one launch serves at most (the virtual batch and the lane's sums stay within HHE_CHUNK items)
 // Fused key-switch row kernel (ks_row_kernel): for one (item b, key limb J, row tile) it runs the forward ROW pass of the
 // L digit transforms T[b][I][J] (their strided pass has already run), multiplies each finished tile with key[I][0..1][J]
 // (Shoup products, 64-bit lazy sums kept in registers), and runs the inverse ROW pass on the sums that are
@@ -295,6 +301,12 @@ struct KsRowArgs {
     u32 perm_elt;
     const u64 *c0hat;    // optional [B][L][N]: q_sp * NTT(the node's c0).  Read through the same map it joins S_0[j], so the mod-down
                          // returns galois(c0) + the key-switched part and the KSF epilogue needs no coefficient-domain gather of c0
+    // Hoisted rotations (several children of one node in ONE launch, ks_perm_row_many_kernel): B counts VIRTUAL items child * kid_B + b.  Child
+    // `ch` takes its key, quotients, correction table and element from kids[ch] (a device table the host wrote; read with wave-uniform
+    // loads, never written by a kernel); T and c0hat belong to the node and are indexed by b alone; U0 / U1 / Usp by the virtual item.
+    // null / 0 (every single-child caller): key, key_s, corr and perm_elt above serve all B items
+    const KsKid *kids;
+    int kid_B;
 };
 
 // Correction of the shared-digit key switch (DESIGN.md "FC rotation trie"): the digit d_I of galois_g(c1) differs from

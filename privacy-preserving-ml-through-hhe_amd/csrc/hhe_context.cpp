@@ -387,6 +387,7 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
     if (const char *e = getenv("HHE_FC_LEAFSUM")) c->fc_leaf_sums = atoi(e);
     if (const char *e = getenv("HHE_FC_LEAFGROUP")) c->fc_leaf_group = std::max(1, std::min(HHE_LEAF_GROUP, atoi(e)));
     if (const char *e = getenv("HHE_FC_SHARED")) c->fc_shared = atoi(e);
+    if (const char *e = getenv("HHE_ROT_HOIST")) c->rot_hoist = std::max(0, std::min(2, atoi(e)));
     if (const char *e = getenv("HHE_FC_CHUNK")) c->fc_chunk = (size_t)std::max(0, atoi(e));
     if (const char *e = getenv("HHE_STREAMS")) c->nstreams = std::max(0, std::min(HHE_MAX_STREAMS, atoi(e)));
     if (const char *e = getenv("HHE_CHUNK")) c->chunk = (size_t)std::max(1, atoi(e));
@@ -434,7 +435,7 @@ static void free_lane(Lane &ln)
 {
     rt_free(ln.ws_T); rt_free(ln.ws_S); rt_free(ln.ws_d); rt_free(ln.ws_ct3); rt_free(ln.ws_plain); rt_free(ln.ws_vals);
     for (auto &p : ln.ws_ct) { rt_free(p); p = nullptr; }
-    ln.ws_rot.release(); ln.ws_aff.release(); ln.ws_fcp.release(); ln.ws_leaf.release();
+    ln.ws_rot.release(); ln.ws_aff.release(); ln.ws_fcp.release(); ln.ws_rotm.release(); ln.ws_leaf.release();
     for (auto &sl : ln.fc_slots) { rt_free(sl.tp); rt_free(sl.ct); rt_free(sl.c0hat); }
     ln.fc_slots.clear(); ln.fc_slot_cap = 0;
     for (u64 *p : ln.csum_bufs) rt_free(p);
@@ -535,7 +536,7 @@ extern "C" void hhe_ctx_destroy(hhe_ctx *c)
     rt_free(c->d_feistel_mask);
     rt_free(c->d_zero_corr);
     rt_free(c->d_qsp_poly);
-    c->d_blocks.release(); c->d_flags.release();
+    c->d_blocks.release(); c->d_flags.release(); c->d_rot_kids.release();
     c->l0_tab.release(); c->l0_ptrs.release();
     c->ks_tab.release(); c->ks_flags.release(); c->fin_dev.release(); c->fin_host.release();
     rt_free(c->d_tables); rt_free(c->d_mods); rt_free(c->d_behz); rt_free(c->d_slot_map); rt_free(c->d_slot_inv); rt_free(c->d_fin); rt_free(c->d_fin_itw);
@@ -644,6 +645,11 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "mod_switch_launches") return c->mod_switch_launches;  // kernel launches of hhe_mod_switch: one per call of up to one chunk
     if (w == "key_proj_launches") return c->key_proj_launches;      // kernel launches of hhe_keyset_derive_level into this context's sets: one per key
     if (w == "fc_packed_key_switches") return c->fc_packed_key_switches;  // Galois key switches per item of the last hhe_fc_packed_ks call
+    if (w == "rot_hoist") return c->rot_hoist;
+    if (w == "rot_many_fallbacks") return c->rot_many_fallbacks;
+    if (w == "rot_many_key_switches") return c->rot_many_key_switches;  // of the last hhe_rotate_rows_many_ks / hhe_fc_packed_hoisted_ks call: nodes of its trie
+    if (w == "rot_many_launches") return c->rot_many_launches;          // ... and its multi-child launches of ks_perm_row_kernel per chunk
+    if (w == "rot_many_group") return HHE_ROT_GROUP;                    // children one such launch serves at most
     if (w == "add_many_launches") return c->add_many_launches;            // launches of the sum kernel (hhe_add_many: one per call)
     if (w == "noise_form") return (u64)c->noise_form;  // the last hhe_noise_budget launch: limb count of its register form, 0 = the LDS form
     if (w == "public_device") return (u64)(int64_t)c->public_device;  // HHE_PUBLIC_DEVICE: 0 host, 1 device; unset: (uint64_t)-1, the path is chosen per call

@@ -138,6 +138,7 @@ struct Lane {
     GrowBuf<u64> ws_rot;     // [16][B][2][L][N]: PASTA's babystep rotations, and the FC's product + per-depth buffers of the unshared walk
     GrowBuf<u64> ws_aff;     // [n1 + n2][B][2][L][N] baby-step ciphertexts | inner sums of hhe_packed_affine (BSGS)
     GrowBuf<u64> ws_fcp;     // [r][B][2][L][N] rotations | [r][B][3][L][N] products of a chunk of hhe_fc_packed_ks
+    GrowBuf<u64> ws_rotm;    // hoisted rotations: ciphertexts of the trie nodes a chunk does not write straight into its output, [nodes][B][2][L][N]
     // FC shared digits: one slot per trie node that is still needed -- the digit transforms of its un-rotated c1 (tp [B][L][K][N]) and its
     // ciphertext (ct [B][2][L][N]); refs = 1 while the depth-first walk is below the node + 1 per queued leaf key switch that reads it
     struct FcSlot { u64 *tp = nullptr, *ct = nullptr, *c0hat = nullptr; int refs = 0; int tp_polys = 0; };  // c0hat [B][L][N]: NTT form of the node's c0 (nodes with a non-leaf child)  // tp_polys: K, or 1 when tp holds the special-prime transforms only
@@ -254,6 +255,11 @@ struct hhe_ctx {
     std::vector<hhe_enc_matrix *> enc_mats;    // encrypted-matrix handles created on this context
     u64 fc_packed_key_switches = 0;            // Galois key switches per item of the last hhe_fc_packed_ks call (hhe_ctx_query("fc_packed_key_switches"))
     u64 add_many_launches = 0;                 // launches of the sum kernel, by hhe_add_many and by the packed FC (hhe_ctx_query("add_many_launches"))
+    int rot_hoist = 1;                         // hhe_rotate_rows_many_ks and the hoisted packed FC: 1 = children of a trie node share the digit transforms of its c1
+                                               // (HHE_ROT_HOIST; 0: every step through op_rotate_rows, 2: every chunk also recomputed that way -- tests)
+    u64 rot_many_fallbacks = 0;                // chunks recomputed step by step because a digit load met a zero residue (hhe_ctx_query("rot_many_fallbacks"))
+    u64 rot_many_key_switches = 0, rot_many_launches = 0;  // of the last call: the trie's nodes; multi-child launches of ks_perm_row_kernel per chunk
+    GrowBuf<KsKid> d_rot_kids;                 // the per-child tables of the running call's trie, node after node (KsRowArgs::kids)
     hhe_keyset *gks = &keys0, *rks = &keys0;
     u64 next_serial = 0;                       // the last hhe_keyset::serial handed out
     std::map<const u64 *, u64 *> d_key_shoup;  // per key-switch key (by device address): Shoup quotients of its words (fused row kernel), built on first use

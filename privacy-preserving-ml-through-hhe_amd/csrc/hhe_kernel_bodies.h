@@ -1231,26 +1231,36 @@ HD void ks_row_mac_phase(const KsRowArgs &x, const NttArgs &fa, int bx, int b, i
 // The same products for a child of an FC trie node (shared digits): the digit transforms T of the node's UN-rotated c1 are complete
 // (both passes) and read through the NTT-domain Galois map -- no tile, no rounds; the map sends aligned pairs to aligned pairs (possibly
 // swapped), so a lane's pair is one 16-byte load.  The correction table of the key (KsCorrArgs) joins the sums after the last digit.
-template <int CM, int CC>
-HD void ks_row_mac_gather(const KsRowArgs &x, const NttArgs &fa, int bx, int b, int J, int I, int tid, u64 *acc0, u64 *acc1)
+// MANY: the multi-child launch of the hoisted rotations (KsRowArgs::kids); false compiles to the single-child body as it was
+template <int CM, int CC, bool MANY>
+HD void ks_row_mac_gather_t(const KsRowArgs &x, const NttArgs &fa, int bx, int b, int J, int I, int tid, u64 *acc0, u64 *acc1)
 {
     const NttGeom g = ntt_geom<CM, CC>(fa, bx, J);
     const ModDev m = mod_at_u(fa.mods, J);
     const u64 nq = m.nq;
     const size_t kofs = (((size_t)I * 2) * x.K + J) * g.n, kstep = (size_t)x.K * g.n;
+    // multi-child launch (hoisted rotations): b is the virtual item child * kid_B + item; the child's row of the table is wave-uniform
+    const u64 *key = x.key, *key_s = x.key_s, *corr = x.corr;
+    u32 perm_elt = x.perm_elt;
+    if (MANY) {
+        const int ch = b / x.kid_B;
+        b -= ch * x.kid_B;
+        const KsKid kd = x.kids[ch];
+        key = kd.key; key_s = kd.key_s; corr = kd.corr; perm_elt = kd.elt;
+    }
     const u64 *T = x.T + (((size_t)b * x.L + I) * x.K + J) * g.n;
     const bool fold = (I % 3) == 2 && I != x.L - 1;
     U2 t[KSROW_NP], k0[KSROW_NP], k0s[KSROW_NP], k1[KSROW_NP], k1s[KSROW_NP];
 #pragma unroll
     for (int k = 0; k < KSROW_NP; k++) {   // every gathered pair of the digit is requested before the first product
-        const u32 p0 = ntt_perm_index((u32)ks_row_idx<CM, CC>(fa, g, tid, k).gi, fa.logn, x.perm_elt);
+        const u32 p0 = ntt_perm_index((u32)ks_row_idx<CM, CC>(fa, g, tid, k).gi, fa.logn, perm_elt);
         t[k] = ld2(T + (p0 & ~1u));
         if (p0 & 1) t[k] = U2{t[k].b, t[k].a};
     }
     auto request = [&](int k) {
         const int gi = ks_row_idx<CM, CC>(fa, g, tid, k).gi;
-        k0[k] = ld2(x.key + kofs + gi); k0s[k] = ld2(x.key_s + kofs + gi);
-        k1[k] = ld2(x.key + kofs + kstep + gi); k1s[k] = ld2(x.key_s + kofs + kstep + gi);
+        k0[k] = ld2(key + kofs + gi); k0s[k] = ld2(key_s + kofs + gi);
+        k1[k] = ld2(key + kofs + kstep + gi); k1s[k] = ld2(key_s + kofs + kstep + gi);
     };
     request(0);
 #pragma unroll
@@ -1269,7 +1279,7 @@ HD void ks_row_mac_gather(const KsRowArgs &x, const NttArgs &fa, int bx, int b, 
         }
     }
     if (I == x.L - 1) {   // + corr[k][J] (canonical words): the sums stay below 2q + 3 * 4q + q
-        const u64 *e0 = x.corr + ((size_t)0 * x.K + J) * g.n, *e1 = x.corr + ((size_t)1 * x.K + J) * g.n;
+        const u64 *e0 = corr + ((size_t)0 * x.K + J) * g.n, *e1 = corr + ((size_t)1 * x.K + J) * g.n;
 #pragma unroll
         for (int k = 0; k < KSROW_NP; k++) {
             const int gi = ks_row_idx<CM, CC>(fa, g, tid, k).gi;
@@ -1282,7 +1292,7 @@ HD void ks_row_mac_gather(const KsRowArgs &x, const NttArgs &fa, int bx, int b, 
             U2 v[KSROW_NP];
 #pragma unroll
             for (int k = 0; k < KSROW_NP; k++) {
-                const u32 p0 = ntt_perm_index((u32)ks_row_idx<CM, CC>(fa, g, tid, k).gi, fa.logn, x.perm_elt);
+                const u32 p0 = ntt_perm_index((u32)ks_row_idx<CM, CC>(fa, g, tid, k).gi, fa.logn, perm_elt);
                 v[k] = ld2(ch + (p0 & ~1u));
                 if (p0 & 1) v[k] = U2{v[k].b, v[k].a};
             }
@@ -1293,6 +1303,13 @@ HD void ks_row_mac_gather(const KsRowArgs &x, const NttArgs &fa, int bx, int b, 
             }
         }
     }
+}
+// the form the launchers' loops call (the tests-only emulator among them): the table decides
+template <int CM, int CC>
+HD void ks_row_mac_gather(const KsRowArgs &x, const NttArgs &fa, int bx, int b, int J, int I, int tid, u64 *acc0, u64 *acc1)
+{
+    if (x.kids) ks_row_mac_gather_t<CM, CC, true>(x, fa, bx, b, J, I, tid, acc0, acc1);
+    else ks_row_mac_gather_t<CM, CC, false>(x, fa, bx, b, J, I, tid, acc0, acc1);
 }
 // sums -> LDS in [0,2q) (input range of the inverse rounds); optionally also canonical to global (S_0[j])
 template <int CM, int CC>

@@ -497,11 +497,11 @@ __global__ void __launch_bounds__(KSROW_THREADS, KSROW_WAVES) ks_row_kernel(NttA
 // (ks_row_mac_gather) + the inverse row pass of all 2K sums, one (item, key limb, row tile) per single-wave workgroup -- the sums never
 // make a round trip (before: ks_mac_kernel wrote S, a row-pass launch read it back).  Same block order and outputs as the generic
 // variant of ks_row_kernel (U0 / U1 / Usp).
-template <int LOGM>
 #ifndef PERMROW_WAVES
 #define PERMROW_WAVES 3   // 154 VGPRs, no spills; at 4 waves per SIMD (128 VGPRs) 14 registers spill: 34.5 vs 32.5 ms per MNIST sample
 #endif
-__global__ void __launch_bounds__(KSROW_THREADS, PERMROW_WAVES) ks_perm_row_kernel(NttArgs a, KsRowArgs x)
+template <int LOGM, bool MANY>
+__device__ __forceinline__ void ks_perm_row_wg(const NttArgs &a, const KsRowArgs &x)
 {
     constexpr bool TWL = LOGM == 8;
     __shared__ u64 lds[KSROW_LDS + (TWL ? KSROW_TWL : 0)];
@@ -516,7 +516,7 @@ __global__ void __launch_bounds__(KSROW_THREADS, PERMROW_WAVES) ks_perm_row_kern
 #pragma unroll
     for (int k = 0; k < 2 * KSROW_NP; k++) { acc0[k] = 0; acc1[k] = 0; }
     if (TWL) ks_row_twiddle_fill<LOGM, CC>(a, bx, J, true, tid, twl);
-    for (int I = 0; I < x.L; I++) ks_row_mac_gather<LOGM, CC>(x, a, bx, b, J, I, tid, acc0, acc1);
+    for (int I = 0; I < x.L; I++) ks_row_mac_gather_t<LOGM, CC, MANY>(x, a, bx, b, J, I, tid, acc0, acc1);
     u64 *const out0 = J < x.L ? x.U0 + (size_t)b * x.u_stride + (size_t)J * n : x.Usp + ((size_t)b * 2 + 0) * n;
     u64 *const out1 = J < x.L ? x.U1 + (size_t)b * x.u_stride + (size_t)J * n : x.Usp + ((size_t)b * 2 + 1) * n;
     ks_row_flush_phase<LOGM, CC>(a, bx, J, tid, lds, acc0, nullptr);
@@ -529,6 +529,12 @@ __global__ void __launch_bounds__(KSROW_THREADS, PERMROW_WAVES) ks_perm_row_kern
     ntt_tile_rounds<LOGM, false, true, CC, T, SCH, TWL, true>(a, bx, J, lds, twl);
     ks_row_store_phase<LOGM, CC>(a, bx, J, tid, lds, out1);
 }
+template <int LOGM>
+__global__ void __launch_bounds__(KSROW_THREADS, PERMROW_WAVES) ks_perm_row_kernel(NttArgs a, KsRowArgs x) { ks_perm_row_wg<LOGM, false>(a, x); }
+// ... and ALL children of a node in one launch (hoisted rotations): a workgroup belongs to a (child, item, key limb, row tile), x.B counts
+// the virtual items child * kid_B + item, and the child's key, quotients, correction table and element come from x.kids (hhe_common.h)
+template <int LOGM>
+__global__ void __launch_bounds__(KSROW_THREADS, PERMROW_WAVES) ks_perm_row_many_kernel(NttArgs a, KsRowArgs x) { ks_perm_row_wg<LOGM, true>(a, x); }
 int k_ks_perm_row(const NttArgs &a0, const KsRowArgs &x, rt_stream s)
 {
     NttArgs a = a0;
@@ -540,10 +546,13 @@ int k_ks_perm_row(const NttArgs &a0, const KsRowArgs &x, rt_stream s)
     const size_t units = ((size_t)x.K << a.tiles_log);   // (limb, tile) units; with tiles_log >= 3 a multiple of eight
     dim3 grid((unsigned)(((units + 7) & ~(size_t)7) * x.B));
     hipStream_t st = (hipStream_t)s;
-    switch (n2) {
+    switch (x.kids ? -n2 : n2) {
     case 6: hipLaunchKernelGGL((ks_perm_row_kernel<6>), grid, dim3(KSROW_THREADS), 0, st, a, x); break;
     case 7: hipLaunchKernelGGL((ks_perm_row_kernel<7>), grid, dim3(KSROW_THREADS), 0, st, a, x); break;
     case 8: hipLaunchKernelGGL((ks_perm_row_kernel<8>), grid, dim3(KSROW_THREADS), 0, st, a, x); break;
+    case -6: hipLaunchKernelGGL((ks_perm_row_many_kernel<6>), grid, dim3(KSROW_THREADS), 0, st, a, x); break;
+    case -7: hipLaunchKernelGGL((ks_perm_row_many_kernel<7>), grid, dim3(KSROW_THREADS), 0, st, a, x); break;
+    case -8: hipLaunchKernelGGL((ks_perm_row_many_kernel<8>), grid, dim3(KSROW_THREADS), 0, st, a, x); break;
     default: snprintf(g_rt_err, sizeof(g_rt_err), "ks_perm_row: unsupported row pass size 2^%d", n2); return -1;
     }
     return 0;
