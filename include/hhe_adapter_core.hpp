@@ -465,6 +465,19 @@ public:
         check(hhe_fc_packed_hoisted_ks(h(), r.get(), g.get(), m.get(), d, d, 1));
         download(d, 1, 2, dst);
     }
+    // ... with ONE BEHZ floor over the sum of the r products (hhe_fc_packed_sum_ks); hoisted: the rotations of fc_packed_hoisted instead
+    // of fc_packed's chain; same slots, other words.  More diagonals than one floor takes ("behz_sum_cap") are refused by the device call.
+    template <class RK, class GK, class Sink>
+    void fc_packed_sum(const uint64_t *vi, const EncMatrix &m, const RK &rk, const GK &gk, Sink dst, bool hoisted = false)
+    {
+        if (!m) throw std::invalid_argument("fc_packed: no encrypted matrix");
+        std::lock_guard<std::mutex> lk(arena_.mutex());
+        const KeySet r = named(set(rk), "fc_packed: empty key object"), g = named(set(gk), "fc_packed: empty key object");
+        uint64_t *d = arena_.get(0, ct_words() * 8);
+        upload(d, vi);
+        check(hhe_fc_packed_sum_ks(h(), r.get(), g.get(), m.get(), d, d, 1, hoisted ? 1 : 0));
+        download(d, 1, 2, dst);
+    }
     // Hoisted rotations (hhe_rotate_rows_many_ks): item k of dst = Evaluator::rotate_rows(in, steps[k], gk), the digit transforms of `in`
     // (and of every node of the steps' NAF trie) computed once.  An empty step list is refused by the device call.
     template <class GK, class Sink> void rotate_rows_many(const uint64_t *in_words, const std::vector<int> &steps, const GK &gk, Sink dst)

@@ -156,6 +156,28 @@ int hhe_rotate_rows_ks(hhe_ctx *c, const hhe_keyset *gk, const uint64_t *ct_dptr
 int hhe_rotate_columns_ks(hhe_ctx *c, const hhe_keyset *gk, const uint64_t *ct_dptr, uint64_t *out_dptr, size_t B);
 /* Evaluator::multiply (seal/evaluator.h:214-277; BEHZ) -> size-3 ct [B][3][L][N] */
 int hhe_multiply(hhe_ctx *c, const uint64_t *a_dptr, const uint64_t *b_dptr, uint64_t *out3_dptr, size_t B);
+/* The BEHZ floor of a SUM of K products: a [K][B][2][L][N], b [K][B][2][L][N] or, with b_bcast set, [K][1][2][L][N] (addend k of every
+ * item multiplies b[k]); out3 [B][3][L][N].  The steps of Evaluator::bfv_multiply with the tensor step replaced by a sum:
+ *   1. every operand is extended to q u B_sk as a product's operands are (fastbconv_m_tilde + sm_mrq);
+ *   2. under every modulus of q u B_sk the three tensor polynomials (a0 b0, a0 b1 + a1 b0, a1 b1) of the K pairs of an item are summed,
+ *      in the NTT domain;
+ *   3. the sum is multiplied by t, floored ONCE (fast_floor) and converted back ONCE (fastbconv_sk).
+ * K == 1 gives the words of hhe_multiply.  The result does not depend on the order of the K pairs.  It lies within L + 1 of
+ * floor((2 t D + Q) / (2 Q)) per coefficient, D the sum of the K integer tensor products of the operands' centred lifts, whatever K is:
+ * the summed value passes through one fast conversion (at most L - 1 multiples of Q too much), one floor against round, and one unit for
+ * the representative sm_mrq leaves -- the bound of a single product (DESIGN.md section 4 has the argument).
+ * The cap on K.  fastbconv_sk recovers the floored value from its residues exactly while it stays below B (floor(m_sk / 2) - L) in
+ * magnitude, B the product of the first L primes of B_sk.  An operand leaves sm_mrq within (Q / 2)(1 + rho), rho = (2L + 1) / 2^32, so
+ * the floored value is at most K N t Q (1 + rho)^2 / 2 + L.  A call is admitted when
+ *     K N t Q (1 + rho)^2 / 2 + L  <  B (floor(m_sk / 2) - L),
+ * and hhe_ctx_query("behz_sum_cap") is the largest such K of the context (from its own primes, saturating at 2^63 - 1; 0 when there is
+ * none).  K >= 2 above it: HHE_ERR_INVALID, out3 untouched.  K == 1 is always served, as hhe_multiply serves it.
+ * Also HHE_ERR_INVALID: a null pointer, K == 0, B == 0, out3 overlapping an operand, K * B operands whose extended polynomials pass
+ * 2^31 coefficients.  The workspaces grow to K * B operands the way
+ * hhe_multiply's grow to B.  One launch of the summed tensor kernel per modulus set ("multiply_sum_launches" counts them); its 128-bit
+ * sums are reduced every "multiply_sum_fold_q" / "multiply_sum_fold_bsk" addends (2^(127 - 2 bits) for the widest modulus of the set, at
+ * most 128).  Enqueues on the context's stream like hhe_multiply. */
+int hhe_multiply_sum(hhe_ctx *c, const uint64_t *a_dptr, const uint64_t *b_dptr, size_t K, int b_bcast, uint64_t *out3_dptr, size_t B);
 /* Evaluator::relinearize_inplace (seal/evaluator.h:301-304) size 3 -> 2 */
 int hhe_relinearize(hhe_ctx *c, const uint64_t *a3_dptr, uint64_t *out_dptr, size_t B);
 /* the same with the RelinKeys object of `slot` (hhe_set_relin_key_slot): Evaluator::relinearize_inplace(record, csp_rk) at
@@ -342,6 +364,16 @@ int hhe_rotate_rows_many_ks(hhe_ctx *c, const hhe_keyset *gk, const uint64_t *ct
 int hhe_fc_packed_hoisted_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *mat, const uint64_t *vi_dptr,
                              uint64_t *out_dptr, size_t B);
 int hhe_fc_packed_hoisted_galois_steps(size_t N, size_t rows, size_t cols, int *steps_out, size_t *count);
+/* The layer with ONE floor per item: hhe_fc_packed_ks (hoisted == 0) or hhe_fc_packed_hoisted_ks (hoisted != 0) with steps 3 and 4
+ * replaced by y = relinearize(multiply_sum(rot_0 .. rot_{r-1}, W_0 .. W_{r-1}), rk) -- hhe_multiply_sum with K = r against the handle's
+ * resident diagonals.  Steps 1, 2 and 5, the handle, the keys, the refusals, the in-place call, the chunking, the exactness fallback of
+ * the hoisted rotation and the levels are those of the form it follows; r >= 2 above "behz_sum_cap" is refused too (HHE_ERR_INVALID).
+ * The words differ from the per-product forms' (one floor instead of r); slots [0, rows) decrypt to the same (M x) mod t.  A chunk keeps
+ * its r rotations and one size-3 product per item, (2r + 3) L N words; it still holds max(1, HHE_CHUNK / r) items, since the operands of
+ * its r x items products are extended at once.  "fc_packed_floors" after a packed FC call: the polynomials floored per item, 3 here and
+ * 3 r for the two other forms; the sum kernel of hhe_add_many is not launched.  Synchronous. */
+int hhe_fc_packed_sum_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *mat, const uint64_t *vi_dptr,
+                         uint64_t *out_dptr, size_t B, int hoisted);
 /* Evaluator::add_many (seal/evaluator.h:150) for K stacked batches in_dptr [K][B][size][L][N], size 2 or 3: out [B][size][L][N] = their
  * sum, in ONE kernel launch whatever K is (hhe_ctx_query("add_many_launches") counts them); the sum of a coefficient is kept in two
  * words and reduced once.  out may be one of the K operands.  K == 0, B == 0, a null pointer or another size: HHE_ERR_INVALID.

@@ -125,16 +125,22 @@ struct EncMatrix {
     }
     // slots [0, rows) of the decryption of `out` are (M x) mod t; rk / gal_keys: the parties' ordinary, top-level key objects
     // hoisted: the rotation chain of the layer as rotations of one ciphertext (fc_packed_hoisted)
-    void apply(const Ciphertext &vi, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out, bool hoisted = false) const
+    // sum: one BEHZ floor over the sum of the layer's r products (fc_packed_sum), with either rotation schedule
+    void apply(const Ciphertext &vi, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out, bool hoisted = false, bool sum = false) const
     {
         if (!core) throw std::invalid_argument("fc_packed: no encrypted matrix");
         const bool top = core.get() == context.get();
         hhe::KeySet r = context->keys().relin(detail::words(rk)), g = context->keys().galois(detail::words(gal_keys));
         if (!top) { r = core->derived(r); g = core->derived(g); }
         const uint64_t *x = detail::level_words(*core, context->data_limbs(), vi);
-        if (hoisted) core->fc_packed_hoisted(x, handle, r, g, detail::into_level(*core, out));
+        if (sum) core->fc_packed_sum(x, handle, r, g, detail::into_level(*core, out), hoisted);
+        else if (hoisted) core->fc_packed_hoisted(x, handle, r, g, detail::into_level(*core, out));
         else core->fc_packed(x, handle, r, g, detail::into_level(*core, out));
         if (top) out.limbs = 0;  // the data level, as every cipher object's results
+    }
+    void apply_sum(const Ciphertext &vi, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out, bool hoisted = false) const
+    {
+        apply(vi, rk, gal_keys, out, hoisted, true);
     }
     std::shared_ptr<HheContext> context;      // the chain's core: its key-set cache holds the sets the calls name
     std::shared_ptr<hhe::AdapterCore> core;   // where the handle lives: the chain's core, or a level's
@@ -209,6 +215,11 @@ public:
     {
         if (mat.core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
         mat.apply(vi, rk, gal_keys, out, true);
+    }
+    void fc_packed_sum(const Ciphertext &vi, const EncMatrix &mat, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out, bool hoisted = false)
+    {
+        if (mat.core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
+        mat.apply_sum(vi, rk, gal_keys, out, hoisted);
     }
     // hoisted rotations at this level: out[k] = Evaluator::rotate_rows(ct, steps[k], gal_keys) with the key object the call names
     void rotate_rows_many(const Ciphertext &ct, const std::vector<int> &steps, const GaloisKeys &gal_keys, std::vector<Ciphertext> &o)
@@ -633,6 +644,13 @@ inline void fc_packed_hoisted(const pasta::Ciphertext &vi, const EncMatrix &mat,
                               pasta::Ciphertext &out)
 {
     mat.apply(vi, rk, gal_keys, out, true);
+}
+// ... with ONE BEHZ floor per item: the r products are summed before the floor (hhe_gfx950.h hhe_fc_packed_sum_ks); hoisted chooses the
+// rotations of fc_packed_hoisted instead of fc_packed's chain.  The slots are the same, the words are not
+inline void fc_packed_sum(const pasta::Ciphertext &vi, const EncMatrix &mat, const pasta::RelinKeys &rk, const pasta::GaloisKeys &gal_keys,
+                          pasta::Ciphertext &out, bool hoisted = false)
+{
+    mat.apply_sum(vi, rk, gal_keys, out, hoisted);
 }
 // out[k] = Evaluator::rotate_rows(ct, steps[k], gal_keys), hoisted (hhe_gfx950.h "Hoisted rotations")
 inline void rotate_rows_many(pasta::HheContext &ctx, const pasta::Ciphertext &ct, const std::vector<int> &steps, const pasta::GaloisKeys &gal_keys,

@@ -192,13 +192,20 @@ struct EncMatrix {
     }
     // slots [0, rows) of the decryption of `out` are (M x) mod t; rk / gal_keys: the parties' ordinary, top-level key objects
     // hoisted: the rotation chain of the layer as rotations of one ciphertext (fc_packed_hoisted)
-    void apply(const seal::Ciphertext &vi, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out, bool hoisted = false) const
+    // sum: one BEHZ floor over the sum of the layer's r products (fc_packed_sum), with either rotation schedule
+    void apply(const seal::Ciphertext &vi, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out, bool hoisted = false,
+               bool sum = false) const
     {
         if (!core) throw std::invalid_argument("fc_packed: no encrypted matrix");
         hhe::KeySet r = device->relin_set(rk), g = device->galois_set(gal_keys);
         if (core.get() != device.get()) { r = core->derived(r); g = core->derived(g); }
-        if (hoisted) core->fc_packed_hoisted(in(vi), handle, r, g, gfx950::DeviceContext::into_level(*context, out, id, 2));
+        if (sum) core->fc_packed_sum(in(vi), handle, r, g, gfx950::DeviceContext::into_level(*context, out, id, 2), hoisted);
+        else if (hoisted) core->fc_packed_hoisted(in(vi), handle, r, g, gfx950::DeviceContext::into_level(*context, out, id, 2));
         else core->fc_packed(in(vi), handle, r, g, gfx950::DeviceContext::into_level(*context, out, id, 2));
+    }
+    void apply_sum(const seal::Ciphertext &vi, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out, bool hoisted = false) const
+    {
+        apply(vi, rk, gal_keys, out, hoisted, true);
     }
     std::shared_ptr<seal::SEALContext> context;
     std::shared_ptr<gfx950::DeviceContext> device;  // the chain's core: its key-set cache holds the sets the calls name
@@ -297,6 +304,12 @@ public:
     {
         if (mat.core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
         mat.apply(vi, rk, gal_keys, out, true);
+    }
+    void fc_packed_sum(const seal::Ciphertext &vi, const EncMatrix &mat, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out,
+                       bool hoisted = false)
+    {
+        if (mat.core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
+        mat.apply_sum(vi, rk, gal_keys, out, hoisted);
     }
     // hoisted rotations at this level: o[k] = Evaluator::rotate_rows(ct, steps[k], gal_keys) with the key object the call names
     void rotate_rows_many(const seal::Ciphertext &ct, const std::vector<int> &steps, const seal::GaloisKeys &gal_keys, std::vector<seal::Ciphertext> &o)
@@ -720,6 +733,13 @@ inline void fc_packed_hoisted(const seal::Ciphertext &vi, const EncMatrix &mat, 
                               seal::Ciphertext &out)
 {
     mat.apply(vi, rk, gal_keys, out, true);
+}
+// ... with ONE BEHZ floor per item: the r products are summed before the floor (hhe_gfx950.h hhe_fc_packed_sum_ks); hoisted chooses the
+// rotations of fc_packed_hoisted instead of fc_packed's chain.  The slots are the same, the words are not
+inline void fc_packed_sum(const seal::Ciphertext &vi, const EncMatrix &mat, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys,
+                          seal::Ciphertext &out, bool hoisted = false)
+{
+    mat.apply_sum(vi, rk, gal_keys, out, hoisted);
 }
 // out[k] = Evaluator::rotate_rows(ct, steps[k], gal_keys), hoisted (hhe_gfx950.h "Hoisted rotations"); the Evaluator argument is unused
 inline void rotate_rows_many(const seal::Ciphertext &ct, const std::vector<int> &steps, const seal::GaloisKeys &gal_keys,

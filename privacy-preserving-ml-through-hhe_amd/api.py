@@ -50,11 +50,13 @@ _SYMBOLS = [
     "hhe_fc_packed_shape", "hhe_fc_packed_diagonals", "hhe_fc_packed_galois_steps", "hhe_enc_matrix_create", "hhe_enc_matrix_destroy",
     "hhe_enc_matrix_bytes", "hhe_fc_packed_ks", "hhe_add_many",
     "hhe_rotate_rows_many_ks", "hhe_fc_packed_hoisted_ks", "hhe_fc_packed_hoisted_galois_steps",
+    "hhe_multiply_sum", "hhe_fc_packed_sum_ks",
 ]
 
 _FC_PACKED_SYMBOLS = {"hhe_fc_packed_shape", "hhe_fc_packed_diagonals", "hhe_fc_packed_galois_steps", "hhe_enc_matrix_create",
                       "hhe_enc_matrix_destroy", "hhe_enc_matrix_bytes", "hhe_fc_packed_ks", "hhe_add_many"}
 _ROT_MANY_SYMBOLS = {"hhe_rotate_rows_many_ks", "hhe_fc_packed_hoisted_ks", "hhe_fc_packed_hoisted_galois_steps"}
+_MULT_SUM_SYMBOLS = {"hhe_multiply_sum", "hhe_fc_packed_sum_ks"}
 _NONCE_SYMBOLS = {"hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystream_nonce", "hhe_pasta3_plain_crypt_nonce",
                   "hhe_pasta3_transcipher_nonce_ks", "hhe_decompose_nonce_ks", "hhe_pasta3_block_randomness_dev",
                   "hhe_pasta3_prepare_tables"}
@@ -65,7 +67,7 @@ _NONCE_SYMBOLS = {"hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystre
 _OPTIONAL = {"hhe_pasta3_clear_keystream_cache", "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin",
              "hhe_keyset_generate_galois", "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
              "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level",
-             "hhe_noise_budget", "hhe_ctx_create_level", "hhe_keyset_derive_level"} | _NONCE_SYMBOLS | _FC_PACKED_SYMBOLS | _ROT_MANY_SYMBOLS
+             "hhe_noise_budget", "hhe_ctx_create_level", "hhe_keyset_derive_level"} | _NONCE_SYMBOLS | _FC_PACKED_SYMBOLS | _ROT_MANY_SYMBOLS | _MULT_SUM_SYMBOLS
 
 
 def exported_symbols():
@@ -275,6 +277,14 @@ class EncMatrix:
         self.ctx._chk(self.ctx._need("hhe_fc_packed_hoisted_ks")(self.ctx.h, _ks(rk), _ks(gk), self.h, _ptr(ct), _ptr(out), C.c_size_t(B)))
         return out
 
+    def apply_sum(self, ct, B, rk=None, gk=None, out=None, hoisted=False):
+        """the layer with one BEHZ floor per item (hhe_fc_packed_sum_ks): the r products are summed before the floor (multiply_sum);
+        hoisted: the rotations of apply_hoisted instead of apply's chain.  Same slots, other words."""
+        out = ct if out is None else out
+        self.ctx._chk(self.ctx._need("hhe_fc_packed_sum_ks")(self.ctx.h, _ks(rk), _ks(gk), self.h, _ptr(ct), _ptr(out), C.c_size_t(B),
+                                                             C.c_int(1 if hoisted else 0)))
+        return out
+
     def destroy(self):
         if getattr(self, "h", None) and getattr(self.ctx, "h", None):
             self.ctx.lib.hhe_enc_matrix_destroy(self.h)
@@ -414,6 +424,10 @@ class Context:
         """out[b] = the packed encrypted FC layer `mat` (an EncMatrix) on ct[b] with the rotation chain hoisted; out may be ct"""
         return mat.apply_hoisted(ct, B, rk=rk, gk=gk, out=out)
 
+    def fc_packed_sum(self, ct, mat, out, B, rk=None, gk=None, hoisted=False):
+        """out[b] = the packed encrypted FC layer `mat` on ct[b] with one floor over the sum of its r products; out may be ct"""
+        return mat.apply_sum(ct, B, rk=rk, gk=gk, out=out, hoisted=hoisted)
+
     def rotate_columns(self, ct, out, B, gk=None):
         self._chk(self.lib.hhe_rotate_columns_ks(self.h, _ks(gk), _ptr(ct), _ptr(out), C.c_size_t(B)))
 
@@ -435,6 +449,12 @@ class Context:
 
     def multiply(self, a, b, out3, B):
         self._chk(self.lib.hhe_multiply(self.h, _ptr(a), _ptr(b), _ptr(out3), C.c_size_t(B)))
+
+    def multiply_sum(self, a, b, K, out3, B, b_bcast=False):
+        """out3 [B][3][L][N] = the BEHZ floor of the sum of the K tensor products of a [K][B][2][L][N] and b [K][B][2][L][N]
+        (b_bcast: [K][1][2][L][N]); K above query("behz_sum_cap") is refused"""
+        self._chk(self._need("hhe_multiply_sum")(self.h, _ptr(a), _ptr(b), C.c_size_t(K), C.c_int(1 if b_bcast else 0), _ptr(out3),
+                                                 C.c_size_t(B)))
 
     def relinearize(self, a3, out, B, slot=None, rk=None):
         if rk is not None:

@@ -254,16 +254,19 @@ void op_behz_operand(hhe_ctx *c, const u64 *in, u64 *oq, u64 *ob, size_t B)
     k_ntt(ntt_args(c, in, oq, B * 2 * L, 0, L), false, c->w->stream);
 }
 // The passes of a BEHZ product behind its operands: the first operand of B items in the lane's bz_aq / bz_ab, the second at bq / bb in
-// the same form; b_div > 0: item b multiplies ciphertext b / b_div of the second operand (TensorArgs::b_div)
-void behz_product(hhe_ctx *c, const u64 *bq, const u64 *bb, size_t b_div, u64 *out3, size_t B)
+// the same form; b_div > 0: item b multiplies ciphertext b / b_div of the second operand (TensorArgs::b_div).
+// sum > 0: the operands are [sum][B] (the second [sum][1] when b_div is set) and the B results are the floors of the sums of their
+// `sum` tensor products (hhe_multiply_sum): one summed tensor launch per modulus set, then the same passes over B * 3 polynomials
+void behz_product(hhe_ctx *c, const u64 *bq, const u64 *bb, size_t b_div, u64 *out3, size_t B, size_t sum = 0)
 {
     const int L = c->L, K = c->K;
     TensorArgs t = zeroed<TensorArgs>();
-    t.mods = c->d_mods; t.logn = c->logn; t.B = (int)B; t.b_div = (int)b_div;
-    t.a = c->w->bz_aq; t.b = bq; t.d = c->w->bz_dq; t.limbs = L; t.mod_base = 0;
+    t.mods = c->d_mods; t.logn = c->logn; t.B = (int)B; t.b_div = (int)b_div; t.sum = (int)sum;
+    t.a = c->w->bz_aq; t.b = bq; t.d = c->w->bz_dq; t.limbs = L; t.mod_base = 0; t.fold = c->sum_fold_q;
     k_tensor(t, c->w->stream);
-    t.a = c->w->bz_ab; t.b = bb; t.d = c->w->bz_db; t.limbs = L + 1; t.mod_base = K;
+    t.a = c->w->bz_ab; t.b = bb; t.d = c->w->bz_db; t.limbs = L + 1; t.mod_base = K; t.fold = c->sum_fold_bsk;
     k_tensor(t, c->w->stream);
+    if (sum) c->multiply_sum_launches += 2;
     op_ntt(c, c->w->bz_dq, B * 3 * L, 0, L, true, STORE_SCALE_T);
     op_ntt(c, c->w->bz_db, B * 3 * (L + 1), K, L + 1, true, STORE_SCALE_T);
     BehzFloorArgs f = zeroed<BehzFloorArgs>();
@@ -286,6 +289,12 @@ void op_multiply_enc(hhe_ctx *c, const u64 *x, const hhe_enc_matrix *m, u64 *out
 {
     op_behz_operand(c, x, c->w->bz_aq, c->w->bz_ab, m->r * per);
     behz_product(c, m->wq, m->wb, per, out3, m->r * per);
+}
+// ... with the r products of an item summed before the floor (hhe_multiply_sum over x and the resident diagonals): out3 [per][3][L][N]
+void op_multiply_sum_enc(hhe_ctx *c, const u64 *x, const hhe_enc_matrix *m, u64 *out3, size_t per)
+{
+    op_behz_operand(c, x, c->w->bz_aq, c->w->bz_ab, m->r * per);
+    behz_product(c, m->wq, m->wb, 1, out3, per, m->r);
 }
 
 int op_relinearize(hhe_ctx *c, const u64 *a3, u64 *out, size_t B)
@@ -992,6 +1001,23 @@ extern "C" int hhe_multiply(hhe_ctx *c, const uint64_t *a, const uint64_t *b, ui
     int rc = need(c, B);
     if (rc) return rc;
     op_multiply(c, a, b, out3, B);
+    return HHE_OK;
+}
+// the definition and the cap are in include/hhe_gfx950.h; DESIGN.md section 4 "One floor over a sum of products"
+extern "C" int hhe_multiply_sum(hhe_ctx *c, const uint64_t *a, const uint64_t *b, size_t K, int b_bcast, uint64_t *out3, size_t B)
+{
+    HHE_LOCK(c);
+    if (!c || !a || !b || !out3 || K == 0 || B == 0) return fail(HHE_ERR_INVALID, "hhe_multiply_sum: null argument, no addend or empty batch");
+    if (K >= 2 && K > c->behz_sum_cap) return fail(HHE_ERR_INVALID, "hhe_multiply_sum: more addends than one floor takes (behz_sum_cap)");
+    if (K > 0x7fffffff / B || K * B > ((size_t)0x7fffffff >> c->logn) / (2 * (c->L + 1))) return fail(HHE_ERR_INVALID, "hhe_multiply_sum: batch too large");
+    const size_t ctw = c->ct_words(), nb = b_bcast ? K : K * B;
+    auto overlaps = [&](const u64 *p, size_t words) { return out3 < p + words && p < out3 + B * 3 * c->L * c->n; };
+    if (overlaps(a, K * B * ctw) || overlaps(b, nb * ctw)) return fail(HHE_ERR_INVALID, "hhe_multiply_sum: out3 overlaps an operand");
+    int rc = need(c, K * B);
+    if (rc) return rc;
+    op_behz_operand(c, a, c->w->bz_aq, c->w->bz_ab, K * B);
+    op_behz_operand(c, b, c->w->bz_bq, c->w->bz_bb, nb);
+    behz_product(c, c->w->bz_bq, c->w->bz_bb, b_bcast ? 1 : 0, out3, B, K);
     return HHE_OK;
 }
 extern "C" int hhe_relinearize_ks(hhe_ctx *c, const hhe_keyset *rk, const uint64_t *a3, uint64_t *out, size_t B)
@@ -2547,7 +2573,9 @@ void fc_packed_steps(size_t n, size_t r, size_t cc, std::vector<int> &steps)
 // one chunk on the current lane: in / out [per][2][L][N] (may be the same buffer); the lane is reserved for r * per items
 // hoist: step 2 as rotations of the x of step 1 (hhe_fc_packed_hoisted_ks) -- one hoisted rotation of the chunk's items into rot + per * ctw,
 // or with `stepwise` each through op_rotate_rows (HHE_ROT_HOIST=0 and the exactness fallback); null: the chain of hhe_fc_packed_ks
-int fc_packed_chunk(hhe_ctx *c, const hhe_enc_matrix *m, const u64 *in, u64 *out, size_t per, const RotPlan *hoist = nullptr, bool stepwise = false)
+// sum: steps 3 and 4 as one multiply_sum (hhe_fc_packed_sum_ks) -- prod is [per][3][L][N] and the sum kernel is not launched
+int fc_packed_chunk(hhe_ctx *c, const hhe_enc_matrix *m, const u64 *in, u64 *out, size_t per, const RotPlan *hoist = nullptr, bool stepwise = false,
+                    bool sum = false)
 {
     const size_t ctw = c->ct_words(), r = m->r;
     Lane &w = *c->w;
@@ -2560,8 +2588,9 @@ int fc_packed_chunk(hhe_ctx *c, const hhe_enc_matrix *m, const u64 *in, u64 *out
     } else
         for (size_t i = 1; i < r; ++i)
             if ((rc = op_rotate_rows(c, rot + (i - 1) * per * ctw, 1, rot + i * per * ctw, per))) return rc;
-    op_multiply_enc(c, rot, m, prod, per);
-    if (r > 1) {  // acc = the sum of the r products of every item, into the first one
+    if (sum) op_multiply_sum_enc(c, rot, m, prod, per);
+    else op_multiply_enc(c, rot, m, prod, per);
+    if (r > 1 && !sum) {  // acc = the sum of the r products of every item, into the first one
         k_elt(elt_args(c, prod, nullptr, prod, per * 3 * c->L, 0, c->L, (int)r), ELT_ADDMANY, w.stream);
         ++c->add_many_launches;
     }
@@ -2653,12 +2682,19 @@ extern "C" void hhe_enc_matrix_destroy(hhe_enc_matrix *m)
 }
 extern "C" size_t hhe_enc_matrix_bytes(const hhe_enc_matrix *m) { return m ? m->bytes : 0; }
 
-extern "C" int hhe_fc_packed_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi,
-                                uint64_t *out, size_t B)
+// what a chunk keeps on its lane: the r rotations of its items and their r size-3 products, or with `sum` the one summed product
+static size_t fc_packed_words(const hhe_ctx *c, const hhe_enc_matrix *m, size_t per, bool sum)
+{
+    return (m->r * 2 + (sum ? 1 : m->r) * 3) * per * (size_t)c->L * c->n;
+}
+// sum: hhe_fc_packed_sum_ks with hoisted == 0
+static int fc_packed_run(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi, uint64_t *out, size_t B,
+                         bool sum)
 {
     HHE_LOCK(c);
     if (!c || !m || !vi || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed: null argument or empty batch");
     if (m->ctx != c) return fail(HHE_ERR_INVALID, "encrypted matrix belongs to another context");
+    if (sum && m->r >= 2 && m->r > c->behz_sum_cap) return fail(HHE_ERR_INVALID, "hhe_fc_packed_sum: more diagonals than one floor takes (behz_sum_cap)");
     int rc = check_sets(c, rk, gk);
     if (rc) return rc;
     KeyScope keys(c, gk, rk);
@@ -2677,12 +2713,20 @@ extern "C" int hhe_fc_packed_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keys
     const size_t ctw = c->ct_words();
     for (int s = plan.first_lane(); s <= plan.last_lane(); ++s) {
         if ((rc = lane_reserve(c, c->lanes[s], m->r * per))) return rc;
-        if ((rc = c->lanes[s].ws_fcp.reserve(c, m->r * per * (size_t)5 * c->L * c->n, "hhe_fc_packed: rotations and products"))) return rc;
+        if ((rc = c->lanes[s].ws_fcp.reserve(c, fc_packed_words(c, m, per, sum), "hhe_fc_packed: rotations and products"))) return rc;
     }
-    rc = run_chunks(c, plan, [&](Lane &, size_t, size_t b0, size_t bc) { return fc_packed_chunk(c, m, vi + b0 * ctw, out + b0 * ctw, bc); });
+    rc = run_chunks(c, plan, [&](Lane &, size_t, size_t b0, size_t bc) { return fc_packed_chunk(c, m, vi + b0 * ctw, out + b0 * ctw, bc, nullptr, false, sum); });
     if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_fc_packed");
-    if (!rc) c->fc_packed_key_switches = steps.size() - (m->r > 1 ? 1 : 0) + (m->r - 1);
+    if (!rc) {
+        c->fc_packed_key_switches = steps.size() - (m->r > 1 ? 1 : 0) + (m->r - 1);
+        c->fc_packed_floors = sum ? 3 : 3 * m->r;
+    }
     return rc;
+}
+extern "C" int hhe_fc_packed_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi,
+                                uint64_t *out, size_t B)
+{
+    return fc_packed_run(c, rk, gk, m, vi, out, B, false);
 }
 
 // the steps of the hoisted layer: -c unless the row is full, 1 .. r-1, the tail r 2^k < c
@@ -2707,12 +2751,14 @@ extern "C" int hhe_fc_packed_hoisted_galois_steps(size_t N, size_t rows, size_t 
     std::copy(steps.begin(), steps.end(), steps_out);
     return HHE_OK;
 }
-extern "C" int hhe_fc_packed_hoisted_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi,
-                                        uint64_t *out, size_t B)
+// sum: hhe_fc_packed_sum_ks with hoisted != 0
+static int fc_packed_hoisted_run(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi, uint64_t *out,
+                                 size_t B, bool sum)
 {
     HHE_LOCK(c);
     if (!c || !m || !vi || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed_hoisted: null argument or empty batch");
     if (m->ctx != c) return fail(HHE_ERR_INVALID, "encrypted matrix belongs to another context");
+    if (sum && m->r >= 2 && m->r > c->behz_sum_cap) return fail(HHE_ERR_INVALID, "hhe_fc_packed_sum: more diagonals than one floor takes (behz_sum_cap)");
     int rc = check_sets(c, rk, gk);
     if (rc) return rc;
     KeyScope keys(c, gk, rk);
@@ -2734,7 +2780,7 @@ extern "C" int hhe_fc_packed_hoisted_ks(hhe_ctx *c, const hhe_keyset *rk, const 
     const size_t ctw = c->ct_words();
     auto reserve = [&](Lane &ln, bool h) {
         int r = rot_many_reserve(c, ln, plan, h, true, per, m->r * per);
-        if (!r) r = ln.ws_fcp.reserve(c, m->r * per * (size_t)5 * c->L * c->n, "hhe_fc_packed: rotations and products");
+        if (!r) r = ln.ws_fcp.reserve(c, fc_packed_words(c, m, per, sum), "hhe_fc_packed: rotations and products");
         return r;
     };
     for (int s = cp.first_lane(); s <= cp.last_lane(); ++s)
@@ -2753,7 +2799,7 @@ extern "C" int hhe_fc_packed_hoisted_ks(hhe_ctx *c, const hhe_keyset *rk, const 
     }
     rc = run_chunks(c, cp, [&](Lane &ln, size_t idx, size_t b0, size_t bc) {
         ln.zero_flag = hoisted ? flags + idx : nullptr;
-        return fc_packed_chunk(c, m, vi + b0 * ctw, res + b0 * ctw, bc, &plan, !hoisted);
+        return fc_packed_chunk(c, m, vi + b0 * ctw, res + b0 * ctw, bc, &plan, !hoisted, sum);
     });
     if (hoisted && !rc) {
         std::vector<u32> h(cp.nch, 0);
@@ -2762,7 +2808,7 @@ extern "C" int hhe_fc_packed_hoisted_ks(hhe_ctx *c, const hhe_keyset *rk, const 
             if (h[idx] || c->rot_hoist == 2) {
                 c->rot_many_fallbacks++;
                 main.zero_flag = nullptr;
-                if (!(rc = reserve(main, false))) rc = fc_packed_chunk(c, m, vi + idx * per * ctw, res + idx * per * ctw, cp.count(idx), &plan, true);
+                if (!(rc = reserve(main, false))) rc = fc_packed_chunk(c, m, vi + idx * per * ctw, res + idx * per * ctw, cp.count(idx), &plan, true, sum);
             }
         if (!rc && res != out) rt_d2d(out, res, B * ctw * 8, main.stream);
     }
@@ -2771,8 +2817,19 @@ extern "C" int hhe_fc_packed_hoisted_ks(hhe_ctx *c, const hhe_keyset *rk, const 
         c->rot_many_key_switches = m->r > 1 ? plan.trie.size() - 1 : 0;
         c->rot_many_launches = hoisted ? plan.launches : 0;
         c->fc_packed_key_switches = own.size() - (m->r > 1 ? 1 : 0) + c->rot_many_key_switches;
+        c->fc_packed_floors = sum ? 3 : 3 * m->r;
     }
     return rc;
+}
+extern "C" int hhe_fc_packed_hoisted_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi,
+                                        uint64_t *out, size_t B)
+{
+    return fc_packed_hoisted_run(c, rk, gk, m, vi, out, B, false);
+}
+extern "C" int hhe_fc_packed_sum_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi,
+                                    uint64_t *out, size_t B, int hoisted)
+{
+    return hoisted ? fc_packed_hoisted_run(c, rk, gk, m, vi, out, B, true) : fc_packed_run(c, rk, gk, m, vi, out, B, true);
 }
 
 extern "C" int hhe_add_many(hhe_ctx *c, const uint64_t *in, size_t K, uint64_t *out, size_t B, int size)

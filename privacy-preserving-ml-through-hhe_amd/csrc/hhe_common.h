@@ -501,7 +501,14 @@ struct TensorArgs {  // d[b][0..2][j] from a[b][0..1][j], b[b][0..1][j]; NTT dom
     int logn, B, limbs, mod_base;
     int b_div;  // > 0: the second operand of item b is ciphertext b / b_div of `b` (the resident diagonals of a packed encrypted FC layer,
                 // each shared by the b_div items of a chunk; a kernel of its own); 0: item b of `b`
+    int sum;    // > 0: d[b] = the sum over k < sum of the tensor products of a[k][b] and b[k][b] (b[k][0] when b_div is set), `a` being
+                // [sum][B][2][limbs][N] and `b` [sum][B or 1][2][limbs][N] (hhe_multiply_sum; a kernel of its own); 0: one product
+    int fold;   // with sum: the addends a 128-bit sum takes between two reductions (tensor_sum_fold of the widest modulus of the launch)
 };
+// Addends between two reductions of tensor_sum_body's sums under a modulus of `bits` bits.  The middle polynomial takes two products
+// below 2^(2 bits) per addend on top of a residue below 2^bits, and 2 f (2^bits - 1)^2 + 2^bits < 2^128 holds for f = 2^(127 - 2 bits)
+// (32 at 61 bits, 128 at 60).  Capped at 128: past that a reduction is under 1 % of the products, and every interval stays testable.
+inline int tensor_sum_fold(int bits) { return bits > 63 ? 1 : 127 - 2 * bits >= 7 ? 128 : 1 << (127 - 2 * bits); }
 
 struct BehzFloorArgs {  // (dq [P][L][N], db [P][L+1][N]) coeff, already *t -> out [P][L][N]
     const u64 *dq, *db;

@@ -202,6 +202,52 @@ extern "C" int hhe_bfv_default_coeff_modulus(size_t n, uint64_t *out, size_t *co
     return HHE_OK;
 }
 
+// hhe_ctx_query("behz_sum_cap"): the largest K <= 2^63 - 1 with
+//     K N t Q (2^32 + 2L + 1)^2 + 2^65 L  <  2^65 B (floor(m_sk / 2) - L)
+// (the condition of hhe_multiply_sum in hhe_gfx950.h, cleared of its fractions), 0 when not even K = 1 meets it.  Found by bisection
+// over K with word-by-integer products, so no long division is needed.
+static u64 behz_sum_cap(const std::vector<u64> &dq, const std::vector<u64> &Bq, u64 msk, u64 t, size_t n)
+{
+    typedef std::vector<u64> Big;  // little endian, no leading zero words
+    auto mul = [](Big x, u64 m) {
+        u64 carry = 0;
+        for (u64 &w : x) { const u128 p = (u128)w * m + carry; w = (u64)p; carry = (u64)(p >> 64); }
+        if (carry) x.push_back(carry);
+        while (!x.empty() && !x.back()) x.pop_back();
+        return x;
+    };
+    auto add = [](Big x, const Big &y) {
+        if (x.size() < y.size()) x.resize(y.size(), 0);
+        u64 carry = 0;
+        for (size_t i = 0; i < x.size(); ++i) { const u128 s = (u128)x[i] + (i < y.size() ? y[i] : 0) + carry; x[i] = (u64)s; carry = (u64)(s >> 64); }
+        if (carry) x.push_back(carry);
+        return x;
+    };
+    auto less = [](const Big &x, const Big &y) {
+        if (x.size() != y.size()) return x.size() < y.size();
+        for (size_t i = x.size(); i-- > 0;)
+            if (x[i] != y[i]) return x[i] < y[i];
+        return false;
+    };
+    const u64 L = dq.size();
+    if (msk / 2 <= L) return 0;
+    Big rhs = {0, 2};  // 2^65
+    for (u64 b : Bq) rhs = mul(rhs, b);
+    rhs = mul(rhs, msk / 2 - L);
+    const Big slack = {0, 2 * L};  // 2^65 L
+    Big unit = {(u64)n};
+    unit = mul(unit, t);
+    for (u64 p : dq) unit = mul(unit, p);
+    unit = mul(mul(unit, ((u64)1 << 32) + 2 * L + 1), ((u64)1 << 32) + 2 * L + 1);
+    u64 lo = 0, hi = 0x7fffffffffffffffULL;  // lo is admitted (or 0), everything above hi is not
+    while (lo < hi) {
+        const u64 mid = lo + (hi - lo + 1) / 2;
+        if (less(add(mul(unit, mid), slack), rhs)) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
 extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, int device, hhe_ctx **out)
 {
     if (!out || !q || logn < 10 || logn > 16 || K < 2 || K > HHE_MAXK) {
@@ -268,6 +314,15 @@ extern "C" int hhe_ctx_create(int logn, int K, const uint64_t *q, uint64_t t, in
 
     std::vector<u64> dq(c->q.begin(), c->q.begin() + L), Bq(c->bsk.begin(), c->bsk.begin() + L);
     const u64 msk = c->bsk[L], MT = (u64)1 << 32;
+    // hhe_multiply_sum: the most products one floor takes, and the reduction intervals of its sums under the two modulus sets
+    c->behz_sum_cap = behz_sum_cap(dq, Bq, msk, t, n);
+    auto widest = [](const std::vector<u64> &ps) {
+        int bits = 0;
+        for (u64 p : ps) bits = std::max(bits, 64 - __builtin_clzll(p));
+        return bits;
+    };
+    c->sum_fold_q = tensor_sum_fold(widest(dq));
+    c->sum_fold_bsk = tensor_sum_fold(widest(c->bsk));
     // add_plain scaling variant
     AddPlainArgs &ap = c->apl;
     memset(&ap, 0, sizeof(ap));
@@ -651,6 +706,11 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "rot_many_launches") return c->rot_many_launches;          // ... and its multi-child launches of ks_perm_row_kernel per chunk
     if (w == "rot_many_group") return HHE_ROT_GROUP;                    // children one such launch serves at most
     if (w == "add_many_launches") return c->add_many_launches;            // launches of the sum kernel (hhe_add_many: one per call)
+    if (w == "behz_sum_cap") return c->behz_sum_cap;                      // most products hhe_multiply_sum sums under one floor (K = 1 is always served)
+    if (w == "multiply_sum_fold_q") return (u64)c->sum_fold_q;            // addends between two reductions of its sums: under the data primes,
+    if (w == "multiply_sum_fold_bsk") return (u64)c->sum_fold_bsk;        // ... under the B_sk primes
+    if (w == "multiply_sum_launches") return c->multiply_sum_launches;    // launches of the summed tensor kernel: one per modulus set per call or chunk
+    if (w == "fc_packed_floors") return c->fc_packed_floors;              // polynomials floored per item of the last packed encrypted FC call
     if (w == "noise_form") return (u64)c->noise_form;  // the last hhe_noise_budget launch: limb count of its register form, 0 = the LDS form
     if (w == "public_device") return (u64)(int64_t)c->public_device;  // HHE_PUBLIC_DEVICE: 0 host, 1 device; unset: (uint64_t)-1, the path is chosen per call
     if (w == "public_device_built") return c->last_public_built;     // pairs whose randomness the last call drew on the device

@@ -137,7 +137,7 @@ struct Lane {
     size_t ptr_cap = 0;
     GrowBuf<u64> ws_rot;     // [16][B][2][L][N]: PASTA's babystep rotations, and the FC's product + per-depth buffers of the unshared walk
     GrowBuf<u64> ws_aff;     // [n1 + n2][B][2][L][N] baby-step ciphertexts | inner sums of hhe_packed_affine (BSGS)
-    GrowBuf<u64> ws_fcp;     // [r][B][2][L][N] rotations | [r][B][3][L][N] products of a chunk of hhe_fc_packed_ks
+    GrowBuf<u64> ws_fcp;     // [r][B][2][L][N] rotations | [r][B][3][L][N] products of a chunk of hhe_fc_packed_ks ([B][3][L][N], the one summed product, for hhe_fc_packed_sum_ks)
     GrowBuf<u64> ws_rotm;    // hoisted rotations: ciphertexts of the trie nodes a chunk does not write straight into its output, [nodes][B][2][L][N]
     // FC shared digits: one slot per trie node that is still needed -- the digit transforms of its un-rotated c1 (tp [B][L][K][N]) and its
     // ciphertext (ct [B][2][L][N]); refs = 1 while the depth-first walk is below the node + 1 per queued leaf key switch that reads it
@@ -255,6 +255,10 @@ struct hhe_ctx {
     std::vector<hhe_enc_matrix *> enc_mats;    // encrypted-matrix handles created on this context
     u64 fc_packed_key_switches = 0;            // Galois key switches per item of the last hhe_fc_packed_ks call (hhe_ctx_query("fc_packed_key_switches"))
     u64 add_many_launches = 0;                 // launches of the sum kernel, by hhe_add_many and by the packed FC (hhe_ctx_query("add_many_launches"))
+    u64 behz_sum_cap = 0;                      // most products hhe_multiply_sum floors as one sum (hhe_ctx_query("behz_sum_cap"); the condition is in hhe_gfx950.h)
+    int sum_fold_q = 1, sum_fold_bsk = 1;      // tensor_sum_fold of the widest data prime / B_sk prime ("multiply_sum_fold_q" / "multiply_sum_fold_bsk")
+    u64 multiply_sum_launches = 0;             // launches of the summed tensor kernel: one per modulus set per hhe_multiply_sum call or packed FC chunk
+    u64 fc_packed_floors = 0;                  // polynomials floored per item by the last packed encrypted FC call: 3 r, or 3 for hhe_fc_packed_sum_ks
     int rot_hoist = 1;                         // hhe_rotate_rows_many_ks and the hoisted packed FC: 1 = children of a trie node share the digit transforms of its c1
                                                // (HHE_ROT_HOIST; 0: every step through op_rotate_rows, 2: every chunk also recomputed that way -- tests)
     u64 rot_many_fallbacks = 0;                // chunks recomputed step by step because a digit load met a zero residue (hhe_ctx_query("rot_many_fallbacks"))

@@ -1696,10 +1696,48 @@ template <bool BCAST> HD void tensor_body_t(const TensorArgs &a, size_t gid)
     a.d[((b * 3 + 1) * lim + j) * n + i] = barrett128(s.lo, s.hi, m);
     a.d[((b * 3 + 2) * lim + j) * n + i] = mulmod(a1, b1, m);
 }
+// The sum of a.sum tensor products per item (hhe_multiply_sum): gid over [limbs][N / 128][B][64].  A lane holds two neighbouring
+// coefficients (16 B loads and stores) and the three polynomials' sums in 128 bits, reduced every a.fold addends (tensor_sum_fold;
+// acc_mac_nw checks that no sum wraps under -DHHE_RANGE_CHECK) and once at the end: every output word is written once.  The items
+// are the fastest index above the wavefront, so the waves of a workgroup and the workgroups that follow it read the same 1 KiB of a
+// shared second operand (b_div set: the resident diagonals) -- it comes from the cache, not once per item from memory.
+HD void tensor_sum_body(const TensorArgs &a, size_t gid)
+{
+    const size_t n = (size_t)1 << a.logn;
+    const u32 lane = (u32)gid & 63;
+    size_t r = gid >> 6;
+    const size_t b = r % (u32)a.B;
+    r /= (u32)a.B;
+    const size_t tile = r & (((size_t)1 << (a.logn - 7)) - 1);
+    const size_t j = r >> (a.logn - 7);
+    if (j >= (size_t)a.limbs) return;
+    const ModDev m = mod_at(a.mods, a.mod_base + (int)j);
+    const size_t ps = (size_t)a.limbs * n, i = (tile << 7) + 2 * lane;
+    const size_t ka = (size_t)a.B * 2 * ps, kb = a.b_div ? 2 * ps : ka;  // from one addend's operands to the next
+    const u64 *pa = a.a + b * 2 * ps + j * n + i;
+    const u64 *pb = a.b + (a.b_div ? 0 : b * 2 * ps) + j * n + i;
+    Acc128 s[3][2] = {};
+    int left = a.fold;
+    for (int k = 0; k < a.sum; k++, pa += ka, pb += kb) {
+        const U2 a0 = ld2(pa), a1 = ld2(pa + ps), b0 = ld2(pb), b1 = ld2(pb + ps);
+        acc_mac_nw(s[0][0], a0.a, b0.a); acc_mac_nw(s[0][1], a0.b, b0.b);
+        acc_mac_nw(s[1][0], a0.a, b1.a); acc_mac_nw(s[1][1], a0.b, b1.b);
+        acc_mac_nw(s[1][0], a1.a, b0.a); acc_mac_nw(s[1][1], a1.b, b0.b);
+        acc_mac_nw(s[2][0], a1.a, b1.a); acc_mac_nw(s[2][1], a1.b, b1.b);
+        if (--left == 0) {
+            left = a.fold;
+            for (int p = 0; p < 3; p++)
+                for (int e = 0; e < 2; e++) { s[p][e].lo = barrett128(s[p][e].lo, s[p][e].hi, m); s[p][e].hi = 0; }
+        }
+    }
+    u64 *d = a.d + b * 3 * ps + j * n + i;
+    for (int p = 0; p < 3; p++) st2(d + p * ps, U2{barrett128(s[p][0].lo, s[p][0].hi, m), barrett128(s[p][1].lo, s[p][1].hi, m)});
+}
 // the launch as the tests-only emulator loops it; on the device each form is a kernel of its own
 HD void tensor_body(const TensorArgs &a, size_t gid)
 {
-    if (a.b_div) tensor_body_t<true>(a, gid);
+    if (a.sum) tensor_sum_body(a, gid);
+    else if (a.b_div) tensor_body_t<true>(a, gid);
     else tensor_body_t<false>(a, gid);
 }
 

@@ -647,6 +647,7 @@ __global__ void __launch_bounds__(ELT_THREADS) bsgs_diag_kernel(BsgsDiagArgs a) 
 __global__ void __launch_bounds__(ELT_THREADS) behz_extend_kernel(BehzExtendArgs a) { behz_extend_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) tensor_kernel(TensorArgs a) { tensor_body_t<false>(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) tensor_bcast_kernel(TensorArgs a) { tensor_body_t<true>(a, GID); }
+__global__ void __launch_bounds__(ELT_THREADS) tensor_sum_kernel(TensorArgs a) { tensor_sum_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) behz_floor_kernel(BehzFloorArgs a) { behz_floor_body(a, GID); }
 
 #define LAUNCH1D(kern, total, s, ...)                                                                   \
@@ -748,7 +749,8 @@ void k_bsgs_diag(const BsgsDiagArgs &a, rt_stream s) { LAUNCH1D(bsgs_diag_kernel
 void k_behz_extend(const BehzExtendArgs &a, rt_stream s) { LAUNCH1D(behz_extend_kernel, (size_t)a.P << a.logn, s, a); }
 void k_tensor(const TensorArgs &a, rt_stream s)
 {
-    if (a.b_div) LAUNCH1D(tensor_bcast_kernel, ((size_t)a.B * a.limbs) << a.logn, s, a);
+    if (a.sum) LAUNCH1D(tensor_sum_kernel, ((size_t)a.B * a.limbs) << (a.logn - 1), s, a);  // a lane holds two coefficients
+    else if (a.b_div) LAUNCH1D(tensor_bcast_kernel, ((size_t)a.B * a.limbs) << a.logn, s, a);
     else LAUNCH1D(tensor_kernel, ((size_t)a.B * a.limbs) << a.logn, s, a);
 }
 void k_behz_floor(const BehzFloorArgs &a, rt_stream s) { LAUNCH1D(behz_floor_kernel, (size_t)a.P << a.logn, s, a); }
