@@ -173,20 +173,66 @@ HD u64 plain_scaled32(u32 m, u32 fix, u64 delta, u64 delta_s, u64 q)
 #ifndef FIN_ITEM_C1_EARLY
 #define FIN_ITEM_C1_EARLY 1
 #endif
-// limb j of one pair with the 32-bit scaling: what fin_store_limb writes; C1: the c1 half too
-template <bool C1> HD void fin_store_limb32(const NttArgs &a, const NttGeom &g, int gi, int j, const u32 *mv, const u32 *fix, U2 c0, U2 c1)
+// the c0 word as one lazy sum with two conditional subtractions (fin_word32; FIN_ITEM_LAZY 0: negmod, plain_scaled32, addmod: A/B builds)
+#ifndef FIN_ITEM_LAZY
+#define FIN_ITEM_LAZY 1
+#endif
+// word `w` of an array whose base is uniform over the workgroup, for w < 2^29: the byte offset is formed in 32 bits, so the access
+// takes a scalar base and ONE offset register where a 64-bit index costs a 64-bit vector address per access
+HD gptr fin_at(gptr base, u32 w)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (gptr)((const __attribute__((address_space(1))) char *)base + (w << 3));
+#else
+    return base + w;
+#endif
+}
+HD u64 *fin_at(u64 *base, u32 w) { return reinterpret_cast<u64 *>(reinterpret_cast<char *>(base) + (w << 3)); }
+// The item's keystream [2][L][N].  The table entry is uniform over the workgroup (the item is the workgroup) and constant while
+// the kernel runs, so it is read through the constant address space: one scalar load per kernel, handed to every phase.
+HD gptr fin_item_ks(const NttArgs &a, int item)
+{
+    return as_global(a.mul_ptrs ? ld_const(&a.mul_ptrs[item]) : a.mul + ((size_t)item * 2 * a.L << a.logn));
+}
+// -c0 + (m delta_j + fix) mod q_j with ONE reduction.  With H as in plain_scaled32, r = m delta_j - H q_j lies in [0, 2 q_j); c0 is
+// a residue, so q_j - c0 lies in (0, q_j] and needs no test for zero; fix < t < q_j (fin_scale32_ok).  The sum
+//   u = (q_j - c0) + r + fix  lies in (0, 3 q_j + t), below 4 q_j < 2^63 (q_j < 2^61): no 64-bit carry,
+// and u - 2 q_j where u >= 2 q_j, then u - q_j where u >= q_j, leave the canonical residue: the word
+// addmod(negmod(c0), plain_scaled32(m, fix)) of the three-step form, two conditional subtractions instead of four.
+HD u64 fin_word32(u64 c0, u32 m, u32 fix, u64 delta, u64 delta_s, u64 q)
+{
+    const u64 h = ((u64)m * (u32)(delta_s >> 32) + mulhi32(m, (u32)delta_s)) >> 32;
+    const u64 r = (u64)m * delta - h * q;
+    u64 u = (q - c0) + r + fix;
+#if defined(HHE_RANGE_CHECK) && !defined(__HIP_DEVICE_COMPILE__)
+    if (r >= 2 * q) hhe_range_violation("fused 32-bit scaling: remainder not below 2q");
+    if (c0 >= q || fix >= q || u == 0 || u >= 4 * q) hhe_range_violation("fused 32-bit scaling: lazy sum not in (0, 4q)");
+#endif
+    const u64 q2 = q << 1;
+    u = u >= q2 ? u - q2 : u;
+    return u >= q ? u - q : u;
+}
+// limb j of one pair with the 32-bit scaling: what fin_store_limb writes; C1: the c1 half too.  `o` is the item's output [2][L][N]:
+// an address is that base, uniform over the workgroup, plus a 32-bit offset (fin_at; 2 L N <= 2^21 words)
+template <bool C1> HD void fin_store_limb32(const NttArgs &a, u64 *o, u32 n, u32 gi, int j, const u32 *mv, const u32 *fix, U2 c0, U2 c1)
 {
     const u64 q = mod_at_u(a.mods, j).q;
     const u64 d = ld_const(&a.fin->delta[j]), ds = ld_const(&a.fin->delta_s[j]);
-    u64 *o = a.aux_out + ((size_t)g.poly * 2 * a.L + j) * g.n + gi;
     U2 o0;
+#if FIN_ITEM_LAZY
+    o0.a = fin_word32(c0.a, mv[0], fix[0], d, ds, q);
+    o0.b = fin_word32(c0.b, mv[1], fix[1], d, ds, q);
+#else
     o0.a = addmod(negmod(c0.a, q), plain_scaled32(mv[0], fix[0], d, ds, q), q);
     o0.b = addmod(negmod(c0.b, q), plain_scaled32(mv[1], fix[1], d, ds, q), q);
-    st2_stream(o, o0);
-    if (C1) st2_stream(o + (size_t)a.L * g.n, U2{negmod(c1.a, q), negmod(c1.b, q)});
+#endif
+    st2_stream(fin_at(o, (u32)j * n + gi), o0);
+    if (C1) st2_stream(fin_at(o, (u32)(a.L + j) * n + gi), U2{negmod(c1.a, q), negmod(c1.b, q)});
 }
-// SCALE32 = false (the default) is the shared definition: fin_store_fetch / fin_store_vals, both halves written here
-template <int T, bool SCALE32 = false, bool C1 = !FIN_ITEM_C1_EARLY> HD void fin_item_store(const NttArgs &a, int item, int tid, const u32 *lds)
+// SCALE32 = false (the default) is the shared definition: fin_store_fetch / fin_store_vals, both halves written here.
+// kp = fin_item_ks(a, item), which the 32-bit instantiation reads through
+template <int T, bool SCALE32 = false, bool C1 = !FIN_ITEM_C1_EARLY>
+HD void fin_item_store(const NttArgs &a, int item, int tid, const u32 *lds, gptr kp)
 {
     constexpr int G = FIN_ITEM_G;
     NttGeom g = {};
@@ -216,57 +262,66 @@ template <int T, bool SCALE32 = false, bool C1 = !FIN_ITEM_C1_EARLY> HD void fin
         }
     } else {
         const FinScale32 sc = fin_scale32_consts(a.fin);
-        const gptr kp = as_global(a.mul_ptrs ? a.mul_ptrs[item] : a.mul + (size_t)item * 2 * a.L * g.n);
+        const u32 n = (u32)g.n, L = (u32)a.L;
+        u64 *o = a.aux_out + ((size_t)item * 2 * L << a.logn);
         for (int e0 = tid; e0 < E2; e0 += G * T) {
             U2 k0[G][FIN_PRE], k1[G][FIN_PRE] = {};
-            int gi[G];
+            u32 gi[G];
 #pragma unroll
             for (int k = 0; k < G; k++) {
                 if (e0 + k * T >= E2) continue;
-                gi[k] = 2 * (e0 + k * T);
+                gi[k] = 2 * (u32)(e0 + k * T);
 #pragma unroll
                 for (int j = 0; j < FIN_PRE; j++)
                     if (j < a.L) {
-                        k0[k][j] = ld2g(kp + (size_t)j * g.n + gi[k]);
-                        if (C1) k1[k][j] = ld2g(kp + (size_t)(a.L + j) * g.n + gi[k]);
+                        k0[k][j] = ld2g(fin_at(kp, (u32)j * n + gi[k]));
+                        if (C1) k1[k][j] = ld2g(fin_at(kp, (L + j) * n + gi[k]));
                     }
             }
 #pragma unroll
             for (int k = 0; k < G; k++) {
                 if (e0 + k * T >= E2) continue;
-                const u32 at = fin_lds_at((u32)gi[k]);
+                const u32 at = fin_lds_at(gi[k]);
                 const u32 p0 = lds[at & ~1u], p1 = lds[at | 1u];
                 const bool sw = at & 1;
                 const u32 mv[2] = {csub32(sw ? p1 : p0, t), csub32(sw ? p0 : p1, t)};
                 const u32 fix[2] = {plain_fix32(sc, mv[0]), plain_fix32(sc, mv[1])};
 #pragma unroll
                 for (int j = 0; j < FIN_PRE; j++)
-                    if (j < a.L) fin_store_limb32<C1>(a, g, gi[k], j, mv, fix, k0[k][j], k1[k][j]);
+                    if (j < a.L) fin_store_limb32<C1>(a, o, n, gi[k], j, mv, fix, k0[k][j], k1[k][j]);
                 for (int j = FIN_PRE; j < a.L; j++)
-                    fin_store_limb32<C1>(a, g, gi[k], j, mv, fix, ld2g(kp + (size_t)j * g.n + gi[k]),
-                                         C1 ? ld2g(kp + (size_t)(a.L + j) * g.n + gi[k]) : U2{0, 0});
+                    fin_store_limb32<C1>(a, o, n, gi[k], j, mv, fix, ld2g(fin_at(kp, (u32)j * n + gi[k])),
+                                         C1 ? ld2g(fin_at(kp, (L + j) * n + gi[k])) : U2{0, 0});
             }
         }
     }
 }
+template <int T, bool SCALE32 = false, bool C1 = !FIN_ITEM_C1_EARLY>
+HD void fin_item_store(const NttArgs &a, int item, int tid, const u32 *lds)
+{
+    fin_item_store<T, SCALE32, C1>(a, item, tid, lds, fin_item_ks(a, item));
+}
 
 // slice `slice` of `nslices` of the item's c1 half, out[b][1][j] = -c1[j] (L N words as 16-byte pairs, limb j the pairs
 // [j N/2, (j+1) N/2)): loads of G pairs, then their stores.  The kernel issues one slice in front of each of its other phases --
-// clear, encode, every register round: fin_item_c1_slices -- so that memory drains it while the wave works in LDS; a barrier
-// waits for the wave's outstanding memory operations, which is why a slice is sized to one phase and the half is not hoisted whole.
+// clear, encode, every register round: fin_item_c1_slices -- so that memory drains it while the wave works in LDS.  A barrier
+// itself does not wait for the wave's stores (the compiled code waits for LDS and scalar loads in front of it, not for vector
+// memory); the next vector load that is waited for does, the counter being one for loads and stores: a round's first twiddle.
+// So a slice is sized to one phase and the half is not hoisted whole.  `ks` = fin_item_ks(a, item).
 template <int LOGN> constexpr int fin_item_c1_slices() { return 2 + FinItemSched<LOGN>::R; }
 #ifndef FIN_ITEM_C1_G
 #define FIN_ITEM_C1_G 4
 #endif
-template <int T> HD void fin_item_c1(const NttArgs &a, int item, int tid, int slice, int nslices)
+template <int T> HD void fin_item_c1(const NttArgs &a, int item, int tid, int slice, int nslices, gptr ks)
 {
     constexpr int G = FIN_ITEM_C1_G;
-    const int n = 1 << a.logn, half = a.logn - 1;
+    const int half = a.logn - 1;
     const int P = a.L << half;  // at most 2^19 pairs: P * nslices fits an int
     // slice boundaries on multiples of 8 pairs (128 bytes; P is one): no cache line is written in two parts by two phases or two waves
     const int lo = (P * slice / nslices) & ~7, hi = slice + 1 == nslices ? P : (P * (slice + 1) / nslices) & ~7;
-    const gptr kp = as_global(a.mul_ptrs ? a.mul_ptrs[item] : a.mul + (size_t)item * 2 * a.L * n) + (size_t)a.L * n;
-    u64 *o = a.aux_out + ((size_t)item * 2 + 1) * a.L * n;
+    // both bases are uniform over the workgroup; a pair is addressed from them by fin_at (L N <= 2^20 words)
+    const gptr kp = ks + ((size_t)a.L << a.logn);
+    u64 *o = a.aux_out + (((size_t)item * 2 + 1) * a.L << a.logn);
     for (int j = lo >> half; (j << half) < hi; j++) {  // the limbs the slice touches: the prime is uniform over the workgroup
         const u64 q = mod_at_u(a.mods, j).q;
         const int p_lo = lo > (j << half) ? lo : (j << half), p_hi = hi < ((j + 1) << half) ? hi : ((j + 1) << half);
@@ -274,10 +329,14 @@ template <int T> HD void fin_item_c1(const NttArgs &a, int item, int tid, int sl
             U2 v[G];
 #pragma unroll
             for (int k = 0; k < G; k++)
-                if (p0 + k * T < p_hi) v[k] = ld2g(kp + 2 * (size_t)(p0 + k * T));
+                if (p0 + k * T < p_hi) v[k] = ld2g(fin_at(kp, 2 * (u32)(p0 + k * T)));
 #pragma unroll
             for (int k = 0; k < G; k++)
-                if (p0 + k * T < p_hi) st2_stream(o + 2 * (size_t)(p0 + k * T), U2{negmod(v[k].a, q), negmod(v[k].b, q)});
+                if (p0 + k * T < p_hi) st2_stream(fin_at(o, 2 * (u32)(p0 + k * T)), U2{negmod(v[k].a, q), negmod(v[k].b, q)});
         }
     }
+}
+template <int T> HD void fin_item_c1(const NttArgs &a, int item, int tid, int slice, int nslices)
+{
+    fin_item_c1<T>(a, item, tid, slice, nslices, fin_item_ks(a, item));
 }

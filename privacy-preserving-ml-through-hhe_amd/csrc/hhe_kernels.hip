@@ -165,15 +165,16 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) ntt_fin_kernel(NttArgs a)
 }
 // the finishing pass with one workgroup per item (hhe_fin_bodies.h): encode into LDS, the whole inverse transform mod t in 32-bit
 // words there, add_plain epilogue.  LDS is 4 N bytes, so N = 2^15 takes one CU per item and N = 2^14 places two items on a CU.
-// C1: fin_item_c1_slices<LOGN>() slices of the c1 half are issued, one in front of each phase; `slice` counts them (clear 0, encode 1)
+// C1: fin_item_c1_slices<LOGN>() slices of the c1 half are issued, one in front of each phase; `slice` counts them (clear 0, encode 1);
+// ks is the item's keystream (fin_item_ks)
 template <int LOGN, int R, bool C1 = false>
-static __device__ __forceinline__ void fin_item_rounds(const NttArgs &a, u32 *lds, int item = 0)
+static __device__ __forceinline__ void fin_item_rounds(const NttArgs &a, u32 *lds, int item = 0, gptr ks = nullptr)
 {
     if constexpr (R < FinItemSched<LOGN>::R) {
-        if constexpr (C1) fin_item_c1<FIN_ITEM_THREADS>(a, item, threadIdx.x, 2 + R, fin_item_c1_slices<LOGN>());
+        if constexpr (C1) fin_item_c1<FIN_ITEM_THREADS>(a, item, threadIdx.x, 2 + R, fin_item_c1_slices<LOGN>(), ks);
         fin_item_round<LOGN, FinItemSched<LOGN>::s0(R), FinItemSched<LOGN>::rho(R), FIN_ITEM_THREADS>(a, threadIdx.x, lds);
         __syncthreads();
-        fin_item_rounds<LOGN, R + 1, C1>(a, lds, item);
+        fin_item_rounds<LOGN, R + 1, C1>(a, lds, item, ks);
     }
 }
 template <int LOGN>
@@ -188,21 +189,23 @@ __global__ void __launch_bounds__(FIN_ITEM_THREADS) fin_item_kernel(NttArgs a)
     fin_item_rounds<LOGN, 0>(a, lds);
     fin_item_store<FIN_ITEM_THREADS>(a, item, threadIdx.x, lds);
 }
-// the same with the 32-bit scaling of the plaintext (FinArgs::scale32) and the c1 half written ahead of and between the phases
+// the same with the 32-bit scaling of the plaintext (FinArgs::scale32) and the c1 half written ahead of and between the phases;
+// the item's keystream pointer is read once, with a scalar load, and handed to every phase
 template <int LOGN>
 __global__ void __launch_bounds__(FIN_ITEM_THREADS) fin_item32_kernel(NttArgs a)
 {
     __shared__ __attribute__((aligned(16))) u32 lds[1 << LOGN];
     constexpr bool C1 = FIN_ITEM_C1_EARLY;
     const int item = blockIdx.x;
-    if constexpr (C1) fin_item_c1<FIN_ITEM_THREADS>(a, item, threadIdx.x, 0, fin_item_c1_slices<LOGN>());
+    const gptr ks = fin_item_ks(a, item);
+    if constexpr (C1) fin_item_c1<FIN_ITEM_THREADS>(a, item, threadIdx.x, 0, fin_item_c1_slices<LOGN>(), ks);
     fin_item_clear<FIN_ITEM_THREADS>(a, threadIdx.x, lds);
     __syncthreads();
-    if constexpr (C1) fin_item_c1<FIN_ITEM_THREADS>(a, item, threadIdx.x, 1, fin_item_c1_slices<LOGN>());
+    if constexpr (C1) fin_item_c1<FIN_ITEM_THREADS>(a, item, threadIdx.x, 1, fin_item_c1_slices<LOGN>(), ks);
     fin_item_encode<FIN_ITEM_THREADS>(a, item, threadIdx.x, lds);
     __syncthreads();
-    fin_item_rounds<LOGN, 0, C1>(a, lds, item);
-    fin_item_store<FIN_ITEM_THREADS, true>(a, item, threadIdx.x, lds);
+    fin_item_rounds<LOGN, 0, C1>(a, lds, item, ks);
+    fin_item_store<FIN_ITEM_THREADS, true, !C1>(a, item, threadIdx.x, lds, ks);
 }
 static void launch_fin_item(const NttArgs &a, hipStream_t st)
 {
