@@ -323,7 +323,7 @@ public:
     {
         DevBuf a(ct_words() * 8), o3(ct_words(3) * 8);
         upload(a.u64(), vi);
-        check(hhe_multiply(h(), a.u64(), a.u64(), o3.u64(), 1));
+        check(hhe_square(h(), a.u64(), o3.u64(), 1));  // the words of hhe_multiply(a, a): one operand extension, the squaring kernel
         check(hhe_relinearize_ks(h(), or_empty(rk).get(), o3.u64(), a.u64(), 1));
         download(a.u64(), 1, 2, dst);
     }
@@ -477,6 +477,43 @@ public:
         upload(d, vi);
         check(hhe_fc_packed_sum_ks(h(), r.get(), g.get(), m.get(), d, d, 1, hoisted ? 1 : 0));
         download(d, 1, 2, dst);
+    }
+    // ---- chainable packed FC (hhe_gfx950.h "Chainable packed FC"): the diagonals that do not wrap.  An open handle takes fc_open and mlp,
+    // a cyclic one the three forms above; the device calls refuse the other kind.
+    std::pair<size_t, size_t> fc_open_shape(size_t rows, size_t cols) const
+    {
+        size_t r = 0, c = 0;
+        check(hhe_fc_open_shape(n_, rows, cols, &r, &c));
+        return {r, c};
+    }
+    EncMatrix enc_matrix_open(const std::vector<const uint64_t *> &diagonals, size_t rows, size_t cols)
+    {
+        if (diagonals.size() != fc_open_shape(rows, cols).first) throw std::invalid_argument("enc_matrix_open: one ciphertext per open diagonal");
+        DevBuf d(diagonals.size() * ct_words() * 8);
+        for (size_t i = 0; i < diagonals.size(); i++) upload(d.u64() + i * ct_words(), diagonals[i]);
+        hhe_enc_matrix *raw = nullptr;
+        check(hhe_enc_matrix_create_open(h(), d.u64(), rows, cols, &raw));
+        return EncMatrix(raw, hhe_enc_matrix_destroy);
+    }
+    // the network on one ciphertext: layers[0] open, square + relinearize, layers[1] open, ...; one layer is fc_open.  No slot of the input
+    // outside [0, cols) of the first layer needs to be zero
+    template <class RK, class GK, class Sink> void mlp(const uint64_t *vi, const std::vector<EncMatrix> &layers, const RK &rk, const GK &gk, Sink dst)
+    {
+        std::vector<const hhe_enc_matrix *> raw;
+        for (const EncMatrix &m : layers) {
+            if (!m) throw std::invalid_argument("mlp: no encrypted matrix");
+            raw.push_back(m.get());
+        }
+        std::lock_guard<std::mutex> lk(arena_.mutex());
+        const KeySet r = named(set(rk), "mlp: empty key object"), g = named(set(gk), "mlp: empty key object");
+        uint64_t *d = arena_.get(0, ct_words() * 8);
+        upload(d, vi);
+        check(hhe_mlp_ks(h(), r.get(), g.get(), raw.data(), raw.size(), d, d, 1));
+        download(d, 1, 2, dst);
+    }
+    template <class RK, class GK, class Sink> void fc_open(const uint64_t *vi, const EncMatrix &m, const RK &rk, const GK &gk, Sink dst)
+    {
+        mlp(vi, std::vector<EncMatrix>{m}, rk, gk, dst);
     }
     // Hoisted rotations (hhe_rotate_rows_many_ks): item k of dst = Evaluator::rotate_rows(in, steps[k], gk), the digit transforms of `in`
     // (and of every node of the steps' NAF trie) computed once.  An empty step list is refused by the device call.

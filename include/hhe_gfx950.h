@@ -93,7 +93,8 @@ int hhe_ctx_profile(hhe_ctx *c, int enable);
 int hhe_ctx_profile_read(hhe_ctx *c, char *kernel_name, size_t name_cap, uint64_t *launches, double *total_ms, uint64_t *items);
 /* derived parameters, for cross-checking against SEAL's context: what in
  * {"root" i<K, "bsk" i<=L (B_0.., m_sk), "gamma", "galois_elt" i=step, "fc_fallbacks", "fc_csum_closes", "fc_packed_key_switches",
- * "add_many_launches", "rot_hoist", "rot_many_fallbacks", "rot_many_key_switches", "rot_many_launches", "rot_many_group"};
+ * "add_many_launches", "rot_hoist", "rot_many_fallbacks", "rot_many_key_switches", "rot_many_launches", "rot_many_group",
+ * "mlp_layers", "mlp_key_switches", "tensor_launches", "square_launches"};
  * which kernels the context dispatches to (read-only diagnostics): "row_kernel" (1 = the fused key-switch row kernels run,
  * 0 = the separate-kernel path), "pm_ok" i<K (coefficient prime i has the pseudo-Mersenne form the lazy kernels need),
  * "digit_reduce" (key-switch digits are reduced before their transforms: some q_I >= 4 q_J) */
@@ -374,6 +375,52 @@ int hhe_fc_packed_hoisted_galois_steps(size_t N, size_t rows, size_t cols, int *
  * 3 r for the two other forms; the sum kernel of hhe_add_many is not launched.  Synchronous. */
 int hhe_fc_packed_sum_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *mat, const uint64_t *vi_dptr,
                          uint64_t *out_dptr, size_t B, int hoisted);
+/* ---- Chainable packed FC: diagonals that do not wrap ("open"), the square, and the FC-square-FC network in one call.
+ *      The output of a cyclic layer above is not a legal input of the next: partial sums outside [0, rows), and a precondition on slots
+ *      [c, N/2).  The open layout needs neither a precondition nor a mask between layers.
+ *      Shape: r = the smallest power of two >= rows; c = the smallest power of two >= cols + r - 1; c <= N/2, else HHE_ERR_TOO_FEW_SLOTS.
+ *      Diagonals (host): D_e[j] = M[j mod r][j - e] if j mod r < rows and 0 <= j - e < cols, else 0, e in [0, r), j in [0, c); the analyst
+ *      encodes D_e into slots [0, c) of row 0 and encrypts it: W_0 .. W_{r-1}.
+ *      The layer on an input ciphertext x, in SEAL's operations:
+ *        1. rot_0 = x;  rot_e = rotate_rows(x, -e, gk), e = 1 .. r-1   (every rotation from x, served as hhe_rotate_rows_many_ks serves them)
+ *        2. y = relinearize(multiply_sum(rot_0 .. rot_{r-1}, W_0 .. W_{r-1}), rk)   (hhe_multiply_sum, K = r, the resident diagonals)
+ *        3. for s = r, 2r, .., c/2:  y = add(y, rotate_rows(y, s, gk))
+ *      Slot m < rows of y is sum_k sum_e x[m + kr - e] M[m][m + kr - e]; kr - e takes every value in [-(r-1), c - r] once, so every column
+ *      in [0, cols) is met once, and every other slot of x meets a zero of a diagonal before any sum: THERE IS NO PRECONDITION on the
+ *      input.  Row 1 of the batching is carried along independently.  The other slots of y hold partial sums, which the next open layer
+ *      (or the square before it) may be handed as they are. ---- */
+/* host only: r and c of the open layout; refusals as hhe_fc_packed_shape, HHE_ERR_TOO_FEW_SLOTS when c > N/2 */
+int hhe_fc_open_shape(size_t N, size_t rows, size_t cols, size_t *r_out, size_t *c_out);
+/* host only: the open diagonals of M_hptr (row-major rows x cols, entries < t, else HHE_ERR_INVALID) as slot vectors vals_hptr [r][c] */
+int hhe_fc_open_diagonals(uint64_t t, const uint64_t *M_hptr, size_t rows, size_t cols, uint64_t *vals_hptr);
+/* host only: the keys of the one-pass schedule: -1 .. -(r-1), then r, 2r, .. below c.  *count as hhe_fc_packed_galois_steps */
+int hhe_fc_open_galois_steps(size_t N, size_t rows, size_t cols, int *steps_out, size_t *count);
+/* hhe_enc_matrix_create for the open layout: the same handle type and resident form, marked open, r and c of the open shape.  The
+ * hhe_fc_packed calls refuse an open handle and the calls below a cyclic one (HHE_ERR_INVALID, `out` untouched). */
+int hhe_enc_matrix_create_open(hhe_ctx *c, const uint64_t *wdiag_dptr, size_t rows, size_t cols, hhe_enc_matrix **out);
+/* One open layer.  Keys, in-place call, chunking (max(1, HHE_CHUNK / r) items per chunk), levels, refusals and the exactness fallback of
+ * the hoisted rotation (HHE_ROT_HOIST) are those of hhe_fc_packed_sum_ks with hoisted != 0; r >= 2 above "behz_sum_cap" is refused.  The
+ * tail steps need keys of their own; the steps -e are served from gk directly or through their NAF terms.  After the call
+ * "fc_packed_key_switches" is the trie's nodes + log2(c / r) and "fc_packed_floors" is 3.  Synchronous. */
+int hhe_fc_open_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *mat, const uint64_t *vi_dptr,
+                   uint64_t *out_dptr, size_t B);
+/* Evaluator::square at size 2: a [B][2][L][N] -> out3 [B][3][L][N], the words of hhe_multiply(a, a), with hhe_multiply's refusals.  One
+ * operand extension instead of a second operand, and a tensor kernel of its own that reads the operand's two polynomials once and
+ * writes a0^2, 2 a0 a1, a1^2 ("square_launches" counts its launches, two per call; hhe_multiply keeps the one-product kernel, counted by
+ * "tensor_launches").  Enqueues on the context's stream like hhe_multiply. */
+int hhe_square(hhe_ctx *c, const uint64_t *a_dptr, uint64_t *out3_dptr, size_t B);
+/* The network: mats_hptr is a host array of n_layers open handles;
+ *   x_0 = vi;  y_k = fc_open(mats[k], x_k);  x_{k+1} = relinearize(square(y_k), rk);  out = y_{n_layers - 1}.
+ * The words of `out` are the words of that composition made from hhe_fc_open_ks, hhe_square and hhe_relinearize_ks; n_layers == 1 gives
+ * hhe_fc_open_ks.  A chunk of max(1, HHE_CHUNK / max_k r_k) items runs all its layers on its lane with no host wait in between; the
+ * plans and tables of all layers are made before the first chunk.  One flag per chunk covers the hoisted rotations of every layer: a
+ * flagged chunk is recomputed whole, from vi, step by step, after the wait.  out == vi is allowed.
+ * Refused before anything is written: n_layers == 0, a null or cyclic handle, a handle of another context, rows of layer k != cols of
+ * layer k + 1, a layer above "behz_sum_cap" (HHE_ERR_INVALID); a missing relinearization or Galois key of any layer (their codes).
+ * "mlp_layers" and "mlp_key_switches" (Galois key switches per item, summed over the layers; relinearizations are not counted)
+ * describe the last call.  Synchronous.  Not built: a bias (hhe_add_plain between calls), a change of level between layers. */
+int hhe_mlp_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *const *mats_hptr, size_t n_layers,
+               const uint64_t *vi_dptr, uint64_t *out_dptr, size_t B);
 /* Evaluator::add_many (seal/evaluator.h:150) for K stacked batches in_dptr [K][B][size][L][N], size 2 or 3: out [B][size][L][N] = their
  * sum, in ONE kernel launch whatever K is (hhe_ctx_query("add_many_launches") counts them); the sum of a coefficient is kept in two
  * words and reduced once.  out may be one of the K operands.  K == 0, B == 0, a null pointer or another size: HHE_ERR_INVALID.

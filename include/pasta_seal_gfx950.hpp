@@ -116,13 +116,35 @@ struct EncMatrix {
     EncMatrix() = default;
     EncMatrix(std::shared_ptr<HheContext> con, const std::vector<Ciphertext> &diagonals, size_t rows, size_t cols)
         : EncMatrix(con, con, diagonals, rows, cols) {}
-    EncMatrix(std::shared_ptr<HheContext> con, std::shared_ptr<hhe::AdapterCore> at, const std::vector<Ciphertext> &diagonals, size_t rows, size_t cols)
-        : context(std::move(con)), core(std::move(at)), rows(rows), cols(cols)
+    // open: the diagonals that do not wrap (hhe_fc_open_diagonals) -- the kind fc_open and mlp take; a cyclic one takes the fc_packed forms
+    EncMatrix(std::shared_ptr<HheContext> con, std::shared_ptr<hhe::AdapterCore> at, const std::vector<Ciphertext> &diagonals, size_t rows, size_t cols,
+              bool open = false)
+        : context(std::move(con)), core(std::move(at)), rows(rows), cols(cols), open(open)
     {
         std::vector<const uint64_t *> p;
         for (auto &ct : diagonals) p.push_back(detail::level_words(*core, context->data_limbs(), ct));
-        handle = core->enc_matrix(p, rows, cols);
+        handle = open ? core->enc_matrix_open(p, rows, cols) : core->enc_matrix(p, rows, cols);
     }
+    // the network layers[0], square + relinearize, layers[1], ... on one ciphertext (hhe_mlp_ks); one layer is the open layer alone.
+    // Every layer is an open matrix of one core; rk / gal_keys: the parties' ordinary, top-level key objects
+    static void mlp(const std::vector<const EncMatrix *> &layers, const Ciphertext &vi, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out)
+    {
+        if (layers.empty() || !layers[0] || !layers[0]->core) throw std::invalid_argument("mlp: no encrypted matrix");
+        const EncMatrix &first = *layers[0];
+        std::vector<hhe::EncMatrix> handles;
+        for (const EncMatrix *m : layers) {
+            if (!m || !m->core) throw std::invalid_argument("mlp: no encrypted matrix");
+            if (m->core.get() != first.core.get()) throw std::invalid_argument("mlp: the layers are not at one level");
+            handles.push_back(m->handle);
+        }
+        const bool top = first.core.get() == first.context.get();
+        hhe::KeySet r = first.context->keys().relin(detail::words(rk)), g = first.context->keys().galois(detail::words(gal_keys));
+        if (!top) { r = first.core->derived(r); g = first.core->derived(g); }
+        const uint64_t *x = detail::level_words(*first.core, first.context->data_limbs(), vi);
+        first.core->mlp(x, handles, r, g, detail::into_level(*first.core, out));
+        if (top) out.limbs = 0;  // the data level, as every cipher object's results
+    }
+    void apply_open(const Ciphertext &vi, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out) const { mlp({this}, vi, rk, gal_keys, out); }
     // slots [0, rows) of the decryption of `out` are (M x) mod t; rk / gal_keys: the parties' ordinary, top-level key objects
     // hoisted: the rotation chain of the layer as rotations of one ciphertext (fc_packed_hoisted)
     // sum: one BEHZ floor over the sum of the layer's r products (fc_packed_sum), with either rotation schedule
@@ -146,6 +168,7 @@ struct EncMatrix {
     std::shared_ptr<hhe::AdapterCore> core;   // where the handle lives: the chain's core, or a level's
     hhe::EncMatrix handle;                    // declared after the cores: released before them
     size_t rows = 0, cols = 0;
+    bool open = false;
 };
 
 // What SEALZpCipher::level(levels_from_last) returns: the evaluation members of a cipher object, bound to one level of the modulus
@@ -210,6 +233,21 @@ public:
     {
         if (mat.core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
         mat.apply(vi, rk, gal_keys, out);
+    }
+    // chainable packed FC at this level: open diagonals, one open layer, the FC-square-FC network
+    EncMatrix enc_matrix_open(const std::vector<Ciphertext> &diagonals, size_t rows, size_t cols)
+    {
+        return EncMatrix(context, core, diagonals, rows, cols, true);
+    }
+    void fc_open(const Ciphertext &vi, const EncMatrix &mat, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out)
+    {
+        mlp({&mat}, vi, rk, gal_keys, out);
+    }
+    void mlp(const std::vector<const EncMatrix *> &layers, const Ciphertext &vi, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &vo)
+    {
+        for (const EncMatrix *m : layers)
+            if (m && m->core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
+        EncMatrix::mlp(layers, vi, rk, gal_keys, vo);
     }
     void fc_packed_hoisted(const Ciphertext &vi, const EncMatrix &mat, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out)
     {
@@ -390,6 +428,21 @@ public:
     void packed_square(Ciphertext &vo, const Ciphertext &vi)  // evaluator.square + relinearize_inplace(he_rk)
     {
         context->square_relinearize(detail::words(*context, vi), rk_set, detail::into(*context, vo));
+    }
+
+    // Chainable packed FC (no reference counterpart: hhe_pktnn_2fc_inference stops after fc1): the analyst's open diagonals as a resident
+    // matrix, one open layer, and the FC-square-FC network as one device call, with the key objects the call names
+    EncMatrix enc_matrix_open(const std::vector<Ciphertext> &diagonals, size_t rows, size_t cols)
+    {
+        return EncMatrix(context, context, diagonals, rows, cols, true);
+    }
+    void fc_open(const Ciphertext &vi, const EncMatrix &mat, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &out)
+    {
+        EncMatrix::mlp({&mat}, vi, rk, gal_keys, out);
+    }
+    void mlp(const std::vector<const EncMatrix *> &layers, const Ciphertext &vi, const RelinKeys &rk, const GaloisKeys &gal_keys, Ciphertext &vo)
+    {
+        EncMatrix::mlp(layers, vi, rk, gal_keys, vo);
     }
 
     // Hoisted rotations (no reference counterpart: SEAL rotates one step per call): out[k] = Evaluator::rotate_rows(ct, steps[k], gal_keys)
@@ -651,6 +704,18 @@ inline void fc_packed_sum(const pasta::Ciphertext &vi, const EncMatrix &mat, con
                           pasta::Ciphertext &out, bool hoisted = false)
 {
     mat.apply_sum(vi, rk, gal_keys, out, hoisted);
+}
+// The open layer (mat from enc_matrix_open) and the FC-square-FC network as ONE device call (hhe_gfx950.h "Chainable packed FC"): no slot
+// of vi outside [0, cols) of the first layer needs to be zero, and no mask stands between two layers
+inline void fc_open(const pasta::Ciphertext &vi, const EncMatrix &mat, const pasta::RelinKeys &rk, const pasta::GaloisKeys &gal_keys,
+                    pasta::Ciphertext &out)
+{
+    EncMatrix::mlp({&mat}, vi, rk, gal_keys, out);
+}
+inline void mlp(const std::vector<const EncMatrix *> &layers, const pasta::Ciphertext &vi, const pasta::RelinKeys &rk,
+                const pasta::GaloisKeys &gal_keys, pasta::Ciphertext &vo)
+{
+    EncMatrix::mlp(layers, vi, rk, gal_keys, vo);
 }
 // out[k] = Evaluator::rotate_rows(ct, steps[k], gal_keys), hoisted (hhe_gfx950.h "Hoisted rotations")
 inline void rotate_rows_many(pasta::HheContext &ctx, const pasta::Ciphertext &ct, const std::vector<int> &steps, const pasta::GaloisKeys &gal_keys,

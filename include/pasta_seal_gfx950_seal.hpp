@@ -182,13 +182,36 @@ struct EncMatrix {
     EncMatrix(std::shared_ptr<seal::SEALContext> con, const std::vector<seal::Ciphertext> &diagonals, std::size_t rows, std::size_t cols)
         : EncMatrix(con, gfx950::DeviceContext::get(*con), nullptr, con->first_parms_id(), diagonals, rows, cols) {}
     // at: the core of a level (null: the chain's own), level_id: that level's parms_id
+    // open: the diagonals that do not wrap (hhe_fc_open_diagonals) -- the kind fc_open and mlp take; a cyclic one takes the fc_packed forms
     EncMatrix(std::shared_ptr<seal::SEALContext> con, std::shared_ptr<gfx950::DeviceContext> dev, std::shared_ptr<hhe::AdapterCore> at,
-              seal::parms_id_type level_id, const std::vector<seal::Ciphertext> &diagonals, std::size_t rows, std::size_t cols)
-        : context(std::move(con)), device(std::move(dev)), core(at ? std::move(at) : std::shared_ptr<hhe::AdapterCore>(device)), id(level_id), rows(rows), cols(cols)
+              seal::parms_id_type level_id, const std::vector<seal::Ciphertext> &diagonals, std::size_t rows, std::size_t cols, bool open = false)
+        : context(std::move(con)), device(std::move(dev)), core(at ? std::move(at) : std::shared_ptr<hhe::AdapterCore>(device)), id(level_id), rows(rows), cols(cols),
+          open(open)
     {
         std::vector<const std::uint64_t *> p;
         for (const auto &ct : diagonals) p.push_back(in(ct));
-        handle = core->enc_matrix(p, rows, cols);
+        handle = open ? core->enc_matrix_open(p, rows, cols) : core->enc_matrix(p, rows, cols);
+    }
+    // the network layers[0], square + relinearize, layers[1], ... on one ciphertext (hhe_mlp_ks); one layer is the open layer alone.
+    // Every layer is an open matrix of one core; rk / gal_keys: the parties' ordinary, top-level key objects
+    static void mlp(const std::vector<const EncMatrix *> &layers, const seal::Ciphertext &vi, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys,
+                    seal::Ciphertext &out)
+    {
+        if (layers.empty() || !layers[0] || !layers[0]->core) throw std::invalid_argument("mlp: no encrypted matrix");
+        const EncMatrix &first = *layers[0];
+        std::vector<hhe::EncMatrix> handles;
+        for (const EncMatrix *m : layers) {
+            if (!m || !m->core) throw std::invalid_argument("mlp: no encrypted matrix");
+            if (m->core.get() != first.core.get()) throw std::invalid_argument("mlp: the layers are not at one level");
+            handles.push_back(m->handle);
+        }
+        hhe::KeySet r = first.device->relin_set(rk), g = first.device->galois_set(gal_keys);
+        if (first.core.get() != first.device.get()) { r = first.core->derived(r); g = first.core->derived(g); }
+        first.core->mlp(first.in(vi), handles, r, g, gfx950::DeviceContext::into_level(*first.context, out, first.id, 2));
+    }
+    void apply_open(const seal::Ciphertext &vi, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out) const
+    {
+        mlp({this}, vi, rk, gal_keys, out);
     }
     // slots [0, rows) of the decryption of `out` are (M x) mod t; rk / gal_keys: the parties' ordinary, top-level key objects
     // hoisted: the rotation chain of the layer as rotations of one ciphertext (fc_packed_hoisted)
@@ -213,6 +236,7 @@ struct EncMatrix {
     seal::parms_id_type id{};                       // the level of the diagonals, the inputs and the results
     hhe::EncMatrix handle;                          // declared after the cores: released before them
     std::size_t rows = 0, cols = 0;
+    bool open = false;
 
 private:
     const std::uint64_t *in(const seal::Ciphertext &ct) const
@@ -299,6 +323,22 @@ public:
     {
         if (mat.core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
         mat.apply(vi, rk, gal_keys, out);
+    }
+    // chainable packed FC at this level: open diagonals, one open layer, the FC-square-FC network
+    EncMatrix enc_matrix_open(const std::vector<seal::Ciphertext> &diagonals, std::size_t rows, std::size_t cols)
+    {
+        return EncMatrix(context, device, core, id, diagonals, rows, cols, true);
+    }
+    void fc_open(const seal::Ciphertext &vi, const EncMatrix &mat, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out)
+    {
+        mlp({&mat}, vi, rk, gal_keys, out);
+    }
+    void mlp(const std::vector<const EncMatrix *> &layers, const seal::Ciphertext &vi, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys,
+             seal::Ciphertext &vo)
+    {
+        for (const EncMatrix *m : layers)
+            if (m && m->core.get() != core.get()) throw std::invalid_argument("encrypted matrix is not at the level of this object");
+        EncMatrix::mlp(layers, vi, rk, gal_keys, vo);
     }
     void fc_packed_hoisted(const seal::Ciphertext &vi, const EncMatrix &mat, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out)
     {
@@ -544,6 +584,21 @@ public:
     {
         device->square_relinearize(device->words(vi), rk_set, device->into(*context, vo));
     }
+    // Chainable packed FC (no reference counterpart: hhe_pktnn_2fc_inference stops after fc1): the analyst's open diagonals as a resident
+    // matrix, one open layer, and the FC-square-FC network as one device call, with the key objects the call names
+    EncMatrix enc_matrix_open(const std::vector<seal::Ciphertext> &diagonals, std::size_t rows, std::size_t cols)
+    {
+        return EncMatrix(context, device, nullptr, context->first_parms_id(), diagonals, rows, cols, true);
+    }
+    void fc_open(const seal::Ciphertext &vi, const EncMatrix &mat, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out)
+    {
+        EncMatrix::mlp({&mat}, vi, rk, gal_keys, out);
+    }
+    void mlp(const std::vector<const EncMatrix *> &layers, const seal::Ciphertext &vi, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys,
+             seal::Ciphertext &vo)
+    {
+        EncMatrix::mlp(layers, vi, rk, gal_keys, vo);
+    }
     void packed_enc_mul(const seal::Ciphertext &encrypted1, const seal::Ciphertext &encrypted2, seal::Ciphertext &destination)
     {
         device->multiply(device->words(encrypted1), device->words(encrypted2), device->into(*context, destination, 3));
@@ -740,6 +795,17 @@ inline void fc_packed_sum(const seal::Ciphertext &vi, const EncMatrix &mat, cons
                           seal::Ciphertext &out, bool hoisted = false)
 {
     mat.apply_sum(vi, rk, gal_keys, out, hoisted);
+}
+// The open layer (mat from enc_matrix_open) and the FC-square-FC network as ONE device call (hhe_gfx950.h "Chainable packed FC"): no slot
+// of vi outside [0, cols) of the first layer needs to be zero, and no mask stands between two layers
+inline void fc_open(const seal::Ciphertext &vi, const EncMatrix &mat, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys, seal::Ciphertext &out)
+{
+    EncMatrix::mlp({&mat}, vi, rk, gal_keys, out);
+}
+inline void mlp(const std::vector<const EncMatrix *> &layers, const seal::Ciphertext &vi, const seal::RelinKeys &rk, const seal::GaloisKeys &gal_keys,
+                seal::Ciphertext &vo)
+{
+    EncMatrix::mlp(layers, vi, rk, gal_keys, vo);
 }
 // out[k] = Evaluator::rotate_rows(ct, steps[k], gal_keys), hoisted (hhe_gfx950.h "Hoisted rotations"); the Evaluator argument is unused
 inline void rotate_rows_many(const seal::Ciphertext &ct, const std::vector<int> &steps, const seal::GaloisKeys &gal_keys,

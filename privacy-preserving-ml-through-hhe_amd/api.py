@@ -51,12 +51,16 @@ _SYMBOLS = [
     "hhe_enc_matrix_bytes", "hhe_fc_packed_ks", "hhe_add_many",
     "hhe_rotate_rows_many_ks", "hhe_fc_packed_hoisted_ks", "hhe_fc_packed_hoisted_galois_steps",
     "hhe_multiply_sum", "hhe_fc_packed_sum_ks",
+    "hhe_fc_open_shape", "hhe_fc_open_diagonals", "hhe_fc_open_galois_steps", "hhe_enc_matrix_create_open", "hhe_fc_open_ks",
+    "hhe_square", "hhe_mlp_ks",
 ]
 
 _FC_PACKED_SYMBOLS = {"hhe_fc_packed_shape", "hhe_fc_packed_diagonals", "hhe_fc_packed_galois_steps", "hhe_enc_matrix_create",
                       "hhe_enc_matrix_destroy", "hhe_enc_matrix_bytes", "hhe_fc_packed_ks", "hhe_add_many"}
 _ROT_MANY_SYMBOLS = {"hhe_rotate_rows_many_ks", "hhe_fc_packed_hoisted_ks", "hhe_fc_packed_hoisted_galois_steps"}
 _MULT_SUM_SYMBOLS = {"hhe_multiply_sum", "hhe_fc_packed_sum_ks"}
+_MLP_SYMBOLS = {"hhe_fc_open_shape", "hhe_fc_open_diagonals", "hhe_fc_open_galois_steps", "hhe_enc_matrix_create_open", "hhe_fc_open_ks",
+                "hhe_square", "hhe_mlp_ks"}
 _NONCE_SYMBOLS = {"hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystream_nonce", "hhe_pasta3_plain_crypt_nonce",
                   "hhe_pasta3_transcipher_nonce_ks", "hhe_decompose_nonce_ks", "hhe_pasta3_block_randomness_dev",
                   "hhe_pasta3_prepare_tables"}
@@ -67,7 +71,7 @@ _NONCE_SYMBOLS = {"hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystre
 _OPTIONAL = {"hhe_pasta3_clear_keystream_cache", "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin",
              "hhe_keyset_generate_galois", "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
              "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level",
-             "hhe_noise_budget", "hhe_ctx_create_level", "hhe_keyset_derive_level"} | _NONCE_SYMBOLS | _FC_PACKED_SYMBOLS | _ROT_MANY_SYMBOLS | _MULT_SUM_SYMBOLS
+             "hhe_noise_budget", "hhe_ctx_create_level", "hhe_keyset_derive_level"} | _NONCE_SYMBOLS | _FC_PACKED_SYMBOLS | _ROT_MANY_SYMBOLS | _MULT_SUM_SYMBOLS | _MLP_SYMBOLS
 
 
 def exported_symbols():
@@ -256,13 +260,23 @@ class Matrix:
 
 class EncMatrix:
     """The encrypted weight matrix of a packed encrypted FC layer on the device (hhe_enc_matrix): its r generalized diagonals,
-    extended and transformed once.  diag_cts: device uint64 [r][2][L][N], the encryptions of fc_packed_diagonals' slot vectors."""
+    extended and transformed once.  diag_cts: device uint64 [r][2][L][N], the encryptions of fc_packed_diagonals' slot vectors.
+    open: the diagonals that do not wrap (fc_open_diagonals, hhe_enc_matrix_create_open); such a handle takes apply_open and
+    Context.mlp, a cyclic one the other three forms."""
 
-    def __init__(self, ctx, diag_cts, rows, cols):
-        self.ctx, self.rows, self.cols = ctx, int(rows), int(cols)
+    def __init__(self, ctx, diag_cts, rows, cols, open=False):
+        self.ctx, self.rows, self.cols, self.open = ctx, int(rows), int(cols), bool(open)
         h = C.c_void_p()
-        ctx._chk(ctx._need("hhe_enc_matrix_create")(ctx.h, _ptr(diag_cts), C.c_size_t(rows), C.c_size_t(cols), C.byref(h)))
+        create = ctx._need("hhe_enc_matrix_create_open" if open else "hhe_enc_matrix_create")
+        ctx._chk(create(ctx.h, _ptr(diag_cts), C.c_size_t(rows), C.c_size_t(cols), C.byref(h)))
         self.h = h
+
+    def apply_open(self, ct, B, rk=None, gk=None, out=None):
+        """out[b] = the open layer on ct[b] (hhe_fc_open_ks): whatever ct[b] holds outside slots [0, cols) meets an encrypted zero, so
+        the output of a previous layer or of a square is a legal input.  out None: in place.  Returns out."""
+        out = ct if out is None else out
+        self.ctx._chk(self.ctx._need("hhe_fc_open_ks")(self.ctx.h, _ks(rk), _ks(gk), self.h, _ptr(ct), _ptr(out), C.c_size_t(B)))
+        return out
 
     def apply(self, ct, B, rk=None, gk=None, out=None):
         """out[b] = the layer on ct[b] (device [B][2][L][N]; out None: in place); slots [0, rows) of the decryption are (M x) mod t.
@@ -442,6 +456,21 @@ class Context:
     def enc_matrix(self, diag_cts, rows, cols):
         """resident encrypted matrix of a packed encrypted FC layer from its r diagonal ciphertexts (device [r][2][L][N])"""
         return EncMatrix(self, diag_cts, rows, cols)
+
+    def enc_matrix_open(self, diag_cts, rows, cols):
+        """resident encrypted matrix of an open layer from the encryptions of fc_open_diagonals' slot vectors (device [r][2][L][N])"""
+        return EncMatrix(self, diag_cts, rows, cols, open=True)
+
+    def square(self, a, out3, B):
+        """out3 [B][3][L][N] = Evaluator::square(a) at size 2: the words of multiply(a, a, ..), one operand extension"""
+        self._chk(self._need("hhe_square")(self.h, _ptr(a), _ptr(out3), C.c_size_t(B)))
+
+    def mlp(self, handles, ct, out, B, rk=None, gk=None):
+        """out[b] = the network on ct[b] (hhe_mlp_ks): handles[0] open, square + relinearize, handles[1] open, ...; every layer of a
+        chunk on its lane with no host wait in between.  handles: open EncMatrix objects, rows of one == cols of the next; out may be ct"""
+        arr = (C.c_void_p * max(len(handles), 1))(*[None if m is None else m.h for m in handles])
+        self._chk(self._need("hhe_mlp_ks")(self.h, _ks(rk), _ks(gk), arr, C.c_size_t(len(handles)), _ptr(ct), _ptr(out), C.c_size_t(B)))
+        return out
 
     def add_many(self, stacked, K, out, B, size=2):
         """out [B][size][L][N] = the sum of the K batches stacked [K][B][size][L][N] (Evaluator::add_many), one launch"""
@@ -751,6 +780,42 @@ def fc_packed_hoisted_galois_steps(n, rows, cols, lib=None):
     out = (C.c_int * max(int(n), 64))()
     cnt = C.c_size_t(len(out))
     rc = _lib_fn(lib, "hhe_fc_packed_hoisted_galois_steps")(C.c_size_t(n), C.c_size_t(rows), C.c_size_t(cols), out, C.byref(cnt))
+    if rc:
+        raise HheError(rc, lib.hhe_last_error().decode())
+    return [int(v) for v in out[:cnt.value]]
+
+
+def fc_open_shape(n, rows, cols, lib=None):
+    """(r, c) of the open layout at degree n: r = pow2 >= rows, c = pow2 >= cols + r - 1; HheError when c > n / 2"""
+    lib = lib or load_library()
+    r, c = C.c_size_t(0), C.c_size_t(0)
+    rc = _lib_fn(lib, "hhe_fc_open_shape")(C.c_size_t(n), C.c_size_t(rows), C.c_size_t(cols), C.byref(r), C.byref(c))
+    if rc:
+        raise HheError(rc, lib.hhe_last_error().decode())
+    return int(r.value), int(c.value)
+
+
+def fc_open_diagonals(t, M, lib=None):
+    """the diagonals that do not wrap, as slot vectors [r][c]: D_e[j] = M[j mod r][j - e] where that entry exists, else 0"""
+    lib = lib or load_library()
+    M = np.ascontiguousarray(M, dtype=np.uint64)
+    assert M.ndim == 2
+    rows, cols = M.shape
+    r = 1 << max(rows - 1, 0).bit_length()
+    c = 1 << max(cols + r - 2, 0).bit_length()
+    vals = np.zeros((r, c), np.uint64)
+    rc = _lib_fn(lib, "hhe_fc_open_diagonals")(C.c_uint64(t), _ptr(M), C.c_size_t(rows), C.c_size_t(cols), _ptr(vals))
+    if rc:
+        raise HheError(rc, lib.hhe_last_error().decode())
+    return vals
+
+
+def fc_open_galois_steps(n, rows, cols, lib=None):
+    """the Galois keys of the one-pass schedule of an open layer: -1 .. -(r-1), then r, 2r, .. below c"""
+    lib = lib or load_library()
+    out = (C.c_int * max(int(n), 64))()
+    cnt = C.c_size_t(len(out))
+    rc = _lib_fn(lib, "hhe_fc_open_galois_steps")(C.c_size_t(n), C.c_size_t(rows), C.c_size_t(cols), out, C.byref(cnt))
     if rc:
         raise HheError(rc, lib.hhe_last_error().decode())
     return [int(v) for v in out[:cnt.value]]

@@ -257,16 +257,19 @@ void op_behz_operand(hhe_ctx *c, const u64 *in, u64 *oq, u64 *ob, size_t B)
 // the same form; b_div > 0: item b multiplies ciphertext b / b_div of the second operand (TensorArgs::b_div).
 // sum > 0: the operands are [sum][B] (the second [sum][1] when b_div is set) and the B results are the floors of the sums of their
 // `sum` tensor products (hhe_multiply_sum): one summed tensor launch per modulus set, then the same passes over B * 3 polynomials
-void behz_product(hhe_ctx *c, const u64 *bq, const u64 *bb, size_t b_div, u64 *out3, size_t B, size_t sum = 0)
+// square: the second operand is the first (hhe_square): bq / bb are not read and the squaring kernel runs
+void behz_product(hhe_ctx *c, const u64 *bq, const u64 *bb, size_t b_div, u64 *out3, size_t B, size_t sum = 0, bool square = false)
 {
     const int L = c->L, K = c->K;
     TensorArgs t = zeroed<TensorArgs>();
-    t.mods = c->d_mods; t.logn = c->logn; t.B = (int)B; t.b_div = (int)b_div; t.sum = (int)sum;
+    t.mods = c->d_mods; t.logn = c->logn; t.B = (int)B; t.b_div = (int)b_div; t.sum = (int)sum; t.square = square;
     t.a = c->w->bz_aq; t.b = bq; t.d = c->w->bz_dq; t.limbs = L; t.mod_base = 0; t.fold = c->sum_fold_q;
     k_tensor(t, c->w->stream);
     t.a = c->w->bz_ab; t.b = bb; t.d = c->w->bz_db; t.limbs = L + 1; t.mod_base = K; t.fold = c->sum_fold_bsk;
     k_tensor(t, c->w->stream);
     if (sum) c->multiply_sum_launches += 2;
+    else if (square) c->square_launches += 2;
+    else c->tensor_launches += 2;
     op_ntt(c, c->w->bz_dq, B * 3 * L, 0, L, true, STORE_SCALE_T);
     op_ntt(c, c->w->bz_db, B * 3 * (L + 1), K, L + 1, true, STORE_SCALE_T);
     BehzFloorArgs f = zeroed<BehzFloorArgs>();
@@ -281,6 +284,12 @@ void op_multiply(hhe_ctx *c, const u64 *x, const u64 *y, u64 *out3, size_t B)
     const u64 *bq = c->w->bz_aq, *bb = c->w->bz_ab;
     if (y != x) { op_behz_operand(c, y, c->w->bz_bq, c->w->bz_bb, B); bq = c->w->bz_bq; bb = c->w->bz_bb; }
     behz_product(c, bq, bb, 0, out3, B);
+}
+// Evaluator::square at size 2: one operand extension and the squaring kernel; the words of op_multiply(c, x, x, ..)
+void op_square(hhe_ctx *c, const u64 *x, u64 *out3, size_t B)
+{
+    op_behz_operand(c, x, c->w->bz_aq, c->w->bz_ab, B);
+    behz_product(c, nullptr, nullptr, 0, out3, B, 0, true);
 }
 // ... against a resident encrypted matrix: x [r][per][2][L][N], the r rotations of `per` items, rotation-major; product (i, b) is
 // multiply(x[i][b], W_i) with W_i in the form the handle keeps -> out3 [r][per][3][L][N].  One extension, one transform and one floor
@@ -1001,6 +1010,14 @@ extern "C" int hhe_multiply(hhe_ctx *c, const uint64_t *a, const uint64_t *b, ui
     int rc = need(c, B);
     if (rc) return rc;
     op_multiply(c, a, b, out3, B);
+    return HHE_OK;
+}
+extern "C" int hhe_square(hhe_ctx *c, const uint64_t *a, uint64_t *out3, size_t B)
+{
+    HHE_LOCK(c);
+    int rc = need(c, B);
+    if (rc) return rc;
+    op_square(c, a, out3, B);
     return HHE_OK;
 }
 // the definition and the cap are in include/hhe_gfx950.h; DESIGN.md section 4 "One floor over a sum of products"
@@ -2389,7 +2406,9 @@ int rot_plan_build(const hhe_ctx *c, const int *steps, size_t n_steps, RotPlan &
 }
 // Everything the chunks read that is made once per call, on the main lane before they fork: the correction table of every key of the
 // trie (and its Shoup quotients where the row kernels run), and the per-child table on the device
-int rot_plan_tables(hhe_ctx *c, RotPlan &p)
+// ofs / total: the plan's rows start at row `ofs` of a table of `total` rows (the layers of hhe_mlp_ks share one table; the caller
+// lays the plans out one behind the other, a plan having one row per node below its root); total == 0: the table is this plan's alone
+int rot_plan_tables(hhe_ctx *c, RotPlan &p, size_t ofs = 0, size_t total = 0)
 {
     int rc;
     p.kids.clear();
@@ -2407,10 +2426,10 @@ int rot_plan_tables(hhe_ctx *c, RotPlan &p)
     }
     if (!p.rowk || p.kids.empty()) return HHE_OK;
     if (ensure_qsp_poly(c)) return dev_fail("hoisted rotations: workspace");
-    if ((rc = c->d_rot_kids.reserve(c, p.kids.size(), "hoisted rotations: child table"))) return rc;
+    if ((rc = c->d_rot_kids.reserve(c, std::max(total, ofs + p.kids.size()), "hoisted rotations: child table"))) return rc;
     // the earlier call's chunks have completed (the calls are synchronous); the host copy must outlive the upload
-    if (rt_h2d(c->d_rot_kids.p, p.kids.data(), p.kids.size() * sizeof(KsKid), c->w->stream) || rt_sync(c->w->stream)) return dev_fail("hoisted rotations: child table");
-    p.d_kids = c->d_rot_kids.p;
+    if (rt_h2d(c->d_rot_kids.p + ofs, p.kids.data(), p.kids.size() * sizeof(KsKid), c->w->stream) || rt_sync(c->w->stream)) return dev_fail("hoisted rotations: child table");
+    p.d_kids = c->d_rot_kids.p + ofs;
     return HHE_OK;
 }
 // The children of `node` may be written straight into the output when they land there as one block: the chunk covers the whole stride
@@ -2570,7 +2589,25 @@ void fc_packed_steps(size_t n, size_t r, size_t cc, std::vector<int> &steps)
     if (r > 1) steps.push_back(1);
     for (size_t s = r; s < cc; s <<= 1) steps.push_back((int)s);
 }
+// r and c of the open layout (hhe_fc_open_shape): the diagonals do not wrap, so c covers cols + r - 1 slots; c <= N/2 is the only slot rule
+int fc_open_dims(size_t n, size_t rows, size_t cols, size_t &r, size_t &cc)
+{
+    if (rows == 0 || cols == 0 || rows > ((size_t)1 << 30) || cols > ((size_t)1 << 30)) return fail(HHE_ERR_INVALID, "open FC: rows and cols must be positive (and at most 2^30)");
+    if (n && (n < 4 || (n & (n - 1)))) return fail(HHE_ERR_INVALID, "open FC: the degree must be a power of two");
+    r = pow2_ceil(rows);
+    cc = pow2_ceil(cols + r - 1);
+    if (n && cc * 2 > n) return fail(HHE_ERR_TOO_FEW_SLOTS, "too little slots for matmul implementation!");
+    return HHE_OK;
+}
+// the rotate_rows steps of the open layer: -1 .. -(r-1) into `rot`, the tail r 2^k < c into `tail`
+void fc_open_steps(size_t r, size_t cc, std::vector<int> &rot, std::vector<int> &tail)
+{
+    rot.clear(); tail.clear();
+    for (size_t e = 1; e < r; ++e) rot.push_back(-(int)e);
+    for (size_t s = r; s < cc; s <<= 1) tail.push_back((int)s);
+}
 // one chunk on the current lane: in / out [per][2][L][N] (may be the same buffer); the lane is reserved for r * per items
+// an open handle (hhe_fc_open_ks): no step 1, and the hoisted plan holds the steps -1 .. -(r-1)
 // hoist: step 2 as rotations of the x of step 1 (hhe_fc_packed_hoisted_ks) -- one hoisted rotation of the chunk's items into rot + per * ctw,
 // or with `stepwise` each through op_rotate_rows (HHE_ROT_HOIST=0 and the exactness fallback); null: the chain of hhe_fc_packed_ks
 // sum: steps 3 and 4 as one multiply_sum (hhe_fc_packed_sum_ks) -- prod is [per][3][L][N] and the sum kernel is not launched
@@ -2582,7 +2619,7 @@ int fc_packed_chunk(hhe_ctx *c, const hhe_enc_matrix *m, const u64 *in, u64 *out
     u64 *rot = w.ws_fcp.p, *prod = rot + r * per * ctw;  // [r][per][2][L][N] | [r][per][3][L][N]
     int rc;
     rt_d2d(rot, in, per * ctw * 8, w.stream);
-    if (m->c * 2 != c->n && (rc = op_prep_rows(c, rot, -(int)m->c, w.ws_ct[2], per))) return rc;
+    if (!m->open && m->c * 2 != c->n && (rc = op_prep_rows(c, rot, -(int)m->c, w.ws_ct[2], per))) return rc;
     if (hoist) {
         if (r > 1 && (rc = rot_many_chunk(c, *hoist, !stepwise, rot, rot + per * ctw, per, per))) return rc;
     } else
@@ -2650,16 +2687,17 @@ extern "C" int hhe_fc_packed_galois_steps(size_t N, size_t rows, size_t cols, in
     return HHE_OK;
 }
 
-extern "C" int hhe_enc_matrix_create(hhe_ctx *c, const uint64_t *wdiag, size_t rows, size_t cols, hhe_enc_matrix **out)
+// open: the shape and the mark of hhe_enc_matrix_create_open; the resident form is the same
+static int enc_matrix_create(hhe_ctx *c, const uint64_t *wdiag, size_t rows, size_t cols, bool open, hhe_enc_matrix **out)
 {
     HHE_LOCK(c);
     if (!c || !wdiag || !out) return fail(HHE_ERR_INVALID, "hhe_enc_matrix_create: null argument");
     size_t r, cc;
-    int rc = fc_packed_dims(c->n, rows, cols, r, cc);
+    int rc = open ? fc_open_dims(c->n, rows, cols, r, cc) : fc_packed_dims(c->n, rows, cols, r, cc);
     if (rc) return rc;
     const size_t n = c->n, L = c->L;
     hhe_enc_matrix *m = new hhe_enc_matrix();
-    m->ctx = c; m->rows = rows; m->cols = cols; m->r = r; m->c = cc;
+    m->ctx = c; m->rows = rows; m->cols = cols; m->r = r; m->c = cc; m->open = open;
     m->wq = (u64 *)rt_malloc(r * 2 * L * n * 8);
     m->wb = (u64 *)rt_malloc(r * 2 * (L + 1) * n * 8);
     if (!m->wq || !m->wb) { enc_matrix_free(m); return dev_fail("hhe_enc_matrix_create: table alloc"); }
@@ -2670,6 +2708,14 @@ extern "C" int hhe_enc_matrix_create(hhe_ctx *c, const uint64_t *wdiag, size_t r
     c->enc_mats.push_back(m);
     *out = m;
     return HHE_OK;
+}
+extern "C" int hhe_enc_matrix_create(hhe_ctx *c, const uint64_t *wdiag, size_t rows, size_t cols, hhe_enc_matrix **out)
+{
+    return enc_matrix_create(c, wdiag, rows, cols, false, out);
+}
+extern "C" int hhe_enc_matrix_create_open(hhe_ctx *c, const uint64_t *wdiag, size_t rows, size_t cols, hhe_enc_matrix **out)
+{
+    return enc_matrix_create(c, wdiag, rows, cols, true, out);
 }
 extern "C" void hhe_enc_matrix_destroy(hhe_enc_matrix *m)
 {
@@ -2694,6 +2740,7 @@ static int fc_packed_run(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk,
     HHE_LOCK(c);
     if (!c || !m || !vi || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed: null argument or empty batch");
     if (m->ctx != c) return fail(HHE_ERR_INVALID, "encrypted matrix belongs to another context");
+    if (m->open) return fail(HHE_ERR_INVALID, "hhe_fc_packed: an open handle (hhe_enc_matrix_create_open) takes hhe_fc_open_ks or hhe_mlp_ks");
     if (sum && m->r >= 2 && m->r > c->behz_sum_cap) return fail(HHE_ERR_INVALID, "hhe_fc_packed_sum: more diagonals than one floor takes (behz_sum_cap)");
     int rc = check_sets(c, rk, gk);
     if (rc) return rc;
@@ -2758,6 +2805,7 @@ static int fc_packed_hoisted_run(hhe_ctx *c, const hhe_keyset *rk, const hhe_key
     HHE_LOCK(c);
     if (!c || !m || !vi || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed_hoisted: null argument or empty batch");
     if (m->ctx != c) return fail(HHE_ERR_INVALID, "encrypted matrix belongs to another context");
+    if (m->open) return fail(HHE_ERR_INVALID, "hhe_fc_packed: an open handle (hhe_enc_matrix_create_open) takes hhe_fc_open_ks or hhe_mlp_ks");
     if (sum && m->r >= 2 && m->r > c->behz_sum_cap) return fail(HHE_ERR_INVALID, "hhe_fc_packed_sum: more diagonals than one floor takes (behz_sum_cap)");
     int rc = check_sets(c, rk, gk);
     if (rc) return rc;
@@ -2830,6 +2878,180 @@ extern "C" int hhe_fc_packed_sum_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_
                                     uint64_t *out, size_t B, int hoisted)
 {
     return hoisted ? fc_packed_hoisted_run(c, rk, gk, m, vi, out, B, true) : fc_packed_run(c, rk, gk, m, vi, out, B, true);
+}
+
+// ====================================================================== open packed FC and the FC-square-FC network
+// The definition is in include/hhe_gfx950.h; DESIGN.md section 4 "Open diagonals and the network call" has the layout and the chunk.
+extern "C" int hhe_fc_open_shape(size_t N, size_t rows, size_t cols, size_t *r_out, size_t *c_out)
+{
+    if (!r_out || !c_out || N == 0) return fail(HHE_ERR_INVALID, "hhe_fc_open_shape: null argument or no degree");
+    size_t r, cc;
+    int rc = fc_open_dims(N, rows, cols, r, cc);
+    if (rc) return rc;
+    *r_out = r; *c_out = cc;
+    return HHE_OK;
+}
+extern "C" int hhe_fc_open_diagonals(uint64_t t, const uint64_t *M, size_t rows, size_t cols, uint64_t *vals)
+{
+    if (!M || !vals) return fail(HHE_ERR_INVALID, "hhe_fc_open_diagonals: null argument");
+    size_t r, cc;
+    int rc = fc_open_dims(0, rows, cols, r, cc);
+    if (rc) return rc;
+    for (size_t i = 0; i < rows * cols; ++i)
+        if (M[i] >= t) return fail(HHE_ERR_INVALID, "hhe_fc_open_diagonals: matrix entry not below the plain modulus");
+    // D_e[j] = M[j mod r][j - e] where that entry exists, else 0: no index wraps
+    for (size_t e = 0; e < r; ++e)
+        for (size_t j = 0; j < cc; ++j) {
+            const size_t row = j % r;
+            vals[e * cc + j] = row < rows && j >= e && j - e < cols ? M[row * cols + (j - e)] : 0;
+        }
+    return HHE_OK;
+}
+extern "C" int hhe_fc_open_galois_steps(size_t N, size_t rows, size_t cols, int *steps_out, size_t *count)
+{
+    if (!count || N == 0) return fail(HHE_ERR_INVALID, "hhe_fc_open_galois_steps: null argument or no degree");
+    size_t r, cc;
+    int rc = fc_open_dims(N, rows, cols, r, cc);
+    if (rc) return rc;
+    std::vector<int> steps, tail;
+    fc_open_steps(r, cc, steps, tail);
+    steps.insert(steps.end(), tail.begin(), tail.end());
+    const size_t cap = *count;
+    *count = steps.size();
+    if (!steps_out || cap < steps.size()) return fail(HHE_ERR_CAPACITY, "hhe_fc_open_galois_steps: output too small");
+    std::copy(steps.begin(), steps.end(), steps_out);
+    return HHE_OK;
+}
+
+// one chunk of the network on the current lane: every layer of `per` items with no host wait in between.  x_k lives in the lane's
+// ws_ct[1] and the size-3 square in ws_ct3, which no step of a layer touches; the lane's ws_fcp is reserved for the largest layer
+static int mlp_chunk(hhe_ctx *c, const hhe_enc_matrix *const *mats, size_t n_layers, const RotPlan *plans, const u64 *in, u64 *out, size_t per,
+                     bool stepwise)
+{
+    Lane &w = *c->w;
+    u64 *x = w.ws_ct[1];
+    int rc;
+    for (size_t k = 0; k < n_layers; ++k) {
+        const bool last = k + 1 == n_layers;
+        if ((rc = fc_packed_chunk(c, mats[k], k ? x : in, last ? out : x, per, &plans[k], stepwise, true))) return rc;
+        if (last) break;
+        op_square(c, x, w.ws_ct3, per);
+        if ((rc = op_relinearize(c, w.ws_ct3, x, per))) return rc;
+    }
+    return HHE_OK;
+}
+// hhe_mlp_ks, and hhe_fc_open_ks as its one-layer case (`who` names the entry point in messages)
+static int mlp_run(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *const *mats, size_t n_layers, const uint64_t *vi,
+                   uint64_t *out, size_t B, const char *who)
+{
+    HHE_LOCK(c);
+    const std::string w(who);
+    if (!c || !mats || !vi || !out || B == 0 || n_layers == 0) return fail(HHE_ERR_INVALID, w + ": null argument, empty batch or no layer");
+    size_t max_r = 1;
+    for (size_t k = 0; k < n_layers; ++k) {
+        const hhe_enc_matrix *m = mats[k];
+        if (!m) return fail(HHE_ERR_INVALID, w + ": null handle");
+        if (m->ctx != c) return fail(HHE_ERR_INVALID, "encrypted matrix belongs to another context");
+        if (!m->open) return fail(HHE_ERR_INVALID, w + ": a cyclic handle (hhe_enc_matrix_create) takes the hhe_fc_packed calls");
+        if (k && mats[k - 1]->rows != m->cols) return fail(HHE_ERR_INVALID, w + ": rows of a layer differ from cols of the next");
+        if (m->r >= 2 && m->r > c->behz_sum_cap) return fail(HHE_ERR_INVALID, w + ": more diagonals than one floor takes (behz_sum_cap)");
+        max_r = std::max(max_r, m->r);
+    }
+    int rc = check_sets(c, rk, gk);
+    if (rc) return rc;
+    KeyScope keys(c, gk, rk);
+    if (!c->rks->rk) return fail(HHE_ERR_NO_RELIN_KEY, "relinearization key not set");
+    // the tail steps need their own keys (their NAF has one term); -1 .. -(r-1) are served as hhe_rotate_rows_many_ks serves them.
+    // The plans of all layers are built, and refuse, before anything is written
+    std::vector<RotPlan> plans(n_layers);
+    size_t kid_rows = 0, key_switches = 0;
+    bool any_hoisted = false;
+    for (size_t k = 0; k < n_layers; ++k) {
+        std::vector<int> rot, tail;
+        fc_open_steps(mats[k]->r, mats[k]->c, rot, tail);
+        for (int s : tail)
+            if (!c->gks->gk.count(galois_elt_from_step(c, s))) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+        if (!rot.empty() && (rc = rot_plan_build(c, rot.data(), rot.size(), plans[k]))) return rc;
+        if (!rot.empty()) kid_rows += plans[k].trie.size() - 1;
+        key_switches += (rot.empty() ? 0 : plans[k].trie.size() - 1) + tail.size();
+        any_hoisted |= c->rot_hoist != 0 && !rot.empty();
+    }
+    Lane &main = c->lanes[0];
+    c->w = &main;
+    auto hoisted = [&](size_t k) { return c->rot_hoist != 0 && mats[k]->r > 1; };
+    for (size_t k = 0, ofs = 0; k < n_layers; ++k)
+        if (hoisted(k)) {
+            if ((rc = rot_plan_tables(c, plans[k], ofs, kid_rows))) return rc;
+            ofs += plans[k].trie.size() - 1;
+        }
+    const size_t per = std::min(B, std::max<size_t>(1, c->chunk / max_r));
+    const ChunkPlan cp(B, per, c->nstreams);
+    const size_t ctw = c->ct_words();
+    auto reserve = [&](Lane &ln, bool h) {
+        int r = HHE_OK;
+        size_t words = 0;
+        for (size_t k = 0; k < n_layers && !r; ++k) {
+            r = rot_many_reserve(c, ln, plans[k], h && hoisted(k), true, per, max_r * per);
+            words = std::max(words, fc_packed_words(c, mats[k], per, true));
+        }
+        if (!r) r = ln.ws_fcp.reserve(c, words, "hhe_mlp: rotations and products of the largest layer");
+        return r;
+    };
+    for (int s = cp.first_lane(); s <= cp.last_lane(); ++s)
+        if ((rc = reserve(c->lanes[s], true))) return rc;
+    // in place, a recomputed chunk would read its own result: the results then wait in a buffer of the context until the flags are known
+    u64 *res = out;
+    if (any_hoisted && vi == out) {
+        if ((rc = c->d_blocks.reserve(c, B * ctw, "hhe_mlp: results in place"))) return rc;
+        res = c->d_blocks.p;
+    }
+    u32 *flags = nullptr;
+    if (any_hoisted) {
+        if ((rc = c->d_flags.reserve(c, cp.nch, "hhe_mlp"))) return rc;  // one flag per chunk, for the hoisted rotations of every layer
+        flags = c->d_flags.p;
+        rt_memset(flags, 0, cp.nch * 4, main.stream);
+    }
+    rc = run_chunks(c, cp, [&](Lane &ln, size_t idx, size_t b0, size_t bc) {
+        ln.zero_flag = any_hoisted ? flags + idx : nullptr;
+        return mlp_chunk(c, mats, n_layers, plans.data(), vi + b0 * ctw, res + b0 * ctw, bc, !any_hoisted);
+    });
+    if (any_hoisted && !rc) {
+        std::vector<u32> h(cp.nch, 0);
+        if (rt_d2h(h.data(), flags, cp.nch * 4, main.stream) || rt_sync(main.stream)) rc = dev_fail(who);
+        // a zero residue in some c1 of some layer: that chunk is recomputed whole, from vi, step by step on the main lane
+        for (size_t idx = 0; idx < cp.nch && !rc; ++idx)
+            if (h[idx] || c->rot_hoist == 2) {
+                c->rot_many_fallbacks++;
+                main.zero_flag = nullptr;
+                if (!(rc = reserve(main, false))) rc = mlp_chunk(c, mats, n_layers, plans.data(), vi + idx * per * ctw, res + idx * per * ctw, cp.count(idx), true);
+            }
+        if (!rc && res != out) rt_d2d(out, res, B * ctw * 8, main.stream);
+    }
+    if (rt_sync(main.stream) && !rc) rc = dev_fail(who);
+    if (!rc) {
+        const hhe_enc_matrix *last = mats[n_layers - 1];
+        const RotPlan &lp = plans[n_layers - 1];
+        size_t tail = 0;
+        for (size_t s = last->r; s < last->c; s <<= 1) ++tail;
+        c->rot_many_key_switches = last->r > 1 ? lp.trie.size() - 1 : 0;
+        c->rot_many_launches = hoisted(n_layers - 1) ? lp.launches : 0;
+        c->fc_packed_key_switches = c->rot_many_key_switches + tail;
+        c->fc_packed_floors = 3;
+        c->mlp_layers = n_layers;
+        c->mlp_key_switches = key_switches;
+    }
+    return rc;
+}
+extern "C" int hhe_fc_open_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi, uint64_t *out,
+                              size_t B)
+{
+    if (!m) return fail(HHE_ERR_INVALID, "hhe_fc_open: null argument");
+    return mlp_run(c, rk, gk, &m, 1, vi, out, B, "hhe_fc_open");
+}
+extern "C" int hhe_mlp_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *const *mats, size_t n_layers,
+                          const uint64_t *vi, uint64_t *out, size_t B)
+{
+    return mlp_run(c, rk, gk, mats, n_layers, vi, out, B, "hhe_mlp");
 }
 
 extern "C" int hhe_add_many(hhe_ctx *c, const uint64_t *in, size_t K, uint64_t *out, size_t B, int size)

@@ -504,6 +504,7 @@ struct TensorArgs {  // d[b][0..2][j] from a[b][0..1][j], b[b][0..1][j]; NTT dom
     int sum;    // > 0: d[b] = the sum over k < sum of the tensor products of a[k][b] and b[k][b] (b[k][0] when b_div is set), `a` being
                 // [sum][B][2][limbs][N] and `b` [sum][B or 1][2][limbs][N] (hhe_multiply_sum; a kernel of its own); 0: one product
     int fold;   // with sum: the addends a 128-bit sum takes between two reductions (tensor_sum_fold of the widest modulus of the launch)
+    int square; // != 0: d[b] = the tensor product of a[b] with itself (hhe_square; a kernel of its own); `b`, b_div, sum and fold are not read
 };
 // Addends between two reductions of tensor_sum_body's sums under a modulus of `bits` bits.  The middle polynomial takes two products
 // below 2^(2 bits) per addend on top of a residue below 2^bits, and 2 f (2^bits - 1)^2 + 2^bits < 2^128 holds for f = 2^(127 - 2 bits)

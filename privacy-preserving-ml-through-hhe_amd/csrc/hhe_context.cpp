@@ -711,6 +711,10 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "multiply_sum_fold_bsk") return (u64)c->sum_fold_bsk;        // ... under the B_sk primes
     if (w == "multiply_sum_launches") return c->multiply_sum_launches;    // launches of the summed tensor kernel: one per modulus set per call or chunk
     if (w == "fc_packed_floors") return c->fc_packed_floors;              // polynomials floored per item of the last packed encrypted FC call
+    if (w == "tensor_launches") return c->tensor_launches;                // launches of tensor_kernel / tensor_bcast_kernel: two per BEHZ product of two operands
+    if (w == "square_launches") return c->square_launches;                // launches of tensor_square_kernel: two per hhe_square
+    if (w == "mlp_layers") return c->mlp_layers;                          // layers of the last hhe_mlp_ks call
+    if (w == "mlp_key_switches") return c->mlp_key_switches;              // ... and its Galois key switches per item, summed over the layers
     if (w == "noise_form") return (u64)c->noise_form;  // the last hhe_noise_budget launch: limb count of its register form, 0 = the LDS form
     if (w == "public_device") return (u64)(int64_t)c->public_device;  // HHE_PUBLIC_DEVICE: 0 host, 1 device; unset: (uint64_t)-1, the path is chosen per call
     if (w == "public_device_built") return c->last_public_built;     // pairs whose randomness the last call drew on the device

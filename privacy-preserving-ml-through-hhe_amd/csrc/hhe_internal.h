@@ -111,6 +111,7 @@ struct hhe_matrix {
 struct hhe_enc_matrix {
     hhe_ctx *ctx = nullptr;
     size_t rows = 0, cols = 0, r = 0, c = 0;
+    bool open = false;           // hhe_enc_matrix_create_open: the diagonals that do not wrap, r and c of the open shape
     u64 *wq = nullptr;           // [r][2][L][N]: NTT form under the data primes
     u64 *wb = nullptr;           // [r][2][L+1][N]: NTT form of the extension to B_sk
     size_t bytes = 0;            // device footprint of wq + wb
@@ -258,6 +259,8 @@ struct hhe_ctx {
     u64 behz_sum_cap = 0;                      // most products hhe_multiply_sum floors as one sum (hhe_ctx_query("behz_sum_cap"); the condition is in hhe_gfx950.h)
     int sum_fold_q = 1, sum_fold_bsk = 1;      // tensor_sum_fold of the widest data prime / B_sk prime ("multiply_sum_fold_q" / "multiply_sum_fold_bsk")
     u64 multiply_sum_launches = 0;             // launches of the summed tensor kernel: one per modulus set per hhe_multiply_sum call or packed FC chunk
+    u64 tensor_launches = 0, square_launches = 0;  // launches of the one-product tensor kernels (plain or broadcast) / of the squaring kernel ("tensor_launches" / "square_launches")
+    u64 mlp_layers = 0, mlp_key_switches = 0;  // of the last hhe_mlp_ks call: its layers; Galois key switches per item summed over them ("mlp_layers" / "mlp_key_switches")
     u64 fc_packed_floors = 0;                  // polynomials floored per item by the last packed encrypted FC call: 3 r, or 3 for hhe_fc_packed_sum_ks
     int rot_hoist = 1;                         // hhe_rotate_rows_many_ks and the hoisted packed FC: 1 = children of a trie node share the digit transforms of its c1
                                                // (HHE_ROT_HOIST; 0: every step through op_rotate_rows, 2: every chunk also recomputed that way -- tests)

@@ -1733,10 +1733,44 @@ HD void tensor_sum_body(const TensorArgs &a, size_t gid)
     u64 *d = a.d + b * 3 * ps + j * n + i;
     for (int p = 0; p < 3; p++) st2(d + p * ps, U2{barrett128(s[p][0].lo, s[p][0].hi, m), barrett128(s[p][1].lo, s[p][1].hi, m)});
 }
+// The tensor product of a ciphertext with itself (hhe_square): gid over [limbs][N / 128][B][64], the geometry of tensor_sum_body -- a
+// lane holds two neighbouring coefficients, 16 B loads and stores.  The operand's two polynomials are read once and three are written:
+// a0^2, 2 a0 a1 and a1^2.  The middle one is ONE wide product doubled in 128 bits and reduced once: 2 (q - 1)^2 < 2^123 at 61 bits, so
+// nothing wraps (add_nw checks the high word under -DHHE_RANGE_CHECK).  barrett128 and mulmod return the canonical residue, so the
+// words are those of tensor_body_t on (a, a).
+HD u64 square_mid(u64 x, u64 y, const ModDev &m)
+{
+    Acc128 s = {0, 0};
+    acc_mac_nw(s, x, y);
+    const u64 carry = s.lo >> 63;
+    s.lo <<= 1;
+    s.hi = add_nw(s.hi, s.hi + carry);
+    return barrett128(s.lo, s.hi, m);
+}
+HD void tensor_square_body(const TensorArgs &a, size_t gid)
+{
+    const size_t n = (size_t)1 << a.logn;
+    const u32 lane = (u32)gid & 63;
+    size_t r = gid >> 6;
+    const size_t b = r % (u32)a.B;
+    r /= (u32)a.B;
+    const size_t tile = r & (((size_t)1 << (a.logn - 7)) - 1);
+    const size_t j = r >> (a.logn - 7);
+    if (j >= (size_t)a.limbs) return;
+    const ModDev m = mod_at(a.mods, a.mod_base + (int)j);
+    const size_t ps = (size_t)a.limbs * n, i = (tile << 7) + 2 * lane;
+    const u64 *pa = a.a + b * 2 * ps + j * n + i;
+    const U2 a0 = ld2(pa), a1 = ld2(pa + ps);
+    u64 *d = a.d + b * 3 * ps + j * n + i;
+    st2(d, U2{mulmod(a0.a, a0.a, m), mulmod(a0.b, a0.b, m)});
+    st2(d + ps, U2{square_mid(a0.a, a1.a, m), square_mid(a0.b, a1.b, m)});
+    st2(d + 2 * ps, U2{mulmod(a1.a, a1.a, m), mulmod(a1.b, a1.b, m)});
+}
 // the launch as the tests-only emulator loops it; on the device each form is a kernel of its own
 HD void tensor_body(const TensorArgs &a, size_t gid)
 {
-    if (a.sum) tensor_sum_body(a, gid);
+    if (a.square) tensor_square_body(a, gid);
+    else if (a.sum) tensor_sum_body(a, gid);
     else if (a.b_div) tensor_body_t<true>(a, gid);
     else tensor_body_t<false>(a, gid);
 }

@@ -651,6 +651,7 @@ __global__ void __launch_bounds__(ELT_THREADS) behz_extend_kernel(BehzExtendArgs
 __global__ void __launch_bounds__(ELT_THREADS) tensor_kernel(TensorArgs a) { tensor_body_t<false>(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) tensor_bcast_kernel(TensorArgs a) { tensor_body_t<true>(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) tensor_sum_kernel(TensorArgs a) { tensor_sum_body(a, GID); }
+__global__ void __launch_bounds__(ELT_THREADS) tensor_square_kernel(TensorArgs a) { tensor_square_body(a, GID); }
 __global__ void __launch_bounds__(ELT_THREADS) behz_floor_kernel(BehzFloorArgs a) { behz_floor_body(a, GID); }
 
 #define LAUNCH1D(kern, total, s, ...)                                                                   \
@@ -752,7 +753,8 @@ void k_bsgs_diag(const BsgsDiagArgs &a, rt_stream s) { LAUNCH1D(bsgs_diag_kernel
 void k_behz_extend(const BehzExtendArgs &a, rt_stream s) { LAUNCH1D(behz_extend_kernel, (size_t)a.P << a.logn, s, a); }
 void k_tensor(const TensorArgs &a, rt_stream s)
 {
-    if (a.sum) LAUNCH1D(tensor_sum_kernel, ((size_t)a.B * a.limbs) << (a.logn - 1), s, a);  // a lane holds two coefficients
+    if (a.square) LAUNCH1D(tensor_square_kernel, ((size_t)a.B * a.limbs) << (a.logn - 1), s, a);  // a lane holds two coefficients
+    else if (a.sum) LAUNCH1D(tensor_sum_kernel, ((size_t)a.B * a.limbs) << (a.logn - 1), s, a);
     else if (a.b_div) LAUNCH1D(tensor_bcast_kernel, ((size_t)a.B * a.limbs) << a.logn, s, a);
     else LAUNCH1D(tensor_kernel, ((size_t)a.B * a.limbs) << a.logn, s, a);
 }
