@@ -173,6 +173,13 @@ int hhe_multiply(hhe_ctx *c, const uint64_t *a_dptr, const uint64_t *b_dptr, uin
  *     K N t Q (1 + rho)^2 / 2 + L  <  B (floor(m_sk / 2) - L),
  * and hhe_ctx_query("behz_sum_cap") is the largest such K of the context (from its own primes, saturating at 2^63 - 1; 0 when there is
  * none).  K >= 2 above it: HHE_ERR_INVALID, out3 untouched.  K == 1 is always served, as hhe_multiply serves it.
+ * "behz_sum_cap" == 0 (a 60-bit t over 60-bit primes at N = 1024, for one) means that even ONE product of arbitrary words is outside
+ * the proved bound: on operands whose coefficients sit at +-Q / 2, hhe_multiply is then far more than L + 1 from the rounded integer
+ * product -- word for word what Evaluator::multiply gives, the limit of BEHZ at such parameters and not of this library.  The calls
+ * that floor one product at a time (hhe_multiply, hhe_square, hhe_fc_packed_ks, hhe_fc_packed_hoisted_ks) are still served, as SEAL
+ * serves them, and decrypt correctly on real encryptions where the parameters leave noise budget (the words of an encryption are
+ * uniform, far from that worst case); the sum forms with two addends or more (hhe_multiply_sum, hhe_fc_packed_sum_ks, hhe_fc_open_ks,
+ * hhe_mlp_ks with r >= 2) refuse.
  * Also HHE_ERR_INVALID: a null pointer, K == 0, B == 0, out3 overlapping an operand, K * B operands whose extended polynomials pass
  * 2^31 coefficients.  The workspaces grow to K * B operands the way
  * hhe_multiply's grow to B.  One launch of the summed tensor kernel per modulus set ("multiply_sum_launches" counts them); its 128-bit

@@ -114,6 +114,14 @@ class Env:
             a[:, j, ::2 if alternate else 1] = self.q[j] - 1
         return a
 
+    def half(self, size, negative=False):
+        """every coefficient the residues of (Q - 1) / 2, the largest centred value; negative: of (Q + 1) / 2, which is -(Q - 1) / 2"""
+        v = (self.Q + 1) // 2 if negative else (self.Q - 1) // 2
+        a = np.zeros((size, self.L, self.n), np.uint64)
+        for j in range(self.L):
+            a[:, j] = v % self.q[j]
+        return a
+
 
 _envs = {}
 
@@ -689,10 +697,11 @@ def centred_lift(E, a):
 
 
 def behz_pairs(E, seed):
-    """two encryptions; every word at q_j - 1 squared; q_j - 1 alternating with 0 against all q_j - 1; two pairs of uniform words"""
+    """two encryptions; every word at q_j - 1 squared; q_j - 1 alternating with 0 against all q_j - 1; two pairs of uniform words;
+    'half': every coefficient (Q - 1) / 2, squared -- the centred values of largest magnitude, where 'max' is the integer -1"""
     rng = np.random.default_rng(seed)
     return [(E.encryption(seed + 30), E.encryption(seed + 31)), (E.maxed(2), E.maxed(2)), (E.maxed(2, True), E.maxed(2)),
-            (E.uniform(rng, 2), E.uniform(rng, 2)), (E.uniform(rng, 2), E.uniform(rng, 2))]
+            (E.uniform(rng, 2), E.uniform(rng, 2)), (E.uniform(rng, 2), E.uniform(rng, 2)), (E.half(2), E.half(2))]
 
 
 def behz_distance(E, a, b, out3, idx):

@@ -245,7 +245,8 @@ def check_network(X, S, mem, shapes, B=2, seed=0, in_place=False, data=None, slo
 
 
 def square_operands(E, B, pattern, seed):
-    """[B][2][L][N]: 'enc' encryptions, 'max' every word q_j - 1, 'alt' q_j - 1 alternating with 0, 'rand' uniform words"""
+    """[B][2][L][N]: 'enc' encryptions, 'max' every word q_j - 1, 'alt' q_j - 1 alternating with 0, 'rand' uniform words, 'half' every
+    coefficient (Q - 1) / 2"""
     import mult_sum_common as ms
     return ms.operands(E, 1, B, pattern, seed)[0][0]
 

@@ -77,6 +77,19 @@ class Restate:
         r = np.array([v - MT if v >= MT // 2 else v for v in r], dtype=object)
         return xq + [(y[i] + self.Q * r) * pow(MT, -1, p) % p for i, p in enumerate(self.bsk)]
 
+    def representative(self, x):
+        """one polynomial [L][N] -> object array of the integers sm_mrq leaves for it: the CRT over q u B_sk of extend(x), centred.
+        It is congruent to x modulo Q and within (Q / 2)(1 + rho), rho = (2L + 1) / 2^32 -- the premise of the cap, asserted here --
+        and it is the centred lift except where x is within L Q / 2^32 of -Q / 2, where it is the lift + Q"""
+        L, mods = len(self.qd), self.qd + self.bsk
+        M = self.Q * self.B * self.msk
+        acc = np.zeros(self.E.n, dtype=object)
+        for res, p in zip(self.extend(x), mods):
+            acc = acc + res * ((M // p) * pow(M // p, -1, p) % M)
+        rep = np.array([v - M if v > M // 2 else v for v in (acc % M)], dtype=object)
+        assert all(abs(int(v)) * (1 << 33) <= self.Q * (MT + 2 * L + 1) for v in rep), "an operand leaves sm_mrq outside (Q / 2)(1 + rho)"
+        return rep
+
     def transformed(self, ct):
         """a ciphertext [2][L][N] -> [2][2L + 1] transforms of its extended polynomials, object arrays"""
         O = self.E.O
@@ -158,11 +171,13 @@ def restate(E):
     return E.stored("mult_sum_restate", lambda: Restate(E))
 
 
-def sum_distance(E, a, b, out3, idx):
+def sum_distance(E, a, b, out3, idx, lift=None):
     """behz_distance for a sum: max over the three polynomials and the coefficients idx of the centred distance between CRT(out) and
-    floor((2 t sum_k d_k + Q) / (2 Q)), d_k the integer tensor product of the centred lifts of pair k"""
+    floor((2 t sum_k d_k + Q) / (2 Q)), d_k the integer tensor product of the centred lifts of pair k.  lift: another integer
+    representative of a polynomial [L][N] than its centred lift (Restate.representative)"""
     Q, t = E.Q, E.t
-    pairs = distinct_pairs(a, b, lambda ct: [dc.centred_lift(E, ct[k]) for k in range(2)])
+    lift = lift or (lambda x: dc.centred_lift(E, x))
+    pairs = distinct_pairs(a, b, lambda ct: [lift(ct[k]) for k in range(2)])
     coef = [(Q // qj) * pow(Q // qj, -1, qj) % Q for qj in E.q[:E.L]]
     worst = 0
     for l in idx:
@@ -181,7 +196,17 @@ def sum_distance(E, a, b, out3, idx):
 # ---- inputs ----
 def operands(E, K, B, pattern, seed):
     """(a, b) [K][B][2][L][N]: 'enc' real encryptions, 'max' every word q_j - 1, 'alt' q_j - 1 alternating with 0 against all q_j - 1,
-    'rand' uniform words"""
+    'rand' uniform words; 'half' every coefficient of every operand (Q - 1) / 2, the centred value of largest magnitude, 'half_neg' the
+    same against (Q + 1) / 2 = -(Q - 1) / 2, 'half_mixed' K - 1 'half' pairs and a last pair of uniform words"""
+    if pattern in ("half", "half_neg", "half_mixed"):
+        h = E.half(2)
+        a = np.broadcast_to(h, (K, B) + h.shape).copy()
+        b_ = np.broadcast_to(E.half(2, True) if pattern == "half_neg" else h, (K, B) + h.shape).copy()
+        if pattern == "half_mixed":
+            rng = np.random.default_rng(seed)
+            for item in range(B):
+                a[K - 1, item], b_[K - 1, item] = E.uniform(rng, 2), E.uniform(rng, 2)
+        return a, b_
     if pattern == "enc":
         pool = [E.encryption(seed + i) for i in range(4)]
         a = np.stack([np.stack([pool[(k + b) % 4] for b in range(B)]) for k in range(K)])

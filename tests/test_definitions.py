@@ -76,8 +76,8 @@ def test_add_plain_is_the_rounded_scaling(orc, api, emu_lib, mem, name):
 
 @pytest.mark.parametrize("name", BOTH)
 def test_behz_multiply_distance(orc, api, emu_lib, mem, name):
-    """f. at most L + 1 = 3 from the rounded integer tensor product at 32 coefficients, five input pairs.  Largest distance observed,
-    on the oracle and on the emulator alike: 2 at N = 1024 (3 x 50 bits) and 2 at N = 4096 (3 x 60 bits); per pair 2, 1, 1, 2, 2 at
-    both (two encryptions; all q_j - 1 squared; alternating against all q_j - 1; two uniform pairs)."""
+    """f. at most L + 1 = 3 from the rounded integer tensor product at 32 coefficients, six input pairs.  Largest distance observed,
+    on the oracle and on the emulator alike: 2 at N = 1024 (3 x 50 bits) and 2 at N = 4096 (3 x 60 bits); per pair 2, 1, 1, 2, 2, 2 at
+    both (two encryptions; all q_j - 1 squared; alternating against all q_j - 1; two uniform pairs; all (Q - 1) / 2 squared)."""
     E, make_ctx = dc.setup(orc, api, emu_lib, name)
     dc.check_behz(make_ctx, E, mem)

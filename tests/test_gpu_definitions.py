@@ -82,7 +82,7 @@ def test_add_plain_is_the_rounded_scaling(orc, api, lib, mem, name):
 
 @pytest.mark.parametrize("name", ["n1024", "row12", "A"])
 def test_behz_multiply_distance(orc, api, lib, mem, name):
-    """f. at most L + 1 = 3 from the rounded integer tensor product at 32 coefficients, five input pairs.  Largest distance observed on
+    """f. at most L + 1 = 3 from the rounded integer tensor product at 32 coefficients, six input pairs (the last: every coefficient (Q - 1) / 2, squared).  Largest distance observed on
     the oracle: 2 at N = 1024 (3 x 50 bits), 2 at N = 4096 (3 x 60 bits) and 2 on BFVDefault(4096)."""
     E, make_ctx = dc.setup(orc, api, lib, name)
     dc.check_behz(make_ctx, E, mem)

@@ -67,7 +67,7 @@ def test_k1_cap_and_intervals(orc, api, lib, mem, name):
     X = api.Context(E.logn, E.q, E.t, lib=lib)
     assert ms.check_cap(X, E) > E.n // 2
     assert X.query("multiply_sum_fold_q") == ms.hand_fold(E.q[:E.L]) and X.query("multiply_sum_fold_bsk") == ms.hand_fold(E.bsk)
-    for pattern in ("enc", "max", "alt", "rand"):
+    for pattern in ("enc", "max", "alt", "rand", "half"):
         a, b = ms.operands(E, 1, 3, pattern, 11)
         want = mem.empty((3, 3, E.L, E.n))
         X.multiply(mem.to_dev(a[0]), mem.to_dev(b[0]), want, 3)
@@ -78,12 +78,13 @@ def test_k1_cap_and_intervals(orc, api, lib, mem, name):
 @pytest.mark.parametrize("which", range(5))
 @pytest.mark.parametrize("name", list(PARAMS))
 def test_sums_against_the_restatement(orc, api, lib, mem, name, which):
-    """K = 2, 3, 16 and one above each reduction interval; encryptions, q_j - 1 everywhere, alternating with 0, uniform; B = 1 and 3"""
+    """K = 2, 3, 16 and one above each reduction interval; encryptions, q_j - 1 everywhere, alternating with 0, uniform,
+    (Q - 1) / 2 everywhere; B = 1 and 3"""
     E = _env(orc, name)
     K = [2, 3, 16, ms.hand_fold(E.bsk) + 1, ms.hand_fold(E.q[:E.L]) + 1][which]
     X = api.Context(E.logn, E.q, E.t, lib=lib)
     worst = 0
-    for pattern in ("enc", "max", "alt", "rand"):
+    for pattern in ("enc", "max", "alt", "rand", "half"):
         for B in ((1, 3) if K <= 3 else (1,)):
             worst = max(worst, ms.check_words(X, E, mem, K, B, pattern, seed=20 + which))
     print("worst summed BEHZ distance, %s, K = %d: %d (cap L + 1 = %d)" % (name, K, worst, E.L + 1))

@@ -60,7 +60,7 @@ def test_square_is_the_oracles_multiply(orc, api, lib, mem, name):
     logn, bits = PARAMS[name]
     E = dc.env(orc, logn, orc.coeff_modulus_create(1 << logn, bits), T)
     X = api.Context(E.logn, E.q, E.t, lib=lib)
-    for pattern in ("enc", "max", "alt", "rand"):
+    for pattern in ("enc", "max", "alt", "rand", "half"):
         for B in (1, 3):
             mc.check_square(X, E, mem, B, pattern, seed=11 + B)
     X.close()

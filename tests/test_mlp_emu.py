@@ -72,7 +72,7 @@ def test_helper_refusals(api, emu_lib):
 
 
 # ---- 2. the square ----
-@pytest.mark.parametrize("pattern", ["enc", "max", "alt", "rand"])
+@pytest.mark.parametrize("pattern", ["enc", "max", "alt", "rand", "half"])
 @pytest.mark.parametrize("name", list(PARAMS))
 def test_square_is_the_oracles_multiply(orc, api, emu_lib, mem, name, pattern):
     logn, bits = PARAMS[name]

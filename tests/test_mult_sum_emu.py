@@ -68,7 +68,7 @@ def test_cap_and_intervals_against_python(orc, api, emu_lib, name):
 def test_k1_gives_the_words_of_multiply(orc, api, emu_lib, mem, name):
     E = _env(orc, name)
     X = _ctx(api, emu_lib, E)
-    for pattern in ("enc", "max", "alt", "rand"):
+    for pattern in ("enc", "max", "alt", "rand", "half"):
         a, b = ms.operands(E, 1, 3, pattern, 11)
         want = mem.empty((3, 3, E.L, E.n))
         X.multiply(mem.to_dev(a[0]), mem.to_dev(b[0]), want, 3)
@@ -93,7 +93,7 @@ def test_sums_against_the_restatement(orc, api, emu_lib, mem, name, which):
     if which >= 3:
         assert K == (X.query("multiply_sum_fold_bsk"), X.query("multiply_sum_fold_q"))[which - 3] + 1
     worst = 0
-    for pattern in ("enc", "max", "alt", "rand"):
+    for pattern in ("enc", "max", "alt", "rand", "half"):
         for B in ((1, 3) if K <= 3 else (1,)):
             worst = max(worst, ms.check_words(X, E, mem, K, B, pattern, seed=20 + which))
     print("worst summed BEHZ distance, %s, K = %d: %d (cap L + 1 = %d)" % (name, K, worst, E.L + 1))
