@@ -805,7 +805,8 @@ void shared_l0_tail(hhe_ctx *c, const u64 *sums, size_t B)
 }
 
 // ------------------------------------------------------------------ chunk scheduler of the batched calls
-// hhe_pasta3_transcipher, hhe_fc_row and hhe_packed_affine cut a batch into independent chunks of `per` items (the last one may be
+// Every batched call -- hhe_pasta3_transcipher, hhe_packed_affine, and through run_chunks_checked hhe_fc_row, hhe_rotate_rows_many_ks,
+// the packed encrypted layers and hhe_mlp_ks -- cuts its batch into independent chunks of `per` items (the last one may be
 // shorter): a chunk's working set stays cache resident, and chunks on concurrent streams de-phase the load / butterfly / store phases
 // of the transforms.  Chunk idx runs on internal lane 1 + idx % ns; with ns = 0 every chunk runs on the main lane, in order.
 struct ChunkPlan {
@@ -843,6 +844,67 @@ int run_chunks(hhe_ctx *c, const ChunkPlan &pl, const std::function<int(Lane &, 
     }
     c->w = &main;
     return rc;
+}
+// A call whose result may alias its input (`in == out`, `item_words` words per item): a recomputed chunk would read its own result, so
+// run_chunks_checked parks the results in c->d_blocks (reserved under `what`) and copies them out after the recomputations.  The
+// chunks write to `res`, which the runner sets
+struct Parked {
+    const u64 *in; u64 *out; size_t item_words; const char *what;
+    u64 *res;
+};
+// The whole of a call that has an optimistic form, exact unless a digit load meets a zero residue, and an exact one (DESIGN.md
+// section 1, "Checked chunks").  reserve(lane, fast) reserves a lane for a chunk of pl.per items; chunk(lane, idx, b0, count, fast)
+// enqueues one, as for run_chunks.  fast: every chunk runs in the optimistic form with lane.zero_flag on a flag of its own; the flags
+// are read back after the join, and every chunk whose flag is up (every chunk with force_exact) counts in `fallbacks` and is
+// recomputed in the exact form on the main lane -- which is reserved for that form only then: everything has completed.
+// !fast: the chunks run in the exact form, no flag is made or read.  Ends with the call's final wait; `who` names the call in a
+// device failure, `flags_what` its flags in an allocation failure.
+int run_chunks_checked(hhe_ctx *c, const ChunkPlan &pl, const char *who, const char *flags_what, bool fast, bool force_exact, u64 &fallbacks,
+                       const std::function<int(Lane &, bool)> &reserve,
+                       const std::function<int(Lane &, size_t, size_t, size_t, bool)> &chunk, Parked *park = nullptr)
+{
+    Lane &main = c->lanes[0];
+    int rc;
+    for (int s = pl.first_lane(); s <= pl.last_lane(); ++s)
+        if ((rc = reserve(c->lanes[s], fast))) return rc;
+    const bool parked = fast && park && park->in == park->out;
+    if (park) park->res = park->out;
+    if (parked) {
+        if ((rc = c->d_blocks.reserve(c, pl.B * park->item_words, park->what))) return rc;
+        park->res = c->d_blocks.p;
+    }
+    u32 *flags = nullptr;
+    if (fast) {
+        if ((rc = c->d_flags.reserve(c, pl.nch, flags_what))) return rc;  // one flag per chunk
+        flags = c->d_flags.p;
+        rt_memset(flags, 0, pl.nch * 4, main.stream);
+    }
+    rc = run_chunks(c, pl, [&](Lane &ln, size_t idx, size_t b0, size_t bc) {
+        ln.zero_flag = fast ? flags + idx : nullptr;
+        return chunk(ln, idx, b0, bc, fast);
+    });
+    if (fast && !rc) {
+        std::vector<u32> h(pl.nch, 0);
+        if (rt_d2h(h.data(), flags, pl.nch * 4, main.stream) || rt_sync(main.stream)) rc = dev_fail(who);
+        for (size_t idx = 0; idx < pl.nch && !rc; ++idx)
+            if (h[idx] || force_exact) {
+                fallbacks++;
+                main.zero_flag = nullptr;
+                if (!(rc = reserve(main, false))) rc = chunk(main, idx, idx * pl.per, pl.count(idx), false);
+            }
+        if (!rc && parked) rt_d2d(park->out, park->res, pl.B * park->item_words * 8, main.stream);
+    }
+    if (rt_sync(main.stream) && !rc) rc = dev_fail(who);
+    return rc;
+}
+// the tail of the *_galois_steps entry points: the count always, the steps when they fit
+int steps_out_copy(const char *who, const std::vector<int> &steps, int *steps_out, size_t *count)
+{
+    const size_t cap = *count;
+    *count = steps.size();
+    if (!steps_out || cap < steps.size()) return fail(HHE_ERR_CAPACITY, std::string(who) + ": output too small");
+    std::copy(steps.begin(), steps.end(), steps_out);
+    return HHE_OK;
 }
 
 }  // namespace
@@ -2079,40 +2141,17 @@ static int fc_row_impl(hhe_ctx *c, const uint64_t *vi, const uint64_t *w, size_t
     ChunkPlan plan(B, std::min(per, B), c->nstreams);
     if (plan.nch == 1) plan.ns = 0;
     const size_t ctw = c->ct_words();
-    Lane &main = c->lanes[0];
-    const bool shared = c->fc_shared != 0;
-    auto reserve = [&](Lane &ln) {
-        int r = lane_reserve(c, ln, plan.per);
-        if (!r) r = ln.ws_rot.reserve(c, plan.per * ROT_SLOTS * ctw, "hhe_fc_row workspace");
-        if (!r && c->fc_leaf_sums) r = ln.ws_leaf.reserve(c, plan.per * 4 * (size_t)HHE_LEAF_GROUP * c->n, "hhe_fc_row workspace");
-        return r;
-    };
-    for (int s = plan.first_lane(); s <= plan.last_lane(); ++s)
-        if ((rc = reserve(c->lanes[s]))) return rc;
-    u32 *flags = nullptr;
-    if (shared) {
-        if ((rc = c->d_flags.reserve(c, plan.nch, "hhe_fc_row"))) return rc;  // one flag per chunk
-        flags = c->d_flags.p;
-        rt_memset(flags, 0, plan.nch * 4, main.stream);
-    }
-    auto chunk = [&](Lane &ln, size_t idx, size_t b0, size_t bc, bool sh) {
-        ln.zero_flag = sh ? flags + idx : nullptr;
-        return fc_row_chunk(c, sh, trie, max_depth, vi + b0 * ctw, w, W, out + b0 * ctw, bc);
-    };
-    rc = run_chunks(c, plan, [&](Lane &ln, size_t idx, size_t b0, size_t bc) { return chunk(ln, idx, b0, bc, shared); });
-    if (shared && !rc) {
-        std::vector<u32> h(plan.nch, 0);
-        if (rt_d2h(h.data(), flags, plan.nch * 4, main.stream) || rt_sync(main.stream)) rc = dev_fail("hhe_fc_row");
-        // a zero coefficient in some c1 (probability ~ N/q per ciphertext): that chunk is recomputed with per-child transforms, on the
-        // main lane (which grows, if it must, before the first of them: everything has completed by then)
-        for (size_t idx = 0; idx < plan.nch && !rc; ++idx)
-            if (h[idx] || c->fc_shared == 2) {
-                c->fc_fallbacks++;
-                if (!(rc = reserve(main))) rc = chunk(main, idx, idx * plan.per, plan.count(idx), false);
-            }
-    }
-    if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_fc_row");
-    return rc;
+    // a zero coefficient in some c1 (probability ~ N/q per ciphertext): that chunk is recomputed with per-child transforms
+    return run_chunks_checked(c, plan, "hhe_fc_row", "hhe_fc_row", c->fc_shared != 0, c->fc_shared == 2, c->fc_fallbacks,
+        [&](Lane &ln, bool) {
+            int r = lane_reserve(c, ln, plan.per);
+            if (!r) r = ln.ws_rot.reserve(c, plan.per * ROT_SLOTS * ctw, "hhe_fc_row workspace");
+            if (!r && c->fc_leaf_sums) r = ln.ws_leaf.reserve(c, plan.per * 4 * (size_t)HHE_LEAF_GROUP * c->n, "hhe_fc_row workspace");
+            return r;
+        },
+        [&](Lane &, size_t, size_t b0, size_t bc, bool shared) {
+            return fc_row_chunk(c, shared, trie, max_depth, vi + b0 * ctw, w, W, out + b0 * ctw, bc);
+        });
 }
 extern "C" int hhe_fc_row_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const uint64_t *vi, const uint64_t *w, size_t W, size_t n_inputs,
                              uint64_t *out, size_t B)
@@ -2238,12 +2277,7 @@ extern "C" int hhe_affine_galois_steps(size_t N, size_t dim, size_t n1, size_t n
     if (!count) return fail(HHE_ERR_INVALID, "hhe_affine_galois_steps: null argument");
     std::vector<int> steps;
     int rc = affine_steps(N, dim, n1, n2, steps);
-    if (rc) return rc;
-    const size_t cap = *count;
-    *count = steps.size();
-    if (!steps_out || cap < steps.size()) return fail(HHE_ERR_CAPACITY, "hhe_affine_galois_steps: output too small");
-    std::copy(steps.begin(), steps.end(), steps_out);
-    return HHE_OK;
+    return rc ? rc : steps_out_copy("hhe_affine_galois_steps", steps, steps_out, count);
 }
 
 extern "C" int hhe_matrix_create(hhe_ctx *c, const uint64_t *M, size_t dim, const uint64_t *bias, size_t n1, size_t n2, hhe_matrix **out)
@@ -2532,32 +2566,13 @@ extern "C" int hhe_rotate_rows_many_ks(hhe_ctx *c, const hhe_keyset *gk, const u
     const size_t per = std::min(B, std::max<size_t>(1, c->chunk / plan.group()));
     const ChunkPlan cp(B, per, c->nstreams);
     const bool whole = cp.nch == 1;   // ostride == per
-    for (int s = cp.first_lane(); s <= cp.last_lane(); ++s)
-        if ((rc = rot_many_reserve(c, c->lanes[s], plan, hoisted, whole, per))) return rc;
-    u32 *flags = nullptr;
-    if (hoisted) {
-        if ((rc = c->d_flags.reserve(c, cp.nch, "hhe_rotate_rows_many"))) return rc;  // one flag per chunk
-        flags = c->d_flags.p;
-        rt_memset(flags, 0, cp.nch * 4, main.stream);
-    }
-    rc = run_chunks(c, cp, [&](Lane &ln, size_t idx, size_t b0, size_t bc) {
-        ln.zero_flag = hoisted ? flags + idx : nullptr;
-        // a shorter last chunk of several does not cover the stride: its children go through the arena, which is sized for that
-        return rot_many_chunk(c, plan, hoisted, ct + b0 * ctw, out + b0 * ctw, B, bc);
-    });
-    if (hoisted && !rc) {
-        std::vector<u32> h(cp.nch, 0);
-        if (rt_d2h(h.data(), flags, cp.nch * 4, main.stream) || rt_sync(main.stream)) rc = dev_fail("hhe_rotate_rows_many");
-        // a zero residue in some c1: that chunk is recomputed step by step on the main lane (everything has completed by then)
-        for (size_t idx = 0; idx < cp.nch && !rc; ++idx)
-            if (h[idx] || c->rot_hoist == 2) {
-                c->rot_many_fallbacks++;
-                main.zero_flag = nullptr;
-                if (!(rc = rot_many_reserve(c, main, plan, false, false, per)))
-                    rc = rot_many_chunk(c, plan, false, ct + idx * per * ctw, out + idx * per * ctw, B, cp.count(idx));
-            }
-    }
-    if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_rotate_rows_many");
+    // a zero residue in some c1: that chunk is recomputed step by step.  out does not overlap ct, so nothing is parked
+    rc = run_chunks_checked(c, cp, "hhe_rotate_rows_many", "hhe_rotate_rows_many", hoisted, c->rot_hoist == 2, c->rot_many_fallbacks,
+        [&](Lane &ln, bool h) { return rot_many_reserve(c, ln, plan, h, h && whole, per); },
+        [&](Lane &, size_t, size_t b0, size_t bc, bool h) {
+            // a shorter last chunk of several does not cover the stride: its children go through the arena, which is sized for that
+            return rot_many_chunk(c, plan, h, ct + b0 * ctw, out + b0 * ctw, B, bc);
+        });
     if (!rc) { c->rot_many_key_switches = plan.trie.size() - 1; c->rot_many_launches = hoisted ? plan.launches : 0; }
     return rc;
 }
@@ -2571,40 +2586,55 @@ size_t pow2_ceil(size_t v)
     while (p < v) p <<= 1;
     return p;
 }
-// r and c of a rows x cols layer; n = 0: no degree, no slot rule (the diagonals' layout does not depend on it)
-int fc_packed_dims(size_t n, size_t rows, size_t cols, size_t &r, size_t &cc)
+// r and c of a rows x cols layer; n = 0: no degree, no slot rule (the diagonals' layout does not depend on it).  Cyclic: c covers cols,
+// and fills the row or leaves room for the copy at -c.  Open (hhe_fc_open_shape): the diagonals do not wrap, so c covers cols + r - 1
+// slots; c <= N/2 is the only slot rule
+int fc_dims(bool open, size_t n, size_t rows, size_t cols, size_t &r, size_t &cc)
 {
-    if (rows == 0 || cols == 0 || rows > ((size_t)1 << 30) || cols > ((size_t)1 << 30)) return fail(HHE_ERR_INVALID, "packed FC: rows and cols must be positive (and at most 2^30)");
-    if (n && (n < 4 || (n & (n - 1)))) return fail(HHE_ERR_INVALID, "packed FC: the degree must be a power of two");
+    const std::string w = open ? "open FC" : "packed FC";
+    if (rows == 0 || cols == 0 || rows > ((size_t)1 << 30) || cols > ((size_t)1 << 30)) return fail(HHE_ERR_INVALID, w + ": rows and cols must be positive (and at most 2^30)");
+    if (n && (n < 4 || (n & (n - 1)))) return fail(HHE_ERR_INVALID, w + ": the degree must be a power of two");
     r = pow2_ceil(rows);
-    cc = std::max(pow2_ceil(cols), r);
-    if (n && cc * 2 != n && cc * 4 > n) return fail(HHE_ERR_TOO_FEW_SLOTS, "too little slots for matmul implementation!");
+    cc = open ? pow2_ceil(cols + r - 1) : std::max(pow2_ceil(cols), r);
+    if (n && (open ? cc * 2 > n : cc * 2 != n && cc * 4 > n)) return fail(HHE_ERR_TOO_FEW_SLOTS, "too little slots for matmul implementation!");
     return HHE_OK;
 }
-// the rotate_rows steps in the order the layer takes them: -c unless the row is full, +1 when there is a chain, the tail r 2^k < c
-void fc_packed_steps(size_t n, size_t r, size_t cc, std::vector<int> &steps)
+// The rotate_rows steps of a layer in the order it takes them (what the *_galois_steps entry points list): -c unless the row is full
+// (cyclic only), the steps of the r - 1 rotations, the tail r 2^k < c.  The rotations are all[rot0, rot0 + nrot): 1 .. r-1 of a cyclic
+// layer, -1 .. -(r-1) of an open one -- they go into the layer's RotPlan, which serves them as hhe_rotate_rows_many_ks does -- or,
+// chained, the one step 1 that is taken r - 1 times.  Every other step needs its own key: its NAF has one term, so
+// Evaluator::rotate_rows throws without it
+struct FcSteps {
+    std::vector<int> all;
+    size_t rot0 = 0, nrot = 0;
+    size_t own() const { return all.size() - nrot; }
+};
+FcSteps fc_layer_steps(bool open, bool chained, size_t n, size_t r, size_t cc)
 {
-    steps.clear();
-    if (cc * 2 != n) steps.push_back(-(int)cc);
-    if (r > 1) steps.push_back(1);
-    for (size_t s = r; s < cc; s <<= 1) steps.push_back((int)s);
+    FcSteps s;
+    if (!open && cc * 2 != n) s.all.push_back(-(int)cc);
+    s.rot0 = s.all.size();
+    for (size_t i = 1; i < (chained ? std::min<size_t>(r, 2) : r); ++i) s.all.push_back(open ? -(int)i : (int)i);
+    s.nrot = s.all.size() - s.rot0;
+    for (size_t t = r; t < cc; t <<= 1) s.all.push_back((int)t);
+    return s;
 }
-// r and c of the open layout (hhe_fc_open_shape): the diagonals do not wrap, so c covers cols + r - 1 slots; c <= N/2 is the only slot rule
-int fc_open_dims(size_t n, size_t rows, size_t cols, size_t &r, size_t &cc)
+// the shape and the step list entry points of both layouts
+int fc_shape(const char *who, bool open, size_t N, size_t rows, size_t cols, size_t *r_out, size_t *c_out)
 {
-    if (rows == 0 || cols == 0 || rows > ((size_t)1 << 30) || cols > ((size_t)1 << 30)) return fail(HHE_ERR_INVALID, "open FC: rows and cols must be positive (and at most 2^30)");
-    if (n && (n < 4 || (n & (n - 1)))) return fail(HHE_ERR_INVALID, "open FC: the degree must be a power of two");
-    r = pow2_ceil(rows);
-    cc = pow2_ceil(cols + r - 1);
-    if (n && cc * 2 > n) return fail(HHE_ERR_TOO_FEW_SLOTS, "too little slots for matmul implementation!");
+    if (!r_out || !c_out || N == 0) return fail(HHE_ERR_INVALID, std::string(who) + ": null argument or no degree");
+    size_t r, cc;
+    int rc = fc_dims(open, N, rows, cols, r, cc);
+    if (rc) return rc;
+    *r_out = r; *c_out = cc;
     return HHE_OK;
 }
-// the rotate_rows steps of the open layer: -1 .. -(r-1) into `rot`, the tail r 2^k < c into `tail`
-void fc_open_steps(size_t r, size_t cc, std::vector<int> &rot, std::vector<int> &tail)
+int fc_galois_steps(const char *who, bool open, bool chained, size_t N, size_t rows, size_t cols, int *steps_out, size_t *count)
 {
-    rot.clear(); tail.clear();
-    for (size_t e = 1; e < r; ++e) rot.push_back(-(int)e);
-    for (size_t s = r; s < cc; s <<= 1) tail.push_back((int)s);
+    if (!count || N == 0) return fail(HHE_ERR_INVALID, std::string(who) + ": null argument or no degree");
+    size_t r, cc;
+    int rc = fc_dims(open, N, rows, cols, r, cc);
+    return rc ? rc : steps_out_copy(who, fc_layer_steps(open, chained, N, r, cc).all, steps_out, count);
 }
 // one chunk on the current lane: in / out [per][2][L][N] (may be the same buffer); the lane is reserved for r * per items
 // an open handle (hhe_fc_open_ks): no step 1, and the hoisted plan holds the steps -1 .. -(r-1)
@@ -2649,18 +2679,13 @@ void enc_matrix_free(hhe_enc_matrix *m)
 
 extern "C" int hhe_fc_packed_shape(size_t N, size_t rows, size_t cols, size_t *r_out, size_t *c_out)
 {
-    if (!r_out || !c_out || N == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed_shape: null argument or no degree");
-    size_t r, cc;
-    int rc = fc_packed_dims(N, rows, cols, r, cc);
-    if (rc) return rc;
-    *r_out = r; *c_out = cc;
-    return HHE_OK;
+    return fc_shape("hhe_fc_packed_shape", false, N, rows, cols, r_out, c_out);
 }
 extern "C" int hhe_fc_packed_diagonals(uint64_t t, const uint64_t *M, size_t rows, size_t cols, uint64_t *vals)
 {
     if (!M || !vals) return fail(HHE_ERR_INVALID, "hhe_fc_packed_diagonals: null argument");
     size_t r, cc;
-    int rc = fc_packed_dims(0, rows, cols, r, cc);
+    int rc = fc_dims(false, 0, rows, cols, r, cc);
     if (rc) return rc;
     for (size_t i = 0; i < rows * cols; ++i)
         if (M[i] >= t) return fail(HHE_ERR_INVALID, "hhe_fc_packed_diagonals: matrix entry not below the plain modulus");
@@ -2674,17 +2699,7 @@ extern "C" int hhe_fc_packed_diagonals(uint64_t t, const uint64_t *M, size_t row
 }
 extern "C" int hhe_fc_packed_galois_steps(size_t N, size_t rows, size_t cols, int *steps_out, size_t *count)
 {
-    if (!count || N == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed_galois_steps: null argument or no degree");
-    size_t r, cc;
-    int rc = fc_packed_dims(N, rows, cols, r, cc);
-    if (rc) return rc;
-    std::vector<int> steps;
-    fc_packed_steps(N, r, cc, steps);
-    const size_t cap = *count;
-    *count = steps.size();
-    if (!steps_out || cap < steps.size()) return fail(HHE_ERR_CAPACITY, "hhe_fc_packed_galois_steps: output too small");
-    std::copy(steps.begin(), steps.end(), steps_out);
-    return HHE_OK;
+    return fc_galois_steps("hhe_fc_packed_galois_steps", false, true, N, rows, cols, steps_out, count);
 }
 
 // open: the shape and the mark of hhe_enc_matrix_create_open; the resident form is the same
@@ -2693,7 +2708,7 @@ static int enc_matrix_create(hhe_ctx *c, const uint64_t *wdiag, size_t rows, siz
     HHE_LOCK(c);
     if (!c || !wdiag || !out) return fail(HHE_ERR_INVALID, "hhe_enc_matrix_create: null argument");
     size_t r, cc;
-    int rc = open ? fc_open_dims(c->n, rows, cols, r, cc) : fc_packed_dims(c->n, rows, cols, r, cc);
+    int rc = fc_dims(open, c->n, rows, cols, r, cc);
     if (rc) return rc;
     const size_t n = c->n, L = c->L;
     hhe_enc_matrix *m = new hhe_enc_matrix();
@@ -2733,169 +2748,145 @@ static size_t fc_packed_words(const hhe_ctx *c, const hhe_enc_matrix *m, size_t 
 {
     return (m->r * 2 + (sum ? 1 : m->r) * 3) * per * (size_t)c->L * c->n;
 }
-// sum: hhe_fc_packed_sum_ks with hoisted == 0
-static int fc_packed_run(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi, uint64_t *out, size_t B,
-                         bool sum)
+// one chunk of a call on the current lane: every layer of `per` items, a square and a relinearization between two layers, with no host
+// wait in between.  x_k lives in the lane's ws_ct[1] and the size-3 square in ws_ct3, which no step of a layer touches; the lane's
+// ws_fcp is reserved for the largest layer.  plans: one RotPlan per layer, or null for the chain of hhe_fc_packed_ks
+static int mlp_chunk(hhe_ctx *c, const hhe_enc_matrix *const *mats, size_t n_layers, const RotPlan *plans, const u64 *in, u64 *out, size_t per,
+                     bool stepwise, bool sum)
+{
+    Lane &w = *c->w;
+    u64 *x = w.ws_ct[1];
+    int rc;
+    for (size_t k = 0; k < n_layers; ++k) {
+        const bool last = k + 1 == n_layers;
+        if ((rc = fc_packed_chunk(c, mats[k], k ? x : in, last ? out : x, per, plans ? &plans[k] : nullptr, stepwise, sum))) return rc;
+        if (last) break;
+        op_square(c, x, w.ws_ct3, per);
+        if ((rc = op_relinearize(c, w.ws_ct3, x, per))) return rc;
+    }
+    return HHE_OK;
+}
+// What tells the packed encrypted layer calls apart.  `who` names the entry point in messages; the calls on cyclic handles keep the
+// texts they had as separate drivers
+struct FcForm {
+    bool open;     // open handles (hhe_enc_matrix_create_open), any number of layers, always summed; else ONE cyclic handle
+    bool chained;  // step 2 as the chain of r - 1 rotations by 1: no RotPlan, nothing optimistic; else the hoisted rotations of the plan
+    bool sum;      // steps 3 and 4 as one multiply_sum
+    const char *who;
+};
+// hhe_fc_packed_ks, hhe_fc_packed_hoisted_ks, hhe_fc_packed_sum_ks, hhe_fc_open_ks and hhe_mlp_ks: the first four are one-layer cases
+static int fc_layers_run(hhe_ctx *c, const FcForm &f, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *const *mats, size_t n_layers,
+                         const uint64_t *vi, uint64_t *out, size_t B)
 {
     HHE_LOCK(c);
-    if (!c || !m || !vi || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed: null argument or empty batch");
-    if (m->ctx != c) return fail(HHE_ERR_INVALID, "encrypted matrix belongs to another context");
-    if (m->open) return fail(HHE_ERR_INVALID, "hhe_fc_packed: an open handle (hhe_enc_matrix_create_open) takes hhe_fc_open_ks or hhe_mlp_ks");
-    if (sum && m->r >= 2 && m->r > c->behz_sum_cap) return fail(HHE_ERR_INVALID, "hhe_fc_packed_sum: more diagonals than one floor takes (behz_sum_cap)");
+    const std::string w(f.who);
+    if (!c || !mats || !vi || !out || B == 0 || n_layers == 0 || (!f.open && !mats[0]))
+        return fail(HHE_ERR_INVALID, w + (f.open ? ": null argument, empty batch or no layer" : ": null argument or empty batch"));
+    size_t max_r = 1;
+    for (size_t k = 0; k < n_layers; ++k) {
+        const hhe_enc_matrix *m = mats[k];
+        if (!m) return fail(HHE_ERR_INVALID, w + ": null handle");
+        if (m->ctx != c) return fail(HHE_ERR_INVALID, "encrypted matrix belongs to another context");
+        if (f.open && !m->open) return fail(HHE_ERR_INVALID, w + ": a cyclic handle (hhe_enc_matrix_create) takes the hhe_fc_packed calls");
+        if (!f.open && m->open) return fail(HHE_ERR_INVALID, "hhe_fc_packed: an open handle (hhe_enc_matrix_create_open) takes hhe_fc_open_ks or hhe_mlp_ks");
+        if (k && mats[k - 1]->rows != m->cols) return fail(HHE_ERR_INVALID, w + ": rows of a layer differ from cols of the next");
+        if (f.sum && m->r >= 2 && m->r > c->behz_sum_cap)
+            return fail(HHE_ERR_INVALID, (f.open ? w : "hhe_fc_packed_sum") + ": more diagonals than one floor takes (behz_sum_cap)");
+        max_r = std::max(max_r, m->r);
+    }
     int rc = check_sets(c, rk, gk);
     if (rc) return rc;
     KeyScope keys(c, gk, rk);
-    // everything the layer needs, before anything is written: the relinearization key, and every step's own key -- the NAF of +- a
-    // power of two has one term, so Evaluator::rotate_rows throws without it
+    // everything the layers need, before anything is written: the relinearization key, every step's own key, and the plans of all
+    // layers, which refuse a rotation that the named set cannot serve (rot_plan_build is host only)
     if (!c->rks->rk) return fail(HHE_ERR_NO_RELIN_KEY, "relinearization key not set");
-    std::vector<int> steps;
-    fc_packed_steps(c->n, m->r, m->c, steps);
-    for (int s : steps)
-        if (!c->gks->gk.count(galois_elt_from_step(c, s))) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+    std::vector<RotPlan> plans(n_layers);
+    auto hoisted = [&](size_t k) { return !f.chained && c->rot_hoist != 0 && mats[k]->r > 1; };
+    size_t kid_rows = 0, key_switches = 0, rot_ks = 0, layer_ks = 0;   // rot_ks, layer_ks: of the last layer
+    bool any_hoisted = false;
+    for (size_t k = 0; k < n_layers; ++k) {
+        const FcSteps s = fc_layer_steps(f.open, f.chained, c->n, mats[k]->r, mats[k]->c);
+        for (size_t i = 0; i < s.all.size(); ++i)
+            if ((f.chained || i < s.rot0 || i >= s.rot0 + s.nrot) && !c->gks->gk.count(galois_elt_from_step(c, s.all[i])))
+                return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+        rot_ks = f.chained ? mats[k]->r - 1 : 0;
+        if (!f.chained && s.nrot) {
+            if ((rc = rot_plan_build(c, s.all.data() + s.rot0, s.nrot, plans[k]))) return rc;
+            kid_rows += rot_ks = plans[k].trie.size() - 1;
+        }
+        key_switches += layer_ks = s.own() + rot_ks;
+        any_hoisted |= hoisted(k);
+    }
     Lane &main = c->lanes[0];
     c->w = &main;
+    // the layers share one child table: the plans lie one behind the other, a plan having one row per node below its root
+    for (size_t k = 0, ofs = 0; k < n_layers; ++k)
+        if (hoisted(k)) {
+            if ((rc = rot_plan_tables(c, plans[k], ofs, kid_rows))) return rc;
+            ofs += plans[k].trie.size() - 1;
+        }
     // a chunk runs the BEHZ passes of its r * per products at once: r * per stays within the HHE_CHUNK items a lane is reserved for elsewhere
-    const size_t per = std::min(B, std::max<size_t>(1, c->chunk / m->r));
-    const ChunkPlan plan(B, per, c->nstreams);
+    const size_t per = std::min(B, std::max<size_t>(1, c->chunk / max_r));
+    const ChunkPlan cp(B, per, c->nstreams);
     const size_t ctw = c->ct_words();
-    for (int s = plan.first_lane(); s <= plan.last_lane(); ++s) {
-        if ((rc = lane_reserve(c, c->lanes[s], m->r * per))) return rc;
-        if ((rc = c->lanes[s].ws_fcp.reserve(c, fc_packed_words(c, m, per, sum), "hhe_fc_packed: rotations and products"))) return rc;
+    Parked park{vi, out, ctw, f.open ? "hhe_mlp: results in place" : "hhe_fc_packed_hoisted: results in place", out};
+    // one flag per chunk, for the hoisted rotations of every layer; a flagged chunk is recomputed whole, from vi, step by step
+    rc = run_chunks_checked(c, cp, f.who, f.open ? "hhe_mlp" : "hhe_fc_packed_hoisted", any_hoisted, c->rot_hoist == 2, c->rot_many_fallbacks,
+        [&](Lane &ln, bool h) {
+            int r = HHE_OK;
+            size_t words = 0;
+            for (size_t k = 0; k < n_layers && !r; ++k) {
+                r = rot_many_reserve(c, ln, plans[k], h && hoisted(k), true, per, max_r * per);
+                words = std::max(words, fc_packed_words(c, mats[k], per, f.sum));
+            }
+            if (!r) r = ln.ws_fcp.reserve(c, words, f.open ? "hhe_mlp: rotations and products of the largest layer" : "hhe_fc_packed: rotations and products");
+            return r;
+        },
+        [&](Lane &, size_t, size_t b0, size_t bc, bool h) {
+            return mlp_chunk(c, mats, n_layers, f.chained ? nullptr : plans.data(), vi + b0 * ctw, park.res + b0 * ctw, bc, !h, f.sum);
+        }, &park);
+    if (rc) return rc;
+    const size_t last = n_layers - 1;
+    if (!f.chained) {
+        c->rot_many_key_switches = rot_ks;
+        c->rot_many_launches = hoisted(last) ? plans[last].launches : 0;
     }
-    rc = run_chunks(c, plan, [&](Lane &, size_t, size_t b0, size_t bc) { return fc_packed_chunk(c, m, vi + b0 * ctw, out + b0 * ctw, bc, nullptr, false, sum); });
-    if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_fc_packed");
-    if (!rc) {
-        c->fc_packed_key_switches = steps.size() - (m->r > 1 ? 1 : 0) + (m->r - 1);
-        c->fc_packed_floors = sum ? 3 : 3 * m->r;
-    }
-    return rc;
+    c->fc_packed_key_switches = layer_ks;
+    c->fc_packed_floors = f.sum ? 3 : 3 * mats[last]->r;
+    if (f.open) { c->mlp_layers = n_layers; c->mlp_key_switches = key_switches; }
+    return HHE_OK;
 }
 extern "C" int hhe_fc_packed_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi,
                                 uint64_t *out, size_t B)
 {
-    return fc_packed_run(c, rk, gk, m, vi, out, B, false);
-}
-
-// the steps of the hoisted layer: -c unless the row is full, 1 .. r-1, the tail r 2^k < c
-static void fc_packed_hoisted_steps(size_t n, size_t r, size_t cc, std::vector<int> &steps)
-{
-    steps.clear();
-    if (cc * 2 != n) steps.push_back(-(int)cc);
-    for (size_t i = 1; i < r; ++i) steps.push_back((int)i);
-    for (size_t s = r; s < cc; s <<= 1) steps.push_back((int)s);
+    return fc_layers_run(c, {false, true, false, "hhe_fc_packed"}, rk, gk, &m, 1, vi, out, B);
 }
 extern "C" int hhe_fc_packed_hoisted_galois_steps(size_t N, size_t rows, size_t cols, int *steps_out, size_t *count)
 {
-    if (!count || N == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed_hoisted_galois_steps: null argument or no degree");
-    size_t r, cc;
-    int rc = fc_packed_dims(N, rows, cols, r, cc);
-    if (rc) return rc;
-    std::vector<int> steps;
-    fc_packed_hoisted_steps(N, r, cc, steps);
-    const size_t cap = *count;
-    *count = steps.size();
-    if (!steps_out || cap < steps.size()) return fail(HHE_ERR_CAPACITY, "hhe_fc_packed_hoisted_galois_steps: output too small");
-    std::copy(steps.begin(), steps.end(), steps_out);
-    return HHE_OK;
-}
-// sum: hhe_fc_packed_sum_ks with hoisted != 0
-static int fc_packed_hoisted_run(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi, uint64_t *out,
-                                 size_t B, bool sum)
-{
-    HHE_LOCK(c);
-    if (!c || !m || !vi || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_fc_packed_hoisted: null argument or empty batch");
-    if (m->ctx != c) return fail(HHE_ERR_INVALID, "encrypted matrix belongs to another context");
-    if (m->open) return fail(HHE_ERR_INVALID, "hhe_fc_packed: an open handle (hhe_enc_matrix_create_open) takes hhe_fc_open_ks or hhe_mlp_ks");
-    if (sum && m->r >= 2 && m->r > c->behz_sum_cap) return fail(HHE_ERR_INVALID, "hhe_fc_packed_sum: more diagonals than one floor takes (behz_sum_cap)");
-    int rc = check_sets(c, rk, gk);
-    if (rc) return rc;
-    KeyScope keys(c, gk, rk);
-    if (!c->rks->rk) return fail(HHE_ERR_NO_RELIN_KEY, "relinearization key not set");
-    // -c and the tail need their own keys (their NAF has one term); 1 .. r-1 are served as hhe_rotate_rows_many_ks serves them
-    std::vector<int> own, chain;
-    fc_packed_steps(c->n, m->r, m->c, own);
-    for (int s : own)
-        if (s != 1 && !c->gks->gk.count(galois_elt_from_step(c, s))) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
-    for (size_t i = 1; i < m->r; ++i) chain.push_back((int)i);
-    RotPlan plan;
-    if (m->r > 1 && (rc = rot_plan_build(c, chain.data(), chain.size(), plan))) return rc;
-    Lane &main = c->lanes[0];
-    c->w = &main;
-    const bool hoisted = c->rot_hoist != 0 && m->r > 1;
-    if (hoisted && (rc = rot_plan_tables(c, plan))) return rc;
-    const size_t per = std::min(B, std::max<size_t>(1, c->chunk / m->r));
-    const ChunkPlan cp(B, per, c->nstreams);
-    const size_t ctw = c->ct_words();
-    auto reserve = [&](Lane &ln, bool h) {
-        int r = rot_many_reserve(c, ln, plan, h, true, per, m->r * per);
-        if (!r) r = ln.ws_fcp.reserve(c, fc_packed_words(c, m, per, sum), "hhe_fc_packed: rotations and products");
-        return r;
-    };
-    for (int s = cp.first_lane(); s <= cp.last_lane(); ++s)
-        if ((rc = reserve(c->lanes[s], hoisted))) return rc;
-    // in place, a recomputed chunk would read its own result: the results then wait in a buffer of the context until the flags are known
-    u64 *res = out;
-    if (hoisted && vi == out) {
-        if ((rc = c->d_blocks.reserve(c, B * ctw, "hhe_fc_packed_hoisted: results in place"))) return rc;
-        res = c->d_blocks.p;
-    }
-    u32 *flags = nullptr;
-    if (hoisted) {
-        if ((rc = c->d_flags.reserve(c, cp.nch, "hhe_fc_packed_hoisted"))) return rc;
-        flags = c->d_flags.p;
-        rt_memset(flags, 0, cp.nch * 4, main.stream);
-    }
-    rc = run_chunks(c, cp, [&](Lane &ln, size_t idx, size_t b0, size_t bc) {
-        ln.zero_flag = hoisted ? flags + idx : nullptr;
-        return fc_packed_chunk(c, m, vi + b0 * ctw, res + b0 * ctw, bc, &plan, !hoisted, sum);
-    });
-    if (hoisted && !rc) {
-        std::vector<u32> h(cp.nch, 0);
-        if (rt_d2h(h.data(), flags, cp.nch * 4, main.stream) || rt_sync(main.stream)) rc = dev_fail("hhe_fc_packed_hoisted");
-        for (size_t idx = 0; idx < cp.nch && !rc; ++idx)
-            if (h[idx] || c->rot_hoist == 2) {
-                c->rot_many_fallbacks++;
-                main.zero_flag = nullptr;
-                if (!(rc = reserve(main, false))) rc = fc_packed_chunk(c, m, vi + idx * per * ctw, res + idx * per * ctw, cp.count(idx), &plan, true, sum);
-            }
-        if (!rc && res != out) rt_d2d(out, res, B * ctw * 8, main.stream);
-    }
-    if (rt_sync(main.stream) && !rc) rc = dev_fail("hhe_fc_packed_hoisted");
-    if (!rc) {
-        c->rot_many_key_switches = m->r > 1 ? plan.trie.size() - 1 : 0;
-        c->rot_many_launches = hoisted ? plan.launches : 0;
-        c->fc_packed_key_switches = own.size() - (m->r > 1 ? 1 : 0) + c->rot_many_key_switches;
-        c->fc_packed_floors = sum ? 3 : 3 * m->r;
-    }
-    return rc;
+    return fc_galois_steps("hhe_fc_packed_hoisted_galois_steps", false, false, N, rows, cols, steps_out, count);
 }
 extern "C" int hhe_fc_packed_hoisted_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi,
                                         uint64_t *out, size_t B)
 {
-    return fc_packed_hoisted_run(c, rk, gk, m, vi, out, B, false);
+    return fc_layers_run(c, {false, false, false, "hhe_fc_packed_hoisted"}, rk, gk, &m, 1, vi, out, B);
 }
 extern "C" int hhe_fc_packed_sum_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi,
                                     uint64_t *out, size_t B, int hoisted)
 {
-    return hoisted ? fc_packed_hoisted_run(c, rk, gk, m, vi, out, B, true) : fc_packed_run(c, rk, gk, m, vi, out, B, true);
+    return fc_layers_run(c, {false, !hoisted, true, hoisted ? "hhe_fc_packed_hoisted" : "hhe_fc_packed"}, rk, gk, &m, 1, vi, out, B);
 }
 
 // ====================================================================== open packed FC and the FC-square-FC network
 // The definition is in include/hhe_gfx950.h; DESIGN.md section 4 "Open diagonals and the network call" has the layout and the chunk.
 extern "C" int hhe_fc_open_shape(size_t N, size_t rows, size_t cols, size_t *r_out, size_t *c_out)
 {
-    if (!r_out || !c_out || N == 0) return fail(HHE_ERR_INVALID, "hhe_fc_open_shape: null argument or no degree");
-    size_t r, cc;
-    int rc = fc_open_dims(N, rows, cols, r, cc);
-    if (rc) return rc;
-    *r_out = r; *c_out = cc;
-    return HHE_OK;
+    return fc_shape("hhe_fc_open_shape", true, N, rows, cols, r_out, c_out);
 }
 extern "C" int hhe_fc_open_diagonals(uint64_t t, const uint64_t *M, size_t rows, size_t cols, uint64_t *vals)
 {
     if (!M || !vals) return fail(HHE_ERR_INVALID, "hhe_fc_open_diagonals: null argument");
     size_t r, cc;
-    int rc = fc_open_dims(0, rows, cols, r, cc);
+    int rc = fc_dims(true, 0, rows, cols, r, cc);
     if (rc) return rc;
     for (size_t i = 0; i < rows * cols; ++i)
         if (M[i] >= t) return fail(HHE_ERR_INVALID, "hhe_fc_open_diagonals: matrix entry not below the plain modulus");
@@ -2909,149 +2900,18 @@ extern "C" int hhe_fc_open_diagonals(uint64_t t, const uint64_t *M, size_t rows,
 }
 extern "C" int hhe_fc_open_galois_steps(size_t N, size_t rows, size_t cols, int *steps_out, size_t *count)
 {
-    if (!count || N == 0) return fail(HHE_ERR_INVALID, "hhe_fc_open_galois_steps: null argument or no degree");
-    size_t r, cc;
-    int rc = fc_open_dims(N, rows, cols, r, cc);
-    if (rc) return rc;
-    std::vector<int> steps, tail;
-    fc_open_steps(r, cc, steps, tail);
-    steps.insert(steps.end(), tail.begin(), tail.end());
-    const size_t cap = *count;
-    *count = steps.size();
-    if (!steps_out || cap < steps.size()) return fail(HHE_ERR_CAPACITY, "hhe_fc_open_galois_steps: output too small");
-    std::copy(steps.begin(), steps.end(), steps_out);
-    return HHE_OK;
-}
-
-// one chunk of the network on the current lane: every layer of `per` items with no host wait in between.  x_k lives in the lane's
-// ws_ct[1] and the size-3 square in ws_ct3, which no step of a layer touches; the lane's ws_fcp is reserved for the largest layer
-static int mlp_chunk(hhe_ctx *c, const hhe_enc_matrix *const *mats, size_t n_layers, const RotPlan *plans, const u64 *in, u64 *out, size_t per,
-                     bool stepwise)
-{
-    Lane &w = *c->w;
-    u64 *x = w.ws_ct[1];
-    int rc;
-    for (size_t k = 0; k < n_layers; ++k) {
-        const bool last = k + 1 == n_layers;
-        if ((rc = fc_packed_chunk(c, mats[k], k ? x : in, last ? out : x, per, &plans[k], stepwise, true))) return rc;
-        if (last) break;
-        op_square(c, x, w.ws_ct3, per);
-        if ((rc = op_relinearize(c, w.ws_ct3, x, per))) return rc;
-    }
-    return HHE_OK;
-}
-// hhe_mlp_ks, and hhe_fc_open_ks as its one-layer case (`who` names the entry point in messages)
-static int mlp_run(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *const *mats, size_t n_layers, const uint64_t *vi,
-                   uint64_t *out, size_t B, const char *who)
-{
-    HHE_LOCK(c);
-    const std::string w(who);
-    if (!c || !mats || !vi || !out || B == 0 || n_layers == 0) return fail(HHE_ERR_INVALID, w + ": null argument, empty batch or no layer");
-    size_t max_r = 1;
-    for (size_t k = 0; k < n_layers; ++k) {
-        const hhe_enc_matrix *m = mats[k];
-        if (!m) return fail(HHE_ERR_INVALID, w + ": null handle");
-        if (m->ctx != c) return fail(HHE_ERR_INVALID, "encrypted matrix belongs to another context");
-        if (!m->open) return fail(HHE_ERR_INVALID, w + ": a cyclic handle (hhe_enc_matrix_create) takes the hhe_fc_packed calls");
-        if (k && mats[k - 1]->rows != m->cols) return fail(HHE_ERR_INVALID, w + ": rows of a layer differ from cols of the next");
-        if (m->r >= 2 && m->r > c->behz_sum_cap) return fail(HHE_ERR_INVALID, w + ": more diagonals than one floor takes (behz_sum_cap)");
-        max_r = std::max(max_r, m->r);
-    }
-    int rc = check_sets(c, rk, gk);
-    if (rc) return rc;
-    KeyScope keys(c, gk, rk);
-    if (!c->rks->rk) return fail(HHE_ERR_NO_RELIN_KEY, "relinearization key not set");
-    // the tail steps need their own keys (their NAF has one term); -1 .. -(r-1) are served as hhe_rotate_rows_many_ks serves them.
-    // The plans of all layers are built, and refuse, before anything is written
-    std::vector<RotPlan> plans(n_layers);
-    size_t kid_rows = 0, key_switches = 0;
-    bool any_hoisted = false;
-    for (size_t k = 0; k < n_layers; ++k) {
-        std::vector<int> rot, tail;
-        fc_open_steps(mats[k]->r, mats[k]->c, rot, tail);
-        for (int s : tail)
-            if (!c->gks->gk.count(galois_elt_from_step(c, s))) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
-        if (!rot.empty() && (rc = rot_plan_build(c, rot.data(), rot.size(), plans[k]))) return rc;
-        if (!rot.empty()) kid_rows += plans[k].trie.size() - 1;
-        key_switches += (rot.empty() ? 0 : plans[k].trie.size() - 1) + tail.size();
-        any_hoisted |= c->rot_hoist != 0 && !rot.empty();
-    }
-    Lane &main = c->lanes[0];
-    c->w = &main;
-    auto hoisted = [&](size_t k) { return c->rot_hoist != 0 && mats[k]->r > 1; };
-    for (size_t k = 0, ofs = 0; k < n_layers; ++k)
-        if (hoisted(k)) {
-            if ((rc = rot_plan_tables(c, plans[k], ofs, kid_rows))) return rc;
-            ofs += plans[k].trie.size() - 1;
-        }
-    const size_t per = std::min(B, std::max<size_t>(1, c->chunk / max_r));
-    const ChunkPlan cp(B, per, c->nstreams);
-    const size_t ctw = c->ct_words();
-    auto reserve = [&](Lane &ln, bool h) {
-        int r = HHE_OK;
-        size_t words = 0;
-        for (size_t k = 0; k < n_layers && !r; ++k) {
-            r = rot_many_reserve(c, ln, plans[k], h && hoisted(k), true, per, max_r * per);
-            words = std::max(words, fc_packed_words(c, mats[k], per, true));
-        }
-        if (!r) r = ln.ws_fcp.reserve(c, words, "hhe_mlp: rotations and products of the largest layer");
-        return r;
-    };
-    for (int s = cp.first_lane(); s <= cp.last_lane(); ++s)
-        if ((rc = reserve(c->lanes[s], true))) return rc;
-    // in place, a recomputed chunk would read its own result: the results then wait in a buffer of the context until the flags are known
-    u64 *res = out;
-    if (any_hoisted && vi == out) {
-        if ((rc = c->d_blocks.reserve(c, B * ctw, "hhe_mlp: results in place"))) return rc;
-        res = c->d_blocks.p;
-    }
-    u32 *flags = nullptr;
-    if (any_hoisted) {
-        if ((rc = c->d_flags.reserve(c, cp.nch, "hhe_mlp"))) return rc;  // one flag per chunk, for the hoisted rotations of every layer
-        flags = c->d_flags.p;
-        rt_memset(flags, 0, cp.nch * 4, main.stream);
-    }
-    rc = run_chunks(c, cp, [&](Lane &ln, size_t idx, size_t b0, size_t bc) {
-        ln.zero_flag = any_hoisted ? flags + idx : nullptr;
-        return mlp_chunk(c, mats, n_layers, plans.data(), vi + b0 * ctw, res + b0 * ctw, bc, !any_hoisted);
-    });
-    if (any_hoisted && !rc) {
-        std::vector<u32> h(cp.nch, 0);
-        if (rt_d2h(h.data(), flags, cp.nch * 4, main.stream) || rt_sync(main.stream)) rc = dev_fail(who);
-        // a zero residue in some c1 of some layer: that chunk is recomputed whole, from vi, step by step on the main lane
-        for (size_t idx = 0; idx < cp.nch && !rc; ++idx)
-            if (h[idx] || c->rot_hoist == 2) {
-                c->rot_many_fallbacks++;
-                main.zero_flag = nullptr;
-                if (!(rc = reserve(main, false))) rc = mlp_chunk(c, mats, n_layers, plans.data(), vi + idx * per * ctw, res + idx * per * ctw, cp.count(idx), true);
-            }
-        if (!rc && res != out) rt_d2d(out, res, B * ctw * 8, main.stream);
-    }
-    if (rt_sync(main.stream) && !rc) rc = dev_fail(who);
-    if (!rc) {
-        const hhe_enc_matrix *last = mats[n_layers - 1];
-        const RotPlan &lp = plans[n_layers - 1];
-        size_t tail = 0;
-        for (size_t s = last->r; s < last->c; s <<= 1) ++tail;
-        c->rot_many_key_switches = last->r > 1 ? lp.trie.size() - 1 : 0;
-        c->rot_many_launches = hoisted(n_layers - 1) ? lp.launches : 0;
-        c->fc_packed_key_switches = c->rot_many_key_switches + tail;
-        c->fc_packed_floors = 3;
-        c->mlp_layers = n_layers;
-        c->mlp_key_switches = key_switches;
-    }
-    return rc;
+    return fc_galois_steps("hhe_fc_open_galois_steps", true, false, N, rows, cols, steps_out, count);
 }
 extern "C" int hhe_fc_open_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *m, const uint64_t *vi, uint64_t *out,
                               size_t B)
 {
     if (!m) return fail(HHE_ERR_INVALID, "hhe_fc_open: null argument");
-    return mlp_run(c, rk, gk, &m, 1, vi, out, B, "hhe_fc_open");
+    return fc_layers_run(c, {true, false, true, "hhe_fc_open"}, rk, gk, &m, 1, vi, out, B);
 }
 extern "C" int hhe_mlp_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *const *mats, size_t n_layers,
                           const uint64_t *vi, uint64_t *out, size_t B)
 {
-    return mlp_run(c, rk, gk, mats, n_layers, vi, out, B, "hhe_mlp");
+    return fc_layers_run(c, {true, false, true, "hhe_mlp"}, rk, gk, mats, n_layers, vi, out, B);
 }
 
 extern "C" int hhe_add_many(hhe_ctx *c, const uint64_t *in, size_t K, uint64_t *out, size_t B, int size)

@@ -10,7 +10,8 @@ entry point whose result is not there on return fails, and `SyncedMem` waits for
 the asynchronous generic ops (as TorchMem does on the GPU).  Each test ends by asserting that work really was deferred and forced:
 a run in which the lazy order did not engage has tested nothing.
 
-Shapes: N = 1024 over 3 x 50 bits (L = 2) and N = 2048 over 4 x 60 bits (L = 3), what the emulator suites use."""
+Shapes: N = 1024 over 3 x 50 bits (L = 2) and N = 2048 over 4 x 60 bits (L = 3), what the emulator suites use; N = 4096 over 3 x 60
+bits once, for the row kernels of the hoisted rotations, and N = 1024 over 4 x 18 bits once, where a residue of c1 can be set to 0."""
 import contextlib
 import ctypes
 
@@ -19,11 +20,15 @@ import pytest
 
 import affine_common as ac
 import dedup_common as dc
+import fc_packed_common as fp
 import fused_finish_common as ff
 import keygen_common as kg
 import kscache_common as kc
+import mlp_common as mc
 import mod_switch_common as ms
+import mult_sum_common as msc
 import parity_common as pc
+import rot_many_common as rm
 import shared_l0_common as tsl
 from conftest import Setup
 
@@ -315,3 +320,210 @@ def test_generated_keys_then_calls_under_them(orc, api, emu_lib, monkeypatch):
         X, O = api.Context(10, q, 65537, lib=emu_lib), orc.Oracle(10, q, 65537)
         kg.check_regeneration_drops_keystreams(X, O, orc, SyncedMem(emu_lib))
         X.close()
+
+
+# ---- the calls that run their chunks optimistically, read one flag per chunk back and recompute the flagged ones on the main lane ----
+ROT_MIXED = [1, -1, 3, 5, -5, 7, 100, -100, 511, -511, 0]   # tests/test_rot_many_emu.py's MIXED
+
+
+def _q1024(orc):
+    return orc.coeff_modulus_create(1024, [50] * 3)
+
+
+@pytest.fixture(scope="module")
+def rot10(orc):
+    """N = 1024, L = 2: every default Galois key and a key for step 3 (tests/test_rot_many_emu.py's S10three)"""
+    return rm.setup_with_steps(orc, 10, _q1024(orc), [3], all_default=True)
+
+
+@pytest.fixture(scope="module")
+def rot12(orc):
+    """N = 4096, 3 x 60 bits (the row kernels): every default key and a key for each of 1 .. 17"""
+    return rm.setup_with_steps(orc, 12, orc.coeff_modulus_create(4096, [60] * 3), list(range(1, 18)), all_default=True)
+
+
+@pytest.fixture(scope="module")
+def layer10(orc):
+    """N = 1024, L = 2, every default Galois key: the set-up of the packed encrypted layers' emulator suites"""
+    return fp.make_setup(orc, 10, _q1024(orc))
+
+
+@pytest.fixture(scope="module")
+def net10(orc):
+    return mc.network_setup(orc, "6x20_3x6")
+
+
+def _loaded(api, lib, S):
+    return lambda: rm.load_ctx(api, lib, S)
+
+
+@pytest.mark.parametrize("knob", [None, "2"])
+def test_rotate_rows_many_chunked(orc, api, emu_lib, mem, rot10, monkeypatch, knob):
+    """tests/test_rot_many_emu.py::test_chunks_and_streams_do_not_change_the_words with two items per chunk: B = 5 in chunks of 2, 2, 1
+    on two lanes (no chunk covers the stride: the arena and the copies); knob 2: every chunk is recomputed step by step on the main
+    lane after the join"""
+    S = rot10
+    cts = rm.encryptions(S, 5, seed=220)
+    X = rm.load_ctx(api, emu_lib, S)
+    got, refs = rm.check_rot_many(X, S, mem, orc, ROT_MIXED, cts=cts)
+    group = min(rm.RotTrie(orc, S.n, ROT_MIXED, S.gk.elts).kid_counts[0], X.query("rot_many_group"))
+    X.close()
+    monkeypatch.setenv("HHE_CHUNK", str(2 * group))   # a chunk keeps the sums of `group` children of its items at once
+    monkeypatch.setenv("HHE_STREAMS", "2")
+    if knob:
+        monkeypatch.setenv("HHE_ROT_HOIST", knob)
+    with lazy_order(emu_lib, monkeypatch):
+        Y = rm.load_ctx(api, emu_lib, S)
+        before = Y.query("rot_many_fallbacks")
+        g2, _ = rm.check_rot_many(Y, S, mem, orc, ROT_MIXED, cts=cts, refs=refs)
+        fallbacks = Y.query("rot_many_fallbacks") - before
+        Y.close()
+    assert (g2 == got).all()
+    assert fallbacks == (3 if knob else 0)
+
+
+def test_rotate_rows_many_chunks_on_the_row_kernels(orc, api, emu_lib, mem, rot12, monkeypatch):
+    """tests/test_rot_many_emu.py::test_chunks_on_the_row_kernels: three children, chunks of 2 + 1 items on two lanes"""
+    cts = rm.encryptions(rot12, 3, seed=230)
+    monkeypatch.setenv("HHE_CHUNK", "6")
+    monkeypatch.setenv("HHE_STREAMS", "2")
+    with lazy_order(emu_lib, monkeypatch):
+        X = rm.load_ctx(api, emu_lib, rot12)
+        assert X.query("row_kernel") == 1
+        rm.check_rot_many(X, rot12, mem, orc, [1, 2, -5, 3], cts=cts)
+        X.close()
+
+
+def test_rotate_rows_many_raised_flag_is_read_after_the_chunks(orc, api, emu_lib, mem, monkeypatch):
+    """tests/test_rot_many_emu.py::test_one_zero_residue_over_small_primes with one item per chunk on two lanes: the one flag that a
+    chunk raises on its lane is on the host when the call decides what to recompute -- exactly that chunk, and its words are the oracle's"""
+    logn, bits = pc.ZERO_CASES["n1024_18x4"][:2]
+    steps = [1, 2, 3]
+    S = rm.setup_with_steps(orc, logn, orc.coeff_modulus_create(1 << logn, bits), steps)
+    cts = None
+    for seed in range(180, 200):   # an encryption whose c1 has no zero residue (they are common at 18 bits)
+        c = rm.encryptions(S, 3, seed=seed)
+        if (c[:, 1] != 0).all():
+            cts = c
+            break
+    assert cts is not None
+    monkeypatch.setenv("HHE_CHUNK", "3")   # three children at once: one item per chunk
+    monkeypatch.setenv("HHE_STREAMS", "2")
+    with lazy_order(emu_lib, monkeypatch):
+        X = rm.load_ctx(api, emu_lib, S)
+        rm.check_rot_many(X, S, mem, orc, steps, cts=cts)
+        assert X.query("rot_many_fallbacks") == 0
+        cts[1, 1, 1, 517] = 0
+        rm.check_rot_many(X, S, mem, orc, steps, cts=cts)
+        assert X.query("rot_many_fallbacks") == 1
+        X.close()
+
+
+def test_fc_packed_chunked(api, emu_lib, mem, layer10, monkeypatch):
+    """hhe_fc_packed_ks: fc_packed_common.check_chunking (B = 5, one item per chunk on two lanes; two per chunk on the caller's stream)"""
+    with lazy_order(emu_lib, monkeypatch):
+        fp.check_chunking(_loaded(api, emu_lib, layer10), layer10, mem, monkeypatch)
+
+
+@pytest.mark.parametrize("hoisted", [0, 1])
+def test_fc_packed_sum_and_hoisted_chunked(api, emu_lib, mem, layer10, monkeypatch, hoisted):
+    """tests/test_mult_sum_emu.py::test_chunks_and_streams_do_not_change_the_words: every call of check_sum_layer runs hhe_fc_packed_ks,
+    hhe_fc_packed_hoisted_ks and hhe_fc_packed_sum_ks on one handle"""
+    S, M = layer10, fp.seeded_matrix(fp.T, 3, 5, 61)
+    X = rm.load_ctx(api, emu_lib, S)
+    got, refs, _ = msc.check_sum_layer(X, S, mem, M, hoisted, B=5, seed=7)
+    X.close()
+    with lazy_order(emu_lib, monkeypatch):
+        for chunk, streams in (("2", "2"), ("8", "0")):
+            monkeypatch.setenv("HHE_CHUNK", chunk)
+            monkeypatch.setenv("HHE_STREAMS", streams)
+            Y = rm.load_ctx(api, emu_lib, S)
+            g2, _, _ = msc.check_sum_layer(Y, S, mem, M, hoisted, B=5, seed=7, refs=refs)
+            assert (g2 == got).all(), (chunk, streams)
+            Y.close()
+
+
+def test_fc_packed_hoisted_in_place_under_the_fallback(orc, api, emu_lib, mem, monkeypatch):
+    """tests/test_rot_many_emu.py::test_layer_in_place_and_under_the_fallback on two lanes: in place every chunk's result waits in
+    the context's buffer, the chunks are recomputed from the untouched input and the results copied out after them"""
+    S = rm.setup_with_steps(orc, 10, _q1024(orc), rm.hand_hoisted_steps(1024, 3, 5), all_default=True)
+    M = fp.seeded_matrix(fp.T, 3, 5, 62)
+    X = rm.load_ctx(api, emu_lib, S)
+    got, refs, _ = rm.check_hoisted_layer(X, S, mem, orc, M, B=3, seed=8)
+    X.close()
+    monkeypatch.setenv("HHE_CHUNK", "8")   # r = 4: two items per chunk
+    monkeypatch.setenv("HHE_STREAMS", "2")
+    with lazy_order(emu_lib, monkeypatch):
+        for knob in ("1", "2"):
+            monkeypatch.setenv("HHE_ROT_HOIST", knob)
+            Y = rm.load_ctx(api, emu_lib, S)
+            g3, _, _ = rm.check_hoisted_layer(Y, S, mem, orc, M, B=3, seed=8, in_place=True, refs=refs, chain=False)
+            assert (g3 == got).all() and Y.query("rot_many_fallbacks") == (2 if knob == "2" else 0)
+            Y.close()
+
+
+def test_fc_packed_sum_in_place_under_the_fallback(api, emu_lib, mem, layer10, monkeypatch):
+    """hhe_fc_packed_sum_ks with hoisted = 1 in place, every chunk recomputed (tests/test_mult_sum_emu.py's test_in_place and
+    test_forced_fallback_of_the_hoisted_rotation in one)"""
+    S, M = layer10, fp.seeded_matrix(fp.T, 3, 5, 63)
+    X = rm.load_ctx(api, emu_lib, S)
+    got, refs, _ = msc.check_sum_layer(X, S, mem, M, 1, B=3, seed=9)
+    X.close()
+    monkeypatch.setenv("HHE_CHUNK", "8")
+    monkeypatch.setenv("HHE_STREAMS", "2")
+    monkeypatch.setenv("HHE_ROT_HOIST", "2")
+    with lazy_order(emu_lib, monkeypatch):
+        Y = rm.load_ctx(api, emu_lib, S)
+        before = Y.query("rot_many_fallbacks")
+        g2, _, _ = msc.check_sum_layer(Y, S, mem, M, 1, B=3, seed=9, in_place=True, refs=refs)
+        assert Y.query("rot_many_fallbacks") > before
+        Y.close()
+    assert (g2 == got).all()
+
+
+def test_mlp_chunked(api, emu_lib, mem, net10, monkeypatch):
+    """hhe_mlp_ks and hhe_fc_open_ks (the layers one by one inside check_network): mlp_common.check_chunking"""
+    with lazy_order(emu_lib, monkeypatch):
+        mc.check_chunking(_loaded(api, emu_lib, net10), net10, mem, monkeypatch)
+
+
+def test_mlp_fallback_on_two_lanes(api, emu_lib, mem, net10, monkeypatch):
+    """mlp_common.check_fallback with one item per chunk on two lanes: every chunk recomputed whole from vi on the main lane, and in
+    place under the fallback"""
+    monkeypatch.setenv("HHE_CHUNK", "8")   # max r = 8
+    monkeypatch.setenv("HHE_STREAMS", "2")
+    with lazy_order(emu_lib, monkeypatch):
+        mc.check_fallback(_loaded(api, emu_lib, net10), net10, mem, monkeypatch)
+
+
+@pytest.fixture(scope="module")
+def fc10(orc):
+    """N = 1024, L = 2, every default Galois key"""
+    return Setup(orc, 10, [50] * 3, all_galois=True)
+
+
+@pytest.mark.parametrize("shared", ["2", "1"])
+def test_fc_row_chunks_on_two_lanes(orc, api, emu_lib, mem, fc10, monkeypatch, shared):
+    """hhe_fc_row, B = 3 with one item per chunk on two lanes, against the oracle's row as tests/test_host_emu.py compares it
+    (parity_common.check_fc_variants' inputs); shared 2: every chunk recomputed with per-child transforms on the main lane"""
+    S, O, n_in, B = fc10, fc10.O, 21, 3
+    rng = np.random.default_rng(8)
+    v, w = rng.integers(0, 4, n_in), rng.integers(-8, 9, n_in)
+    wc = O.encrypt(S.pk, O.encode(w), 43)
+    vi = np.stack([O.encrypt(S.pk, O.encode(v), 41 + b) for b in range(B)])
+    refs = [O.fc_row(vi[b], wc, S.rk, S.gk, n_in)[0] for b in range(B)]
+    monkeypatch.setenv("HHE_FC_CHUNK", "1")
+    monkeypatch.setenv("HHE_STREAMS", "2")
+    monkeypatch.setenv("HHE_FC_SHARED", shared)
+    with lazy_order(emu_lib, monkeypatch):
+        X = api.Context(S.logn, S.q, S.t, lib=emu_lib)
+        S.load_keys(X)
+        before = X.query("fc_fallbacks")
+        out = mem.empty((B,) + O.ct_shape)
+        X.fc_row(mem.to_dev(vi), mem.to_dev(wc[None]), 1, n_in, out, B, relin_slot=0, default_galois_only=False)
+        got = mem.to_host(out)
+        fallbacks = X.query("fc_fallbacks") - before
+        X.close()
+    for b in range(B):
+        assert (got[b] == refs[b]).all(), (shared, b)
+    assert fallbacks == (B if shared == "2" else 0)
