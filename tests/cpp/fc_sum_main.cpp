@@ -16,21 +16,9 @@
 #include <iostream>
 #include <vector>
 #include "pasta_seal_gfx950.hpp"
+#include "driver_common.hpp"
 
-static std::vector<uint64_t> read_words(FILE *f, size_t n)
-{
-    std::vector<uint64_t> v(n);
-    if (fread(v.data(), 8, n, f) != n) { fprintf(stderr, "short read\n"); exit(2); }
-    return v;
-}
-static void put(FILE *o, const std::vector<uint64_t> &v) { if (o) fwrite(v.data(), 8, v.size(), o); }
 #define REQUIRE(x) do { if (!(x)) { std::cout.flush(); fprintf(stderr, "failed: %s (line %d)\n", #x, __LINE__); return 1; } } while (0)
-template <class F> static bool throws_invalid(F &&f)
-{
-    try { f(); } catch (const std::invalid_argument &) { return true; } catch (...) { return false; }
-    return false;
-}
-static int64_t centred(uint64_t v, uint64_t t) { return v > (t + 1) / 2 ? (int64_t)v - (int64_t)t : (int64_t)v; }
 
 int main(int argc, char **argv)
 {

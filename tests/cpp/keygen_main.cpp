@@ -5,14 +5,8 @@
 #include <cstdlib>
 #include <vector>
 #include "pasta_seal_gfx950.hpp"
+#include "driver_common.hpp"
 
-static std::vector<uint64_t> read_words(FILE *f, size_t n)
-{
-    std::vector<uint64_t> v(n);
-    if (fread(v.data(), 8, n, f) != n) { fprintf(stderr, "short read\n"); exit(2); }
-    return v;
-}
-static void put(FILE *o, const std::vector<uint64_t> &v) { fwrite(v.data(), 8, v.size(), o); }
 int main(int argc, char **argv)
 {
     if (argc < 3) return 2;

@@ -6,13 +6,16 @@
 #include <cstdlib>
 #include <vector>
 #include "pasta_seal_gfx950.hpp"
+#include "driver_common.hpp"
 
-static std::vector<uint64_t> read_words(FILE *f, size_t n)
-{
-    std::vector<uint64_t> v(n);
-    if (fread(v.data(), 8, n, f) != n) { fprintf(stderr, "short read\n"); exit(2); }
-    return v;
-}
+// every member of the shared templates (include/hhe_adapter_front.hpp) against the word containers, whether or not a driver calls it
+template struct hhe::BoundT<pasta::Boundary>;
+template struct hhe::EncMatrixT<pasta::Boundary>;
+template class hhe::EvalT<pasta::Boundary>;
+template class hhe::LevelT<pasta::Boundary>;
+template class hhe::CipherT<pasta::Boundary>;
+template struct hhe::FreeT<pasta::Boundary>;
+
 int main(int argc, char **argv)
 {
     if (argc < 3) return 2;

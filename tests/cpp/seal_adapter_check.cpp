@@ -3,6 +3,14 @@
 // the same argument types.  Compiled with g++ -fsyntax-only (tests/test_seal_adapter.py); never linked or run.
 #include "pasta_seal_gfx950_seal.hpp"
 
+// every member of the shared templates (include/hhe_adapter_front.hpp) against seal:: types, whether or not a check file calls it
+template struct hhe::BoundT<pasta::gfx950::Boundary>;
+template struct hhe::EncMatrixT<pasta::gfx950::Boundary>;
+template class hhe::EvalT<pasta::gfx950::Boundary>;
+template class hhe::LevelT<pasta::gfx950::Boundary>;
+template class hhe::CipherT<pasta::gfx950::Boundary>;
+template struct hhe::FreeT<pasta::gfx950::Boundary>;
+
 using namespace seal;
 using namespace std;
 
