@@ -171,7 +171,34 @@ inline void bsgs_indices(size_t slot_count, uint64_t n1, uint64_t n2, std::vecto
 // Public matrices of packed affine layers by content: (dim, n1, n2, every word of the matrix and of the bias).  Shared ownership
 // like KeySetCache: eviction beyond `max_matrices` drops the cache's reference, a call that still computes with a handle keeps it.
 typedef std::shared_ptr<hhe_matrix> Matrix;
+// ... and the plain matrices of the open FC layer under plain weights (hhe_plain_fc: rows x cols, + bias) and the plaintext rows of
+// rotate_plain_sum (hhe_plain_rows), found again the same way: three kinds of handle, one capacity each, one upload count
+typedef std::shared_ptr<hhe_plain_fc> PlainFc;
+typedef std::shared_ptr<hhe_plain_rows> PlainRows;
 class MatrixCache {
+    template <class T> struct Kind {
+        std::list<std::pair<ContentHash, std::shared_ptr<T>>> lru;
+        std::map<ContentHash, typename std::list<std::pair<ContentHash, std::shared_ptr<T>>>::iterator> index;
+    };
+    // caller holds mu_.  make() creates the handle on a miss
+    template <class T, class Make> std::shared_ptr<T> lookup(Kind<T> &k, const ContentHash &h, Make make)
+    {
+        auto it = k.index.find(h);
+        if (it != k.index.end()) {
+            k.lru.splice(k.lru.begin(), k.lru, it->second);
+            return it->second->second;
+        }
+        std::shared_ptr<T> m = make();
+        ++uploads_;
+        k.lru.emplace_front(h, m);
+        k.index[h] = k.lru.begin();
+        while (k.lru.size() > max_) {
+            k.index.erase(k.lru.back().first);
+            k.lru.pop_back();
+        }
+        return m;
+    }
+
 public:
     explicit MatrixCache(hhe_ctx *ctx, size_t max_matrices = 8) : ctx_(ctx), max_(max_matrices) {}
     // M: row-major dim x dim; bias: dim words or null; n1 = n2 = 0: diagonal method
@@ -184,32 +211,52 @@ public:
         h.add_tag(bias ? 1 : 0);
         if (bias) h.add(bias, dim);
         std::lock_guard<std::mutex> lk(mu_);
-        auto it = index_.find(h);
-        if (it != index_.end()) {
-            lru_.splice(lru_.begin(), lru_, it->second);
-            return it->second->second;
-        }
-        hhe_matrix *raw = nullptr;
-        check(hhe_matrix_create(ctx_, M, dim, bias, n1, n2, &raw));
-        Matrix m(raw, hhe_matrix_destroy);
-        ++uploads_;
-        lru_.emplace_front(h, m);
-        index_[h] = lru_.begin();
-        while (lru_.size() > max_) {
-            index_.erase(lru_.back().first);
-            lru_.pop_back();
-        }
-        return m;
+        return lookup(mats_, h, [&] {
+            hhe_matrix *raw = nullptr;
+            check(hhe_matrix_create(ctx_, M, dim, bias, n1, n2, &raw));
+            return Matrix(raw, hhe_matrix_destroy);
+        });
     }
-    size_t resident() const { return lru_.size(); }
+    // M: row-major rows x cols; bias: rows words or null (hhe_plain_fc_create_open)
+    PlainFc get_open(const uint64_t *M, size_t rows, size_t cols, const uint64_t *bias)
+    {
+        ContentHash h;
+        h.add_tag(0x7066);  // "pf"
+        h.add_tag(rows); h.add_tag(cols);
+        h.add(M, rows * cols);
+        h.add_tag(bias ? 1 : 0);
+        if (bias) h.add(bias, rows);
+        std::lock_guard<std::mutex> lk(mu_);
+        return lookup(open_, h, [&] {
+            hhe_plain_fc *raw = nullptr;
+            check(hhe_plain_fc_create_open(ctx_, M, rows, cols, bias, &raw));
+            return PlainFc(raw, hhe_plain_fc_destroy);
+        });
+    }
+    // vals: n plaintexts of `count` slot values each (hhe_plain_rows_create)
+    PlainRows get_rows(const uint64_t *vals, size_t n, size_t count)
+    {
+        ContentHash h;
+        h.add_tag(0x7072);  // "pr"
+        h.add_tag(n); h.add_tag(count);
+        h.add(vals, n * count);
+        std::lock_guard<std::mutex> lk(mu_);
+        return lookup(rows_, h, [&] {
+            hhe_plain_rows *raw = nullptr;
+            check(hhe_plain_rows_create(ctx_, vals, n, count, &raw));
+            return PlainRows(raw, hhe_plain_rows_destroy);
+        });
+    }
+    size_t resident() const { return mats_.lru.size() + open_.lru.size() + rows_.lru.size(); }
     uint64_t uploads() const { return uploads_; }   // how many matrices were sent to the device (a repeated one is not)
 
 private:
     hhe_ctx *ctx_;
     size_t max_;
     std::mutex mu_;
-    std::list<std::pair<ContentHash, Matrix>> lru_;
-    std::map<ContentHash, std::list<std::pair<ContentHash, Matrix>>::iterator> index_;
+    Kind<hhe_matrix> mats_;
+    Kind<hhe_plain_fc> open_;
+    Kind<hhe_plain_rows> rows_;
     uint64_t uploads_ = 0;
 };
 
@@ -525,6 +572,57 @@ public:
         upload(in.u64(), in_words);
         check(hhe_rotate_rows_many_ks(h(), g.get(), in.u64(), steps.data(), steps.size(), out.u64(), 1));
         download(out.u64(), steps.size(), 2, dst);
+    }
+
+    // ---- plain-weights FC (hhe_gfx950.h "Plain-weights sum of rotations"): a rows x cols matrix the CSP holds in the clear, in the open
+    // layout; the handle is found again through the matrix cache, so a CSP that applies the same layer per request uploads it once
+    static std::vector<uint64_t> flat_rows(const std::vector<std::vector<uint64_t>> &M, const char *who, size_t &cols)
+    {
+        if (M.empty() || M[0].empty()) throw std::invalid_argument(std::string(who) + ": empty matrix");
+        cols = M[0].size();
+        std::vector<uint64_t> flat(M.size() * cols);
+        for (size_t r = 0; r < M.size(); r++) {
+            if (M[r].size() != cols) throw std::invalid_argument(std::string(who) + ": rows of different lengths");
+            std::copy(M[r].begin(), M[r].end(), flat.begin() + r * cols);
+        }
+        return flat;
+    }
+    // make the layer resident ahead of its first request; bias: null for none
+    PlainFc plain_fc_open(const std::vector<std::vector<uint64_t>> &M, const std::vector<uint64_t> *bias)
+    {
+        size_t cols = 0;
+        const std::vector<uint64_t> flat = flat_rows(M, "plain_fc_open", cols);
+        if (bias && bias->size() != M.size()) throw std::invalid_argument("plain_fc_open: bias and matrix dimensions differ");
+        return mats_.get_open(flat.data(), M.size(), cols, bias ? bias->data() : nullptr);
+    }
+    // the layer on one ciphertext (hhe_fc_open_plain_ks): slots [0, rows) of the result are (M x + b) mod t; every step of
+    // hhe_fc_open_galois_steps needs a key of its own in gk
+    template <class GK, class Sink>
+    void fc_open_plain(const std::vector<std::vector<uint64_t>> &M, const std::vector<uint64_t> *bias, const uint64_t *vi, const GK &gk, Sink dst)
+    {
+        const PlainFc m = plain_fc_open(M, bias);
+        std::lock_guard<std::mutex> lk(arena_.mutex());
+        const KeySet g = named(set(gk), "Galois key not present");
+        uint64_t *d = arena_.get(0, ct_words() * 8);
+        upload(d, vi);
+        check(hhe_fc_open_plain_ks(h(), g.get(), m.get(), d, d, 1));
+        download(d, 1, 2, dst);
+    }
+    // sum_k rotate_rows(in, steps[k], gk) * plains[k] under one mod-down (hhe_rotate_plain_sum_ks); plains: one slot vector per step, all of
+    // one length.  A step list of all zeros needs no key
+    template <class GK, class Sink>
+    void rotate_plain_sum(const uint64_t *in_words, const std::vector<std::vector<uint64_t>> &plains, const std::vector<int> &steps, const GK &gk, Sink dst)
+    {
+        size_t count = 0;
+        const std::vector<uint64_t> flat = flat_rows(plains, "rotate_plain_sum", count);
+        if (steps.size() != plains.size()) throw std::invalid_argument("rotate_plain_sum: one plaintext per step");
+        const PlainRows rows = mats_.get_rows(flat.data(), plains.size(), count);
+        std::lock_guard<std::mutex> lk(arena_.mutex());
+        const KeySet g = or_empty(set(gk));
+        uint64_t *d = arena_.get(0, ct_words() * 8);
+        upload(d, in_words);
+        check(hhe_rotate_plain_sum_ks(h(), g.get(), rows.get(), steps.data(), steps.size(), d, d, 1));
+        download(d, 1, 2, dst);
     }
 
     // client end: pasta::PASTA::encrypt / decrypt (pasta_3_plain.cpp:9-46) of `count` words in place, key: 256 words

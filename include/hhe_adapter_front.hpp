@@ -207,6 +207,23 @@ public:
     {
         EncMatrixT<B>::mlp(layers, vi, rk, gal_keys, vo);
     }
+    // Plain-weights FC (no reference counterpart: the reference's rectangular layers multiply by encrypted rows): the open layer under a
+    // matrix the CSP holds in the clear, vo = M vi + b in slots [0, rows), as ONE key switch with one mod-down plus the tail rotations
+    // (hhe_gfx950.h "Plain-weights sum of rotations").  The matrix is found again by content (MatrixCache): plain_fc_open makes it
+    // resident ahead of the first request, fc_open_plain uploads it on first use.  b empty: no bias.  gal_keys: the object the call names;
+    // every step of hhe_fc_open_galois_steps needs a key of its own in it
+    void plain_fc_open(const matrix &M, const vector &b = vector()) { core->plain_fc_open(M, b.empty() ? nullptr : &b); }
+    void fc_open_plain(const Ciphertext &vi, const matrix &M, const vector &b, const GaloisKeys &gal_keys, Ciphertext &vo)
+    {
+        const uint64_t *x = in(vi);
+        core->fc_open_plain(M, b.empty() ? nullptr : &b, x, this->galois(gal_keys), out(vo));
+    }
+    // vo = sum_k rotate_rows(ct, steps[k], gal_keys) * encode(plains[k]), the rounding of the key switch taken once over the sum
+    void rotate_plain_sum(const Ciphertext &ct, const matrix &plains, const std::vector<int> &steps, const GaloisKeys &gal_keys, Ciphertext &vo)
+    {
+        const uint64_t *x = in(ct);
+        core->rotate_plain_sum(x, plains, steps, this->galois(gal_keys), out(vo));
+    }
 
 protected:
     bool use_bsgs;
@@ -477,6 +494,17 @@ template <class B> struct FreeT {
     {
         o.resize(steps.size());
         ctx.rotate_rows_many(in(ctx, ct), steps, B::words(gal_keys), [&](size_t i) { return out(ctx, o[i])(0); });
+    }
+    // the open FC layer under plain weights and the primitive under it (hhe_gfx950.h "Plain-weights sum of rotations"); b empty: no bias
+    static void fc_open_plain(Context &ctx, const Ciphertext &vi, const std::vector<std::vector<uint64_t>> &M, const std::vector<uint64_t> &b,
+                              const typename B::GaloisKeys &gal_keys, Ciphertext &vo)
+    {
+        ctx.fc_open_plain(M, b.empty() ? nullptr : &b, in(ctx, vi), B::words(gal_keys), out(ctx, vo));
+    }
+    static void rotate_plain_sum(Context &ctx, const Ciphertext &ct, const std::vector<std::vector<uint64_t>> &plains, const std::vector<int> &steps,
+                                 const typename B::GaloisKeys &gal_keys, Ciphertext &vo)
+    {
+        ctx.rotate_plain_sum(in(ctx, ct), plains, steps, B::words(gal_keys), out(ctx, vo));
     }
 };
 

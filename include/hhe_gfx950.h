@@ -66,13 +66,13 @@ void hhe_ctx_destroy(hhe_ctx *c);
  *    there too: enc_key is taken as what the buffer holds in stream order.  Work the caller has on OTHER streams is not waited for.
  *    Host inputs (cw, ncw, block_index, records, keys, matrices, mask values) are read before the call returns.
  *  - The batched calls return after their work has finished (hhe_pasta3_transcipher[_ks], hhe_decompose[_ks], hhe_fc_row[_ks],
- *    hhe_packed_affine[_ks], hhe_fc_packed_ks, hhe_rotate_rows_many_ks, hhe_fc_packed_hoisted_ks, hhe_mod_switch, every upload, read-back, key generation and matrix creation): they fork onto the
+ *    hhe_packed_affine[_ks], hhe_fc_packed_ks, hhe_rotate_rows_many_ks, hhe_fc_packed_hoisted_ks, hhe_rotate_plain_sum_ks, hhe_fc_open_plain_ks, hhe_mod_switch, every upload, read-back, key generation and matrix creation): they fork onto the
  *    context's internal non-blocking streams (HHE_STREAMS), join the context's stream again and wait for it, so `out` may be read
  *    from any stream when they return.  The generic evaluator ops (hhe_ntt, hhe_encode, hhe_add, hhe_add_many, hhe_negate, hhe_add_plain,
  *    hhe_multiply_plain, hhe_multiply, hhe_relinearize, hhe_apply_galois, hhe_rotate_*, hhe_mask, hhe_flatten) only ENQUEUE on the
  *    context's stream: their result is ordered for later work on that stream, and for the host after hhe_ctx_sync (or a wait for
  *    the stream).  A non-blocking stream is not ordered with the default stream.
- *  - hhe_ctx_create uploads its tables on the default stream and waits.  Key uploads, key generation, hhe_matrix_create and hhe_enc_matrix_create use the
+ *  - hhe_ctx_create uploads its tables on the default stream and waits.  Key uploads, key generation, hhe_matrix_create, hhe_enc_matrix_create, hhe_plain_rows_create and hhe_plain_fc_create_open use the
  *    stream the context has at that call and wait: what they leave resident is complete, whichever stream later calls run on.
  *  - Changing the stream waits for nothing.  Resident objects (keys, block tables, kept keystreams, matrices) stay valid, as they
  *    were finished under a host wait.  Generic ops still in flight on the old stream are NOT ordered with calls on the new one,
@@ -94,6 +94,7 @@ int hhe_ctx_profile_read(hhe_ctx *c, char *kernel_name, size_t name_cap, uint64_
 /* derived parameters, for cross-checking against SEAL's context: what in
  * {"root" i<K, "bsk" i<=L (B_0.., m_sk), "gamma", "galois_elt" i=step, "fc_fallbacks", "fc_csum_closes", "fc_packed_key_switches",
  * "add_many_launches", "rot_hoist", "rot_many_fallbacks", "rot_many_key_switches", "rot_many_launches", "rot_many_group",
+ * "plain_sum_fold", "plain_sum_fallbacks", "plain_sum_launches", "plain_sum_mod_downs",
  * "mlp_layers", "mlp_key_switches", "tensor_launches", "square_launches"};
  * which kernels the context dispatches to (read-only diagnostics): "row_kernel" (1 = the fused key-switch row kernels run,
  * 0 = the separate-kernel path), "pm_ok" i<K (coefficient prime i has the pseudo-Mersenne form the lazy kernels need),
@@ -428,6 +429,60 @@ int hhe_square(hhe_ctx *c, const uint64_t *a_dptr, uint64_t *out3_dptr, size_t B
  * describe the last call.  Synchronous.  Not built: a bias (hhe_add_plain between calls), a change of level between layers. */
 int hhe_mlp_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk, const hhe_enc_matrix *const *mats_hptr, size_t n_layers,
                const uint64_t *vi_dptr, uint64_t *out_dptr, size_t B);
+/* ---- Plain-weights sum of rotations: out = sum_k rotate_rows(ct, steps[k]) * plain_k, with ONE mod-down over the sum.
+ *      The handle holds `n` plaintexts, each given as count <= N slot values < t (vals_hptr [n][count]) and encoded as hhe_encode encodes
+ *      them.  Each is lifted by the rule stated at hhe_multiply_plain (x below (t + 1) / 2 stays, x - t from there on, t on either side of a
+ *      prime) to ALL K primes of the context, the special one included, in NTT form with Shoup quotients: 2 K N words per plaintext
+ *      (hhe_plain_rows_bytes; 38 MB for 16 plaintexts at BFVDefault(16384)).  Resident and explicit like hhe_matrix: it names its context,
+ *      hhe_ctx_destroy releases forgotten ones.  Runs on the stream c has and waits.
+ *      DEFINITION (no composition of SEAL's operations).  q_0 .. q_{L-1} the data primes, Q their product, p = q_{K-1} the special prime;
+ *      * the product in Z[X]/(X^N + 1); sigma_k the Galois map of rotate_rows(., steps[k]); m~_k plaintext k as the integer
+ *      polynomial with centred coefficients (the lift above); key_k the Galois key of that element in gk; [.]_{q_I} the residue in
+ *      [0, q_I) taken as an integer polynomial (the digit of SURVEY A.4).  For an input (c0, c1) and i in {0, 1} let X_i in [0, Q p) be the
+ *      integer polynomial congruent, modulo every prime of q u {p}, to
+ *          sum_{k: steps[k] != 0}  m~_k * sum_{I < L} [sigma_k(c1)]_{q_I} * key_k[I][i].
+ *      Then
+ *          out_0[j] = sum_k m~_k * sigma_k(c0)              + floor((X_0 + floor(p/2)) / p)   mod q_j
+ *          out_1[j] = sum_{k: steps[k] == 0} m~_k * c1      + floor((X_1 + floor(p/2)) / p)   mod q_j.
+ *      (The library carries c0, and c1 for step 0, through the extended basis as multiples of p, which divide out exactly.)  The order of
+ *      the pairs does not matter; repeated steps are allowed.  With n = 1 and the plaintext whose slots are all 1 the words are those of
+ *      hhe_rotate_rows_ks(ct, step) under a key of that step.  Slot s of the decryption is sum_k plain_k[s] x[rot_k(s)] mod t.  The
+ *      rounding of the mod-down is taken once over the sum: the noise of n rotations' roundings is replaced by one.
+ *      KEYS.  Every non-zero step needs a key OF ITS OWN in gk (a NAF chain would need a mod-down between its terms): a step without one
+ *      gives HHE_ERR_NO_GALOIS_KEY.  Refused before anything is written, with HHE_ERR_INVALID: a null pointer, B == 0, n == 0 or n above
+ *      the handle's count, |step| >= N/2, a handle or key set of another context.  out == ct is allowed.  hhe_plain_rows_create refuses
+ *      (HHE_ERR_INVALID) a null pointer, n == 0 or n > 2^20 (polynomial counts of its launches are ints: 2 n K stays below 2^31 for every
+ *      K the library admits), count == 0 or count > N, a slot value >= t.
+ *      SCHEDULE.  Synchronous and batched like hhe_rotate_rows_many_ks (HHE_CHUNK, HHE_STREAMS).  The children share the digit transforms
+ *      of c1; where the row kernels run ("row_kernel" == 1) ONE launch of the key-switch row kernel serves all n children of a chunk: a
+ *      workgroup owns (item, key limb, row tile), forms each child's key-switch sums in registers, multiplies them by the child's
+ *      plaintext and adds them up, and one inverse transform and ONE mod-down per item follow.  Elsewhere the same words come from one
+ *      inner-product launch and the element-wise products per child.  A lane keeps the sums of one child and the sums over the children
+ *      (2 x 2 K N words per item), the NTT forms of c0 and one rotated c1 (2 L N): it is reserved for 2 * per items, so a chunk holds
+ *      per = max(1, HHE_CHUNK / 2) items.  The shared digits are exact unless a residue of c1 is 0; such a chunk is recomputed from the
+ *      digits of each sigma_k(c1) itself ("plain_sum_fallbacks" counts those chunks); HHE_ROT_HOIST 0 / 1 / 2 as for
+ *      hhe_rotate_rows_many_ks.  About the last call: "plain_sum_launches" (fused launches per chunk: 1 where the row kernel runs, else
+ *      0), "plain_sum_mod_downs" (finish launches of the primitive per chunk: 1).  "plain_sum_fold": children between two folds of the
+ *      kernel's outer lazy sums -- a fold leaves less than 2q, a product adds less than 4q, and 2q + 3 * 4q fits the 16q <= 2^64 of the
+ *      primes the kernel runs on: 3. ---- */
+typedef struct hhe_plain_rows hhe_plain_rows;
+int hhe_plain_rows_create(hhe_ctx *c, const uint64_t *vals_hptr, size_t n, size_t count, hhe_plain_rows **out);
+void hhe_plain_rows_destroy(hhe_plain_rows *p);
+size_t hhe_plain_rows_bytes(const hhe_plain_rows *p);
+int hhe_rotate_plain_sum_ks(hhe_ctx *c, const hhe_keyset *gk, const hhe_plain_rows *rows, const int *steps_hptr, size_t n,
+                            const uint64_t *ct_dptr, uint64_t *out_dptr, size_t B);
+/* The open layer (hhe_fc_open_shape / hhe_fc_open_diagonals) under PLAIN weights.  M_hptr row-major rows x cols, entries < t; bias_hptr
+ * `rows` words or NULL.  The handle is the plain-rows form of the r open diagonals D_e plus the encoded bias.  The layer:
+ *   y = rotate_plain_sum(x; steps -e, D_e, e < r);   y = add(y, rotate_rows(y, s, gk)) for s = r, 2r, .., c/2;
+ *   with a bias  y = add_plain(y, encode(bias into slots [0, rows))), the words of hhe_add_plain.
+ * Slots [0, rows) decrypt to (M x + b) mod t; no precondition on the other slots of the input ("Open diagonals" above).  Every step
+ * -1 .. -(r-1) and every tail step needs a key of its own: hhe_fc_open_galois_steps lists exactly these.  Chunks, in-place call, levels
+ * and the refusals are those of the primitive, plus an empty dimension (HHE_ERR_INVALID) and HHE_ERR_TOO_FEW_SLOTS at creation. */
+typedef struct hhe_plain_fc hhe_plain_fc;
+int hhe_plain_fc_create_open(hhe_ctx *c, const uint64_t *M_hptr, size_t rows, size_t cols, const uint64_t *bias_hptr, hhe_plain_fc **out);
+void hhe_plain_fc_destroy(hhe_plain_fc *m);
+size_t hhe_plain_fc_bytes(const hhe_plain_fc *m);
+int hhe_fc_open_plain_ks(hhe_ctx *c, const hhe_keyset *gk, const hhe_plain_fc *mat, const uint64_t *vi_dptr, uint64_t *out_dptr, size_t B);
 /* Evaluator::add_many (seal/evaluator.h:150) for K stacked batches in_dptr [K][B][size][L][N], size 2 or 3: out [B][size][L][N] = their
  * sum, in ONE kernel launch whatever K is (hhe_ctx_query("add_many_launches") counts them); the sum of a coefficient is kept in two
  * words and reduced once.  out may be one of the K operands.  K == 0, B == 0, a null pointer or another size: HHE_ERR_INVALID.

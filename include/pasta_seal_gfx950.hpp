@@ -335,6 +335,18 @@ inline void rotate_rows_many(pasta::HheContext &ctx, const pasta::Ciphertext &ct
 {
     Free::rotate_rows_many(ctx, ct, steps, gal_keys, out);
 }
+// The open FC layer under PLAIN weights, vo = M vi + b in slots [0, rows) (b empty: no bias), and the primitive under it, a sum of
+// rotations times plaintexts with one mod-down (hhe_gfx950.h "Plain-weights sum of rotations"); the matrix is uploaded once per content
+inline void fc_open_plain(pasta::HheContext &ctx, const pasta::Ciphertext &vi, const std::vector<std::vector<uint64_t>> &M, const std::vector<uint64_t> &b,
+                          const pasta::GaloisKeys &gal_keys, pasta::Ciphertext &vo)
+{
+    Free::fc_open_plain(ctx, vi, M, b, gal_keys, vo);
+}
+inline void rotate_plain_sum(pasta::HheContext &ctx, const pasta::Ciphertext &ct, const std::vector<std::vector<uint64_t>> &plains, const std::vector<int> &steps,
+                             const pasta::GaloisKeys &gal_keys, pasta::Ciphertext &vo)
+{
+    Free::rotate_plain_sum(ctx, ct, plains, steps, gal_keys, vo);
+}
 // The whole FC layer under the analyst's encrypted weights as ONE device call and one result ciphertext (the hybrid diagonal method,
 // hhe_gfx950.h "packed encrypted FC"), in place of fc_row per neuron: mat holds the r encrypted generalized diagonals, rk / gal_keys are
 // the key objects CSP.cpp:306 and :312-316 name.  Slots [0, rows) of the decryption are the neurons.

@@ -383,6 +383,18 @@ inline void rotate_rows_many(const seal::Ciphertext &ct, const std::vector<int> 
     (void)evaluator;
     Free::rotate_rows_many(*DeviceContext::find(ct.parms_id()), ct, steps, gal_keys, out);
 }
+// The open FC layer under PLAIN weights, vo = M vi + b in slots [0, rows) (b empty: no bias), and the primitive under it, a sum of
+// rotations times plaintexts with one mod-down (hhe_gfx950.h "Plain-weights sum of rotations"); the matrix is uploaded once per content
+inline void fc_open_plain(const seal::Ciphertext &vi, const std::vector<std::vector<uint64_t>> &M, const std::vector<uint64_t> &b,
+                          const seal::GaloisKeys &gal_keys, seal::Ciphertext &vo)
+{
+    Free::fc_open_plain(*DeviceContext::find(vi.parms_id()), vi, M, b, gal_keys, vo);
+}
+inline void rotate_plain_sum(const seal::Ciphertext &ct, const std::vector<std::vector<uint64_t>> &plains, const std::vector<int> &steps,
+                             const seal::GaloisKeys &gal_keys, seal::Ciphertext &vo)
+{
+    Free::rotate_plain_sum(*DeviceContext::find(ct.parms_id()), ct, plains, steps, gal_keys, vo);
+}
 
 // The whole FC layer under the analyst's encrypted weights as ONE device call and one result ciphertext (the hybrid diagonal method,
 // hhe_gfx950.h "packed encrypted FC"), in place of fc_row per neuron: mat holds the r encrypted generalized diagonals, rk / gal_keys are

@@ -53,6 +53,8 @@ _SYMBOLS = [
     "hhe_multiply_sum", "hhe_fc_packed_sum_ks",
     "hhe_fc_open_shape", "hhe_fc_open_diagonals", "hhe_fc_open_galois_steps", "hhe_enc_matrix_create_open", "hhe_fc_open_ks",
     "hhe_square", "hhe_mlp_ks",
+    "hhe_plain_rows_create", "hhe_plain_rows_destroy", "hhe_plain_rows_bytes", "hhe_rotate_plain_sum_ks",
+    "hhe_plain_fc_create_open", "hhe_plain_fc_destroy", "hhe_plain_fc_bytes", "hhe_fc_open_plain_ks",
 ]
 
 _FC_PACKED_SYMBOLS = {"hhe_fc_packed_shape", "hhe_fc_packed_diagonals", "hhe_fc_packed_galois_steps", "hhe_enc_matrix_create",
@@ -61,6 +63,8 @@ _ROT_MANY_SYMBOLS = {"hhe_rotate_rows_many_ks", "hhe_fc_packed_hoisted_ks", "hhe
 _MULT_SUM_SYMBOLS = {"hhe_multiply_sum", "hhe_fc_packed_sum_ks"}
 _MLP_SYMBOLS = {"hhe_fc_open_shape", "hhe_fc_open_diagonals", "hhe_fc_open_galois_steps", "hhe_enc_matrix_create_open", "hhe_fc_open_ks",
                 "hhe_square", "hhe_mlp_ks"}
+_PLAIN_SUM_SYMBOLS = {"hhe_plain_rows_create", "hhe_plain_rows_destroy", "hhe_plain_rows_bytes", "hhe_rotate_plain_sum_ks",
+                      "hhe_plain_fc_create_open", "hhe_plain_fc_destroy", "hhe_plain_fc_bytes", "hhe_fc_open_plain_ks"}
 _NONCE_SYMBOLS = {"hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystream_nonce", "hhe_pasta3_plain_crypt_nonce",
                   "hhe_pasta3_transcipher_nonce_ks", "hhe_decompose_nonce_ks", "hhe_pasta3_block_randomness_dev",
                   "hhe_pasta3_prepare_tables"}
@@ -71,7 +75,7 @@ _NONCE_SYMBOLS = {"hhe_pasta3_block_randomness_nonce", "hhe_pasta3_plain_keystre
 _OPTIONAL = {"hhe_pasta3_clear_keystream_cache", "hhe_sample_poly", "hhe_keygen_secret", "hhe_keygen_public", "hhe_keyset_generate_relin",
              "hhe_keyset_generate_galois", "hhe_keyset_get_relin", "hhe_keyset_get_galois", "hhe_encrypt",
              "hhe_mod_switch", "hhe_decrypt_level", "hhe_seal_save_ciphertext_level", "hhe_seal_load_ciphertext_level",
-             "hhe_noise_budget", "hhe_ctx_create_level", "hhe_keyset_derive_level"} | _NONCE_SYMBOLS | _FC_PACKED_SYMBOLS | _ROT_MANY_SYMBOLS | _MULT_SUM_SYMBOLS | _MLP_SYMBOLS
+             "hhe_noise_budget", "hhe_ctx_create_level", "hhe_keyset_derive_level"} | _NONCE_SYMBOLS | _FC_PACKED_SYMBOLS | _ROT_MANY_SYMBOLS | _MULT_SUM_SYMBOLS | _MLP_SYMBOLS | _PLAIN_SUM_SYMBOLS
 
 
 def exported_symbols():
@@ -117,6 +121,13 @@ def load_library(path=None):
         lib.hhe_enc_matrix_destroy.restype = None
         lib.hhe_enc_matrix_bytes.argtypes = [C.c_void_p]
         lib.hhe_enc_matrix_bytes.restype = C.c_size_t
+    if hasattr(lib, "hhe_plain_rows_create"):
+        for kind in ("rows", "fc"):
+            destroy, nbytes = getattr(lib, "hhe_plain_%s_destroy" % kind), getattr(lib, "hhe_plain_%s_bytes" % kind)
+            destroy.argtypes = [C.c_void_p]
+            destroy.restype = None
+            nbytes.argtypes = [C.c_void_p]
+            nbytes.restype = C.c_size_t
     return lib
 
 
@@ -315,6 +326,71 @@ class EncMatrix:
         return int(self.ctx.lib.hhe_enc_matrix_bytes(self.h))
 
 
+class PlainRows:
+    """Plaintexts as the right operands of Context.rotate_plain_sum, resident on the device (hhe_plain_rows): vals [n][count] slot
+    values < t, each row encoded, lifted to every prime of the context and transformed once."""
+
+    def __init__(self, ctx, vals):
+        vals = np.ascontiguousarray(vals, dtype=np.uint64)
+        assert vals.ndim == 2
+        self.ctx, self.count = ctx, vals.shape[0]
+        h = C.c_void_p()
+        ctx._chk(ctx._need("hhe_plain_rows_create")(ctx.h, _ptr(vals), C.c_size_t(vals.shape[0]), C.c_size_t(vals.shape[1]), C.byref(h)))
+        self.h = h
+
+    def destroy(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.hhe_plain_rows_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    @property
+    def bytes(self):
+        return int(self.ctx.lib.hhe_plain_rows_bytes(self.h))
+
+
+class PlainFc:
+    """A rows x cols FC layer under PLAIN weights in the open layout, resident on the device (hhe_plain_fc): M row-major with entries
+    < t, bias `rows` words or None."""
+
+    def __init__(self, ctx, M, bias=None):
+        M = np.ascontiguousarray(M, dtype=np.uint64)
+        assert M.ndim == 2
+        self.ctx, (self.rows, self.cols) = ctx, M.shape
+        b = None if bias is None else np.ascontiguousarray(bias, dtype=np.uint64)
+        assert b is None or b.shape == (self.rows,)
+        h = C.c_void_p()
+        ctx._chk(ctx._need("hhe_plain_fc_create_open")(ctx.h, _ptr(M), C.c_size_t(self.rows), C.c_size_t(self.cols), _ptr(b), C.byref(h)))
+        self.h = h
+
+    def apply(self, ct, B, gk=None, out=None):
+        """out[b] = the layer on ct[b] (hhe_fc_open_plain_ks; device [B][2][L][N]; out None: in place): slots [0, rows) of the decryption
+        are (M x + bias) mod t.  Returns out."""
+        out = ct if out is None else out
+        self.ctx._chk(self.ctx._need("hhe_fc_open_plain_ks")(self.ctx.h, _ks(gk), self.h, _ptr(ct), _ptr(out), C.c_size_t(B)))
+        return out
+
+    def destroy(self):
+        if getattr(self, "h", None) and getattr(self.ctx, "h", None):
+            self.ctx.lib.hhe_plain_fc_destroy(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+    @property
+    def bytes(self):
+        return int(self.ctx.lib.hhe_plain_fc_bytes(self.h))
+
+
 class Context:
     """One BFV context on one GPU (hhe_ctx)."""
 
@@ -460,6 +536,22 @@ class Context:
     def enc_matrix_open(self, diag_cts, rows, cols):
         """resident encrypted matrix of an open layer from the encryptions of fc_open_diagonals' slot vectors (device [r][2][L][N])"""
         return EncMatrix(self, diag_cts, rows, cols, open=True)
+
+    def plain_rows(self, vals):
+        """resident plaintexts of rotate_plain_sum from their slot vectors vals [n][count]"""
+        return PlainRows(self, vals)
+
+    def rotate_plain_sum(self, ct, rows, steps, out, B, gk=None):
+        """out[b] = sum_k rotate_rows(ct[b], steps[k], gk) * plaintext k of `rows` (a PlainRows), with one mod-down over the sum
+        (hhe_rotate_plain_sum_ks); every non-zero step needs a key of its own; out may be ct.  Synchronous."""
+        arr = (C.c_int * max(len(steps), 1))(*[int(v) for v in steps])
+        self._chk(self._need("hhe_rotate_plain_sum_ks")(self.h, _ks(gk), None if rows is None else rows.h, arr, C.c_size_t(len(steps)),
+                                                        _ptr(ct), _ptr(out), C.c_size_t(B)))
+        return out
+
+    def plain_fc_open(self, M, bias=None):
+        """resident plain-weights open FC layer from its matrix (and bias)"""
+        return PlainFc(self, M, bias)
 
     def square(self, a, out3, B):
         """out3 [B][3][L][N] = Evaluator::square(a) at size 2: the words of multiply(a, a, ..), one operand extension"""

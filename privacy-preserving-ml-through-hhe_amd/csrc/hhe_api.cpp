@@ -2914,6 +2914,284 @@ extern "C" int hhe_mlp_ks(hhe_ctx *c, const hhe_keyset *rk, const hhe_keyset *gk
     return fc_layers_run(c, {true, false, true, "hhe_mlp"}, rk, gk, mats, n_layers, vi, out, B);
 }
 
+// ====================================================================== plain-weights sum of rotations and the open layer on it
+// hhe_rotate_plain_sum_ks and hhe_fc_open_plain_ks.  The definition is in include/hhe_gfx950.h; DESIGN.md section 4 "Plain-weights FC"
+// has the schedule and the workspace.
+void plain_rows_free(hhe_plain_rows *p)
+{
+    if (!p) return;
+    rt_free(p->tab); p->self.release();
+    delete p;
+}
+void plain_fc_free(hhe_plain_fc *m)
+{
+    if (!m) return;
+    plain_rows_free(m->diag); rt_free(m->bias);
+    delete m;
+}
+namespace {
+// vals [n][count] host slot values -> a handle that is not yet registered with the context
+int plain_rows_make(hhe_ctx *c, const char *who, const uint64_t *vals, size_t n, size_t count, hhe_plain_rows **out)
+{
+    const std::string w(who);
+    if (n == 0 || count == 0 || count > c->n || n > ((size_t)1 << 20)) return fail(HHE_ERR_INVALID, w + ": no plaintext, or more slot values than slots");
+    for (size_t i = 0; i < n * count; ++i)
+        if (vals[i] >= c->t) return fail(HHE_ERR_INVALID, w + ": slot value not below the plain modulus");
+    const size_t N = c->n, K = c->K;
+    c->w = &c->lanes[0];
+    hhe_plain_rows *p = new hhe_plain_rows();
+    p->ctx = c; p->count = n;
+    DevBuf dv(n * count * 8), plain(n * N * 8);
+    p->tab = (u64 *)rt_malloc(2 * n * K * N * 8);
+    if (!dv.p || !plain.p || !p->tab) { plain_rows_free(p); return dev_fail((w + ": table alloc").c_str()); }
+    rt_stream st = c->w->stream;
+    rt_h2d(dv.p, vals, n * count * 8, st);
+    op_encode(c, dv.w(), n, (int)count, (int)count, -1, plain.w());
+    // the lift of op_lift_ntt under every prime of the context, the special one included
+    NttArgs a = ntt_args(c, plain.w(), p->tab, n * K, 0, (int)K);
+    a.src_div = (int)K; a.load_op = LOAD_LIFT;
+    k_ntt(a, false, st);
+    op_elt(c, ELT_SHOUP, p->tab, nullptr, p->tab + n * K * N, n * K, 0, (int)K);
+    if (rt_sync(st)) { plain_rows_free(p); return dev_fail(who); }
+    p->bytes = 2 * n * K * N * 8;
+    *out = p;
+    return HHE_OK;
+}
+// the per-item pointer array k_perm takes, all entries the handle's table (matrix_reserve_self)
+int plain_rows_reserve_self(hhe_ctx *c, hhe_plain_rows *p, size_t per)
+{
+    bool grew = false;
+    int rc = p->self.reserve(c, per, "hhe_rotate_plain_sum: pointer table", &grew);
+    if (rc || !grew) return rc;
+    rt_stream st = c->lanes[0].stream;
+    std::vector<const u64 *> h(p->self.cap, p->tab);
+    if (rt_h2d((void *)p->self.p, h.data(), h.size() * sizeof(u64 *), st) || rt_sync(st)) {
+        rc = dev_fail("hhe_rotate_plain_sum: pointer table");
+        p->self.release();
+        return rc;
+    }
+    return HHE_OK;
+}
+struct PlainSumPlan {
+    hhe_plain_rows *rows = nullptr;
+    std::vector<int> steps;      // pair k: rotate_rows by steps[k], times plaintext k
+    std::vector<KsKid> kids;     // row k: the key, tables and element of pair k (step 0: element 1, step0 set, no key)
+    const KsKid *d_kids = nullptr;
+    bool rowk = false, any_rot = false, any_zero = false;
+    std::vector<int> tail;       // the layer: y += rotate_rows(y, s) for s in tail, then + bias
+    const u64 *bias = nullptr;
+};
+// host only: every step valid and every non-zero step (tail included) with a key of its own in the named set
+int plain_sum_plan(const hhe_ctx *c, const int *steps, size_t n, PlainSumPlan &p)
+{
+    p.steps.assign(steps, steps + n);
+    p.kids.assign(n, zeroed<KsKid>());
+    for (size_t k = 0; k < n; ++k)
+        if ((size_t)std::abs((long long)steps[k]) >= c->n / 2) return fail(HHE_ERR_INVALID, "step count too large");
+    auto own_key = [&](int step) { return c->gks->gk.count(galois_elt_from_step(c, step)) != 0; };
+    for (size_t k = 0; k < n; ++k) {
+        KsKid &kd = p.kids[k];
+        if (steps[k] == 0) { kd.elt = 1; kd.step0 = 1; p.any_zero = true; continue; }
+        if (!own_key(steps[k])) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+        kd.elt = galois_elt_from_step(c, steps[k]);
+        p.any_rot = true;
+    }
+    for (int s : p.tail)
+        if (!own_key(s)) return fail(HHE_ERR_NO_GALOIS_KEY, "Galois key not present");
+    p.rowk = use_row_kernel(c);
+    return HHE_OK;
+}
+// what the chunks read that is made once per call, on the main lane before they fork (rot_plan_tables)
+int plain_sum_tables(hhe_ctx *c, PlainSumPlan &p, size_t per)
+{
+    int rc;
+    for (KsKid &kd : p.kids) {
+        if (kd.step0) continue;
+        if (!(kd.key = galois_key(c, kd.elt))) return HHE_ERR_NO_GALOIS_KEY;
+        if ((rc = fc_corr(c, kd.elt, kd.key, &kd.corr))) return rc;
+        if (p.rowk && (rc = ensure_key_shoup(c, kd.key, &kd.key_s))) return rc;
+    }
+    if (ensure_qsp_poly(c)) return dev_fail("hhe_rotate_plain_sum: workspace");
+    if ((rc = plain_rows_reserve_self(c, p.rows, per))) return rc;
+    if (!p.rowk) return HHE_OK;
+    if ((rc = c->d_rot_kids.reserve(c, p.kids.size(), "hhe_rotate_plain_sum: child table"))) return rc;
+    if (rt_h2d(c->d_rot_kids.p, p.kids.data(), p.kids.size() * sizeof(KsKid), c->w->stream) || rt_sync(c->w->stream)) return dev_fail("hhe_rotate_plain_sum: child table");
+    p.d_kids = c->d_rot_kids.p;
+    return HHE_OK;
+}
+// The primitive for one chunk on the current lane, reserved for 2 * per items: in / out [per][2][L][N].  ws_d holds c0hat | the rotated c1
+// of the exact form, ws_ct[2] c1hat (step 0), ws_T the digit transforms, ws_S the sums of one child | the sums over the children, both
+// split as the fused finish reads them.
+//   fast, row kernels: shared digits, ONE launch of ks_plain_sum_row_kernel, the finish.
+//   fast, elsewhere:   shared digits; per child the inner product through the map (ks_mac_kernel, KS_PERM) and the products by its plaintext.
+//   exact:             per child the digits of the rotated c1 itself, the plain inner product, the same products.
+// The last two end in one inverse transform of the 2K sums and the same finish.  out may be in: nothing reads `in` after the sums
+int plain_sum_chunk(hhe_ctx *c, const PlainSumPlan &p, const u64 *in, u64 *out, size_t per, bool fast)
+{
+    Lane &w = *c->w;
+    const int L = c->L, K = c->K;
+    const size_t n = c->n, ln = (size_t)L * n, ctw = c->ct_words(), nk = p.steps.size();
+    u64 *c0hat = w.ws_d, *rot1 = w.ws_d + per * ln, *c1hat = w.ws_ct[2];
+    u64 *S = w.ws_S, *acc = w.ws_S + per * 2 * K * n;
+    const KsSplit ss = ks_split(c, S, per), sa = ks_split(c, acc, per);
+    op_c0hat(c, in, c0hat, per);
+    if (p.any_zero) op_c0hat(c, in + ln, c1hat, per);
+    if (fast && p.any_rot) fc_parent_digits(c, in, w.ws_T, per);
+    const NttArgs ksf = ks_ksf_args(c, sa, per, nullptr, ctw, 1, 0, out);
+    if (fast && p.rowk) {
+        KsRowArgs x = ks_row_args(c, nullptr, nullptr, per, &sa);
+        x.T = w.ws_T; x.c0hat = c0hat; x.c1hat = c1hat; x.kids = p.d_kids; x.kid_B = (int)per; x.n_kids = (int)nk;
+        x.plain = p.rows->tab; x.plain_s_off = p.rows->s_off();
+        if (k_ks_perm_row(ntt_args(c, nullptr, nullptr, 0, 0, K), x, w.stream)) return dev_fail("hhe_rotate_plain_sum: key-switch row kernel");
+        ks_finish_split(c, sa, ksf, per, false);
+        return HHE_OK;
+    }
+    rt_memset(acc, 0, per * 2 * K * n * 8, w.stream);
+    for (size_t k = 0; k < nk; ++k) {
+        const KsKid &kd = p.kids[k];
+        const u64 *D = p.rows->tab + k * K * n;
+        // q_sp * NTT(galois(c0)) times the plaintext into the first sum (for step 0 also c1 into the second)
+        PermArgs pa = perm_args(c, per * L, c0hat, sa.W, 2 * ln);
+        pa.elt = kd.elt; pa.mac = 1; pa.mul_ptrs = p.rows->self.p; pa.mul_shift = k * K * n;
+        k_perm(pa, w.stream);
+        if (kd.step0) {
+            pa.in = c1hat; pa.out = sa.W + ln;
+            k_perm(pa, w.stream);
+            continue;
+        }
+        KsMacArgs m = ks_mac_args(c, w.ws_T, kd.key, S, per);
+        m.S_sp = ss.Usp;
+        if (fast) { m.perm_elt = kd.elt; m.corr = kd.corr; }
+        else {
+            k_galois(galois_args(c, per, galois_einv(c, kd.elt), in + ln, 2 * ln, rot1, ln), w.stream);
+            k_ntt(ks_digit_args(c, rot1, ln, w.ws_T, per), false, w.stream);
+        }
+        k_ks_mac(m, w.stream);
+        k_elt(elt_args(c, ss.W, D, sa.W, per * 2 * L, 0, L, L), ELT_MAC, w.stream);
+        k_elt(elt_args(c, ss.Usp, D + (size_t)(K - 1) * n, sa.Usp, per * 2, K - 1, 1, 1), ELT_MAC, w.stream);
+    }
+    ks_finish_split(c, sa, ksf, per, true);
+    return HHE_OK;
+}
+// the primitive, and with a tail or a bias the layer built on it: one driver over the checked chunks
+int plain_sum_run(hhe_ctx *c, const char *who, const hhe_keyset *gk, PlainSumPlan &p, const int *steps, size_t n, const u64 *in, u64 *out, size_t B)
+{
+    int rc = check_sets(c, gk);
+    if (rc) return rc;
+    KeyScope keys(c, gk, nullptr);
+    if ((rc = plain_sum_plan(c, steps, n, p))) return rc;
+    Lane &main = c->lanes[0];
+    c->w = &main;
+    // a lane holds the sums of one child and the sums over the children of its items (ws_S), c0hat and one rotated c1 (ws_d): 2 * per
+    // stays within the HHE_CHUNK items a lane is reserved for elsewhere
+    const size_t per = std::min(B, std::max<size_t>(1, c->chunk / 2));
+    if ((rc = plain_sum_tables(c, p, per))) return rc;
+    const ChunkPlan cp(B, per, c->nstreams);
+    const size_t ctw = c->ct_words();
+    const bool fast = c->rot_hoist != 0, layer = !p.tail.empty() || p.bias;
+    Parked park{in, out, ctw, "hhe_rotate_plain_sum: results in place", out};
+    rc = run_chunks_checked(c, cp, who, "hhe_rotate_plain_sum", fast, c->rot_hoist == 2, c->plain_sum_fallbacks,
+        [&](Lane &ln, bool) { return lane_reserve(c, ln, 2 * per); },
+        [&](Lane &ln, size_t, size_t b0, size_t bc, bool f) -> int {
+            u64 *res = park.res + b0 * ctw;
+            if (!layer) return plain_sum_chunk(c, p, in + b0 * ctw, res, bc, f);
+            u64 *y = ln.ws_ct[0];
+            int r = plain_sum_chunk(c, p, in + b0 * ctw, y, bc, f);
+            for (size_t i = 0; i < p.tail.size() && !r; ++i) r = op_prep_rows(c, y, p.tail[i], ln.ws_ct[1], bc);
+            if (r) return r;
+            if (p.bias) op_add_plain(c, y, p.bias, nullptr, 0, true, false, false, res, bc);
+            else rt_d2d(res, y, bc * ctw * 8, ln.stream);
+            return HHE_OK;
+        }, &park);
+    if (!rc) { c->plain_sum_launches = fast && p.rowk ? 1 : 0; c->plain_sum_mod_downs = 1; }
+    return rc;
+}
+}  // namespace
+
+extern "C" int hhe_plain_rows_create(hhe_ctx *c, const uint64_t *vals, size_t n, size_t count, hhe_plain_rows **out)
+{
+    HHE_LOCK(c);
+    if (!c || !vals || !out) return fail(HHE_ERR_INVALID, "hhe_plain_rows_create: null argument");
+    hhe_plain_rows *p = nullptr;
+    int rc = plain_rows_make(c, "hhe_plain_rows_create", vals, n, count, &p);
+    if (rc) return rc;
+    c->plain_rows.push_back(p);
+    *out = p;
+    return HHE_OK;
+}
+extern "C" void hhe_plain_rows_destroy(hhe_plain_rows *p)
+{
+    if (!p) return;
+    hhe_ctx *c = p->ctx;
+    HHE_LOCK(c);
+    sync_ctx(c);
+    c->plain_rows.erase(std::remove(c->plain_rows.begin(), c->plain_rows.end(), p), c->plain_rows.end());
+    plain_rows_free(p);
+}
+extern "C" size_t hhe_plain_rows_bytes(const hhe_plain_rows *p) { return p ? p->bytes : 0; }
+extern "C" int hhe_rotate_plain_sum_ks(hhe_ctx *c, const hhe_keyset *gk, const hhe_plain_rows *rows, const int *steps, size_t n,
+                                       const uint64_t *ct, uint64_t *out, size_t B)
+{
+    HHE_LOCK(c);
+    if (!c || !rows || !steps || !ct || !out || B == 0 || n == 0) return fail(HHE_ERR_INVALID, "hhe_rotate_plain_sum: null argument, empty batch or no pair");
+    if (rows->ctx != c) return fail(HHE_ERR_INVALID, "plain rows belong to another context");
+    if (n > rows->count) return fail(HHE_ERR_INVALID, "hhe_rotate_plain_sum: more pairs than the handle has plaintexts");
+    PlainSumPlan p;
+    p.rows = const_cast<hhe_plain_rows *>(rows);
+    return plain_sum_run(c, "hhe_rotate_plain_sum", gk, p, steps, n, ct, out, B);
+}
+
+extern "C" int hhe_plain_fc_create_open(hhe_ctx *c, const uint64_t *M, size_t rows, size_t cols, const uint64_t *bias, hhe_plain_fc **out)
+{
+    HHE_LOCK(c);
+    if (!c || !M || !out) return fail(HHE_ERR_INVALID, "hhe_plain_fc_create_open: null argument");
+    size_t r, cc;
+    int rc = fc_dims(true, c->n, rows, cols, r, cc);
+    if (rc) return rc;
+    for (size_t i = 0; bias && i < rows; ++i)
+        if (bias[i] >= c->t) return fail(HHE_ERR_INVALID, "hhe_plain_fc_create_open: bias entry not below the plain modulus");
+    std::vector<u64> vals(r * cc);
+    if ((rc = hhe_fc_open_diagonals(c->t, M, rows, cols, vals.data()))) return rc;
+    hhe_plain_fc *m = new hhe_plain_fc();
+    m->ctx = c; m->rows = rows; m->cols = cols; m->r = r; m->c = cc;
+    for (size_t e = 0; e < r; ++e) m->steps.push_back(-(int)e);
+    if ((rc = plain_rows_make(c, "hhe_plain_fc_create_open", vals.data(), r, cc, &m->diag))) { plain_fc_free(m); return rc; }
+    if (bias) {
+        DevBuf bv(rows * 8);
+        m->bias = (u64 *)rt_malloc(c->n * 8);
+        if (!bv.p || !m->bias) { plain_fc_free(m); return dev_fail("hhe_plain_fc_create_open: table alloc"); }
+        rt_stream st = c->w->stream;
+        rt_h2d(bv.p, bias, rows * 8, st);
+        op_encode(c, bv.w(), 1, (int)rows, (int)rows, -1, m->bias);
+        if (rt_sync(st)) { plain_fc_free(m); return dev_fail("hhe_plain_fc_create_open"); }
+    }
+    m->bytes = m->diag->bytes + (bias ? c->n * 8 : 0);
+    c->plain_fcs.push_back(m);
+    *out = m;
+    return HHE_OK;
+}
+extern "C" void hhe_plain_fc_destroy(hhe_plain_fc *m)
+{
+    if (!m) return;
+    hhe_ctx *c = m->ctx;
+    HHE_LOCK(c);
+    sync_ctx(c);
+    c->plain_fcs.erase(std::remove(c->plain_fcs.begin(), c->plain_fcs.end(), m), c->plain_fcs.end());
+    plain_fc_free(m);
+}
+extern "C" size_t hhe_plain_fc_bytes(const hhe_plain_fc *m) { return m ? m->bytes : 0; }
+extern "C" int hhe_fc_open_plain_ks(hhe_ctx *c, const hhe_keyset *gk, const hhe_plain_fc *mat, const uint64_t *vi, uint64_t *out, size_t B)
+{
+    HHE_LOCK(c);
+    if (!c || !mat || !vi || !out || B == 0) return fail(HHE_ERR_INVALID, "hhe_fc_open_plain: null argument or empty batch");
+    if (mat->ctx != c) return fail(HHE_ERR_INVALID, "plain matrix belongs to another context");
+    PlainSumPlan p;
+    p.rows = mat->diag;
+    for (size_t s = mat->r; s < mat->c; s <<= 1) p.tail.push_back((int)s);
+    p.bias = mat->bias;
+    return plain_sum_run(c, "hhe_fc_open_plain", gk, p, mat->steps.data(), mat->steps.size(), vi, out, B);
+}
+
 extern "C" int hhe_add_many(hhe_ctx *c, const uint64_t *in, size_t K, uint64_t *out, size_t B, int size)
 {
     HHE_LOCK(c);

@@ -273,7 +273,8 @@ struct KsMacArgs {  // S[b][k][J][n] = sum_I T[b][I][J][n] * key[I][k][J][n]
 // one child of a node in a multi-child launch of the key-switch row kernel (ks_perm_row_many_kernel; KsRowArgs::kids)
 struct KsKid {
     const u64 *key, *key_s, *corr;   // [L][2][K][N] key and Shoup quotients, [2][K][N] correction table (KsCorrArgs)
-    u32 elt, pad;                    // Galois element of the child's rotation
+    u32 elt, step0;                  // Galois element of the child's rotation; step0 != 0 (plain-weights sum only): the child is step 0, it has no
+                                     // key and enters as q_sp * NTT(c0), q_sp * NTT(c1) on the data limbs
 };
 constexpr int HHE_ROT_GROUP = 16;    // children one launch serves at most (the virtual batch and the lane's sums stay within HHE_CHUNK items)
 // Fused key-switch row kernel (ks_row_kernel): for one (item b, key limb J, row tile) it runs the forward ROW pass of the
@@ -307,7 +308,18 @@ struct KsRowArgs {
     // null / 0 (every single-child caller): key, key_s, corr and perm_elt above serve all B items
     const KsKid *kids;
     int kid_B;
+    // Plain-weights sum (hhe_rotate_plain_sum_ks; ks_plain_sum_row_kernel): B counts REAL items and a workgroup loops over the n_kids children
+    // of kids itself (kid_B = B).  Child ch's sums, complete with corr and c0hat, are multiplied by limb J of its plaintext -- plain + (ch * K + J) * N,
+    // NTT form under all K primes, Shoup quotients plain_s_off words behind -- and added up over the children before the one inverse row
+    // pass.  A step-0 child (KsKid::step0) contributes c0hat and c1hat ([B][L][N]: q_sp * NTT(c1)) on the data limbs, nothing on the special one.
+    // null (every other caller): one child per workgroup, as above
+    const u64 *plain;
+    size_t plain_s_off;
+    const u64 *c1hat;
+    int n_kids;
 };
+constexpr int PLAIN_SUM_FOLD = 3;    // children between two folds of the outer sums of the plain-weights sum: a fold leaves a sum below 2q, a truncated
+                                     // Shoup product adds less than 4q, and 2q + 3 * 4q = 14q fits the 16q <= 2^64 of a pseudo-Mersenne prime where 18q need not
 
 // Correction of the shared-digit key switch (DESIGN.md "FC rotation trie"): the digit d_I of galois_g(c1) differs from
 // galois_g applied mod q_J to the digit of c1 by q_I at every sign-flipped, non-zero coefficient, so

@@ -587,6 +587,8 @@ extern "C" void hhe_ctx_destroy(hhe_ctx *c)
     for (hhe_keyset *ks : c->sets) { keyset_clear(ks); delete ks; }  // sets the caller did not destroy
     for (hhe_matrix *m : c->mats) matrix_free(m);  // handles the caller did not destroy
     for (hhe_enc_matrix *m : c->enc_mats) enc_matrix_free(m);
+    for (hhe_plain_rows *p : c->plain_rows) plain_rows_free(p);
+    for (hhe_plain_fc *m : c->plain_fcs) plain_fc_free(m);
     for (auto &kv : c->d_key_shoup) rt_free(kv.second);
     rt_free(c->d_feistel_mask);
     rt_free(c->d_zero_corr);
@@ -705,6 +707,10 @@ extern "C" uint64_t hhe_ctx_query(const hhe_ctx *c, const char *what, int i)
     if (w == "rot_many_key_switches") return c->rot_many_key_switches;  // of the last hhe_rotate_rows_many_ks / hhe_fc_packed_hoisted_ks call: nodes of its trie
     if (w == "rot_many_launches") return c->rot_many_launches;          // ... and its multi-child launches of ks_perm_row_kernel per chunk
     if (w == "rot_many_group") return HHE_ROT_GROUP;                    // children one such launch serves at most
+    if (w == "plain_sum_fold") return PLAIN_SUM_FOLD;                   // children between two folds of the outer sums of ks_plain_sum_row_kernel
+    if (w == "plain_sum_fallbacks") return c->plain_sum_fallbacks;      // chunks of the plain-weights sum recomputed from per-child digits
+    if (w == "plain_sum_launches") return c->plain_sum_launches;        // of the last such call: launches of ks_plain_sum_row_kernel per chunk (0: separate launches)
+    if (w == "plain_sum_mod_downs") return c->plain_sum_mod_downs;      // ... and finish launches of the primitive per chunk
     if (w == "add_many_launches") return c->add_many_launches;            // launches of the sum kernel (hhe_add_many: one per call)
     if (w == "behz_sum_cap") return c->behz_sum_cap;                      // most products hhe_multiply_sum sums under one floor (K = 1 is always served)
     if (w == "multiply_sum_fold_q") return (u64)c->sum_fold_q;            // addends between two reductions of its sums: under the data primes,

@@ -116,6 +116,26 @@ struct hhe_enc_matrix {
     u64 *wb = nullptr;           // [r][2][L+1][N]: NTT form of the extension to B_sk
     size_t bytes = 0;            // device footprint of wq + wb
 };
+// Plaintexts as the right operands of hhe_rotate_plain_sum_ks, resident (hhe_plain_rows_create): each encoded, lifted to its centred
+// representative under ALL K primes of the context (the special one included) and transformed, with Shoup quotients.
+struct hhe_plain_rows {
+    hhe_ctx *ctx = nullptr;
+    size_t count = 0;
+    u64 *tab = nullptr;          // [count][K][N] words | [count][K][N] their Shoup quotients
+    GrowBuf<const u64 *> self;   // device pointers, all = tab: the per-item pointer array k_perm takes (refilled when it grows)
+    size_t bytes = 0;            // device footprint of tab
+    size_t s_off() const;        // words from a word of tab to its quotient
+};
+// A rows x cols layer under plain weights (hhe_plain_fc_create_open): the plain-rows form of its r open diagonals, the steps -e they
+// are paired with, and the plaintext of the bias
+struct hhe_plain_fc {
+    hhe_ctx *ctx = nullptr;
+    size_t rows = 0, cols = 0, r = 0, c = 0;
+    hhe_plain_rows *diag = nullptr;  // owned by the handle (not in hhe_ctx::plain_rows)
+    u64 *bias = nullptr;             // [N] plaintext of the bias (coefficients mod t), or null
+    std::vector<int> steps;          // 0, -1, .., -(r-1)
+    size_t bytes = 0;
+};
 // one stream + the per-batch workspaces of the ops: lane_reserve allocates the fixed set for `cap` ciphertexts under that one
 // capacity; the GrowBuf members belong to single schedules, grow on their own and go with the lane's workspaces (free_lane)
 struct Lane {
@@ -254,6 +274,10 @@ struct hhe_ctx {
     std::vector<hhe_keyset *> sets;
     std::vector<hhe_matrix *> mats;            // plain-matrix handles created on this context
     std::vector<hhe_enc_matrix *> enc_mats;    // encrypted-matrix handles created on this context
+    std::vector<hhe_plain_rows *> plain_rows;  // plain-rows handles created on this context
+    std::vector<hhe_plain_fc *> plain_fcs;     // plain-weights layer handles created on this context
+    u64 plain_sum_fallbacks = 0;               // chunks of hhe_rotate_plain_sum_ks / hhe_fc_open_plain_ks recomputed from per-child digits ("plain_sum_fallbacks")
+    u64 plain_sum_launches = 0, plain_sum_mod_downs = 0;  // of the last such call, per chunk: launches of ks_plain_sum_row_kernel; finish launches of the primitive
     u64 fc_packed_key_switches = 0;            // Galois key switches per item of the last hhe_fc_packed_ks call (hhe_ctx_query("fc_packed_key_switches"))
     u64 add_many_launches = 0;                 // launches of the sum kernel, by hhe_add_many and by the packed FC (hhe_ctx_query("add_many_launches"))
     u64 behz_sum_cap = 0;                      // most products hhe_multiply_sum floors as one sum (hhe_ctx_query("behz_sum_cap"); the condition is in hhe_gfx950.h)
@@ -367,3 +391,6 @@ inline bool fin_item_on(const hhe_ctx *c) { return c->fin_item != 0 && fin_fused
 inline bool fin_item_for(const hhe_ctx *c, size_t B) { return fin_item_on(c) && (c->fin_item > 0 || B >= c->fin_item_min); }
 void matrix_free(hhe_matrix *m);  // hhe_api.cpp: device memory of a handle and the handle
 void enc_matrix_free(hhe_enc_matrix *m);
+void plain_rows_free(hhe_plain_rows *p);
+void plain_fc_free(hhe_plain_fc *m);
+inline size_t hhe_plain_rows::s_off() const { return count * (size_t)ctx->K * ctx->n; }

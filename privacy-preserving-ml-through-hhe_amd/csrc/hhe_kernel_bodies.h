@@ -1304,10 +1304,61 @@ HD void ks_row_mac_gather_t(const KsRowArgs &x, const NttArgs &fa, int bx, int b
         }
     }
 }
-// the form the launchers' loops call (the tests-only emulator among them): the table decides
+// Plain-weights sum (KsRowArgs::plain): every child of the table for item b -- its key-switch sums as the multi-child launch forms them
+// (digits through the child's map, + corr, + c0hat), or c0hat / c1hat themselves for a step-0 child -- times limb J of the child's
+// plaintext, added into sum0 / sum1.  A child's sums are below 16q (ks_row_mac_gather_t) and shoup_lazy_t takes any word, so they are
+// multiplied as they are; the products are below 4q and the outer sums are folded every PLAIN_SUM_FOLD children (hhe_common.h), the
+// flush phase folds after the last one.
+template <int CM, int CC>
+HD void ks_row_plain_sum(const KsRowArgs &x, const NttArgs &fa, int bx, int b, int J, int tid, u64 *sum0, u64 *sum1)
+{
+    const NttGeom g = ntt_geom<CM, CC>(fa, bx, J);
+    const ModDev m = mod_at_u(fa.mods, J);
+    const u64 nq = m.nq;
+    for (int ch = 0; ch < x.n_kids; ch++) {
+        const bool step0 = x.kids[ch].step0 != 0;
+        if (!step0 || J < x.L) {
+            u64 a0[2 * KSROW_NP], a1[2 * KSROW_NP];
+            if (step0) {
+                const u64 *h0 = x.c0hat + ((size_t)b * x.L + J) * g.n, *h1 = x.c1hat + ((size_t)b * x.L + J) * g.n;
+#pragma unroll
+                for (int k = 0; k < KSROW_NP; k++) {
+                    const int gi = ks_row_idx<CM, CC>(fa, g, tid, k).gi;
+                    const U2 v0 = ld2(h0 + gi), v1 = ld2(h1 + gi);
+                    a0[2 * k] = v0.a; a0[2 * k + 1] = v0.b;
+                    a1[2 * k] = v1.a; a1[2 * k + 1] = v1.b;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 2 * KSROW_NP; k++) { a0[k] = 0; a1[k] = 0; }
+                for (int I = 0; I < x.L; I++) ks_row_mac_gather_t<CM, CC, true>(x, fa, bx, ch * x.kid_B + b, J, I, tid, a0, a1);
+            }
+            const u64 *d = x.plain + ((size_t)ch * x.K + J) * g.n, *ds = d + x.plain_s_off;
+#pragma unroll
+            for (int k = 0; k < KSROW_NP; k++) {
+                const int gi = ks_row_idx<CM, CC>(fa, g, tid, k).gi;
+                const U2 w = ld2(d + gi), ws = ld2(ds + gi);
+                sum0[2 * k] = add_nw(sum0[2 * k], shoup_lazy_t(a0[2 * k], w.a, ws.a, nq));
+                sum0[2 * k + 1] = add_nw(sum0[2 * k + 1], shoup_lazy_t(a0[2 * k + 1], w.b, ws.b, nq));
+                sum1[2 * k] = add_nw(sum1[2 * k], shoup_lazy_t(a1[2 * k], w.a, ws.a, nq));
+                sum1[2 * k + 1] = add_nw(sum1[2 * k + 1], shoup_lazy_t(a1[2 * k + 1], w.b, ws.b, nq));
+            }
+        }
+        if (ch % PLAIN_SUM_FOLD == PLAIN_SUM_FOLD - 1 && ch != x.n_kids - 1) {
+#pragma unroll
+            for (int k = 0; k < 2 * KSROW_NP; k++) { sum0[k] = pm_fold(sum0[k], m); sum1[k] = pm_fold(sum1[k], m); }
+        }
+    }
+}
+// the form the launchers' loops call (the tests-only emulator among them): the table decides.  A plain-weights sum runs its whole child
+// loop on the call for digit 0 and returns on the others
 template <int CM, int CC>
 HD void ks_row_mac_gather(const KsRowArgs &x, const NttArgs &fa, int bx, int b, int J, int I, int tid, u64 *acc0, u64 *acc1)
 {
+    if (x.plain) {
+        if (I == 0) ks_row_plain_sum<CM, CC>(x, fa, bx, b, J, tid, acc0, acc1);
+        return;
+    }
     if (x.kids) ks_row_mac_gather_t<CM, CC, true>(x, fa, bx, b, J, I, tid, acc0, acc1);
     else ks_row_mac_gather_t<CM, CC, false>(x, fa, bx, b, J, I, tid, acc0, acc1);
 }

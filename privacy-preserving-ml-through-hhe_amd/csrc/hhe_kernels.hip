@@ -503,7 +503,7 @@ __global__ void __launch_bounds__(KSROW_THREADS, KSROW_WAVES) ks_row_kernel(NttA
 #ifndef PERMROW_WAVES
 #define PERMROW_WAVES 3   // 154 VGPRs, no spills; at 4 waves per SIMD (128 VGPRs) 14 registers spill: 34.5 vs 32.5 ms per MNIST sample
 #endif
-template <int LOGM, bool MANY>
+template <int LOGM, bool MANY, bool SUM = false>
 __device__ __forceinline__ void ks_perm_row_wg(const NttArgs &a, const KsRowArgs &x)
 {
     constexpr bool TWL = LOGM == 8;
@@ -519,7 +519,9 @@ __device__ __forceinline__ void ks_perm_row_wg(const NttArgs &a, const KsRowArgs
 #pragma unroll
     for (int k = 0; k < 2 * KSROW_NP; k++) { acc0[k] = 0; acc1[k] = 0; }
     if (TWL) ks_row_twiddle_fill<LOGM, CC>(a, bx, J, true, tid, twl);
-    for (int I = 0; I < x.L; I++) ks_row_mac_gather_t<LOGM, CC, MANY>(x, a, bx, b, J, I, tid, acc0, acc1);
+    if (SUM) ks_row_plain_sum<LOGM, CC>(x, a, bx, b, J, tid, acc0, acc1);
+    else
+        for (int I = 0; I < x.L; I++) ks_row_mac_gather_t<LOGM, CC, MANY>(x, a, bx, b, J, I, tid, acc0, acc1);
     u64 *const out0 = J < x.L ? x.U0 + (size_t)b * x.u_stride + (size_t)J * n : x.Usp + ((size_t)b * 2 + 0) * n;
     u64 *const out1 = J < x.L ? x.U1 + (size_t)b * x.u_stride + (size_t)J * n : x.Usp + ((size_t)b * 2 + 1) * n;
     ks_row_flush_phase<LOGM, CC>(a, bx, J, tid, lds, acc0, nullptr);
@@ -538,6 +540,15 @@ __global__ void __launch_bounds__(KSROW_THREADS, PERMROW_WAVES) ks_perm_row_kern
 // the virtual items child * kid_B + item, and the child's key, quotients, correction table and element come from x.kids (hhe_common.h)
 template <int LOGM>
 __global__ void __launch_bounds__(KSROW_THREADS, PERMROW_WAVES) ks_perm_row_many_kernel(NttArgs a, KsRowArgs x) { ks_perm_row_wg<LOGM, true>(a, x); }
+// ... and the plain-weights sum (hhe_rotate_plain_sum_ks): a workgroup belongs to an (item, key limb, row tile) and loops over ALL children
+// of x.kids; each child's sums are multiplied by its plaintext (x.plain) and added up in a second set of registers, so an item has one
+// inverse row pass per sum and one mod-down whatever the number of rotations.  Two sets of 2 x 8 lazy sums and a digit's operands
+// do not fit the 170 VGPRs of three waves per SIMD: the kernel is bounded for two, and keeps everything in registers (no scratch)
+#ifndef PLAINSUM_WAVES
+#define PLAINSUM_WAVES 2
+#endif
+template <int LOGM>
+__global__ void __launch_bounds__(KSROW_THREADS, PLAINSUM_WAVES) ks_plain_sum_row_kernel(NttArgs a, KsRowArgs x) { ks_perm_row_wg<LOGM, true, true>(a, x); }
 int k_ks_perm_row(const NttArgs &a0, const KsRowArgs &x, rt_stream s)
 {
     NttArgs a = a0;
@@ -549,6 +560,15 @@ int k_ks_perm_row(const NttArgs &a0, const KsRowArgs &x, rt_stream s)
     const size_t units = ((size_t)x.K << a.tiles_log);   // (limb, tile) units; with tiles_log >= 3 a multiple of eight
     dim3 grid((unsigned)(((units + 7) & ~(size_t)7) * x.B));
     hipStream_t st = (hipStream_t)s;
+    if (x.plain) {
+        switch (n2) {
+        case 6: hipLaunchKernelGGL((ks_plain_sum_row_kernel<6>), grid, dim3(KSROW_THREADS), 0, st, a, x); break;
+        case 7: hipLaunchKernelGGL((ks_plain_sum_row_kernel<7>), grid, dim3(KSROW_THREADS), 0, st, a, x); break;
+        case 8: hipLaunchKernelGGL((ks_plain_sum_row_kernel<8>), grid, dim3(KSROW_THREADS), 0, st, a, x); break;
+        default: snprintf(g_rt_err, sizeof(g_rt_err), "ks_perm_row: unsupported row pass size 2^%d", n2); return -1;
+        }
+        return 0;
+    }
     switch (x.kids ? -n2 : n2) {
     case 6: hipLaunchKernelGGL((ks_perm_row_kernel<6>), grid, dim3(KSROW_THREADS), 0, st, a, x); break;
     case 7: hipLaunchKernelGGL((ks_perm_row_kernel<7>), grid, dim3(KSROW_THREADS), 0, st, a, x); break;
