@@ -12,6 +12,10 @@ once more, in Python integers, with no transform and no RNS trick, and holds the
   e. add_plain / sub_plain: c0[j] +- floor((m Q + (t + 1) / 2) / t) mod q_j;
   f. BEHZ multiply as a distance: |centred(CRT(out) - floor((2 t d + Q) / (2 Q)))| <= L + 1.
 
+The plaintext boundary continues the list in codec_common.py, on the Env, the tables and the roots of this file: g. the slots
+(hhe_encode and the decode half of hhe_decrypt as evaluations at psi_t^(e_i)) and h. decrypt (the scale-and-round of hhe_decrypt and
+hhe_decrypt_level with its RNS removed).
+
 No expected value here comes from a transform, a CRT or a key switch of the oracle or of the product, with two exceptions that come
 after b has held the oracle's transforms to the definition: a dense key of chosen COEFFICIENTS is brought to the NTT form the ABI
 takes (DenseKey), and the oracle's real keys are brought back to coefficients (lift_key).  The oracle's and the product's
